@@ -16,8 +16,11 @@ finished bands are exchanged once per frame over RCCL (torch.distributed backend
 send/recv for unequal bands, one all-gather for equal ones; two frames in flight so the exchange of frame i
 overlaps the rendering of frame i+1; total work is fixed -> "scaling": "strong".
 
-Timing: --warmup untimed frames, then the block of EXACTLY --steps frames (fence + barrier on both sides, max
-over ranks) is repeated >= --blocks times and >= 0.5 s; ms_per_step is the MEDIAN block, p10 / p90 beside it.
+Timing: --warmup untimed frames, more untimed frames until the warm-up has lasted WARMUP_S, then EXACTLY --steps timed
+frames between two fences (synchronize + barrier on both sides, max over ranks); ms_per_step is that window over --steps.
+
+--dump-outputs DIR: after the timed frames, the frame the last one handed to the caller is written as float32 .npy files
+(dump_outputs below); the inputs are seeded, so two builds run with the same arguments can be compared file for file.
 
 Prints ONE JSON line on rank 0.  Extra keys: roofline (tile kernel, HBM bound), cpu_baseline (the
 CPU oracle timed on this host), frames_per_s, rasterized_fragments_per_s, kernel_ms.
@@ -28,17 +31,14 @@ import os
 import sys
 import time
 
-# The HIP runtime maps a process's streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default), and streams that
-# share one run their work in order.  A rank uses the caller's stream, the library's stage-1 stream and what the
-# collective library creates: give them room, so that stage 1 never shares a queue with the tile kernel it should overlap
-# (set before the runtime starts; an operator's own setting wins).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as g  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec
+WARMUP_S = 1.0  # least wall time of untimed frames before the timed ones: the GPU's clocks settle over a fraction of a second of load
+DUMP_PIXELS = 1 << 21  # --dump-outputs: at most this many pixels, 28 B each in the files (56 MiB)
+DUMP_SEED = 0x53565244
 
 
 def parse():
@@ -61,9 +61,13 @@ def parse():
     ap.add_argument("--partition", default="auto", choices=["auto", "bands", "interleaved"],
                     help="N > 1: contiguous row bands, interleaved tile rows (t %% N == rank), or whichever a short trial of both finds faster")
     ap.add_argument("--cpu-frames", type=int, default=10)
-    ap.add_argument("--blocks", type=int, default=25, help="repetitions of the timed --steps block (the median block is reported)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame of the last timed step to DIR/<name>.npy (float32; a fixed sample of pixels above 2^21)")
     ap.add_argument("--profile-tag", default="r03_h", help="profiles/<tag>_traffic.json and <tag>_valu.json of this build are quoted in the line")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_cores():
@@ -143,6 +147,22 @@ def camera_of(args, S):
         v = [float(x) for x in args.camera.split(",")]
         return (v[0], v[1], v[2]), v[3], v[4]
     return S.config5_camera() if args.instances == 16 else S.config3_camera()
+
+
+def dump_outputs(torch, slot, W, H, out_dir, depth):
+    """The frame a caller holds after the last timed step, as float32: color.npy (the slot's image: the RGBA16F target,
+    or with --gpus N > 1 the exchanged B8G8R8A8 swapchain image) and on one GPU depth.npy (the D32 target).  Above
+    DUMP_PIXELS pixels, a fixed seeded sample of pixels; pixel_index.npy (float64) holds row * W + column of each."""
+    import numpy as np
+    n = W * H
+    idx = np.arange(n) if n <= DUMP_PIXELS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_PIXELS, replace=False))
+    sel = torch.from_numpy(idx).to(slot.image_t.device)
+    arrays = {"pixel_index": idx.astype(np.float64), "color": slot.image_t[:H].reshape(n, 4)[sel].float().cpu().numpy()}
+    if depth:
+        arrays["depth"] = slot.depth[:H].reshape(n)[sel].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -229,6 +249,7 @@ def main():
     r.set_option(A.OPT_COUNT_FRAGMENTS, 0)
 
     note(f"instrumented frame done: {shaded} shaded fragments")
+    t_warm = time.perf_counter()
     for _ in range(args.warmup):
         frame()
     fence()
@@ -253,35 +274,35 @@ def main():
         for _ in range(args.warmup):
             frame()
         fence()
-    r.set_option(A.OPT_KERNEL_TIMING, 1)
-
-    def block():
-        """EXACTLY --steps frames between two fences (barrier + synchronize on both sides), max over ranks."""
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
+    # top the warm-up up to WARMUP_S in fenced chunks of frames; rank 0's clock decides, so every rank runs as many
+    warm_added = 0
+    while True:
+        go = torch.tensor([time.perf_counter() - t_warm < WARMUP_S], dtype=torch.int32, device=dev)
+        if world > 1:
+            dist.broadcast(go, 0)
+        if not int(go.item()):
+            break
+        for _ in range(16):
             frame()
         fence()
-        t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-        if world > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return float(t.item())
+        warm_added += 16
+    note(f"warm-up topped up by {warm_added} frames")
+    r.set_option(A.OPT_KERNEL_TIMING, 1)
 
-    # SURVEY 8d protocol: the block is repeated (>= 25 times and >= 0.5 s in all, at most 400 times) and the MEDIAN
-    # block is the reported one, with p10 / p90 beside it: one block of a few milliseconds is at the mercy of
-    # whatever else the box does in that instant.  Every rank runs the same number of blocks (rank 0 decides).
-    first = block()
-    n_blocks = int(min(400, max(args.blocks, 0.5 / max(first, 1e-6))))
-    nb = torch.tensor([n_blocks], dtype=torch.int64, device=dev)
+    # the timed window: EXACTLY --steps frames between two fences (barrier + synchronize on both sides), max over ranks
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        frame()
+    fence()
+    t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
     if world > 1:
-        dist.broadcast(nb, 0)
-    n_blocks = int(nb.item())
-    note(f"first block {first * 1e3:.2f} ms, {n_blocks} blocks to go")
-    times = sorted([first] + [block() for _ in range(n_blocks - 1)])
-    note(f"timed blocks done, rows {plan.bounds}")
-    pick = lambda q: times[min(len(times) - 1, max(0, int(round(q * (len(times) - 1)))))]
-    dt, dt_p10, dt_p90 = pick(0.5), pick(0.1), pick(0.9)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    dt = float(t.item())
+    note(f"timed frames done, rows {plan.bounds}")
     st = r.get_stats()
     r.set_option(A.OPT_KERNEL_TIMING, 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, slots[(state["i"] - 1) & 1], W, H, args.dump_outputs, depth=world == 1)
 
     if rank == 0:
         fps = args.steps / dt
@@ -308,8 +329,7 @@ def main():
         achieved = tile_bytes / tile_s / 1e9 if tile_s > 0 else 0.0
         out = {
             "metric": "shaded fragments/s", "value": shaded * fps, "unit": "fragments/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "ms_per_step_p10": dt_p10 / args.steps * 1e3, "ms_per_step_p90": dt_p90 / args.steps * 1e3, "timed_blocks": len(times),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_frames_added": warm_added, "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": (f"glTF file {os.path.basename(args.gltf)}, {counts_scene['triangles']} triangles, {W}x{H}, RGBA16F+D32,"

@@ -2,11 +2,12 @@
 """Records the facts the oracle's restatement of the shaders relies on, read from the reference's COMMITTED
 SPIR-V (shaders/*.spv, what a Vulkan driver would actually run), into tests/golden/spv_facts.json.
 
-Runs in the container only (it reads /root/reference); tests/test_spv_facts.py checks the recorded facts
-against the constants of the arithmetic contract and, where the reference tree is
-present, re-derives them.  This pins nothing numerically — the draw path stays "parity unpinned" — it stops the
-restatement from drifting away from the shaders' structure: operation order of the vertex transform, which
-uniform member scales the light, the clamp constant, the absence of NoContraction, the vertex layout.
+Runs where the reference tree is (it reads its shaders/*.spv); tests/test_spv_facts.py checks the recorded facts
+against the constants of the arithmetic contract.  Rerunning this script and finding no
+difference in the file shows the recorded facts still match the reference.  This pins nothing numerically — the
+draw path stays "parity unpinned" — it stops the restatement from drifting away from the shaders' structure:
+operation order of the vertex transform, which uniform member scales the light, the clamp constant, the absence of
+NoContraction, the vertex layout.
 
     python tests/golden/make_spv_facts.py
 """

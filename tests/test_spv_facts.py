@@ -3,7 +3,6 @@ tests/golden/make_spv_facts.py in the container) against what the oracle and the
 of mesh.vert's transform (contract C0/C1), the uniform member that scales the light and the clamp constant of
 mesh.frag (C10), the vertex and uniform layouts (include/svr.h), no NoContraction anywhere (fma allowed, which the
 contract uses).  Structure only: it does not pin a single pixel — the draw path stays "parity unpinned"."""
-import importlib.util
 import json
 import os
 
@@ -78,13 +77,3 @@ def test_oracle_shades_with_the_members_the_spirv_reads(oracle):
     base = render(1.0, 1.0)
     assert np.array_equal(base, render(123.0, 1.0)) and np.array_equal(base, render(1.0, 0.25))
 
-
-def test_facts_file_matches_the_reference_tree_when_it_is_here():
-    if not os.path.isdir("/root/reference/shaders"):
-        return  # the GPU box: the committed file is all there is
-    spec = importlib.util.spec_from_file_location("make_spv_facts", os.path.join(T.GOLDEN_DIR, "make_spv_facts.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    d = facts()
-    for s in m.SHADERS:
-        assert json.loads(json.dumps(m.facts(s))) == d[s], s
