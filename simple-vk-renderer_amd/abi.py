@@ -85,6 +85,10 @@ SYMBOLS = ["svr_create", "svr_destroy", "svr_set_stream", "svr_bind_targets", "s
            "svr_set_scissor", "svr_set_row_interleave", "svr_set_present_status", "svr_draw_geometry", "svr_draw_colored_triangle", "svr_draw_tex_image",
            "svr_run_mesh_vert", "svr_run_vertex_shader", "svr_set_option", "svr_debug_trace_pixel", "svr_debug_read_trace", "svr_debug_read_bins", "svr_debug_read_tile_cycles", "svr_debug_rcp_sweep", "svr_get_row_costs", "svr_sync", "svr_read_color", "svr_read_depth", "svr_get_stats",
            "svr_last_error", "svr_backend_name"]
+# include/svr_draw_list.h: retained draw lists, HIP library only (the oracle exports exactly SYMBOLS)
+DRAW_LIST_SYMBOLS = ["svr_create_draw_list", "svr_update_draw_list", "svr_destroy_draw_list", "svr_draw_list",
+                     "svr_debug_read_records"]
+DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
 class SvrError(RuntimeError):
@@ -150,6 +154,13 @@ class SvrLib:
         L.svr_read_color.argtypes = [P, P, C.c_size_t, C.c_int]
         L.svr_read_depth.argtypes = [P, P, C.c_size_t]
         L.svr_get_stats.argtypes = [P, C.POINTER(SvrStats)]
+        self.has_draw_lists = hasattr(L, "svr_create_draw_list")
+        if self.has_draw_lists:
+            L.svr_create_draw_list.argtypes = [P, P, C.c_size_t, P, C.c_size_t, C.POINTER(C.c_uint32)]
+            L.svr_update_draw_list.argtypes = [P, C.c_uint32, C.c_size_t, P, C.c_size_t]
+            L.svr_destroy_draw_list.argtypes = [P, C.c_uint32]
+            L.svr_draw_list.argtypes = [P, C.c_uint32, C.POINTER(SvrSceneData), C.POINTER(SvrStats)]
+            L.svr_debug_read_records.argtypes = [P, P, C.c_size_t, P, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 
     @property
     def backend(self):
@@ -318,6 +329,39 @@ class Renderer:
         self.lib.check(self.lib.lib.svr_draw_geometry(self.h, C.byref(scene), op, n_op, tr, n_tr, C.byref(st)))
         return st
 
+    # -- retained draw lists (include/svr_draw_list.h)
+    def _need_draw_lists(self):
+        if not self.lib.has_draw_lists:
+            raise SvrError(-5, f"{self.lib.backend} has no draw lists (include/svr_draw_list.h)")
+
+    def create_draw_list(self, opaque, transparent=None):
+        """A DrawList holding copies of the two RenderObject arrays in device memory."""
+        self._need_draw_lists()
+        op = np.ascontiguousarray(opaque if opaque is not None else np.zeros(0, RENDER_OBJECT_DTYPE), dtype=RENDER_OBJECT_DTYPE)
+        tr = np.ascontiguousarray(transparent if transparent is not None else np.zeros(0, RENDER_OBJECT_DTYPE), dtype=RENDER_OBJECT_DTYPE)
+        out = C.c_uint32()
+        self.lib.check(self.lib.lib.svr_create_draw_list(self.h, op.ctypes.data, op.size, tr.ctypes.data, tr.size, C.byref(out)))
+        return DrawList(self, out.value, op.size, tr.size)
+
+    def draw_list(self, scene, lst):
+        """svr_draw_geometry over the list's objects; the three counts arrive with the pass (get_stats)."""
+        st = SvrStats()
+        handle = lst.handle if isinstance(lst, DrawList) else int(lst)
+        self.lib.check(self.lib.lib.svr_draw_list(self.h, handle, C.byref(scene), C.byref(st)))
+        return st
+
+    def read_records(self):
+        """(DrawDesc records [n, 192] uint8, WaveChunk records [n, 2] uint32) the last pass ran with (fences)."""
+        self._need_draw_lists()
+        nd, nc = C.c_uint32(), C.c_uint32()
+        L = self.lib.lib
+        self.lib.check(L.svr_debug_read_records(self.h, None, 0, None, 0, C.byref(nd), C.byref(nc)))
+        draws = np.zeros((nd.value, DRAW_DESC_BYTES), dtype=np.uint8)
+        chunks = np.zeros((nc.value, 2), dtype=np.uint32)
+        self.lib.check(L.svr_debug_read_records(self.h, draws.ctypes.data, draws.nbytes, chunks.ctypes.data, chunks.nbytes,
+                                                C.byref(nd), C.byref(nc)))
+        return draws, chunks
+
     def draw_colored_triangle(self):
         st = SvrStats()
         self.lib.check(self.lib.lib.svr_draw_colored_triangle(self.h, C.byref(st)))
@@ -406,3 +450,26 @@ class Renderer:
         st = SvrStats()
         self.lib.check(self.lib.lib.svr_get_stats(self.h, C.byref(st)))
         return st
+
+
+class DrawList:
+    """A retained RenderObject list of one Renderer (svr_create_draw_list): opaque objects, then transparent ones."""
+
+    def __init__(self, renderer, handle, n_opaque, n_transparent):
+        self.renderer, self.handle = renderer, handle
+        self.n_opaque, self.n_transparent = int(n_opaque), int(n_transparent)
+
+    def __len__(self):
+        return self.n_opaque + self.n_transparent
+
+    def update(self, first, objects):
+        """replace objects first .. first + len(objects) - 1 (indices over the opaque list, then the transparent one)"""
+        a = np.ascontiguousarray(objects, dtype=RENDER_OBJECT_DTYPE).reshape(-1)
+        r = self.renderer
+        r.lib.check(r.lib.lib.svr_update_draw_list(r.h, self.handle, int(first), a.ctypes.data, a.size))
+
+    def close(self):
+        r = self.renderer
+        if self.handle and r.h:
+            r.lib.check(r.lib.lib.svr_destroy_draw_list(r.h, self.handle))
+        self.handle = 0

@@ -93,7 +93,8 @@ __global__ __launch_bounds__(256) void cull_kernel(FlattenParams F) {
   }
 }
 
-__device__ __forceinline__ void write_draw(const FlattenParams& F, uint32_t slot, const SvrRenderObject& o) {
+// the draw record of one object (tri_base is left 0: the scans fill it in)
+__device__ __forceinline__ DrawDesc make_draw(const FlattenParams& F, const SvrRenderObject& o) {
   const MeshEntry me = F.meshes[o.mesh - 1];
   const MatEntry ma = F.materials[o.material - 1];
   DrawDesc d;
@@ -108,9 +109,14 @@ __device__ __forceinline__ void write_draw(const FlattenParams& F, uint32_t slot
   d.first_index = o.first_index;
   d.pad = 0;
   d.tri_count = o.index_count / 3u;
-  d.tri_base = 0;  // prefix_kernel
+  d.tri_base = 0;
   d.tex = o.material - 1u;
   d.flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (ma.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u);
+  return d;
+}
+
+__device__ __forceinline__ void write_draw(const FlattenParams& F, uint32_t slot, const SvrRenderObject& o) {
+  const DrawDesc d = make_draw(F, o);  // tri_base: prefix_kernel
   F.draws[slot] = d;
   F.draw_tris[slot] = d.tri_count;
   F.chunk_base[slot] = chunk_count(d.first_index, d.tri_count);  // the count for now: prefix_kernel turns it into the base
@@ -212,6 +218,105 @@ __global__ __launch_bounds__(256) void chunks_kernel(FlattenParams F) {
   }
 }
 
+// make_draw stored column by column (the same bytes): a whole DrawDesc in registers beside the scans of list_kernel
+// does not fit its 128 VGPRs
+__device__ __forceinline__ void store_draw(const FlattenParams& F, const float* viewproj, uint32_t slot, const SvrRenderObject& o, uint32_t tri_base) {
+  const MeshEntry me = F.meshes[o.mesh - 1];
+  const MatEntry ma = F.materials[o.material - 1];
+  DrawDesc* d = F.draws + slot;
+  for (int j = 0; j < 4; j++) {
+    const float x = o.transform[4 * j + 0], y = o.transform[4 * j + 1], z = o.transform[4 * j + 2], w = o.transform[4 * j + 3];
+    float col[4];
+    matvec4(viewproj, x, y, z, w, col);  // C0: column j of matmul4(viewproj, mat)
+    reinterpret_cast<float4*>(d->mat)[j] = make_float4(x, y, z, w);
+    reinterpret_cast<float4*>(d->mvp)[j] = make_float4(col[0], col[1], col[2], col[3]);
+  }
+  reinterpret_cast<float4*>(d->color_factors)[0] = make_float4(ma.cf[0], ma.cf[1], ma.cf[2], ma.cf[3]);
+  d->vtx = me.vtx;
+  d->idx = me.idx + o.first_index;
+  d->tri_count = o.index_count / 3u;
+  d->tri_base = tri_base;
+  d->tex = o.material - 1u;
+  d->flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (ma.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u);
+  d->groups = me.groups;
+  d->first_index = o.first_index;
+  d->pad = 0;
+}
+
+// A resident draw list (svr_draw_list, svr_api.hip) in one launch.  The list lies in device memory in DRAW ORDER: its
+// opaque objects were sorted by (material, mesh, submission index) when it was made or updated — the key does not
+// depend on the camera — then come its transparent objects in submission order.  The slot of a visible object is then
+// the number of visible objects in front of it, so cull, rank, the two scans and the records are one pass over the
+// list: a round takes 1024 objects, a lane each (is_visible_dev; transparent objects are never culled), scans
+// (visible, triangles, wave chunks) over the workgroup through LDS, and every visible lane writes its DrawDesc and
+// WaveChunks at the bases it found.  Same records as the host path stages (and as the four kernels above).
+__global__ __launch_bounds__(1024) void list_kernel(FlattenParams F) {
+  __shared__ uint32_t s_sum[3][16];
+  __shared__ float s_vp[16];  // viewproj from LDS: held in SGPRs for both of its uses it spilled 32 of them
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const uint32_t n_all = F.n_opaque + F.n_transparent;
+  if (tid < 16) s_vp[tid] = F.viewproj[tid];
+  __syncthreads();
+  uint32_t base_v = 0, base_t = 0, base_c = 0;  // totals of the rounds before
+  for (uint32_t r0 = 0; r0 < n_all; r0 += 1024u) {
+    const uint32_t i = r0 + tid;
+    bool vis = false;
+    uint32_t tri = 0, chk = 0, fi = 0;
+    if (i < n_all) {
+      const SvrRenderObject& o = F.objects[i];
+      vis = i >= F.n_opaque || is_visible_dev(o, s_vp);
+      if (vis) {
+        fi = o.first_index;
+        tri = o.index_count / 3u;
+        chk = chunk_count(fi, tri);
+      }
+    }
+    uint32_t iv = vis ? 1u : 0u, it = tri, ic = chk;  // inclusive scans within the wave
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t a = __shfl_up(iv, off), b = __shfl_up(it, off), c = __shfl_up(ic, off);
+      if ((int)lane >= off) {
+        iv += a;
+        it += b;
+        ic += c;
+      }
+    }
+    if (lane == 63) {
+      s_sum[0][wv] = iv;
+      s_sum[1][wv] = it;
+      s_sum[2][wv] = ic;
+    }
+    __syncthreads();
+    uint32_t bv = base_v, bt = base_t, bc = base_c;
+    for (uint32_t w = 0; w < 16; w++) {
+      if (w < wv) {
+        bv += s_sum[0][w];
+        bt += s_sum[1][w];
+        bc += s_sum[2][w];
+      }
+      base_v += s_sum[0][w];
+      base_t += s_sum[1][w];
+      base_c += s_sum[2][w];
+    }
+    __syncthreads();  // s_sum is rewritten by the next round
+    if (vis) {
+      const uint32_t slot = bv + iv - 1u, cb = bc + ic - chk;
+      store_draw(F, s_vp, slot, F.objects[i], bt + it - tri);
+      for (uint32_t c = 0; c < chk; c++) {
+        WaveChunk ch;
+        ch.draw = slot;
+        ch.first_tri = chunk_first(fi, c);
+        F.chunks[cb + c] = ch;
+      }
+    }
+  }
+  if (tid == 0) {
+    F.counters->flat_draws = base_v;
+    F.counters->flat_tris = base_t;
+    F.counters->flat_chunks = base_c;
+    F.counters->flat_culled = F.n_opaque - (base_v - F.n_transparent);
+  }
+}
+
 void launch_flatten(const FlattenParams& F, hipStream_t s) {
   const uint32_t n_all = F.n_opaque + F.n_transparent;
   if (n_all == 0) return;
@@ -219,6 +324,15 @@ void launch_flatten(const FlattenParams& F, hipStream_t s) {
   hipLaunchKernelGGL(rank_kernel, dim3((F.n_opaque + 15u) / 16u + (F.n_transparent + 255u) / 256u), dim3(256), 0, s, F);
   hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, s, F);
   hipLaunchKernelGGL(chunks_kernel, dim3((n_all + 255u) / 256u), dim3(256), 0, s, F);
+}
+
+void launch_list_flatten(const FlattenParams& F, hipStream_t s) {
+  const uint32_t n_all = F.n_opaque + F.n_transparent;
+  if (n_all == 0) return;
+  if (n_all <= LIST_FUSED_MAX)
+    hipLaunchKernelGGL(list_kernel, dim3(1), dim3(1024), 0, s, F);
+  else
+    launch_flatten(F, s);  // F.objects is the resident copy: cull_kernel pulls it into the set's scratch like host memory
 }
 
 }  // namespace svr

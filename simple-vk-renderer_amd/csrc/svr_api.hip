@@ -17,9 +17,12 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <memory>
+#include <numeric>
 #include <string>
 #include <vector>
 
+#include "../../include/svr_draw_list.h"
 #include "svr_cull.h"
 #include "svr_launch.h"
 
@@ -81,6 +84,28 @@ struct MaterialRes {
   uint32_t image, sampler;  // 0-based
 };
 
+// One version of a draw list's device copy (include/svr_draw_list.h).  Copy-on-write: svr_update_draw_list makes a
+// new one, and the list and every logged pass that was enqueued with this one share it; the last to let go frees it
+// (a pass lets go when it is validated, after its completion event — or after its replay).
+struct ListVersion {
+  SvrRenderObject* dev = nullptr;  // DRAW ORDER: opaque objects sorted by (material, mesh, submission index), then the transparent ones
+  uint32_t n_opaque = 0, n_transparent = 0;
+  uint64_t tris_max = 0;  // upper bounds that size the pass's buffers and grids (every object visible)
+  size_t chunks_max = 0;
+  ~ListVersion() {
+    if (dev) (void)hipFree(dev);
+  }
+};
+struct DrawListRes {
+  std::vector<SvrRenderObject> objs;  // submission order: opaque list, then transparent list
+  uint32_t n_opaque = 0;
+  std::shared_ptr<const ListVersion> cur;
+  uint64_t mesh_epoch = 0;  // SvrContext::mesh_epoch when the objects were last validated
+  bool valid = false;       // ... and whether they were valid then
+  std::string why;          // if not: validate_object's text
+  bool alive = false;
+};
+
 // software fp32 -> fp16 (RTE) for the one clear colour the host encodes
 uint16_t host_f32_to_f16(float f) {
   uint32_t x;
@@ -120,6 +145,8 @@ struct SvrContext {
   std::vector<ImageRes> images;
   std::vector<SvrSamplerDesc> samplers;
   std::vector<MaterialRes> materials;
+  std::vector<DrawListRes> lists;  // svr_create_draw_list
+  uint64_t mesh_epoch = 0;         // counts svr_destroy_mesh calls: a draw list re-validates when it has moved
   // Texel arena: every image of the context lives in ONE allocation, so a texel's address is a 32-bit byte
   // offset from one wave-uniform base (FrameParams::tex_arena): the fragment stage's eight gathers per pixel
   // are global loads with an SGPR base and a 32-bit VGPR offset instead of 64-bit pointer arithmetic per tap,
@@ -173,6 +200,8 @@ struct SvrContext {
     // device-flattened pass: the caller's objects (opaque, then transparent) instead of a draw list
     std::vector<SvrRenderObject> objects;
     uint32_t n_opaque_obj = 0, n_transparent_obj = 0;
+    // ... or the version of a resident draw list it was enqueued with (svr_draw_list): the objects stay on the device
+    std::shared_ptr<const ListVersion> list;
   };
   std::deque<LoggedOp> log;
   hipEvent_t op_done[MAX_OPS] = {};
@@ -215,6 +244,7 @@ struct SvrContext {
   double acc_ms[3] = {0, 0, 0};
   uint32_t acc_n = 0;
   FrameParams last{};        // parameters of the pass enqueued last (debug read-backs)
+  uint32_t last_n_draws = 0;  // ... and its draw count, if the host staged its records (svr_debug_read_records)
   bool instrument = false;
   bool tile_cycles = false;
   uint32_t tuning = 0;
@@ -464,7 +494,8 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
     ctx->last_g = g;
   }
   // per-pass inputs: draws + chunks through pinned staging, one copy
-  const size_t n_objects = flat_op ? flat_op->objects.size() : 0;
+  const bool resident = flat_op && flat_op->list;  // the objects are a draw list's device copy: nothing to stage
+  const size_t n_objects = flat_op ? (size_t)flat_op->n_opaque_obj + flat_op->n_transparent_obj : 0;
   size_t draw_bytes = (flat_op ? n_objects : draws.size()) * sizeof(DrawDesc), chunk_bytes = (size_t)P.n_chunks * sizeof(WaveChunk);
   if (int e = set.inputs.ensure(std::max<size_t>(draw_bytes + chunk_bytes + 16, 256))) return e;
   if (flat_op)
@@ -481,12 +512,12 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
     else if (set.used) HIPCHK(hipStreamWaitEvent(g, set.ev_tile, 0));
   }
   void* stage = nullptr;
-  if (int e = stage_buffer(ctx, op_slot, (flat_op ? n_objects * sizeof(SvrRenderObject) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
+  if (int e = stage_buffer(ctx, op_slot, (flat_op ? (resident ? 0 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
   P.host_counters = &ctx->h_counters[op_slot];
   P.host_row_cost = ctx->h_row_cost + (size_t)op_slot * ROW_COST_MAX;
   P.op_seq = seq;
   if (flat_op) {  // the objects themselves are the input; cull, sort, draw records and chunks happen on the device
-    std::memcpy(stage, flat_op->objects.data(), n_objects * sizeof(SvrRenderObject));
+    if (!resident) std::memcpy(stage, flat_op->objects.data(), n_objects * sizeof(SvrRenderObject));
   } else {
     std::memcpy(stage, draws.data(), draw_bytes);
     WaveChunk* ch = reinterpret_cast<WaveChunk*>((char*)stage + draw_bytes);
@@ -515,7 +546,7 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
   if (flat_op) {
     FlattenParams F;
     std::memset(&F, 0, sizeof(F));
-    F.objects = (const SvrRenderObject*)stage;
+    F.objects = resident ? flat_op->list->dev : (const SvrRenderObject*)stage;
     F.n_opaque = flat_op->n_opaque_obj;
     F.n_transparent = flat_op->n_transparent_obj;
     std::memcpy(F.viewproj, P.scene.viewproj, 64);
@@ -528,7 +559,10 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
     F.draws = (DrawDesc*)set.inputs.p;
     F.chunks = (WaveChunk*)((char*)set.inputs.p + draw_bytes);
     F.counters = P.counters;
-    launch_flatten(F, g);
+    if (resident)
+      launch_list_flatten(F, g);
+    else
+      launch_flatten(F, g);
   }
   const bool all_stages = ctx->kernel_timing >= 2;
   if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][0], g));
@@ -552,6 +586,7 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
   set.ev_tile = ctx->op_done[op_slot];
   set.used = true;
   ctx->last = P;
+  ctx->last_n_draws = flat_op ? 0u : (uint32_t)draws.size();
   return SVR_OK;
 }
 
@@ -870,8 +905,10 @@ int upload_flatten_tables(SvrContext* ctx) {
 
 // draw_geometry with cull, sort and the draw records left to the device (k_flatten.hip): the host only
 // validates, sums the upper bounds that size buffers and grids, and hands the objects over.
+// list: a resident draw list's version instead of the two arrays (svr_draw_list)
 int run_pass_flatten(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque,
-                     const SvrRenderObject* transparent, size_t n_transparent, uint64_t tris_max, size_t chunks_max) {
+                     const SvrRenderObject* transparent, size_t n_transparent, uint64_t tris_max, size_t chunks_max,
+                     const std::shared_ptr<const ListVersion>& list = nullptr) {
   if (int e = poll_pending(ctx)) return e;
   if (int e = upload_flatten_tables(ctx)) return e;
   FrameParams P;
@@ -891,11 +928,17 @@ int run_pass_flatten(SvrContext* ctx, const SvrSceneData* scene, const SvrRender
   op.slot = slot;
   op.timed = ctx->kernel_timing == 1;
   op.P = P;
-  op.objects.reserve(n_opaque + n_transparent);
-  op.objects.insert(op.objects.end(), opaque, opaque + n_opaque);
-  op.objects.insert(op.objects.end(), transparent, transparent + n_transparent);
-  op.n_opaque_obj = (uint32_t)n_opaque;
-  op.n_transparent_obj = (uint32_t)n_transparent;
+  if (list) {
+    op.list = list;
+    op.n_opaque_obj = list->n_opaque;
+    op.n_transparent_obj = list->n_transparent;
+  } else {
+    op.objects.reserve(n_opaque + n_transparent);
+    op.objects.insert(op.objects.end(), opaque, opaque + n_opaque);
+    op.objects.insert(op.objects.end(), transparent, transparent + n_transparent);
+    op.n_opaque_obj = (uint32_t)n_opaque;
+    op.n_transparent_obj = (uint32_t)n_transparent;
+  }
   std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
   if (int e = submit_pass(ctx, op.P, op.draws, slot, op.seq, !(ctx->tuning & TUNE_NO_PIPELINE), &op)) {
     ctx->log.pop_back();
@@ -1114,6 +1157,7 @@ int svr_destroy_mesh(SvrContext* ctx, SvrMesh mesh) {
   m->idx = nullptr;
   m->groups = nullptr;
   m->alive = false;
+  ctx->mesh_epoch++;  // draw lists that name it fail at their next svr_draw_list
   return SVR_OK;
 }
 
@@ -1358,20 +1402,22 @@ int svr_set_present_status(SvrContext* ctx, uint32_t* status_dev) {
   return SVR_OK;
 }
 
-static int validate_object(SvrContext* ctx, const SvrRenderObject& o, bool transparent_list) {
+// who: the entry point the texts name (svr_draw_geometry, or the draw-list calls that apply the same rules)
+static int validate_object(SvrContext* ctx, const SvrRenderObject& o, bool transparent_list, const char* who = "svr_draw_geometry") {
   const char* which = transparent_list ? "transparent" : "opaque";
+  const std::string fn(who);
   MeshRes* m = get_mesh(ctx, o.mesh);
-  if (!m) return fail(SVR_ERR_BAD_HANDLE, std::string("svr_draw_geometry: bad mesh handle in ") + which);
+  if (!m) return fail(SVR_ERR_BAD_HANDLE, fn + ": bad mesh handle in " + which);
   if (o.material == 0 || o.material > ctx->materials.size())
-    return fail(SVR_ERR_BAD_HANDLE, std::string("svr_draw_geometry: bad material handle in ") + which);
+    return fail(SVR_ERR_BAD_HANDLE, fn + ": bad material handle in " + which);
   if ((uint64_t)o.first_index + o.index_count > m->n_idx)
-    return fail(SVR_ERR_INVALID_ARGUMENT, std::string("svr_draw_geometry: index range outside the mesh in ") + which);
+    return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": index range outside the mesh in " + which);
   // MeshNode::Draw routes by pass_type (src/vk_engine.cpp:1729-1733)
   bool is_tr = ctx->materials[o.material - 1].pass == SVR_PASS_TRANSPARENT;
   if (is_tr && !transparent_list)
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_geometry: Transparent material in the opaque list");
+    return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": Transparent material in the opaque list");
   if (!is_tr && transparent_list)
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_geometry: non-Transparent material in the transparent list");
+    return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": non-Transparent material in the transparent list");
   return SVR_OK;
 }
 
@@ -1757,6 +1803,171 @@ int svr_get_stats(SvrContext* ctx, SvrStats* out) {
     out->binning_ms = (float)(ctx->acc_ms[1] / ctx->acc_n);
     out->tile_ms = (float)(ctx->acc_ms[2] / ctx->acc_n);
     out->gpu_time_ms = out->geometry_ms + out->binning_ms + out->tile_ms;
+  }
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- retained draw lists (include/svr_draw_list.h)
+static DrawListRes* get_list(SvrContext* ctx, SvrDrawList h) {
+  if (h == 0 || h > ctx->lists.size() || !ctx->lists[h - 1].alive) return nullptr;
+  return &ctx->lists[h - 1];
+}
+
+// validate_object over the whole list; records the outcome against the current mesh epoch
+static int check_list_objects(SvrContext* ctx, DrawListRes& L, const char* who) {
+  int e = SVR_OK;
+  for (size_t i = 0; i < L.objs.size() && e == SVR_OK; i++) e = validate_object(ctx, L.objs[i], i >= L.n_opaque, who);
+  L.mesh_epoch = ctx->mesh_epoch;
+  L.valid = e == SVR_OK;
+  L.why = L.valid ? std::string() : g_err;
+  return e;
+}
+
+// a new device version of the list's objects: opaque in draw order (the host path's stable sort by (material, mesh),
+// over all of them — culling a subset keeps its order), then transparent; blocking copy into fresh memory, so no pass
+// in flight can see it half written
+static int make_list_version(const DrawListRes& L, std::shared_ptr<const ListVersion>* out) {
+  auto v = std::make_shared<ListVersion>();
+  const size_t n = L.objs.size();
+  v->n_opaque = L.n_opaque;
+  v->n_transparent = (uint32_t)(n - L.n_opaque);
+  std::vector<uint32_t> order(L.n_opaque);
+  std::iota(order.begin(), order.end(), 0u);
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t ia, uint32_t ib) {
+    const SvrRenderObject& a = L.objs[ia];
+    const SvrRenderObject& b = L.objs[ib];
+    if (a.material == b.material) return a.mesh < b.mesh;
+    return a.material < b.material;
+  });
+  std::vector<SvrRenderObject> sorted;
+  sorted.reserve(n);
+  for (uint32_t i : order) sorted.push_back(L.objs[i]);
+  sorted.insert(sorted.end(), L.objs.begin() + L.n_opaque, L.objs.end());
+  for (const SvrRenderObject& o : sorted) {
+    const uint32_t t = o.index_count / 3u;
+    v->tris_max += t;
+    v->chunks_max += chunk_count(o.first_index, t);
+  }
+  if (n) {
+    HIPCHK(hipMalloc((void**)&v->dev, n * sizeof(SvrRenderObject)));
+    HIPCHK(hipMemcpy(v->dev, sorted.data(), n * sizeof(SvrRenderObject), hipMemcpyHostToDevice));
+  }
+  *out = std::move(v);
+  return SVR_OK;
+}
+
+constexpr size_t LIST_MAX_OBJECTS = 16384;  // the device flatten's bound (svr_draw_geometry's `fits`)
+
+int svr_create_draw_list(SvrContext* ctx, const SvrRenderObject* opaque, size_t n_opaque, const SvrRenderObject* transparent,
+                         size_t n_transparent, SvrDrawList* out) {
+  if (!ctx || !out || (!opaque && n_opaque) || (!transparent && n_transparent))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_create_draw_list: null argument");
+  if (n_opaque > LIST_MAX_OBJECTS || n_transparent > LIST_MAX_OBJECTS - n_opaque)
+    return fail(SVR_ERR_UNSUPPORTED, "svr_create_draw_list: more than 16384 objects in one list");
+  DrawListRes L;
+  L.n_opaque = (uint32_t)n_opaque;
+  L.objs.reserve(n_opaque + n_transparent);
+  L.objs.insert(L.objs.end(), opaque, opaque + n_opaque);
+  L.objs.insert(L.objs.end(), transparent, transparent + n_transparent);
+  if (int e = check_list_objects(ctx, L, "svr_create_draw_list")) return e;
+  if (int e = use_device(ctx)) return e;
+  if (int e = make_list_version(L, &L.cur)) return e;
+  L.alive = true;
+  ctx->lists.push_back(std::move(L));
+  *out = (SvrDrawList)ctx->lists.size();
+  return SVR_OK;
+}
+
+int svr_update_draw_list(SvrContext* ctx, SvrDrawList list, size_t first, const SvrRenderObject* objs, size_t n) {
+  if (!ctx || (!objs && n)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_update_draw_list: null argument");
+  DrawListRes* L = get_list(ctx, list);
+  if (!L) return fail(SVR_ERR_BAD_HANDLE, "svr_update_draw_list: bad list handle");
+  if (first > L->objs.size() || n > L->objs.size() - first)
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_update_draw_list: objects beyond the end of the list");
+  for (size_t k = 0; k < n; k++)
+    if (int e = validate_object(ctx, objs[k], first + k >= L->n_opaque, "svr_update_draw_list")) return e;
+  if (n == 0) return SVR_OK;
+  if (int e = use_device(ctx)) return e;
+  DrawListRes next;  // copy-on-write: passes in flight keep the version they hold
+  next.n_opaque = L->n_opaque;
+  next.objs = L->objs;
+  std::copy(objs, objs + n, next.objs.begin() + (long)first);
+  if (int e = make_list_version(next, &next.cur)) return e;
+  L->objs.swap(next.objs);
+  L->cur = std::move(next.cur);
+  (void)check_list_objects(ctx, *L, "svr_draw_list");  // objects it did not replace may still name a destroyed mesh
+  return SVR_OK;
+}
+
+int svr_destroy_draw_list(SvrContext* ctx, SvrDrawList list) {
+  DrawListRes* L = ctx ? get_list(ctx, list) : nullptr;
+  if (!L) return fail(SVR_ERR_BAD_HANDLE, "svr_destroy_draw_list: bad list handle");
+  if (int e = use_device(ctx)) return e;
+  L->alive = false;
+  L->cur.reset();  // the device copy goes with the last pass that holds it
+  std::vector<SvrRenderObject>().swap(L->objs);
+  return SVR_OK;
+}
+
+// Per pass the host checks the handle and the mesh epoch, and enqueues the pass of svr_draw_geometry's device
+// flatten with the list's current version (run_pass_flatten): no per-object loop.
+int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
+  if (!ctx || !scene) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list: null argument");
+  auto t0 = std::chrono::steady_clock::now();
+  DrawListRes* L = get_list(ctx, list);
+  if (!L) return fail(SVR_ERR_BAD_HANDLE, "svr_draw_list: bad list handle");
+  if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, "svr_draw_list");  // a mesh was destroyed since
+  if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list: the list is no longer valid (" + L->why + ")");
+  if (int e = use_device(ctx)) return e;
+  if (owned_tile_rows(ctx) == 0) {  // as svr_draw_geometry: this context owns no tile row
+    ctx->pending_clear.valid = false;
+    ctx->stats = SvrStats{};
+    if (out_stats) *out_stats = ctx->stats;
+    return SVR_OK;
+  }
+  if (ctx->tex_slots != ctx->materials.size() + 1)
+    if (int e = upload_tex_table(ctx, nullptr)) return e;
+  const std::shared_ptr<const ListVersion>& v = L->cur;
+  const size_t n_objects = (size_t)v->n_opaque + v->n_transparent;
+  SvrStats st{};
+  int e;
+  if (n_objects == 0) {  // svr_draw_geometry's host path: a pass of no draws
+    std::vector<DrawDesc> draws;
+    e = run_pass(ctx, scene, draws);
+  } else {
+    if (n_objects > LIST_FUSED_MAX && (ctx->meshes.size() >= (1u << 20) || ctx->materials.size() >= (1u << 20)))
+      return fail(SVR_ERR_UNSUPPORTED, "svr_draw_list: lists over 4096 objects need fewer than 2^20 meshes and materials");
+    e = run_pass_flatten(ctx, scene, nullptr, 0, nullptr, 0, v->tris_max, v->chunks_max, v);
+  }
+  auto t1 = std::chrono::steady_clock::now();
+  st.mesh_draw_time = std::chrono::duration<float, std::milli>(t1 - t0).count();
+  ctx->stats = st;
+  if (out_stats) *out_stats = st;
+  return e;
+}
+
+int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void* chunks, size_t chunk_bytes, uint32_t* n_draws,
+                           uint32_t* n_chunks) {
+  if (!ctx || !n_draws || !n_chunks) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_records: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  const FrameParams& P = ctx->last;
+  if (!P.draws) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_records: no pass yet");
+  uint32_t nd = ctx->last_n_draws, nc = P.n_chunks;
+  if (P.flatten) {  // the device knows the counts
+    Counters c;
+    HIPCHK(hipMemcpy(&c, P.counters, sizeof(Counters), hipMemcpyDeviceToHost));
+    nd = c.flat_draws;
+    nc = c.flat_chunks;
+  }
+  *n_draws = nd;
+  *n_chunks = nc;
+  if (draws) {
+    if (draw_bytes < (size_t)nd * sizeof(DrawDesc)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_records: draw buffer too small");
+    if (nd) HIPCHK(hipMemcpy(draws, P.draws, (size_t)nd * sizeof(DrawDesc), hipMemcpyDeviceToHost));
+  }
+  if (chunks) {
+    if (chunk_bytes < (size_t)nc * sizeof(WaveChunk)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_records: chunk buffer too small");
+    if (nc) HIPCHK(hipMemcpy(chunks, P.chunks, (size_t)nc * sizeof(WaveChunk), hipMemcpyDeviceToHost));
   }
   return SVR_OK;
 }

@@ -245,6 +245,11 @@ struct FrameParams {
   SvrSceneData scene;
 };
 
+// Largest resident draw list flattened by the single-workgroup list_kernel: four rounds of 1024 lanes.  Each round is
+// one is_visible per lane and a workgroup scan, back to back on one CU; longer lists go to the four kernels of
+// launch_flatten, which spread the cull over the chip (their N^2 / 16 rank is ~0.4 us at 4096 objects).
+constexpr uint32_t LIST_FUSED_MAX = 4096;
+
 // k_flatten.hip: cull + sort + per-object draw records on the device
 struct FlattenParams {
   const SvrRenderObject* objects;  // pinned host memory: opaque list, then the transparent list

@@ -18,6 +18,9 @@ void launch_vertex_shader(const SvrVertex* vtx, uint32_t first, uint32_t n, cons
                           float* out_varyings, hipStream_t s);
 // k_flatten.hip
 void launch_flatten(const FlattenParams& F, hipStream_t s);
+// a resident draw list (objects in device memory, in draw order): list_kernel up to LIST_FUSED_MAX objects, else the
+// four kernels of launch_flatten (which then need F.objects_dev / keys / draw_tris / chunk_base scratch)
+void launch_list_flatten(const FlattenParams& F, hipStream_t s);
 // k_bin.hip
 void launch_bin_count(const FrameParams& P, hipStream_t s);
 void launch_bin_scan(const FrameParams& P, hipStream_t s);

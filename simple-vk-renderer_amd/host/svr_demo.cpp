@@ -2,7 +2,8 @@
 // submitted and what came back.  Used by tests/test_host_cpp.py (against the oracle on CPU, against the HIP
 // library on the GPU box) and as the smallest example of the call sequence init -> load -> draw().
 //
-//   svr_demo --lib <libsvr_*.so> --width 160 --height 90 --frames 2 --dump /tmp/prefix
+//   svr_demo --lib <libsvr_*.so> --width 160 --height 90 --frames 2 --dump /tmp/prefix [--retained 1]
+//       --retained 1: the engine keeps its draw context in a draw list (include/svr_draw_list.h, HIP library only)
 //   svr_demo --lib libsvr_hip.so --dist libsvr_dist.so --ranks 2 [--transport shm|rccl] [--bounds 0,13,90] [--rebalance 1]
 //       the sharded frame (include/svr_dist.h): one process per rank (forked before anything touches the GPU;
 //       rccl: rank r on device r; shm: every rank on device 0), every rank dumps the exchanged image as
@@ -64,7 +65,7 @@ int main(int argc, char** argv) {
   std::string lib, prefix, gltf, png, dist_lib, transport = "shm", bounds_arg;
   int ranks = 1, rebalance = 0, queue_caps = 0, partition = 0, pick_partition = 0;
   uint32_t w = 160, h = 90;
-  int frames = 2, background = 0;
+  int frames = 2, background = 0, retained = 0;
   float cam[5] = {0, 0, 0, 0, 0};  // position, pitch, yaw
   uint32_t sw = 0, sh = 0;
   for (int i = 1; i + 1 < argc; i += 2) {
@@ -81,6 +82,7 @@ int main(int argc, char** argv) {
     else if (a == "--pick") pick_partition = atoi(argv[i + 1]);     // after N frames of each partition: keep the faster one
     else if (a == "--png") png = argv[i + 1];
     else if (a == "--background") background = atoi(argv[i + 1]);
+    else if (a == "--retained") retained = atoi(argv[i + 1]);  // 1: draw through a draw list (include/svr_draw_list.h)
     else if (a == "--swapchain" && sscanf(argv[i + 1], "%ux%u", &sw, &sh) == 2) {}
     else if (a == "--camera" && sscanf(argv[i + 1], "%f,%f,%f,%f,%f", &cam[0], &cam[1], &cam[2], &cam[3], &cam[4]) == 5) {}
     else if (a == "--width") w = (uint32_t)atoi(argv[i + 1]);
@@ -107,7 +109,8 @@ int main(int argc, char** argv) {
   }
   if (lib.empty()) {
     fprintf(stderr, "usage: svr_demo --lib <shared library exporting svr.h> [--width W --height H --frames N --dump prefix]\n"
-                    "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n");
+                    "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n"
+                    "                [--retained 1]\n");
     return 2;
   }
   // the sharded frame: one process per rank, forked before anything touches the GPU; rank 0 makes the id
@@ -175,6 +178,7 @@ int main(int argc, char** argv) {
   printf("backend %s, %ux%u\n", eng.api.svr_backend_name(), w, h);
 
   eng.current_background_effect = background;
+  eng.retained = retained != 0;
   eng.swapchain_width = sw;
   eng.swapchain_height = sh;
   if (!gltf.empty()) {  // VulkanEngine::init: load_gltf_meshes(this, path) -> loaded_scenes["structure"] (src/vk_engine.cpp:192-198)

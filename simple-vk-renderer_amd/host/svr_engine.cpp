@@ -29,6 +29,11 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   SVR_LOAD(svr_backend_name) SVR_LOAD(svr_draw_background) SVR_LOAD(svr_read_swapchain) SVR_LOAD(svr_copy_to_swapchain)
   SVR_LOAD(svr_set_option)
 #undef SVR_LOAD
+  // optional: only SvrEngine::retained needs them
+  svr_create_draw_list = reinterpret_cast<decltype(svr_create_draw_list)>(dlsym(handle, "svr_create_draw_list"));
+  svr_update_draw_list = reinterpret_cast<decltype(svr_update_draw_list)>(dlsym(handle, "svr_update_draw_list"));
+  svr_destroy_draw_list = reinterpret_cast<decltype(svr_destroy_draw_list)>(dlsym(handle, "svr_destroy_draw_list"));
+  svr_draw_list = reinterpret_cast<decltype(svr_draw_list)>(dlsym(handle, "svr_draw_list"));
   return ok;
 }
 void SvrApi::unload() {
@@ -144,6 +149,8 @@ bool SvrEngine::init(const std::string& library_path, uint32_t w, uint32_t h) {
 }
 
 void SvrEngine::cleanup() {
+  if (ctx && draw_list && api.svr_destroy_draw_list) api.svr_destroy_draw_list(ctx, draw_list);
+  draw_list = 0;
   if (ctx) api.svr_destroy(ctx);
   ctx = nullptr;
   api.unload();
@@ -230,11 +237,54 @@ bool SvrEngine::read_swapchain(std::vector<uint8_t>& out) {
   return true;
 }
 
+static bool same_objects(const SvrRenderObject& a, const SvrRenderObject& b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
+
+bool SvrEngine::sync_draw_list() {
+  if (!api.svr_create_draw_list) {
+    error = "--retained: this library has no draw lists (include/svr_draw_list.h)";
+    return false;
+  }
+  const DrawContext& now = main_draw_context;
+  DrawContext& held = list_context;
+  const size_t n_op = now.opaque_surfaces.size(), n_all = n_op + now.transparent_surfaces.size();
+  auto at = [&](const DrawContext& c, size_t i) -> const SvrRenderObject& {
+    return i < c.opaque_surfaces.size() ? c.opaque_surfaces[i] : c.transparent_surfaces[i - c.opaque_surfaces.size()];
+  };
+  if (draw_list && held.opaque_surfaces.size() == n_op && held.transparent_surfaces.size() == n_all - n_op) {
+    size_t first = 0, last = n_all;  // the run [first, last) that changed
+    while (first < n_all && same_objects(at(now, first), at(held, first))) first++;
+    while (last > first && same_objects(at(now, last - 1), at(held, last - 1))) last--;
+    if (first == last) return true;  // the usual frame: nothing to do
+    std::vector<SvrRenderObject> run;
+    for (size_t i = first; i < last; i++) run.push_back(at(now, i));
+    if (api.svr_update_draw_list(ctx, draw_list, first, run.data(), run.size())) {
+      error = api.svr_last_error();
+      return false;
+    }
+  } else {
+    if (draw_list) api.svr_destroy_draw_list(ctx, draw_list);
+    draw_list = 0;
+    if (api.svr_create_draw_list(ctx, now.opaque_surfaces.data(), n_op, now.transparent_surfaces.data(), n_all - n_op, &draw_list)) {
+      error = api.svr_last_error();
+      return false;
+    }
+  }
+  held.opaque_surfaces = now.opaque_surfaces;
+  held.transparent_surfaces = now.transparent_surfaces;
+  return true;
+}
+
 bool SvrEngine::draw_geometry() {  // src/vk_engine.cpp:1357-1477: the whole body is one call
   SvrStats st{};
-  int rc = api.svr_draw_geometry(ctx, &scene_data, main_draw_context.opaque_surfaces.data(),
-                                 main_draw_context.opaque_surfaces.size(), main_draw_context.transparent_surfaces.data(),
-                                 main_draw_context.transparent_surfaces.size(), &st);
+  int rc;
+  if (retained) {
+    if (!sync_draw_list()) return false;
+    rc = api.svr_draw_list(ctx, draw_list, &scene_data, &st);  // the three counts arrive with the pass (svr_get_stats)
+  } else {
+    rc = api.svr_draw_geometry(ctx, &scene_data, main_draw_context.opaque_surfaces.data(),
+                               main_draw_context.opaque_surfaces.size(), main_draw_context.transparent_surfaces.data(),
+                               main_draw_context.transparent_surfaces.size(), &st);
+  }
   if (rc) {
     error = api.svr_last_error();
     return false;

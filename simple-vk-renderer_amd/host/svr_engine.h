@@ -16,7 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/svr.h"
+#include "../../include/svr_draw_list.h"
 #include "svr_math.h"
 
 namespace svrhost {
@@ -32,6 +32,8 @@ struct SvrApi {
   SVR_FN(svr_write_material) SVR_FN(svr_clear_color) SVR_FN(svr_draw_geometry) SVR_FN(svr_sync) SVR_FN(svr_read_color)
   SVR_FN(svr_read_depth) SVR_FN(svr_get_stats) SVR_FN(svr_last_error) SVR_FN(svr_backend_name)
   SVR_FN(svr_draw_background) SVR_FN(svr_read_swapchain) SVR_FN(svr_copy_to_swapchain) SVR_FN(svr_set_option)
+  // include/svr_draw_list.h: optional (the HIP library has them, the oracle does not); needed by SvrEngine::retained
+  SVR_FN(svr_create_draw_list) SVR_FN(svr_update_draw_list) SVR_FN(svr_destroy_draw_list) SVR_FN(svr_draw_list)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -137,6 +139,13 @@ struct SvrEngine {
   uint32_t swapchain_width = 0, swapchain_height = 0;  // _swap_chain_extent; 0 = the draw extent
   bool draw_background();
   bool draw_geometry();
+  // Retained mode (svr_demo --retained): the draw context goes to a draw list made once; the list is updated only
+  // where the scene graph's output differs from what it holds (a changed run of objects), or made again when the
+  // counts change, and every frame is one svr_draw_list.
+  bool retained = false;
+  SvrDrawList draw_list = 0;
+  DrawContext list_context;  // what draw_list holds
+  bool sync_draw_list();
   bool draw();  // update_scene -> draw_background -> draw_geometry (ImGui/present have no counterpart)
   // the swapchain image of the frame just drawn: vkutil::copy_image at src/vk_engine.cpp:1277 (B8G8R8A8)
   bool read_swapchain(std::vector<uint8_t>& out);
