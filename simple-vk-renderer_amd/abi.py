@@ -88,6 +88,8 @@ SYMBOLS = ["svr_create", "svr_destroy", "svr_set_stream", "svr_bind_targets", "s
 # include/svr_draw_list.h: retained draw lists, HIP library only (the oracle exports exactly SYMBOLS)
 DRAW_LIST_SYMBOLS = ["svr_create_draw_list", "svr_update_draw_list", "svr_destroy_draw_list", "svr_draw_list",
                      "svr_debug_read_records"]
+# include/svr_ids.h: the object and primitive ID target, HIP library only
+ID_SYMBOLS = ["svr_enable_ids", "svr_bind_id_target", "svr_get_id_target", "svr_read_ids", "svr_pick"]
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -161,6 +163,13 @@ class SvrLib:
             L.svr_destroy_draw_list.argtypes = [P, C.c_uint32]
             L.svr_draw_list.argtypes = [P, C.c_uint32, C.POINTER(SvrSceneData), C.POINTER(SvrStats)]
             L.svr_debug_read_records.argtypes = [P, P, C.c_size_t, P, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        self.has_ids = hasattr(L, "svr_enable_ids")
+        if self.has_ids:
+            L.svr_enable_ids.argtypes = [P, C.c_int]
+            L.svr_bind_id_target.argtypes = [P, P]
+            L.svr_get_id_target.argtypes = [P, C.POINTER(P)]
+            L.svr_read_ids.argtypes = [P, P, C.c_size_t]
+            L.svr_pick.argtypes = [P, C.c_uint32, C.c_uint32, P]
 
     @property
     def backend(self):
@@ -450,6 +459,41 @@ class Renderer:
         st = SvrStats()
         self.lib.check(self.lib.lib.svr_get_stats(self.h, C.byref(st)))
         return st
+
+    # ---- the ID target (include/svr_ids.h)
+    def _need_ids(self):
+        if not getattr(self.lib, "has_ids", False):
+            raise SvrError(-5, f"{self.lib.backend} has no ID target (include/svr_ids.h)")
+
+    def enable_ids(self, on=True):
+        """allocate (or free) the context's ID plane: geometry passes then write {object, primitive} per pixel"""
+        self._need_ids()
+        self.lib.check(self.lib.lib.svr_enable_ids(self.h, 1 if on else 0))
+
+    def bind_id_target(self, ptr):
+        """caller-owned device memory (width * height * 8 bytes) as the ID target; None/0 = back to the context's plane"""
+        self._need_ids()
+        self.lib.check(self.lib.lib.svr_bind_id_target(self.h, C.c_void_p(ptr or None)))
+
+    def get_id_target(self):
+        self._need_ids()
+        p = C.c_void_p()
+        self.lib.check(self.lib.lib.svr_get_id_target(self.h, C.byref(p)))
+        return p.value
+
+    def read_ids(self):
+        """(H, W, 2) uint32: {object (1-based in the opaque array, 0 = none), primitive} per pixel"""
+        self._need_ids()
+        out = np.empty((self.height, self.width, 2), dtype=np.uint32)
+        self.lib.check(self.lib.lib.svr_read_ids(self.h, out.ctypes.data, out.nbytes))
+        return out
+
+    def pick(self, x, y):
+        """(object, primitive) at pixel (x, y), or None where no opaque fragment won"""
+        self._need_ids()
+        out = (C.c_uint32 * 2)()
+        self.lib.check(self.lib.lib.svr_pick(self.h, int(x), int(y), out))
+        return None if out[0] == 0 else (int(out[0]), int(out[1]))
 
 
 class DrawList:

@@ -114,6 +114,8 @@ struct ClipLds {
   VOut tmp[CLIP_LANES][12];
   TriGeom geom[CLIP_LANES];
 };
+// IDS: the pieces carry their parent's object and primitive (TriRec::object)
+template <bool IDS>
 __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, uint32_t block, uint32_t n_blocks) {
   const uint32_t lane = threadIdx.x;  // wave 0 of the block
   const uint32_t n = min(P.counters->n_clip, P.clip_cap), n_setup = min(P.counters->n_pairs, P.bin_cap);
@@ -123,10 +125,11 @@ __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, u
     const bool worker = lane < CLIP_LANES && q < n;
     VOut* poly = L.poly[lane & (CLIP_LANES - 1u)];
     int np = 0;
-    uint32_t first = 0, want = 0, used = 0, seq = 0, draw = 0;
+    uint32_t first = 0, want = 0, used = 0, seq = 0, draw = 0, prim = 0;
     if (worker) {
       ClipItem it = P.clip_queue[q];
       draw = it.draw;
+      prim = it.tri;
       const DrawDesc& d = P.draws[draw];
       const uint32_t kind = (d.flags >> F_KIND_SHIFT) & 3u;
       seq = d.tri_base + it.tri;
@@ -168,6 +171,7 @@ __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, u
                              *reinterpret_cast<uint4(*)[16]>(dst), &L.geom[lane])) {
             made = true;
             used++;
+            if (IDS) *reinterpret_cast<uint2*>(dst + REC_ID_PIECE) = make_uint2(d.pad, prim);
             transparent = (d.flags & F_TRANSPARENT) ? 1u : 0u;
             if (P.instrument) atomicAdd(&P.counters->binned, 1ull);
           }
@@ -203,7 +207,9 @@ __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, u
 // at the memory side and serialise per line: unmerged, neighbouring triangles made binning
 // atomic-bound), and its return value is the pair's position in its bin — kept, so the fill is a plain
 // scatter with no second round of atomics.
-__global__ __launch_bounds__(256, 4) void count_kernel(FrameParams P, uint32_t big_blocks, uint32_t clip_blocks) {
+// IDS: count_ids_kernel, for passes with an ID target (clip_and_bin); count_kernel is the kernel as it was
+template <bool IDS>
+__device__ __forceinline__ void count_main(const FrameParams& P, uint32_t big_blocks, uint32_t clip_blocks) {
   __shared__ ClipLds s_clip;
   if (P.counters->overflow) return;  // a queue overflowed: the pass is void, the host grows it and replays
   if (blockIdx.x < big_blocks) {
@@ -212,7 +218,7 @@ __global__ __launch_bounds__(256, 4) void count_kernel(FrameParams P, uint32_t b
   }
   const uint32_t rest_blocks = big_blocks + clip_blocks;
   if (blockIdx.x < rest_blocks) {
-    if (threadIdx.x < 64u) clip_and_bin(P, s_clip, blockIdx.x - big_blocks, clip_blocks);
+    if (threadIdx.x < 64u) clip_and_bin<IDS>(P, s_clip, blockIdx.x - big_blocks, clip_blocks);
     return;
   }
   // Which lanes of the wave target the same bin is found through a small LDS hash table of the wave's own (128
@@ -254,6 +260,12 @@ __global__ __launch_bounds__(256, 4) void count_kernel(FrameParams P, uint32_t b
     }
     __builtin_amdgcn_wave_barrier();
   }
+}
+__global__ __launch_bounds__(256, 4) void count_kernel(FrameParams P, uint32_t big_blocks, uint32_t clip_blocks) {
+  count_main<false>(P, big_blocks, clip_blocks);
+}
+__global__ __launch_bounds__(256, 4) void count_ids_kernel(FrameParams P, uint32_t big_blocks, uint32_t clip_blocks) {
+  count_main<true>(P, big_blocks, clip_blocks);
 }
 
 // Bin offsets without a scan: bins need not lie in tile order, only be disjoint spans, so every wave
@@ -388,7 +400,10 @@ void launch_bin_count(const FrameParams& P, hipStream_t s) {
   // (128 blocks for the queued big triangles also in the 8K x16 frame: with 1024 the kernel is 246 us instead of 168 —
   // what bounds it there is the device atomics on the bins' counters, and more waves only queue up behind them)
   const uint32_t big_blocks = 128, clip_blocks = 512;
-  hipLaunchKernelGGL(count_kernel, dim3(big_blocks + clip_blocks + 1024u), dim3(256), 0, s, P, big_blocks, clip_blocks);
+  if (P.ids)
+    hipLaunchKernelGGL(count_ids_kernel, dim3(big_blocks + clip_blocks + 1024u), dim3(256), 0, s, P, big_blocks, clip_blocks);
+  else
+    hipLaunchKernelGGL(count_kernel, dim3(big_blocks + clip_blocks + 1024u), dim3(256), 0, s, P, big_blocks, clip_blocks);
 }
 void launch_bin_scan(const FrameParams& P, hipStream_t s) {
   hipLaunchKernelGGL(offsets_kernel, dim3((2u * P.n_tiles + 255u) / 256u), dim3(256), 0, s, P);

@@ -57,6 +57,9 @@ __device__ bool is_visible_dev(const SvrRenderObject& obj, const float* viewproj
 
 constexpr unsigned long long KEY_CULLED = ~0ull;
 
+// ID passes (include/svr_ids.h): the number of opaque object i as the caller knows it, its 1-based position as submitted
+__device__ __forceinline__ uint32_t object_number(const FlattenParams& F, uint32_t i) { return F.obj_ids ? F.obj_ids[i] : i + 1u; }
+
 // The objects lie in pinned host memory (108 bytes each).  Read object by object — a lane its own 108 bytes, here and
 // again by rank_kernel's record writers — they crossed the host link twice in requests of a few bytes: 5408 objects,
 // 100 us for the two kernels.  Every block first pulls ITS objects (opaque: 256 per block; the blocks behind them take
@@ -94,7 +97,8 @@ __global__ __launch_bounds__(256) void cull_kernel(FlattenParams F) {
 }
 
 // the draw record of one object (tri_base is left 0: the scans fill it in)
-__device__ __forceinline__ DrawDesc make_draw(const FlattenParams& F, const SvrRenderObject& o) {
+// object: DrawDesc::pad (0 unless the pass has an ID target)
+__device__ __forceinline__ DrawDesc make_draw(const FlattenParams& F, const SvrRenderObject& o, uint32_t object) {
   const MeshEntry me = F.meshes[o.mesh - 1];
   const MatEntry ma = F.materials[o.material - 1];
   DrawDesc d;
@@ -107,7 +111,7 @@ __device__ __forceinline__ DrawDesc make_draw(const FlattenParams& F, const SvrR
   d.idx = me.idx + o.first_index;
   d.groups = me.groups;
   d.first_index = o.first_index;
-  d.pad = 0;
+  d.pad = object;
   d.tri_count = o.index_count / 3u;
   d.tri_base = 0;
   d.tex = o.material - 1u;
@@ -115,8 +119,8 @@ __device__ __forceinline__ DrawDesc make_draw(const FlattenParams& F, const SvrR
   return d;
 }
 
-__device__ __forceinline__ void write_draw(const FlattenParams& F, uint32_t slot, const SvrRenderObject& o) {
-  const DrawDesc d = make_draw(F, o);  // tri_base: prefix_kernel
+__device__ __forceinline__ void write_draw(const FlattenParams& F, uint32_t slot, const SvrRenderObject& o, uint32_t object = 0) {
+  const DrawDesc d = make_draw(F, o, object);  // tri_base: prefix_kernel
   F.draws[slot] = d;
   F.draw_tris[slot] = d.tri_count;
   F.chunk_base[slot] = chunk_count(d.first_index, d.tri_count);  // the count for now: prefix_kernel turns it into the base
@@ -125,7 +129,9 @@ __device__ __forceinline__ void write_draw(const FlattenParams& F, uint32_t slot
 // 16 lanes per opaque object (lane & 15 = the part of the key array it scans); transparent objects: one lane each.
 // The keys go through LDS 2048 at a time (a lane's 338 global loads, one per round of its loop, were the kernel: 86 us
 // at 5408 objects): the block's 16 objects x 16 parts read consecutive keys, the four groups of a wave the same ones.
-__global__ __launch_bounds__(256) void rank_kernel(FlattenParams F) {
+// IDS: the pass has an ID target; opaque records carry their object number (DrawDesc::pad): rank_ids_kernel
+template <bool IDS>
+__device__ __forceinline__ void rank_main(const FlattenParams& F) {
   constexpr uint32_t KT = 2048;
   __shared__ unsigned long long s_keys[KT];
   const uint32_t group = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, part = threadIdx.x & 15u;
@@ -146,7 +152,7 @@ __global__ __launch_bounds__(256) void rank_kernel(FlattenParams F) {
     smaller += __shfl_xor(smaller, 2);
     smaller += __shfl_xor(smaller, 4);
     smaller += __shfl_xor(smaller, 8);
-    if (part == 0 && mine != KEY_CULLED) write_draw(F, smaller, F.objects_dev[group]);
+    if (part == 0 && mine != KEY_CULLED) write_draw(F, smaller, F.objects_dev[group], IDS ? object_number(F, group) : 0u);
   } else {
     // the blocks behind the opaque ones: 256 transparent objects each, a lane per object
     const uint32_t opaque_blocks = (F.n_opaque + 15u) / 16u;
@@ -154,6 +160,8 @@ __global__ __launch_bounds__(256) void rank_kernel(FlattenParams F) {
     if (t < F.n_transparent) write_draw(F, n_vis + t, F.objects_dev[F.n_opaque + t]);
   }
 }
+__global__ __launch_bounds__(256) void rank_kernel(FlattenParams F) { rank_main<false>(F); }
+__global__ __launch_bounds__(256) void rank_ids_kernel(FlattenParams F) { rank_main<true>(F); }
 
 // one workgroup: tri_base and chunk_base of every draw (<= 16 per thread), totals into the counters
 __global__ __launch_bounds__(1024) void prefix_kernel(FlattenParams F) {
@@ -220,7 +228,8 @@ __global__ __launch_bounds__(256) void chunks_kernel(FlattenParams F) {
 
 // make_draw stored column by column (the same bytes): a whole DrawDesc in registers beside the scans of list_kernel
 // does not fit its 128 VGPRs
-__device__ __forceinline__ void store_draw(const FlattenParams& F, const float* viewproj, uint32_t slot, const SvrRenderObject& o, uint32_t tri_base) {
+__device__ __forceinline__ void store_draw(const FlattenParams& F, const float* viewproj, uint32_t slot, const SvrRenderObject& o, uint32_t tri_base,
+                                           uint32_t object) {
   const MeshEntry me = F.meshes[o.mesh - 1];
   const MatEntry ma = F.materials[o.material - 1];
   DrawDesc* d = F.draws + slot;
@@ -240,7 +249,7 @@ __device__ __forceinline__ void store_draw(const FlattenParams& F, const float* 
   d->flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (ma.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u);
   d->groups = me.groups;
   d->first_index = o.first_index;
-  d->pad = 0;
+  d->pad = object;
 }
 
 // A resident draw list (svr_draw_list, svr_api.hip) in one launch.  The list lies in device memory in DRAW ORDER: its
@@ -250,7 +259,9 @@ __device__ __forceinline__ void store_draw(const FlattenParams& F, const float* 
 // list: a round takes 1024 objects, a lane each (is_visible_dev; transparent objects are never culled), scans
 // (visible, triangles, wave chunks) over the workgroup through LDS, and every visible lane writes its DrawDesc and
 // WaveChunks at the bases it found.  Same records as the host path stages (and as the four kernels above).
-__global__ __launch_bounds__(1024) void list_kernel(FlattenParams F) {
+// IDS: list_ids_kernel, for passes with an ID target (DrawDesc::pad = object number); list_kernel is the kernel as it was
+template <bool IDS>
+__device__ __forceinline__ void list_main(const FlattenParams& F) {
   __shared__ uint32_t s_sum[3][16];
   __shared__ float s_vp[16];  // viewproj from LDS: held in SGPRs for both of its uses it spilled 32 of them
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
@@ -300,7 +311,7 @@ __global__ __launch_bounds__(1024) void list_kernel(FlattenParams F) {
     __syncthreads();  // s_sum is rewritten by the next round
     if (vis) {
       const uint32_t slot = bv + iv - 1u, cb = bc + ic - chk;
-      store_draw(F, s_vp, slot, F.objects[i], bt + it - tri);
+      store_draw(F, s_vp, slot, F.objects[i], bt + it - tri, (IDS && i < F.n_opaque) ? object_number(F, i) : 0u);
       for (uint32_t c = 0; c < chk; c++) {
         WaveChunk ch;
         ch.draw = slot;
@@ -316,12 +327,18 @@ __global__ __launch_bounds__(1024) void list_kernel(FlattenParams F) {
     F.counters->flat_culled = F.n_opaque - (base_v - F.n_transparent);
   }
 }
+__global__ __launch_bounds__(1024) void list_kernel(FlattenParams F) { list_main<false>(F); }
+__global__ __launch_bounds__(1024) void list_ids_kernel(FlattenParams F) { list_main<true>(F); }
 
 void launch_flatten(const FlattenParams& F, hipStream_t s) {
   const uint32_t n_all = F.n_opaque + F.n_transparent;
   if (n_all == 0) return;
   hipLaunchKernelGGL(cull_kernel, dim3((n_all + 255u) / 256u), dim3(256), 0, s, F);  // (also pulls every object into device memory)
-  hipLaunchKernelGGL(rank_kernel, dim3((F.n_opaque + 15u) / 16u + (F.n_transparent + 255u) / 256u), dim3(256), 0, s, F);
+  const dim3 rank_grid((F.n_opaque + 15u) / 16u + (F.n_transparent + 255u) / 256u);
+  if (F.ids)
+    hipLaunchKernelGGL(rank_ids_kernel, rank_grid, dim3(256), 0, s, F);
+  else
+    hipLaunchKernelGGL(rank_kernel, rank_grid, dim3(256), 0, s, F);
   hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, s, F);
   hipLaunchKernelGGL(chunks_kernel, dim3((n_all + 255u) / 256u), dim3(256), 0, s, F);
 }
@@ -329,7 +346,9 @@ void launch_flatten(const FlattenParams& F, hipStream_t s) {
 void launch_list_flatten(const FlattenParams& F, hipStream_t s) {
   const uint32_t n_all = F.n_opaque + F.n_transparent;
   if (n_all == 0) return;
-  if (n_all <= LIST_FUSED_MAX)
+  if (n_all <= LIST_FUSED_MAX && F.ids)
+    hipLaunchKernelGGL(list_ids_kernel, dim3(1), dim3(1024), 0, s, F);
+  else if (n_all <= LIST_FUSED_MAX)
     hipLaunchKernelGGL(list_kernel, dim3(1), dim3(1024), 0, s, F);
   else
     launch_flatten(F, s);  // F.objects is the resident copy: cull_kernel pulls it into the set's scratch like host memory

@@ -68,6 +68,9 @@ __device__ __forceinline__ bool chunk_can_be_seen(const FrameParams& P, const fl
   return true;
 }
 
+// IDS: the pass has an ID target (include/svr_ids.h); records carry their object and primitive (TriRec::object).
+// (A template kernel, not a body shared by two: that wrapper alone cost the instance without IDs two VGPRs.)
+template <bool IDS>
 __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
   // the wave's chunk and its draw are wave-uniform: held in SGPRs, so chunk -> draw record is two scalar round
   // trips (read as per-lane values they were a chain of six vector loads in front of the first index fetch)
@@ -190,6 +193,10 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
       }
     }
     if (!ok) piece[0] = make_uint4(1u, 0u, 0u, 0u);
+    if (IDS) {  // (d.idx already starts at the draw's first index: tri is gl_PrimitiveID)
+      piece[REC_ID_PIECE].x = d.pad;
+      piece[REC_ID_PIECE].y = tri;
+    }
     if (ok && P.instrument) atomicAdd(&P.counters->binned, 1ull);
     if (to_clip) {  // slow path: hand over to the clipper (it links its pieces from this slot)
       uint32_t slot = atomicAdd(&P.counters->n_clip, 1u);
@@ -300,7 +307,10 @@ __global__ __launch_bounds__(256) void vertex_shader_kernel(const SvrVertex* vtx
 void launch_setup(const FrameParams& P, hipStream_t s) {
   if (P.n_chunks == 0) return;
   uint32_t blocks = (P.n_chunks + 3) / 4;
-  hipLaunchKernelGGL(setup_kernel, dim3(blocks), dim3(256), 0, s, P);
+  if (P.ids)
+    hipLaunchKernelGGL(setup_kernel<true>, dim3(blocks), dim3(256), 0, s, P);
+  else
+    hipLaunchKernelGGL(setup_kernel<false>, dim3(blocks), dim3(256), 0, s, P);
 }
 // Pass prologue: pull the pass inputs (DrawDesc[] + WaveChunk[], ~100 KB) out of the pinned staging
 // buffer and zero the pass's counters, in one kernel.  A hipMemcpyAsync here is an SDMA packet with

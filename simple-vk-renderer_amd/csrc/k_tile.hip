@@ -1172,7 +1172,7 @@ __device__ __forceinline__ void store_row16(void* p, uint4 v) {
 // by blockIdx alone: sharing one body with run-time row ranges cost the whole-tile path 20-35 spilled
 // registers and 8-13 % of the frame, and choosing by a flag in tile_info put a dependent load in front of
 // every tile (+2 %).
-template <int FMT, bool INSTR, bool QUARTER, bool SPLIT>
+template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS>
 __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, const uint4 i1, uint4* s_cov, uint32_t* s_idx, unsigned char* s_c,
                                           const uint32_t wv, const bool hiz_on, const uint32_t wg_start = 0) {
   typedef Codec<FMT> CD;
@@ -1365,6 +1365,34 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       if (n_tr) s_z[w] = z;
     }
   }
+  // IDS: the ID target (include/svr_ids.h) leaves with the depth, {object, primitive} of the winner's record ({0, 0}: none),
+  // over exactly the pixels the depth store wrote.  Whole rows go through s_cov (8 KiB, idle between phases A and C).
+  if (IDS) {
+    int rx, ry;
+    uint32_t li;
+    lane_pixel(wv, rx, ry, li);
+    uint2 id[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      id[k] = recs[k] == NO_REC ? make_uint2(0u, 0u)
+                                : *reinterpret_cast<const uint2*>(reinterpret_cast<const uint4*>(P.recs + (recs[k] & ~REC_COMMON)) + REC_ID_PIECE);
+    if (inside && aligned) {
+      static_assert(sizeof(uint4) * BATCH * 8 >= TILE * TILE * sizeof(uint2), "an ID tile fits s_cov");
+      uint2* s_id = reinterpret_cast<uint2*>(s_cov);
+#pragma unroll
+      for (int k = 0; k < 4; k++) s_id[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] = id[k];
+      __syncthreads();
+      const uint32_t tid = tid_of(wv), row = tid >> 3, c = (tid & 7u) * 4u;
+      const uint4* src = reinterpret_cast<const uint4*>(s_id + row * TILE + c);
+      uint2* dst = P.ids + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c);
+      store_row16(dst, src[0]);
+      store_row16(dst + 2, src[1]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (pix_ok[k]) P.ids[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = id[k];
+    }
+  }
   __syncthreads();  // the visibility tile is dead: its memory is the tile's colour from here on
 
   if (stamps) stamp[1] = clock64();
@@ -1522,8 +1550,9 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #ifndef SVR_TILE_WAVES
 #define SVR_TILE_WAVES 5  // waves per SIMD (= workgroups per CU) the tile kernel is compiled for (A/B builds: tools/build_variant.sh)
 #endif
-template <int FMT, bool INSTR, bool SPLIT>
-__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_kernel(FrameParams P) {
+// IDS: the pass writes an ID target (FrameParams::ids): tile_ids_kernel below; tile_kernel is the kernel as it was
+template <int FMT, bool INSTR, bool SPLIT, bool IDS>
+__device__ __forceinline__ void tile_main(const FrameParams& P) {
   __shared__ uint4 s_cov[BATCH * 8];
   __shared__ uint32_t s_idx[BATCH];
   __shared__ __attribute__((aligned(16))) unsigned char s_c[PHASE_C_BYTES];  // phase A depth tile, phase C blocks
@@ -1584,14 +1613,18 @@ __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_kernel(FrameParams P
   } else if (SPLIT) {
     if (blockIdx.x < SPLIT_EXTRA) {  // the quarters of split tiles, as many as fill_kernel made
       if (blockIdx.x >= 4u * min(n_split, SPLIT_MAX)) return;
-      tile_body<FMT, INSTR, true, true>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, true, true, IDS>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     } else {
-      tile_body<FMT, INSTR, false, true>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, false, true, IDS>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     }
   } else {
-    tile_body<FMT, INSTR, false, false>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+    tile_body<FMT, INSTR, false, false, IDS>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
   }
 }
+template <int FMT, bool INSTR, bool SPLIT>
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false>(P); }
+template <int FMT, bool INSTR, bool SPLIT>
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_ids_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, true>(P); }
 
 // Instrumented passes only: the counters go to the host (pinned, device-visible) by a one-wave kernel
 // behind the tile kernel.  (A D2H copy packet there costs ~15 us of stream time; a last-workgroup-
@@ -1631,7 +1664,11 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
 #else
   const uint32_t pad = P.n_tiles <= SPLIT_TILES_MAX ? 1280u : 0u;
 #endif
-#define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT) hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P)
+#define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT)                                                                                          \
+  do {                                                                                                                               \
+    if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);    \
+    else hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);              \
+  } while (0)
   if (color_format == SVR_COLOR_RGBA16F) {
     if (count_fragments) {
       if (split) SVR_LAUNCH_TILES(SVR_COLOR_RGBA16F, true, true);

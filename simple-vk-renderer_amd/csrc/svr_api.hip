@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/svr_draw_list.h"
+#include "../../include/svr_ids.h"
 #include "svr_cull.h"
 #include "svr_launch.h"
 
@@ -92,8 +93,10 @@ struct ListVersion {
   uint32_t n_opaque = 0, n_transparent = 0;
   uint64_t tris_max = 0;  // upper bounds that size the pass's buffers and grids (every object visible)
   size_t chunks_max = 0;
+  uint32_t* obj_ids = nullptr;  // [n_opaque] draw order -> position in the opaque array as submitted, + 1 (ID passes: svr_ids.h)
   ~ListVersion() {
     if (dev) (void)hipFree(dev);
+    if (obj_ids) (void)hipFree(obj_ids);
   }
 };
 struct DrawListRes {
@@ -137,6 +140,9 @@ struct SvrContext {
   float* depth_own = nullptr;
   void* color = nullptr;
   float* depth = nullptr;
+  uint2* ids_own = nullptr;  // svr_enable_ids
+  uint2* ids = nullptr;      // the ID target (include/svr_ids.h): a caller's (svr_bind_id_target), ids_own or none
+  bool ids_bound = false;    // ... it is the caller's
   uint32_t sx = 0, sy = 0, sw = 0, sh = 0;
   uint32_t rstride = 1, roff = 0;      // svr_set_row_interleave
   uint32_t* present_status = nullptr;  // svr_set_present_status
@@ -559,6 +565,8 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
     F.draws = (DrawDesc*)set.inputs.p;
     F.chunks = (WaveChunk*)((char*)set.inputs.p + draw_bytes);
     F.counters = P.counters;
+    F.ids = P.ids ? 1u : 0u;
+    F.obj_ids = (P.ids && resident) ? flat_op->list->obj_ids : nullptr;
     if (resident)
       launch_list_flatten(F, g);
     else
@@ -841,7 +849,8 @@ int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tri
   return SVR_OK;
 }
 
-int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws) {
+// ids: a geometry pass, which writes the ID target if there is one (the draws' pad words then carry object numbers)
+int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false) {
   if (int e = poll_pending(ctx)) return e;
   // sequence numbers + wave chunks
   uint64_t n_tris64 = 0;
@@ -854,6 +863,7 @@ int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& 
   FrameParams P;
   const SvrContext::PendingClear asked = ctx->pending_clear;  // folded into P.lazy_clear below: put back if the pass is not enqueued
   if (int e = fill_frame_params(ctx, scene, n_tris64, n_chunks, P)) return e;
+  if (ids) P.ids = ctx->ids;
   int slot = 0;
   if (int e = log_slot(ctx, &slot)) {
     if (P.lazy_clear) ctx->pending_clear = asked;
@@ -915,6 +925,7 @@ int run_pass_flatten(SvrContext* ctx, const SvrSceneData* scene, const SvrRender
   const SvrContext::PendingClear asked = ctx->pending_clear;
   if (int e = fill_frame_params(ctx, scene, tris_max, chunks_max, P)) return e;
   P.flatten = 1u;
+  P.ids = ctx->ids;
   int slot = 0;
   if (int e = log_slot(ctx, &slot)) {
     if (P.lazy_clear) ctx->pending_clear = asked;
@@ -1047,6 +1058,7 @@ void svr_destroy(SvrContext* ctx) {
       if (ctx->tev[i][k]) (void)hipEventDestroy(ctx->tev[i][k]);
   if (ctx->color_own) (void)hipFree(ctx->color_own);
   if (ctx->depth_own) (void)hipFree(ctx->depth_own);
+  if (ctx->ids_own) (void)hipFree(ctx->ids_own);
   delete ctx;
 }
 
@@ -1474,7 +1486,8 @@ int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRende
   std::vector<DrawDesc> draws;
   draws.reserve(order.size() + n_transparent);
   SvrStats st{};
-  auto push = [&](const SvrRenderObject& o) {
+  const bool ids = ctx->ids != nullptr;  // DrawDesc::pad = the opaque object's number (include/svr_ids.h)
+  auto push = [&](const SvrRenderObject& o, uint32_t object) {
     const MeshRes& m = ctx->meshes[o.mesh - 1];
     const MaterialRes& mat = ctx->materials[o.material - 1];
     DrawDesc d;
@@ -1488,14 +1501,15 @@ int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRende
     d.tri_count = o.index_count / 3;
     d.tex = o.material - 1;
     d.flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (mat.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u);
+    d.pad = ids ? object : 0u;
     draws.push_back(d);
     st.drawcall_count++;
     st.triangle_count += (int)(o.index_count / 3);
   };
-  for (uint32_t i : order) push(opaque[i]);
-  for (size_t i = 0; i < n_transparent; i++) push(transparent[i]);
+  for (uint32_t i : order) push(opaque[i], i + 1u);
+  for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
   st.culled_draws = (uint32_t)(n_opaque - order.size());
-  int e = run_pass(ctx, scene, draws);
+  int e = run_pass(ctx, scene, draws, true);
   auto t1 = std::chrono::steady_clock::now();
   st.mesh_draw_time = std::chrono::duration<float, std::milli>(t1 - t0).count();
   ctx->stats = st;
@@ -1852,6 +1866,11 @@ static int make_list_version(const DrawListRes& L, std::shared_ptr<const ListVer
     HIPCHK(hipMalloc((void**)&v->dev, n * sizeof(SvrRenderObject)));
     HIPCHK(hipMemcpy(v->dev, sorted.data(), n * sizeof(SvrRenderObject), hipMemcpyHostToDevice));
   }
+  if (L.n_opaque) {  // object numbers for ID passes (include/svr_ids.h)
+    for (uint32_t& i : order) i += 1u;
+    HIPCHK(hipMalloc((void**)&v->obj_ids, order.size() * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(v->obj_ids, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
   *out = std::move(v);
   return SVR_OK;
 }
@@ -1933,7 +1952,7 @@ int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, 
   int e;
   if (n_objects == 0) {  // svr_draw_geometry's host path: a pass of no draws
     std::vector<DrawDesc> draws;
-    e = run_pass(ctx, scene, draws);
+    e = run_pass(ctx, scene, draws, true);
   } else {
     if (n_objects > LIST_FUSED_MAX && (ctx->meshes.size() >= (1u << 20) || ctx->materials.size() >= (1u << 20)))
       return fail(SVR_ERR_UNSUPPORTED, "svr_draw_list: lists over 4096 objects need fewer than 2^20 meshes and materials");
@@ -1969,6 +1988,69 @@ int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void
     if (chunk_bytes < (size_t)nc * sizeof(WaveChunk)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_records: chunk buffer too small");
     if (nc) HIPCHK(hipMemcpy(chunks, P.chunks, (size_t)nc * sizeof(WaveChunk), hipMemcpyDeviceToHost));
   }
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- the ID target (include/svr_ids.h)
+int svr_enable_ids(SvrContext* ctx, int on) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  if (int e = use_device(ctx)) return e;
+  if (on) {
+    if (!ctx->ids_own) {
+      const size_t bytes = (size_t)ctx->W * ctx->H * sizeof(uint2);
+      if (int e = finish_pending(ctx)) return e;  // the zeroing below runs outside the stream
+      hipError_t r = hipMalloc((void**)&ctx->ids_own, bytes);
+      if (r != hipSuccess) {
+        ctx->ids_own = nullptr;
+        return fail(r == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE, std::string("svr_enable_ids: ") + hipGetErrorString(r));
+      }
+      HIPCHK(hipMemset(ctx->ids_own, 0, bytes));
+    }
+    if (!ctx->ids_bound) ctx->ids = ctx->ids_own;
+    return SVR_OK;
+  }
+  if (!ctx->ids_own) return SVR_OK;
+  if (int e = finish_pending(ctx)) return e;  // passes in flight (and their replays) may still write the plane
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (ctx->ids == ctx->ids_own) ctx->ids = nullptr;
+  (void)hipFree(ctx->ids_own);
+  ctx->ids_own = nullptr;
+  return SVR_OK;
+}
+
+int svr_bind_id_target(SvrContext* ctx, void* ids_dev) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  if (((uintptr_t)ids_dev & 15u) != 0u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_bind_id_target: the target must be 16-byte aligned");
+  if (int e = use_device(ctx)) return e;
+  // no fence: passes already enqueued carry their own ID target (also for a replay), as with svr_bind_targets
+  if (int e = poll_pending(ctx)) return e;
+  ctx->ids_bound = ids_dev != nullptr;
+  ctx->ids = ids_dev ? (uint2*)ids_dev : ctx->ids_own;
+  return SVR_OK;
+}
+
+int svr_get_id_target(SvrContext* ctx, void** ids_dev) {
+  if (!ctx || !ids_dev) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_id_target: null argument");
+  *ids_dev = ctx->ids;
+  return SVR_OK;
+}
+
+int svr_read_ids(SvrContext* ctx, uint32_t* dst_host, size_t bytes) {
+  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ids: null argument");
+  if (!ctx->ids) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ids: no ID target (svr_enable_ids / svr_bind_id_target)");
+  const size_t n = (size_t)ctx->W * ctx->H * sizeof(uint2);
+  if (bytes < n) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ids: buffer too small");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst_host, ctx->ids, n, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+int svr_pick(SvrContext* ctx, uint32_t x, uint32_t y, uint32_t out[2]) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_pick: null argument");
+  if (x >= ctx->W || y >= ctx->H) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_pick: pixel outside the target");
+  if (!ctx->ids) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_pick: no ID target (svr_enable_ids / svr_bind_id_target)");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(out, ctx->ids + (size_t)y * ctx->W + x, sizeof(uint2), hipMemcpyDeviceToHost));
   return SVR_OK;
 }
 

@@ -71,7 +71,7 @@ struct DrawDesc {
   const float* groups;      // the mesh's index-group table (svr_upload_mesh): GROUP_WORDS words per group = float[6] min xyz, max xyz of the vertices
                             // named by indices [192 g, 192 g + 192); NULL = none (the wave chunks are never skipped)
   uint32_t first_index;     // the draw's offset in the mesh's index buffer: locates its chunks' groups
-  uint32_t pad;
+  uint32_t pad;             // passes with an ID target (include/svr_ids.h): the opaque object's number (1-based), else 0
 };
 static_assert(sizeof(DrawDesc) == 192 && offsetof(DrawDesc, vtx) == 144 && offsetof(DrawDesc, groups) == 176, "DrawDesc layout");
 constexpr uint32_t GROUP_INDICES = 192;  // 64 triangles
@@ -143,9 +143,14 @@ struct TriRec {
   // ---- shading half
   float q0, dq1, dq2;              // 1/w
   float a0[8], da1[8], da2[8];     // varyings pre-divided by w: normal.xyz, color.rgb, uv
-  float pad2[5];
+  float pad2;
+  uint32_t object, primitive;      // ID instances only (else 0): DrawDesc::pad and the triangle's index in its draw (a clipper
+                                   // piece: its parent's); the tile kernel's ID target takes them from the winning record
+  float pad3[2];
 };
 static_assert(sizeof(TriRec) == 256, "TriRec layout");
+static_assert(offsetof(TriRec, object) == 240, "TriRec layout: the ID words are piece 15's x and y");
+constexpr uint32_t REC_ID_PIECE = offsetof(TriRec, object) / 16u;
 static_assert(offsetof(TriRec, A) == 32 && offsetof(TriRec, tex_off) == 104 && offsetof(TriRec, tex_wh) == 112 &&
                   offsetof(TriRec, q0) == 128, "TriRec layout");
 
@@ -243,6 +248,8 @@ struct FrameParams {
   uint32_t tuning;                // SVR_OPT_TUNING bits (A/B switches for benchmarking, default 0)
   uint32_t pad_t;
   SvrSceneData scene;
+  uint2* ids;                     // ID target (include/svr_ids.h): {object, primitive} per pixel; NULL = none (the kernels'
+                                  // ID instances run only when it is set)
 };
 
 // Largest resident draw list flattened by the single-workgroup list_kernel: four rounds of 1024 lanes.  Each round is
@@ -264,6 +271,9 @@ struct FlattenParams {
   DrawDesc* draws;
   WaveChunk* chunks;
   Counters* counters;
+  uint32_t ids;              // 1: the pass has an ID target (the IDS instances: DrawDesc::pad = object number)
+  const uint32_t* obj_ids;   // ... of each opaque object: a draw list's draw order -> its position as submitted, + 1;
+                             // NULL: opaque object i is object i + 1
 };
 
 // ------------------------------------------------------------------------------------------------

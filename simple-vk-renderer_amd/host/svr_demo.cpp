@@ -4,6 +4,8 @@
 //
 //   svr_demo --lib <libsvr_*.so> --width 160 --height 90 --frames 2 --dump /tmp/prefix [--retained 1]
 //       --retained 1: the engine keeps its draw context in a draw list (include/svr_draw_list.h, HIP library only)
+//       --select X,Y: after the last frame, print what won pixel (X, Y) (include/svr_ids.h, HIP library only):
+//           select X Y object N mesh <name> surface S primitive P   or   select X Y none
 //   svr_demo --lib libsvr_hip.so --dist libsvr_dist.so --ranks 2 [--transport shm|rccl] [--bounds 0,13,90] [--rebalance 1]
 //       the sharded frame (include/svr_dist.h): one process per rank (forked before anything touches the GPU;
 //       rccl: rank r on device r; shm: every rank on device 0), every rank dumps the exchanged image as
@@ -66,6 +68,8 @@ int main(int argc, char** argv) {
   int ranks = 1, rebalance = 0, queue_caps = 0, partition = 0, pick_partition = 0;
   uint32_t w = 160, h = 90;
   int frames = 2, background = 0, retained = 0;
+  bool select = false;
+  uint32_t sel_x = 0, sel_y = 0;
   float cam[5] = {0, 0, 0, 0, 0};  // position, pitch, yaw
   uint32_t sw = 0, sh = 0;
   for (int i = 1; i + 1 < argc; i += 2) {
@@ -83,6 +87,7 @@ int main(int argc, char** argv) {
     else if (a == "--png") png = argv[i + 1];
     else if (a == "--background") background = atoi(argv[i + 1]);
     else if (a == "--retained") retained = atoi(argv[i + 1]);  // 1: draw through a draw list (include/svr_draw_list.h)
+    else if (a == "--select" && sscanf(argv[i + 1], "%u,%u", &sel_x, &sel_y) == 2) select = true;  // (--pick is the partition pick)
     else if (a == "--swapchain" && sscanf(argv[i + 1], "%ux%u", &sw, &sh) == 2) {}
     else if (a == "--camera" && sscanf(argv[i + 1], "%f,%f,%f,%f,%f", &cam[0], &cam[1], &cam[2], &cam[3], &cam[4]) == 5) {}
     else if (a == "--width") w = (uint32_t)atoi(argv[i + 1]);
@@ -382,6 +387,10 @@ int main(int argc, char** argv) {
     g_exit_ok = true;
     return 0;
   }
+  if (select && !eng.enable_ids()) {
+    fprintf(stderr, "--select: %s\n", eng.error.c_str());
+    return 1;
+  }
   for (int f = 0; f < frames; f++) {
     eng.update_scene();
     if (f == frames - 1 && !prefix.empty()) {
@@ -397,6 +406,17 @@ int main(int argc, char** argv) {
   eng.api.svr_sync(eng.ctx);
   printf("draws %d triangles %d update %.3f ms record %.3f ms\n", eng.stats.drawcall_count, eng.stats.triangle_count,
          eng.stats.scene_update_time, eng.stats.mesh_draw_time);
+  if (select) {
+    SvrEngine::Pick p;
+    if (!eng.pick(sel_x, sel_y, p)) {
+      fprintf(stderr, "--select: %s\n", eng.error.c_str());
+      return 1;
+    }
+    if (p.hit)
+      printf("select %u %u object %u mesh %s surface %u primitive %u\n", sel_x, sel_y, p.object, p.mesh.c_str(), p.surface, p.primitive);
+    else
+      printf("select %u %u none\n", sel_x, sel_y);
+  }
   if (!prefix.empty()) {
     std::vector<uint16_t> color;
     std::vector<float> depth;

@@ -34,6 +34,8 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_update_draw_list = reinterpret_cast<decltype(svr_update_draw_list)>(dlsym(handle, "svr_update_draw_list"));
   svr_destroy_draw_list = reinterpret_cast<decltype(svr_destroy_draw_list)>(dlsym(handle, "svr_destroy_draw_list"));
   svr_draw_list = reinterpret_cast<decltype(svr_draw_list)>(dlsym(handle, "svr_draw_list"));
+  svr_enable_ids = reinterpret_cast<decltype(svr_enable_ids)>(dlsym(handle, "svr_enable_ids"));
+  svr_pick = reinterpret_cast<decltype(svr_pick)>(dlsym(handle, "svr_pick"));
   return ok;
 }
 void SvrApi::unload() {
@@ -69,7 +71,8 @@ void Node::Draw(const mat4& top_matrix, DrawContext& ctx) {  // src/vk_types.h:1
 }
 void MeshNode::Draw(const mat4& top_matrix, DrawContext& ctx) {  // src/vk_engine.cpp:1716-1736
   mat4 node_matrix = svrm::mul(world_transform, top_matrix);     // world * top, as written there
-  for (auto& s : mesh->surfaces) {
+  for (size_t si = 0; si < mesh->surfaces.size(); si++) {
+    const GeoSurface& s = mesh->surfaces[si];
     SvrRenderObject obj{};
     obj.material = s.material->handle;
     obj.index_count = s.count;
@@ -79,8 +82,10 @@ void MeshNode::Draw(const mat4& top_matrix, DrawContext& ctx) {  // src/vk_engin
     std::memcpy(obj.transform, node_matrix.data(), 64);
     if (s.material->pass_type == SVR_PASS_TRANSPARENT)
       ctx.transparent_surfaces.push_back(obj);
-    else
+    else {
       ctx.opaque_surfaces.push_back(obj);
+      ctx.opaque_sources.emplace_back(mesh.get(), (uint32_t)si);
+    }
   }
   Node::Draw(top_matrix, ctx);
 }
@@ -188,6 +193,7 @@ std::shared_ptr<MaterialInstance> SvrEngine::write_material(int pass, const floa
 void SvrEngine::update_scene() {  // src/vk_engine.cpp:1479-1512
   auto t0 = std::chrono::system_clock::now();
   main_draw_context.opaque_surfaces.clear();
+  main_draw_context.opaque_sources.clear();
   main_camera.update();
   mat4 view = main_camera.get_view_matrix();
   for (auto& kv : loaded_scenes) kv.second->Draw(svrm::identity(), main_draw_context);
@@ -294,6 +300,42 @@ bool SvrEngine::draw_geometry() {  // src/vk_engine.cpp:1357-1477: the whole bod
   stats.mesh_draw_time = st.mesh_draw_time;
   main_draw_context.opaque_surfaces.clear();
   main_draw_context.transparent_surfaces.clear();
+  // the IDs of this pass count its opaque list as given (a draw list's too: sync_draw_list made it the list's order)
+  drawn_sources.swap(main_draw_context.opaque_sources);
+  main_draw_context.opaque_sources.clear();
+  return true;
+}
+
+bool SvrEngine::enable_ids() {
+  if (!api.svr_enable_ids || !api.svr_pick) {
+    error = "this library has no ID target (include/svr_ids.h)";
+    return false;
+  }
+  if (api.svr_enable_ids(ctx, 1)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::pick(uint32_t x, uint32_t y, Pick& out) {
+  out = Pick{};
+  uint32_t id[2] = {0, 0};
+  if (!api.svr_pick || api.svr_pick(ctx, x, y, id)) {
+    error = api.svr_pick ? api.svr_last_error() : "this library has no ID target (include/svr_ids.h)";
+    return false;
+  }
+  if (id[0] == 0) return true;
+  if (id[0] > drawn_sources.size()) {
+    error = "pick: object " + std::to_string(id[0]) + " beyond the frame's " + std::to_string(drawn_sources.size()) + " opaque objects";
+    return false;
+  }
+  const auto& src = drawn_sources[id[0] - 1];
+  out.hit = true;
+  out.object = id[0];
+  out.primitive = id[1];
+  out.mesh = src.first->name;
+  out.surface = src.second;
   return true;
 }
 

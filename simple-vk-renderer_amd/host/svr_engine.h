@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/svr_draw_list.h"
+#include "../../include/svr_ids.h"
 #include "svr_math.h"
 
 namespace svrhost {
@@ -34,6 +35,8 @@ struct SvrApi {
   SVR_FN(svr_draw_background) SVR_FN(svr_read_swapchain) SVR_FN(svr_copy_to_swapchain) SVR_FN(svr_set_option)
   // include/svr_draw_list.h: optional (the HIP library has them, the oracle does not); needed by SvrEngine::retained
   SVR_FN(svr_create_draw_list) SVR_FN(svr_update_draw_list) SVR_FN(svr_destroy_draw_list) SVR_FN(svr_draw_list)
+  // include/svr_ids.h: optional as well (HIP library only); needed by SvrEngine::pick
+  SVR_FN(svr_enable_ids) SVR_FN(svr_pick)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -71,6 +74,8 @@ struct MeshAsset {  // src/vk_loader.h:24-28
 };
 struct DrawContext {  // src/vk_engine.h:40-43
   std::vector<SvrRenderObject> opaque_surfaces, transparent_surfaces;
+  // where each opaque object came from (mesh, surface index): what an ID (include/svr_ids.h) names, object - 1
+  std::vector<std::pair<const MeshAsset*, uint32_t>> opaque_sources;
 };
 
 struct Node {  // src/vk_types.h:150-170
@@ -151,6 +156,17 @@ struct SvrEngine {
   bool read_swapchain(std::vector<uint8_t>& out);
   bool read_color_rgba16f(std::vector<uint16_t>& out);
   bool read_depth(std::vector<float>& out);
+  // Object picking (include/svr_ids.h): enable_ids() before the frames; pick() after one reads the pixel's ID of the last
+  // frame drawn and names what won it.  hit = false where no opaque object did.
+  struct Pick {
+    bool hit = false;
+    uint32_t object = 0, primitive = 0;  // object: the RenderObject's 1-based position in the frame's opaque list
+    std::string mesh;                    // MeshAsset::name
+    uint32_t surface = 0;                // index into MeshAsset::surfaces
+  };
+  std::vector<std::pair<const MeshAsset*, uint32_t>> drawn_sources;  // opaque_sources of the frame drawn last
+  bool enable_ids();
+  bool pick(uint32_t x, uint32_t y, Pick& out);
 };
 
 }  // namespace svrhost
