@@ -310,6 +310,290 @@ def empty_frame(lib, size=40):
     return rig.finish()
 
 
+# ---------------------------------------------------------------------------------------------- hierarchical depth test
+# Opaque scenes aimed at the tile kernel's hierarchical depth test (csrc/k_tile.hip: the occluder claim and the 8x8
+# block minima of scan_columns, the deep-bin filter of tile_body).  That test only runs on bins of more than 64 opaque
+# triangles, so every tile these scenes aim at gets more.  The geometry is given in pixels, (px, py, depth), and placed
+# in clip space with w = 1: the viewport maps it back exactly (x_s = px, y_s = py, depth = z), so pixel centres,
+# sub-pixel offsets and depths are what the numbers say.  Each layer is one mesh object.  hiz_geometry(name) returns a
+# scene's layers without rendering it, for the CPU checks of what each scene reaches (tests/test_hiz_scenarios.py).
+SUB = 1.0 / 256.0  # one step of the 24.8 snap (DESIGN C4)
+
+
+class Layer:
+    def __init__(self, tris, color):
+        self.tris = np.asarray(tris, dtype=np.float64).reshape(-1, 3, 3)  # (triangle, vertex, (px, py, z))
+        self.color = color
+
+
+class HizScene:
+    def __init__(self, w, h, layers, scissor=None, color_format=A.COLOR_RGBA16F):
+        self.w, self.h, self.layers, self.scissor, self.color_format = w, h, layers, scissor, color_format
+
+
+def px_quad(x0, y0, x1, y1, z):
+    """The rectangle [x0, x1] x [y0, y1] in pixels (edges on pixel boundaries cover whole pixels): two triangles."""
+    return [[(x0, y0, z), (x1, y0, z), (x1, y1, z)], [(x0, y0, z), (x1, y1, z), (x0, y1, z)]]
+
+
+def tile_occluder(tx, ty, z):
+    """One triangle that covers tile (tx, ty) and reaches at most 31 pixels into the tiles right of and below it: its
+    right angle one pixel above and left of the tile, legs 65.5 px.  Scenes with such occluders put their aimed tiles
+    on even tile coordinates (SLOTS) and leave the odd ones to the overhang."""
+    ox, oy = 32.0 * tx, 32.0 * ty
+    return [(ox - 1, oy - 1, z), (ox + 64.5, oy - 1, z), (ox - 1, oy + 64.5, z)]
+
+
+SLOTS = [(0, 0), (2, 0), (0, 2), (2, 2)]
+
+
+def render_hiz(lib, sc):
+    rig = Rig(lib, sc.w, sc.h, sc.color_format, background=(0, 0, 0, 1))
+    mat = rig.material()
+    ros = []
+    for layer in sc.layers:
+        t = layer.tris
+        if not len(t):
+            continue
+        pos = np.empty((len(t) * 3, 3), dtype=f32)
+        pos[:, 0] = (t[:, :, 0].reshape(-1) * 2.0 / sc.w - 1.0).astype(f32)
+        pos[:, 1] = (t[:, :, 1].reshape(-1) * 2.0 / sc.h - 1.0).astype(f32)
+        pos[:, 2] = t[:, :, 2].reshape(-1).astype(f32)  # (keeps -0.0)
+        mesh = rig.r.upload_mesh(np.arange(len(pos), dtype=np.uint32), make_vertices(pos, colors=[layer.color] * len(pos)))
+        ros.append(render_object(mesh, mat, 0, len(pos), extents=(1e6, 1e6, 1e6)))
+    if sc.scissor:
+        rig.r.set_scissor(*sc.scissor)
+    rig.draw(identity_scene(), ros)
+    return rig.finish()
+
+
+def _padding(rng, tiles, per_tile, zlo, zhi, size=(0.6, 3.0)):
+    """per_tile small triangles inside each 32x32 tile (tx, ty), depths in [zlo, zhi)."""
+    tris = []
+    for tx, ty in tiles:
+        c = rng.uniform(0, 32, (per_tile, 1, 2)) + (32 * tx, 32 * ty)
+        v = c + rng.uniform(-1, 1, (per_tile, 3, 2)) * rng.uniform(*size, (per_tile, 1, 1))
+        v = np.clip(v, (32 * tx, 32 * ty), (32 * tx + 31.99, 32 * ty + 31.99))
+        z = np.repeat(rng.uniform(zlo, zhi, (per_tile, 1, 1)), 3, axis=1)
+        tris.append(np.concatenate([v, z], axis=2))
+    return np.concatenate(tris)
+
+
+RED, GREEN, BLUE, GREY = (1, 0, 0, 1), (0, 1, 0, 1), (0, 0, 1, 1), (0.5, 0.5, 0.5, 1)
+
+# hiz_occluder_edges: one slot per tile, tile rows 0, 2, 4, ... (the odd rows take what the occluders overhang).
+# Slot (corner, offset, flip): one triangle covering its tile whose two legs run along the tile's first or last row and
+# column — through the pixel centres (offset 0), one sub-pixel step outside them (+1: the row is covered, the claim can
+# hold) or inside (-1: the row is not covered).  The right angle sits at the corner; the legs run 36 px along y and far
+# along x, away from the corner, so the hypotenuse passes beyond the tile.  flip swaps the winding.
+EDGE_SLOTS = [(corner, off, flip) for off in (0, 1, -1) for corner in ((0, 0), (1, 0), (0, 1), (1, 1))
+              for flip in ((0, 1) if off == 0 else (off < 0,))]
+EDGE_Z_FRONT, EDGE_Z_BACK, EDGE_Z_BACK2 = 0.75, 0.5, 0.375
+
+
+def edge_slot_origin(k):
+    # corner x = 1 (legs run left) goes in tile column 0, corner x = 0 (legs run right) in column 1: the far leg leaves
+    # the frame without crossing the other column's slots
+    corner = EDGE_SLOTS[k][0]
+    return (0 if corner[0] else 32), 64 * _edge_row(k)
+
+
+def _edge_row(k):
+    col = 0 if EDGE_SLOTS[k][0][0] else 1
+    return sum(1 for j in range(k) if (0 if EDGE_SLOTS[j][0][0] else 1) == col)
+
+
+def hiz_occluder_edges_geometry(seed=31):
+    rng = np.random.default_rng(seed)
+    rows = max(_edge_row(k) for k in range(len(EDGE_SLOTS))) + 1
+    w, h = 64, 64 * rows
+    front, back, back2, tiles = [], [], [], []
+    for k, ((cx, cy), off, flip) in enumerate(EDGE_SLOTS):
+        ox, oy = edge_slot_origin(k)
+        tiles.append((ox // 32, oy // 32))
+        sx, sy = (1, -1)[cx], (1, -1)[cy]  # legs run away from the corner
+        px = ox + (31.5 if cx else 0.5) - sx * off * SUB
+        py = oy + (31.5 if cy else 0.5) - sy * off * SUB
+        a, b, c = (px, py, EDGE_Z_FRONT), (px + sx * 4000.0, py, EDGE_Z_FRONT), (px, py + sy * 36.0, EDGE_Z_FRONT)
+        front.append([a, c, b] if flip else [a, b, c])
+        back += px_quad(ox, oy, ox + 32, oy + 32, EDGE_Z_BACK)
+        back2 += px_quad(ox - 8, oy - 8, ox + 40, oy + 40, EDGE_Z_BACK2)  # larger, behind, drawn after
+    pad = _padding(rng, tiles, 200, 0.05, 0.35)
+    layers = [Layer(pad, GREY), Layer(back, BLUE), Layer(front, RED), Layer(back2, GREEN)]
+    return HizScene(w, h, layers)
+
+
+# hiz_depth_margins: one tile (SLOTS) per kind of front plane — constant, sloped, steep (|dz1|, |dz2| >> z0) and constant
+# again under near-degenerate slivers.  The front is one triangle over its tile, drawn twice (the later copy, GREEN, must
+# win every pixel: ties go to the later object).  Behind it come full-tile layers 64, 8, 2 and 1 ulps and about 2^-21
+# relative below the front's smallest pixel depth in the tile, and last a layer AT it (BLUE: wins where it ties).
+MARGIN_ULPS = (64, 8, 2, 1)
+MARGIN_KINDS = ("constant", "sloped", "steep", "slivers")
+
+
+def _front_plane(kind, ox, oy):
+    """One triangle covering the tile at (ox, oy): (px, py, z) x 3 (tile_occluder)."""
+    z = {"sloped": (0.55, 0.7, 0.6), "steep": (0.0009765625, 0.9990234375, 0.9990234375)}.get(kind, (0.625,) * 3)
+    return [(x, y, zz) for (x, y, _), zz in zip(tile_occluder(ox // 32, oy // 32, 0.0), z)]
+
+
+def _plane_min_depth(tri, ox, oy):
+    """The smallest depth the rasteriser's float chain (DESIGN C5) gives the pixels of the tile: the oracle's setup in
+    numpy (w = 1: vertices are snapped pixels, depths as given)."""
+    X = np.rint(np.array([v[0] for v in tri]) * 256).astype(np.int64)
+    Y = np.rint(np.array([v[1] for v in tri]) * 256).astype(np.int64)
+    Z = np.array([v[2] for v in tri], dtype=f32)
+    area2 = (X[1] - X[0]) * (Y[2] - Y[0]) - (X[2] - X[0]) * (Y[1] - Y[0])
+    if area2 < 0:
+        X[[1, 2]], Y[[1, 2]], Z[[1, 2]], area2 = X[[2, 1]], Y[[2, 1]], Z[[2, 1]], -area2
+    gy, gx = np.mgrid[oy:oy + 32, ox:ox + 32]
+    PX, PY = gx.astype(np.int64) * 256 + 128, gy.astype(np.int64) * 256 + 128
+    e = []
+    for i in (1, 2):
+        a, b = (i + 1) % 3, (i + 2) % 3
+        e.append((X[b] - X[a]) * (PY - Y[a]) - (Y[b] - Y[a]) * (PX - X[a]))
+    inv = f32(1.0) / f32(area2)
+    b1, b2 = e[1].astype(f32) * inv, e[0].astype(f32) * inv  # edge 1 is opposite vertex 1: b1 (all inside: no bias)
+    dz1, dz2 = f32(Z[1] - Z[0]), f32(Z[2] - Z[0])
+    inner = (b1.astype(np.float64) * dz1 + Z[0]).astype(f32)  # fma: the product of two floats is exact in double
+    z = (b2.astype(np.float64) * dz2 + inner).astype(f32)
+    return f32(np.clip(z, 0, 1).min())
+
+
+def hiz_depth_margins_geometry(seed=37):
+    rng = np.random.default_rng(seed)
+    fronts, zmins, tiles = [], [], []
+    for k, kind in enumerate(MARGIN_KINDS):
+        tx, ty = SLOTS[k]
+        ox, oy = 32 * tx, 32 * ty
+        tiles.append((tx, ty))
+        tri = _front_plane(kind, ox, oy)
+        fronts.append(tri)
+        zmins.append(_plane_min_depth(tri, ox, oy))
+    backs = {}
+    for u in MARGIN_ULPS:
+        backs[u] = sum((px_quad(32 * tx, 32 * ty, 32 * tx + 32, 32 * ty + 32,
+                                float(np.nextafter(f32(zm), f32(0)) if u == 1 else f32(zm) - f32(u) * np.spacing(f32(zm))))
+                        for (tx, ty), zm in zip(tiles, zmins)), [])
+    rel = sum((px_quad(32 * tx, 32 * ty, 32 * tx + 32, 32 * ty + 32, float(f32(zm * (1.0 - 2.0 ** -21))))
+               for (tx, ty), zm in zip(tiles, zmins)), [])
+    tie = sum((px_quad(32 * tx, 32 * ty, 32 * tx + 32, 32 * ty + 32, float(zm)) for (tx, ty), zm in zip(tiles, zmins)), [])
+    # slivers: areas of a few 1/256 px steps (inv_area in the thousands), across the last slot at the front's depth
+    # and one ulp either side of it
+    ox, oy = 32 * SLOTS[3][0], 32 * SLOTS[3][1]
+    zf = f32(0.625)
+    slivers = []
+    for j in range(24):
+        y = oy + 1.5 + j - SUB * (1 + j % 2)  # just above a row of pixel centres: the sliver crosses it
+        zz = float([np.nextafter(zf, f32(0)), zf, np.nextafter(zf, f32(1))][j % 3])
+        slivers.append([(ox - 28.0, y, zz), (ox + 3000.0, y + SUB * (1 + j % 4), zz), (ox + 17.0, y + SUB * (2 + j % 3), zz)])
+    pad = _padding(rng, tiles, 200, 0.005, 0.04)  # behind every front, the steep one included
+    layers = [Layer(pad, GREY), Layer(fronts, RED), Layer(fronts, GREEN)]
+    layers += [Layer(backs[u], GREY) for u in MARGIN_ULPS] + [Layer(rel, GREY), Layer(slivers, (1, 1, 0, 1)), Layer(tie, BLUE)]
+    return HizScene(96, 96, layers)
+
+
+# hiz_deep_opaque_N: N opaque layers of two triangles over each of four tiles (one object per layer: each tile's bin
+# holds 2 N triangles).  Depths come from a short list (repeats), in random order; a layer covers a tile whole, a run
+# of its 8x8 blocks, or an arbitrary sub-pixel rectangle.  The nearest layer of each tile (FRONT_Z, full cover) lands
+# late in tile 0 (a later filter window than most of what it hides), early in tile 1, twice in tile 2 (the later copy
+# wins) and in tile 3 covers only half the tile's blocks.
+DEEP_FRONT_Z = 0.875
+
+
+def hiz_deep_opaque_geometry(n_layers, w=64, h=64, seed=41, scissor=None):
+    rng = np.random.default_rng(seed + n_layers)
+    levels = np.round(rng.uniform(0.1, 0.8, 24), 3)
+    tiles = [(0, 0), (1, 0), (0, 1), (1, 1)]
+    front_at = {0: [int(n_layers * 0.8)], 1: [3], 2: [2, n_layers - 2], 3: [n_layers // 2]}
+    layers = []
+    for i in range(n_layers):
+        tris = []
+        for t, (tx, ty) in enumerate(tiles):
+            ox, oy = 32 * tx, 32 * ty
+            if i in front_at[t]:
+                if t == 3:
+                    tris += px_quad(ox, oy, ox + 16, oy + 32, DEEP_FRONT_Z)
+                else:
+                    tris += px_quad(ox, oy, ox + 32, oy + 32, DEEP_FRONT_Z)
+                continue
+            z = float(rng.choice(levels))
+            kind = rng.integers(0, 10)
+            if kind < 6:
+                tris += px_quad(ox, oy, ox + 32, oy + 32, z)
+            elif kind < 8:
+                bx0, by0 = rng.integers(0, 4, 2)
+                bx1, by1 = bx0 + rng.integers(1, 5 - bx0), by0 + rng.integers(1, 5 - by0)
+                tris += px_quad(ox + 8 * bx0, oy + 8 * by0, ox + 8 * bx1, oy + 8 * by1, z)
+            else:
+                x0, y0 = rng.uniform(0, 24, 2)
+                tris += px_quad(ox + x0, oy + y0, ox + x0 + rng.uniform(1, 32 - x0), oy + y0 + rng.uniform(1, 32 - y0), z)
+        c = (0.2 + 0.8 * ((i * 37) % 101) / 100.0, 0.2 + 0.8 * ((i * 53) % 97) / 96.0, 0.2 + 0.8 * ((i * 71) % 89) / 88.0, 1)
+        layers.append(Layer(tris, c))
+    return HizScene(w, h, layers, scissor=scissor)
+
+
+# hiz_clipped_occluders: tile-covering occluders (SLOTS) that the clipper cuts (DESIGN C2), in front of 600-deep opaque
+# stacks: slot 0's reaches beyond the guard band (x = -40 000 px), slot 1's crosses the near plane (z > w) below its
+# tile, slot 2's does both, and in slot 3 the near plane cuts through the tile itself (what lies beyond it is not
+# drawn: the stack shows there).
+def hiz_clipped_occluders_geometry(seed=43, n_stack=600):
+    rng = np.random.default_rng(seed)
+    occ = [
+        [(-40000.0, -1.0, 0.8), (64.5, -1.0, 0.8), (-1.0, 64.5, 0.8)],
+        [(63.0, -1.0, 0.8), (128.5, -1.0, 0.8), (63.0, 64.5, 1.15)],
+        [(-40000.0, 63.0, 0.8), (64.5, 63.0, 0.8), (-1.0, 128.5, 1.15)],
+        [(63.0, 63.0, 0.8), (128.5, 63.0, 1.4), (63.0, 128.5, 0.8)],
+    ]
+    stack = []
+    for i in range(n_stack):
+        z = float(np.round(rng.uniform(0.1, 0.75), 2))
+        stack.append(Layer(sum((px_quad(32 * tx, 32 * ty, 32 * tx + 32, 32 * ty + 32, z) for tx, ty in SLOTS), []), GREY))
+    return HizScene(96, 96, stack[:n_stack // 2] + [Layer(occ, RED)] + stack[n_stack // 2:])
+
+
+# hiz_depth_extremes: tile-covering occluders (SLOTS) at depth 1.0 (slot 0), 0.0 (slot 1) and clip z = -0.0 (slots 2,
+# 3: its fragments store +0.0, DESIGN C5), with full-tile layers at the same depth drawn before (slots 0, 3) and after
+# (slots 0, 1, 2): ties go to the later layer.  Small triangles pad slot 0 from behind and the others from in front.
+def hiz_depth_extremes_geometry(seed=47):
+    rng = np.random.default_rng(seed)
+    zs = [1.0, 0.0, -0.0, -0.0]
+    occ = [tile_occluder(tx, ty, z) for (tx, ty), z in zip(SLOTS, zs)]
+
+    def tie_layer(k, z):
+        tx, ty = SLOTS[k]
+        return px_quad(32 * tx, 32 * ty, 32 * tx + 32, 32 * ty + 32, z)
+
+    before = Layer(tie_layer(0, 1.0) + tie_layer(3, 0.0), BLUE)
+    after = Layer(tie_layer(0, 1.0) + tie_layer(1, 0.0) + tie_layer(2, 0.0) + tie_layer(0, 0.5), GREEN)
+    pad_back = _padding(rng, SLOTS[:1], 150, 0.05, 0.9)
+    pad_front = _padding(rng, SLOTS[1:], 200, 0.05, 0.9, size=(0.6, 1.5))
+    return HizScene(96, 96, [Layer(pad_back, GREY), before, Layer(occ, RED), after, Layer(pad_front, GREY)])
+
+
+HIZ_GEOMETRY = {
+    "hiz_occluder_edges": hiz_occluder_edges_geometry,
+    "hiz_depth_margins": hiz_depth_margins_geometry,
+    "hiz_deep_opaque_65": lambda: hiz_deep_opaque_geometry(33),
+    "hiz_deep_opaque_129": lambda: hiz_deep_opaque_geometry(65),
+    "hiz_deep_opaque_1025": lambda: hiz_deep_opaque_geometry(513),
+    "hiz_deep_opaque_2100": lambda: hiz_deep_opaque_geometry(1050),
+    "hiz_clipped_occluders": hiz_clipped_occluders_geometry,
+    "hiz_depth_extremes": hiz_depth_extremes_geometry,
+    # the stacks at a size that is not a multiple of 32 (the tiles at the right and bottom are cut), and under a
+    # scissor that cuts tiles mid-row and mid-column
+    "hiz_deep_opaque_odd_size": lambda: hiz_deep_opaque_geometry(720, w=53, h=45, seed=3),
+    "hiz_deep_opaque_scissor": lambda: hiz_deep_opaque_geometry(720, seed=5, scissor=(5, 11, 50, 40)),
+    "hiz_deep_opaque_rgba8": lambda: _rgba8(hiz_deep_opaque_geometry(160, seed=7)),
+    "hiz_occluder_edges_rgba8": lambda: _rgba8(hiz_occluder_edges_geometry(seed=53)),
+}
+
+
+def _rgba8(sc):
+    sc.color_format = A.COLOR_RGBA8
+    return sc
+
+
 SCENARIOS = {
     "shading_up": lambda lib: shading_constants(lib, (0, 1, 0)),
     "shading_side": lambda lib: shading_constants(lib, (1, 0, 0)),
@@ -349,3 +633,4 @@ SCENARIOS = {
     "ragged": ragged_draws,
     "empty": empty_frame,
 }
+SCENARIOS.update({name: (lambda lib, make=make: render_hiz(lib, make())) for name, make in HIZ_GEOMETRY.items()})
