@@ -181,33 +181,35 @@ struct SvrContext {
   static const int NSETS = 4;  // stage 1 of a small pass may run three passes ahead of the tile stage; a large one keeps to one (submit_pass)
   PassSet sets[NSETS];
   int set_pos = 0;
-  // operation log (see "the operation log" below)
+  // operation log (see "the operation log" below): a pass, or a fill of the colour target (every other operation)
+  enum class OpKind { Pass, Clear, Background, Blit };
+  enum class PassInput { Draws, Objects, List };  // what a pass reads: the one place that says so (P.flatten follows it)
   struct LoggedOp {
-    bool is_pass = false;
-    uint32_t seq = 0;  // passes: running number, reported by the device if the pass overflows
-    bool timed = false;  // op_start/op_done of the slot bracket the tile kernel: fold into the running mean at retirement
+    OpKind kind = OpKind::Pass;
     int slot = 0;  // index into h_counters / op_done
-    int fill_kind = 0;  // not a pass: 0 clear, 1 background effect, 2 blit to the swapchain image
-    void* clear_rows = nullptr;  // clear: first row, pixel count, format, encoded texel
-    uint32_t clear_pixels = 0;
-    int clear_fmt = 0;
-    uint64_t clear_packed = 0;
-    void* target = nullptr;  // background / blit: colour target, its extent, the scissor's rows
+    // a pass
+    uint32_t seq = 0;  // running number, reported by the device if the pass overflows
+    bool timed = false;  // op_start/op_done of the slot bracket the tile kernel: fold into the running mean at retirement
+    FrameParams P{};  // parameters as recorded
+    PassInput input = PassInput::Draws;
+    std::vector<DrawDesc> draws;  // Draws: records built on the host
+    std::vector<SvrRenderObject> objects;  // Objects: the caller's (opaque, then transparent), flattened on the device
+    uint32_t n_opaque_obj = 0, n_transparent_obj = 0;  // Objects and List
+    // List: the version of a resident draw list it was enqueued with (svr_draw_list): the objects stay on the device
+    std::shared_ptr<const ListVersion> list;
+    bool flattened() const { return input != PassInput::Draws; }
+    // a fill: colour target, its format and extent, the rows it writes
+    void* target = nullptr;
+    int target_fmt = 0;
     uint32_t tw = 0, th = 0, y_first = 0, n_rows = 0;
-    int bg_effect = 0;
+    uint64_t clear_packed = 0;  // Clear: the encoded texel
+    int bg_effect = 0;  // Background
     float bg_data[16] = {};
-    void* blit_dst = nullptr;
+    void* blit_dst = nullptr;  // Blit: the swapchain image
     uint32_t blit_w = 0, blit_h = 0;
     int blit_fmt = 0;
     uint32_t blit_rstride = 1, blit_roff = 0, blit_row_end = 0;  // identity blits of an interleaved pass: its tile rows only
     uint32_t* blit_status = nullptr;
-    FrameParams P{};  // pass: parameters as recorded + its draw list
-    std::vector<DrawDesc> draws;
-    // device-flattened pass: the caller's objects (opaque, then transparent) instead of a draw list
-    std::vector<SvrRenderObject> objects;
-    uint32_t n_opaque_obj = 0, n_transparent_obj = 0;
-    // ... or the version of a resident draw list it was enqueued with (svr_draw_list): the objects stay on the device
-    std::shared_ptr<const ListVersion> list;
   };
   std::deque<LoggedOp> log;
   hipEvent_t op_done[MAX_OPS] = {};
@@ -351,9 +353,11 @@ void arena_free(SvrContext* ctx, size_t off, size_t bytes) {
   }
 }
 
-// (re)upload the binding table: one slot per material + one scratch slot
+// (re)upload the binding table: one slot per material + one scratch slot.  Without a scratch binding only when it is
+// stale (a material was added, or svr_draw_tex_image took the scratch slot).
 int upload_tex_table(SvrContext* ctx, const TexBinding* scratch) {
   size_t n = ctx->materials.size() + 1;
+  if (!scratch && ctx->tex_slots == n) return SVR_OK;
   std::vector<TexBinding> host(n);
   for (size_t i = 0; i < ctx->materials.size(); i++) {
     const MaterialRes& m = ctx->materials[i];
@@ -445,9 +449,12 @@ int bind_pass_buffers(SvrContext* ctx, FrameParams& P, int set_index) {
 // -> ev_bin.  Stage 2 (caller's stream): wait ev_bin, tile kernel, counters to the host
 // (report_kernel) -> op_done.  The caller sees stream order (everything it enqueued before the call precedes the tile
 // stage, the only one that touches the targets); stage 1 depends on host inputs alone, so it overlaps
-// the tile stages of the passes before it.
-int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& draws, int op_slot, uint32_t seq, bool pipe,
-                const SvrContext::LoggedOp* flat_op = nullptr) {
+// the tile stages of the passes before it.  The op holds the pass: its parameters, number, log slot and input.
+int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
+  FrameParams P = op.P;
+  const int op_slot = op.slot;
+  const std::vector<DrawDesc>& draws = op.draws;
+  const bool flatten = op.flattened(), resident = op.input == SvrContext::PassInput::List;
   // queue capacities: generous first guesses; overflow -> replay (recover_from_overflow)
   if (ctx->debug_caps) {  // SVR_OPT_QUEUE_CAPS: start tiny so that tests reach the replay path
     ctx->clip_cap = std::max<uint32_t>(ctx->clip_cap, ctx->debug_caps);
@@ -500,11 +507,11 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
     ctx->last_g = g;
   }
   // per-pass inputs: draws + chunks through pinned staging, one copy
-  const bool resident = flat_op && flat_op->list;  // the objects are a draw list's device copy: nothing to stage
-  const size_t n_objects = flat_op ? (size_t)flat_op->n_opaque_obj + flat_op->n_transparent_obj : 0;
-  size_t draw_bytes = (flat_op ? n_objects : draws.size()) * sizeof(DrawDesc), chunk_bytes = (size_t)P.n_chunks * sizeof(WaveChunk);
+  // (resident: the objects are a draw list's device copy, nothing to stage)
+  const size_t n_objects = flatten ? (size_t)op.n_opaque_obj + op.n_transparent_obj : 0;
+  size_t draw_bytes = (flatten ? n_objects : draws.size()) * sizeof(DrawDesc), chunk_bytes = (size_t)P.n_chunks * sizeof(WaveChunk);
   if (int e = set.inputs.ensure(std::max<size_t>(draw_bytes + chunk_bytes + 16, 256))) return e;
-  if (flat_op)
+  if (flatten)
     if (int e = set.flat.ensure(n_objects * (16 + sizeof(SvrRenderObject)) + 128)) return e;
   if (int e = bind_pass_buffers(ctx, P, set_index)) return e;
   // How far stage 1 runs ahead.  A pass of few tiles (a band of a sharded frame: stage 1 56 us, tiles 50 us) is bounded
@@ -518,12 +525,12 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
     else if (set.used) HIPCHK(hipStreamWaitEvent(g, set.ev_tile, 0));
   }
   void* stage = nullptr;
-  if (int e = stage_buffer(ctx, op_slot, (flat_op ? (resident ? 0 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
+  if (int e = stage_buffer(ctx, op_slot, (flatten ? (resident ? 0 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
   P.host_counters = &ctx->h_counters[op_slot];
   P.host_row_cost = ctx->h_row_cost + (size_t)op_slot * ROW_COST_MAX;
-  P.op_seq = seq;
-  if (flat_op) {  // the objects themselves are the input; cull, sort, draw records and chunks happen on the device
-    if (!resident) std::memcpy(stage, flat_op->objects.data(), n_objects * sizeof(SvrRenderObject));
+  P.op_seq = op.seq;
+  if (flatten) {  // the objects themselves are the input; cull, sort, draw records and chunks happen on the device
+    if (!resident) std::memcpy(stage, op.objects.data(), n_objects * sizeof(SvrRenderObject));
   } else {
     std::memcpy(stage, draws.data(), draw_bytes);
     WaveChunk* ch = reinterpret_cast<WaveChunk*>((char*)stage + draw_bytes);
@@ -547,14 +554,14 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
       if (!ctx->tev[ts][k]) HIPCHK(hipEventCreate(&ctx->tev[ts][k]));
   }
   // inputs out of the staging buffer + zero the counters, class counters and tile_count (adjacent)
-  launch_prologue(stage, set.inputs.p, flat_op ? 0 : draw_bytes + chunk_bytes, P.counters,
-                  TILE_HEAD_BYTES + (size_t)P.n_tiles * 2 * sizeof(uint32_t), flat_op ? 0u : (uint32_t)draws.size(), P.scene, g);
-  if (flat_op) {
+  launch_prologue(stage, set.inputs.p, flatten ? 0 : draw_bytes + chunk_bytes, P.counters,
+                  TILE_HEAD_BYTES + (size_t)P.n_tiles * 2 * sizeof(uint32_t), flatten ? 0u : (uint32_t)draws.size(), P.scene, g);
+  if (flatten) {
     FlattenParams F;
     std::memset(&F, 0, sizeof(F));
-    F.objects = resident ? flat_op->list->dev : (const SvrRenderObject*)stage;
-    F.n_opaque = flat_op->n_opaque_obj;
-    F.n_transparent = flat_op->n_transparent_obj;
+    F.objects = resident ? op.list->dev : (const SvrRenderObject*)stage;
+    F.n_opaque = op.n_opaque_obj;
+    F.n_transparent = op.n_transparent_obj;
     std::memcpy(F.viewproj, P.scene.viewproj, 64);
     F.meshes = (const MeshEntry*)ctx->mesh_table.p;
     F.materials = (const MatEntry*)ctx->mat_table.p;
@@ -566,7 +573,7 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
     F.chunks = (WaveChunk*)((char*)set.inputs.p + draw_bytes);
     F.counters = P.counters;
     F.ids = P.ids ? 1u : 0u;
-    F.obj_ids = (P.ids && resident) ? flat_op->list->obj_ids : nullptr;
+    F.obj_ids = (P.ids && resident) ? op.list->obj_ids : nullptr;
     if (resident)
       launch_list_flatten(F, g);
     else
@@ -594,29 +601,30 @@ int submit_pass(SvrContext* ctx, FrameParams P, const std::vector<DrawDesc>& dra
   set.ev_tile = ctx->op_done[op_slot];
   set.used = true;
   ctx->last = P;
-  ctx->last_n_draws = flat_op ? 0u : (uint32_t)draws.size();
+  ctx->last_n_draws = flatten ? 0u : (uint32_t)draws.size();
   return SVR_OK;
 }
 
-void note_pass_stats(SvrContext* ctx, const FrameParams&, const Counters& c) {  // instrumented passes only
-  ctx->stats.bin_entries = c.total_entries;
-  ctx->stats.rasterized_fragments = c.rasterized;
-  ctx->stats.shaded_fragments = c.shaded;
-  ctx->stats.binned_triangles = c.binned;
-}
-
-// the tile rows' costs of a finished pass (posted by its tile kernel before anything else): svr_get_row_costs
-void note_row_costs(SvrContext* ctx, const FrameParams& Pk, int slot) {
-  const uint32_t* src = ctx->h_row_cost + (size_t)slot * ROW_COST_MAX;
-  ctx->row_cost.assign(src, src + std::min<uint32_t>(Pk.tiles_y, ROW_COST_MAX));
-  ctx->row_cost_y0 = Pk.sy;
-  ctx->row_cost_rows = Pk.sh;
-}
-
-void note_flatten_stats(SvrContext* ctx, const Counters& c) {  // device-flattened passes learn these late
-  ctx->stats.drawcall_count = (int32_t)c.flat_draws;
-  ctx->stats.triangle_count = (int32_t)c.flat_tris;
-  ctx->stats.culled_draws = c.flat_culled;
+// what the host learns from a pass that finished without overflowing, with its counters c
+int retire_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, const Counters& c) {
+  if (op.P.instrument) {
+    ctx->stats.bin_entries = c.total_entries;
+    ctx->stats.rasterized_fragments = c.rasterized;
+    ctx->stats.shaded_fragments = c.shaded;
+    ctx->stats.binned_triangles = c.binned;
+    if (c.hiz_bad) return fail(SVR_ERR_DEVICE, "internal check failed: the hierarchical depth test dropped a fragment that wins (" + std::to_string(c.hiz_bad) + ")");
+  }
+  if (op.flattened()) {  // device-flattened passes learn these late
+    ctx->stats.drawcall_count = (int32_t)c.flat_draws;
+    ctx->stats.triangle_count = (int32_t)c.flat_tris;
+    ctx->stats.culled_draws = c.flat_culled;
+  }
+  // the tile rows' costs (posted by its tile kernel before anything else): svr_get_row_costs
+  const uint32_t* src = ctx->h_row_cost + (size_t)op.slot * ROW_COST_MAX;
+  ctx->row_cost.assign(src, src + std::min<uint32_t>(op.P.tiles_y, ROW_COST_MAX));
+  ctx->row_cost_y0 = op.P.sy;
+  ctx->row_cost_rows = op.P.sh;
+  return SVR_OK;
 }
 
 // ---------------------------------------------------------------- the operation log
@@ -634,14 +642,17 @@ int retire_ops(SvrContext* ctx, bool blocking);
 int flush_clear(SvrContext* ctx);
 
 // replaying: the operation is run again by recover_from_overflow (a present then reports 2 instead of 0)
-int submit_clear(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying = false) {  // every logged operation that is not a pass
-  if (op.fill_kind == 0)
-    launch_fill_color(op.clear_rows, op.clear_pixels, op.clear_fmt, op.clear_packed, ctx->d_poison, ctx->stream);
-  else if (op.fill_kind == 1)
-    launch_background(op.target, op.clear_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison, ctx->stream);
-  else
-    launch_blit(op.target, op.clear_fmt, op.tw, op.th, op.blit_dst, op.blit_w, op.blit_h, op.y_first, op.n_rows, op.blit_fmt, ctx->d_poison,
+int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying = false) {
+  if (op.kind == SvrContext::OpKind::Clear) {
+    const size_t px_bytes = op.target_fmt == SVR_COLOR_RGBA16F ? 8 : 4;
+    launch_fill_color((char*)op.target + (size_t)op.y_first * op.tw * px_bytes, op.tw * op.n_rows, op.target_fmt, op.clear_packed,
+                      ctx->d_poison, ctx->stream);
+  } else if (op.kind == SvrContext::OpKind::Background) {
+    launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison, ctx->stream);
+  } else {
+    launch_blit(op.target, op.target_fmt, op.tw, op.th, op.blit_dst, op.blit_w, op.blit_h, op.y_first, op.n_rows, op.blit_fmt, ctx->d_poison,
                 op.blit_rstride, op.blit_roff, op.blit_row_end, op.blit_status, replaying ? 2u : 0u, ctx->stream);
+  }
   HIPCHK(hipGetLastError());
   return SVR_OK;
 }
@@ -653,9 +664,9 @@ int recover_from_overflow(SvrContext* ctx) {
   const uint32_t failed_seq = *(volatile uint32_t*)ctx->h_failed_seq;
   *ctx->h_failed_seq = 0;
   for (SvrContext::LoggedOp& op : ctx->log) {
-    if (!op.is_pass) {
+    if (op.kind != SvrContext::OpKind::Pass) {
       HIPCHK(hipMemsetAsync(ctx->d_poison, 0, sizeof(uint32_t), ctx->stream));
-      if (int e = submit_clear(ctx, op, true)) return e;
+      if (int e = submit_fill(ctx, op, true)) return e;
       continue;
     }
     bool done = false;
@@ -672,7 +683,7 @@ int recover_from_overflow(SvrContext* ctx) {
         ctx->bin_cap = std::max<uint32_t>(ctx->bin_cap * 2u, need + need / 4u);
       }
       HIPCHK(hipMemsetAsync(ctx->d_poison, 0, sizeof(uint32_t), ctx->stream));
-      if (int e = submit_pass(ctx, op.P, op.draws, op.slot, op.seq, false, op.P.flatten ? &op : nullptr)) return e;
+      if (int e = submit_pass(ctx, op, false)) return e;
       HIPCHK(hipStreamSynchronize(ctx->stream));
       HIPCHK(hipMemcpy(&c, ctx->last.counters, sizeof(Counters), hipMemcpyDeviceToHost));
       *ctx->h_failed_seq = 0;
@@ -682,10 +693,7 @@ int recover_from_overflow(SvrContext* ctx) {
       ctx->log.clear();
       return fail(SVR_ERR_OVERFLOW, "a pass kept overflowing its internal queues after 12 replays");
     }
-    if (op.P.instrument) note_pass_stats(ctx, op.P, c);
-    if (op.P.instrument && c.hiz_bad) return fail(SVR_ERR_DEVICE, "internal check failed: the hierarchical depth test dropped a fragment that wins (" + std::to_string(c.hiz_bad) + ")");
-    if (op.P.flatten) note_flatten_stats(ctx, c);
-    note_row_costs(ctx, op.P, op.slot);
+    if (int e = retire_pass(ctx, op, c)) return e;
     ctx->replayed++;
   }
   HIPCHK(hipMemsetAsync(ctx->d_poison, 0, sizeof(uint32_t), ctx->stream));
@@ -700,7 +708,7 @@ int recover_from_overflow(SvrContext* ctx) {
 int retire_ops(SvrContext* ctx, bool blocking) {
   while (!ctx->log.empty()) {
     size_t k = 0;  // first pass at or behind the front
-    while (k < ctx->log.size() && !ctx->log[k].is_pass) k++;
+    while (k < ctx->log.size() && ctx->log[k].kind != SvrContext::OpKind::Pass) k++;
     if (k == ctx->log.size()) {  // only clears left
       if (!blocking) return SVR_OK;
       HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -729,15 +737,9 @@ int retire_ops(SvrContext* ctx, bool blocking) {
         ctx->acc_n++;
       }
     }
-    if (ctx->log[k].P.instrument) note_pass_stats(ctx, ctx->log[k].P, ctx->h_counters[slot]);
-    if (ctx->log[k].P.instrument && ctx->h_counters[slot].hiz_bad) {
-      const uint32_t bad = ctx->h_counters[slot].hiz_bad;
-      ctx->log.erase(ctx->log.begin(), ctx->log.begin() + (long)k + 1);
-      return fail(SVR_ERR_DEVICE, "internal check failed: the hierarchical depth test dropped a fragment that wins (" + std::to_string(bad) + ")");
-    }
-    if (ctx->log[k].P.flatten) note_flatten_stats(ctx, ctx->h_counters[slot]);
-    note_row_costs(ctx, ctx->log[k].P, slot);
+    const int e = retire_pass(ctx, ctx->log[k], ctx->h_counters[slot]);
     ctx->log.erase(ctx->log.begin(), ctx->log.begin() + (long)k + 1);
+    if (e) return e;
   }
   return SVR_OK;
 }
@@ -748,10 +750,10 @@ int log_slot(SvrContext* ctx, int* slot) {
     if (int e = retire_ops(ctx, false)) return e;
     if ((int)ctx->log.size() >= SvrContext::MAX_OPS) {
       bool any_pass = false;
-      for (const SvrContext::LoggedOp& op : ctx->log) any_pass |= op.is_pass;
+      for (const SvrContext::LoggedOp& op : ctx->log) any_pass |= op.kind == SvrContext::OpKind::Pass;
       if (any_pass) {
         for (const SvrContext::LoggedOp& op : ctx->log)
-          if (op.is_pass) {
+          if (op.kind == SvrContext::OpKind::Pass) {
             HIPCHK(hipEventSynchronize(ctx->op_done[op.slot]));
             break;
           }
@@ -766,6 +768,26 @@ int log_slot(SvrContext* ctx, int* slot) {
   return SVR_OK;
 }
 
+// log a fill of the rows [y_first, y_first + n_rows) of a colour target of the context's extent, in a free slot;
+// the caller sets the fields of its kind and submits it (submit_fill)
+int log_fill(SvrContext* ctx, SvrContext::OpKind kind, void* target, int fmt, uint32_t y_first, uint32_t n_rows,
+             SvrContext::LoggedOp** out) {
+  int slot = 0;
+  if (int e = log_slot(ctx, &slot)) return e;
+  ctx->log.emplace_back();
+  SvrContext::LoggedOp& op = ctx->log.back();
+  op.kind = kind;
+  op.slot = slot;
+  op.target = target;
+  op.target_fmt = fmt;
+  op.tw = ctx->W;
+  op.th = ctx->H;
+  op.y_first = y_first;
+  op.n_rows = n_rows;
+  *out = &op;
+  return SVR_OK;
+}
+
 // A clear of whole scissor rows is not run when it is asked for: the pass that follows writes every
 // pixel of those rows anyway (its tile grid covers the scissor), so it takes the clear value for the
 // pixels it does not cover and the separate 8-bytes-per-pixel fill disappears — what a Vulkan renderer
@@ -776,17 +798,10 @@ int flush_clear(SvrContext* ctx) {
   if (!ctx->pending_clear.valid) return SVR_OK;
   const SvrContext::PendingClear pc = ctx->pending_clear;
   ctx->pending_clear.valid = false;
-  size_t px_bytes = pc.fmt == SVR_COLOR_RGBA16F ? 8 : 4;
-  int slot = 0;
-  if (int e = log_slot(ctx, &slot)) return e;
-  ctx->log.emplace_back();
-  SvrContext::LoggedOp& op = ctx->log.back();
-  op.slot = slot;
-  op.clear_rows = (char*)pc.target + (size_t)pc.y0 * ctx->W * px_bytes;
-  op.clear_pixels = ctx->W * pc.rows;
-  op.clear_fmt = pc.fmt;
-  op.clear_packed = pc.packed;
-  return submit_clear(ctx, op);
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Clear, pc.target, pc.fmt, pc.y0, pc.rows, &op)) return e;
+  op->clear_packed = pc.packed;
+  return submit_fill(ctx, *op);
 }
 
 int finish_pending(SvrContext* ctx) {  // the fence
@@ -849,44 +864,6 @@ int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tri
   return SVR_OK;
 }
 
-// ids: a geometry pass, which writes the ID target if there is one (the draws' pad words then carry object numbers)
-int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false) {
-  if (int e = poll_pending(ctx)) return e;
-  // sequence numbers + wave chunks
-  uint64_t n_tris64 = 0;
-  size_t n_chunks = 0;
-  for (DrawDesc& d : draws) {
-    d.tri_base = (uint32_t)n_tris64;
-    n_tris64 += d.tri_count;
-    n_chunks += chunk_count(d.first_index, d.tri_count);
-  }
-  FrameParams P;
-  const SvrContext::PendingClear asked = ctx->pending_clear;  // folded into P.lazy_clear below: put back if the pass is not enqueued
-  if (int e = fill_frame_params(ctx, scene, n_tris64, n_chunks, P)) return e;
-  if (ids) P.ids = ctx->ids;
-  int slot = 0;
-  if (int e = log_slot(ctx, &slot)) {
-    if (P.lazy_clear) ctx->pending_clear = asked;
-    return e;
-  }
-  ctx->log.emplace_back();
-  SvrContext::LoggedOp& op = ctx->log.back();
-  op.is_pass = true;
-  op.seq = ctx->next_seq++;
-  if (ctx->next_seq == 0) ctx->next_seq = 1;
-  op.slot = slot;
-  op.timed = ctx->kernel_timing == 1;
-  op.P = P;
-  op.draws.swap(draws);
-  std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
-  if (int e = submit_pass(ctx, op.P, op.draws, slot, op.seq, !(ctx->tuning & TUNE_NO_PIPELINE))) {
-    ctx->log.pop_back();
-    if (P.lazy_clear) ctx->pending_clear = asked;
-    return e;
-  }
-  return SVR_OK;
-}
-
 // (re)upload the handle -> resource tables the device flatten pass reads
 int upload_flatten_tables(SvrContext* ctx) {
   if (ctx->mesh_table_n == ctx->meshes.size() && ctx->mat_table_n == ctx->materials.size()) return SVR_OK;
@@ -913,50 +890,89 @@ int upload_flatten_tables(SvrContext* ctx) {
   return SVR_OK;
 }
 
-// draw_geometry with cull, sort and the draw records left to the device (k_flatten.hip): the host only
-// validates, sums the upper bounds that size buffers and grids, and hands the objects over.
-// list: a resident draw list's version instead of the two arrays (svr_draw_list)
-int run_pass_flatten(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque,
-                     const SvrRenderObject* transparent, size_t n_transparent, uint64_t tris_max, size_t chunks_max,
-                     const std::shared_ptr<const ListVersion>& list = nullptr) {
+// Enqueue one pass.  `in` holds its input (in.input and the draws, objects or list version it names), n_tris / n_chunks
+// bound what it draws; ids: a geometry pass, which writes the ID target if there is one (host draws' pad words then carry
+// object numbers).
+int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedOp&& in, uint64_t n_tris, size_t n_chunks, bool ids) {
   if (int e = poll_pending(ctx)) return e;
-  if (int e = upload_flatten_tables(ctx)) return e;
+  if (in.flattened())  // before fill_frame_params: it can fence, and so flush the deferred clear
+    if (int e = upload_flatten_tables(ctx)) return e;
   FrameParams P;
-  const SvrContext::PendingClear asked = ctx->pending_clear;
-  if (int e = fill_frame_params(ctx, scene, tris_max, chunks_max, P)) return e;
-  P.flatten = 1u;
-  P.ids = ctx->ids;
+  const SvrContext::PendingClear asked = ctx->pending_clear;  // folded into P.lazy_clear below: put back if the pass is not enqueued
+  if (int e = fill_frame_params(ctx, scene, n_tris, n_chunks, P)) return e;
+  P.flatten = in.flattened() ? 1u : 0u;
+  if (ids) P.ids = ctx->ids;
   int slot = 0;
-  if (int e = log_slot(ctx, &slot)) {
-    if (P.lazy_clear) ctx->pending_clear = asked;
-    return e;
+  int e = log_slot(ctx, &slot);
+  if (e == SVR_OK) {
+    ctx->log.push_back(std::move(in));
+    SvrContext::LoggedOp& op = ctx->log.back();
+    op.seq = ctx->next_seq++;
+    if (ctx->next_seq == 0) ctx->next_seq = 1;
+    op.slot = slot;
+    op.timed = ctx->kernel_timing == 1;
+    op.P = P;
+    std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
+    e = submit_pass(ctx, op, !(ctx->tuning & TUNE_NO_PIPELINE));
+    if (e) ctx->log.pop_back();
   }
-  ctx->log.emplace_back();
-  SvrContext::LoggedOp& op = ctx->log.back();
-  op.is_pass = true;
-  op.seq = ctx->next_seq++;
-  if (ctx->next_seq == 0) ctx->next_seq = 1;
-  op.slot = slot;
-  op.timed = ctx->kernel_timing == 1;
-  op.P = P;
-  if (list) {
-    op.list = list;
-    op.n_opaque_obj = list->n_opaque;
-    op.n_transparent_obj = list->n_transparent;
-  } else {
-    op.objects.reserve(n_opaque + n_transparent);
-    op.objects.insert(op.objects.end(), opaque, opaque + n_opaque);
-    op.objects.insert(op.objects.end(), transparent, transparent + n_transparent);
-    op.n_opaque_obj = (uint32_t)n_opaque;
-    op.n_transparent_obj = (uint32_t)n_transparent;
+  if (e && P.lazy_clear) ctx->pending_clear = asked;
+  return e;
+}
+
+// a pass of draw records built on the host: numbers their triangles and swaps them into the log
+int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false) {
+  uint64_t n_tris64 = 0;
+  size_t n_chunks = 0;
+  for (DrawDesc& d : draws) {
+    d.tri_base = (uint32_t)n_tris64;
+    n_tris64 += d.tri_count;
+    n_chunks += chunk_count(d.first_index, d.tri_count);
   }
-  std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
-  if (int e = submit_pass(ctx, op.P, op.draws, slot, op.seq, !(ctx->tuning & TUNE_NO_PIPELINE), &op)) {
-    ctx->log.pop_back();
-    if (P.lazy_clear) ctx->pending_clear = asked;
-    return e;
+  SvrContext::LoggedOp in;
+  in.draws.swap(draws);
+  return enqueue_pass(ctx, scene, std::move(in), n_tris64, n_chunks, ids);
+}
+
+// the device flatten's bound on the objects of one pass, and so on those of a draw list (include/svr_draw_list.h)
+constexpr size_t FLATTEN_MAX_OBJECTS = 16384;
+
+// upper bounds on the triangles and wave chunks of a flattened pass over these objects (every object visible): they size
+// the pass's buffers and grids
+void add_object_bounds(const SvrRenderObject* objs, size_t n, uint64_t* tris, size_t* chunks) {
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t t = objs[i].index_count / 3u;
+    *tris += t;
+    *chunks += chunk_count(objs[i].first_index, t);
   }
-  return SVR_OK;
+}
+
+// draw order of opaque objects (src/vk_engine.cpp:1369-1378): indices into objs, sorted by the deterministic key
+// (material, mesh, submission index)
+void sort_draw_order(std::vector<uint32_t>& order, const SvrRenderObject* objs) {
+  std::stable_sort(order.begin(), order.end(), [objs](uint32_t ia, uint32_t ib) {
+    const SvrRenderObject& a = objs[ia];
+    const SvrRenderObject& b = objs[ib];
+    if (a.material == b.material) return a.mesh < b.mesh;
+    return a.material < b.material;
+  });
+}
+
+// the end of a drawing call: its stats become the context's and the caller's; t0: when the call began (mesh_draw_time)
+int finish_draw(SvrContext* ctx, SvrStats st, SvrStats* out_stats, int e,
+                const std::chrono::steady_clock::time_point* t0 = nullptr) {
+  if (t0) st.mesh_draw_time = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - *t0).count();
+  ctx->stats = st;
+  if (out_stats) *out_stats = st;
+  return e;
+}
+
+// interleaved rows and more ranks than tile rows: this context owns no tile row, and a geometry pass draws nothing
+bool owns_nothing(SvrContext* ctx, SvrStats* out_stats) {
+  if (owned_tile_rows(ctx) != 0) return false;
+  ctx->pending_clear.valid = false;
+  finish_draw(ctx, SvrStats{}, out_stats, SVR_OK);
+  return true;
 }
 
 }  // namespace
@@ -1319,21 +1335,11 @@ int svr_draw_background(SvrContext* ctx, int effect, const float data[16]) {
   if (int e = use_device(ctx)) return e;
   if (int e = poll_pending(ctx)) return e;
   if (int e = flush_clear(ctx)) return e;
-  int slot = 0;
-  if (int e = log_slot(ctx, &slot)) return e;
-  ctx->log.emplace_back();
-  SvrContext::LoggedOp& op = ctx->log.back();
-  op.slot = slot;
-  op.fill_kind = 1;
-  op.target = ctx->color;
-  op.clear_fmt = ctx->fmt;
-  op.tw = ctx->W;
-  op.th = ctx->H;
-  op.y_first = ctx->sy;
-  op.n_rows = ctx->sh;
-  op.bg_effect = effect;
-  std::memcpy(op.bg_data, data, sizeof(op.bg_data));
-  return submit_clear(ctx, op);
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Background, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
+  op->bg_effect = effect;
+  std::memcpy(op->bg_data, data, sizeof(op->bg_data));
+  return submit_fill(ctx, *op);
 }
 
 static int blit_checks(SvrContext* ctx, const void* dst, uint32_t dw, uint32_t dh, int fmt, const char* who) {
@@ -1348,32 +1354,22 @@ int svr_copy_to_swapchain(SvrContext* ctx, void* dst_dev, uint32_t dw, uint32_t 
   if (int e = use_device(ctx)) return e;
   if (int e = poll_pending(ctx)) return e;
   if (int e = flush_clear(ctx)) return e;
-  int slot = 0;
-  if (int e = log_slot(ctx, &slot)) return e;
-  ctx->log.emplace_back();
-  SvrContext::LoggedOp& op = ctx->log.back();
-  op.slot = slot;
-  op.fill_kind = 2;
-  op.target = ctx->color;
-  op.clear_fmt = ctx->fmt;
-  op.tw = ctx->W;
-  op.th = ctx->H;
-  op.blit_dst = dst_dev;
-  op.blit_w = dw;
-  op.blit_h = dh;
-  op.blit_fmt = fmt;
   // identity extent: the rows of the scissor (a rank of the multi-GPU path presents its band); scaled: everything
   const bool identity = dw == ctx->W && dh == ctx->H;
-  op.y_first = identity ? ctx->sy : 0u;
-  op.n_rows = identity ? ctx->sh : dh;
-  op.blit_row_end = op.y_first + op.n_rows;
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Blit, ctx->color, ctx->fmt, identity ? ctx->sy : 0u, identity ? ctx->sh : dh, &op)) return e;
+  op->blit_dst = dst_dev;
+  op->blit_w = dw;
+  op->blit_h = dh;
+  op->blit_fmt = fmt;
+  op->blit_row_end = op->y_first + op->n_rows;
   if (identity && ctx->rstride > 1u) {  // a rank of the interleaved form presents its own tile rows, in place
-    op.blit_rstride = ctx->rstride;
-    op.blit_roff = ctx->roff;
-    op.n_rows = owned_tile_rows(ctx) * TILE;
+    op->blit_rstride = ctx->rstride;
+    op->blit_roff = ctx->roff;
+    op->n_rows = owned_tile_rows(ctx) * TILE;
   }
-  op.blit_status = ctx->present_status;
-  return submit_clear(ctx, op);
+  op->blit_status = ctx->present_status;
+  return submit_fill(ctx, *op);
 }
 
 int svr_read_swapchain(SvrContext* ctx, uint32_t dw, uint32_t dh, int fmt, void* dst_host, size_t bytes) {
@@ -1443,46 +1439,31 @@ int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRende
     if (int e = validate_object(ctx, opaque[i], false)) return e;
   for (size_t i = 0; i < n_transparent; i++)
     if (int e = validate_object(ctx, transparent[i], true)) return e;
-  if (owned_tile_rows(ctx) == 0) {  // interleaved rows and more ranks than tile rows: this one owns nothing
-    ctx->pending_clear.valid = false;
-    ctx->stats = SvrStats{};
-    if (out_stats) *out_stats = ctx->stats;
-    return SVR_OK;
-  }
-  if (ctx->tex_slots != ctx->materials.size() + 1)
-    if (int e = upload_tex_table(ctx, nullptr)) return e;
+  if (owns_nothing(ctx, out_stats)) return SVR_OK;
+  if (int e = upload_tex_table(ctx, nullptr)) return e;
   // Many objects: cull, sort and the per-object records run on the device (k_flatten.hip).  The three
   // counts of the stats then only exist after the pass (svr_get_stats); out_stats gets what the host knows.
   const size_t n_objects = n_opaque + n_transparent;
-  const bool fits = n_objects <= 16384 && ctx->meshes.size() < (1u << 20) && ctx->materials.size() < (1u << 20);
+  const bool fits = n_objects <= FLATTEN_MAX_OBJECTS && ctx->meshes.size() < (1u << 20) && ctx->materials.size() < (1u << 20);
   if (fits && n_objects > 0 && (ctx->device_flatten == 1 || (ctx->device_flatten == 0 && n_objects >= 2048))) {
+    SvrContext::LoggedOp in;
+    in.input = SvrContext::PassInput::Objects;
+    in.objects.reserve(n_objects);
+    in.objects.insert(in.objects.end(), opaque, opaque + n_opaque);
+    in.objects.insert(in.objects.end(), transparent, transparent + n_transparent);
+    in.n_opaque_obj = (uint32_t)n_opaque;
+    in.n_transparent_obj = (uint32_t)n_transparent;
     uint64_t tris_max = 0;
     size_t chunks_max = 0;
-    for (size_t i = 0; i < n_objects; i++) {
-      uint32_t t = (i < n_opaque ? opaque[i] : transparent[i - n_opaque]).index_count / 3u;
-      tris_max += t;
-      chunks_max += chunk_count((i < n_opaque ? opaque[i] : transparent[i - n_opaque]).first_index, t);
-    }
-    SvrStats st{};
-    int e = run_pass_flatten(ctx, scene, opaque, n_opaque, transparent, n_transparent, tris_max, chunks_max);
-    auto t1 = std::chrono::steady_clock::now();
-    st.mesh_draw_time = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    ctx->stats = st;
-    if (out_stats) *out_stats = st;
-    return e;
+    add_object_bounds(in.objects.data(), n_objects, &tris_max, &chunks_max);
+    return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), tris_max, chunks_max, true), &t0);
   }
   // cull: opaque only (src/vk_engine.cpp:1361-1367)
   std::vector<uint32_t> order;
   order.reserve(n_opaque);
   for (size_t i = 0; i < n_opaque; i++)
     if (is_visible(opaque[i], scene->viewproj)) order.push_back((uint32_t)i);
-  // sort (src/vk_engine.cpp:1369-1378): deterministic key (material, mesh, submission index)
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t ia, uint32_t ib) {
-    const SvrRenderObject& a = opaque[ia];
-    const SvrRenderObject& b = opaque[ib];
-    if (a.material == b.material) return a.mesh < b.mesh;
-    return a.material < b.material;
-  });
+  sort_draw_order(order, opaque);
   std::vector<DrawDesc> draws;
   draws.reserve(order.size() + n_transparent);
   SvrStats st{};
@@ -1509,20 +1490,14 @@ int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRende
   for (uint32_t i : order) push(opaque[i], i + 1u);
   for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
   st.culled_draws = (uint32_t)(n_opaque - order.size());
-  int e = run_pass(ctx, scene, draws, true);
-  auto t1 = std::chrono::steady_clock::now();
-  st.mesh_draw_time = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  ctx->stats = st;
-  if (out_stats) *out_stats = st;
-  return e;
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, scene, draws, true), &t0);
 }
 
 int svr_draw_colored_triangle(SvrContext* ctx, SvrStats* out_stats) {
   if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
   if (owned_tile_rows(ctx) == 0) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_colored_triangle: this context owns no tile row (svr_set_row_interleave)");
   if (int e = use_device(ctx)) return e;
-  if (ctx->tex_slots != ctx->materials.size() + 1)
-    if (int e = upload_tex_table(ctx, nullptr)) return e;
+  if (int e = upload_tex_table(ctx, nullptr)) return e;
   std::vector<DrawDesc> draws(1);
   std::memset(&draws[0], 0, sizeof(DrawDesc));
   draws[0].tri_count = 1;
@@ -1530,10 +1505,7 @@ int svr_draw_colored_triangle(SvrContext* ctx, SvrStats* out_stats) {
   SvrStats st{};
   st.drawcall_count = 1;
   st.triangle_count = 1;
-  int e = run_pass(ctx, nullptr, draws);
-  ctx->stats = st;
-  if (out_stats) *out_stats = st;
-  return e;
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, nullptr, draws));
 }
 
 int svr_draw_tex_image(SvrContext* ctx, SvrMesh mesh, uint32_t first_index, uint32_t index_count,
@@ -1566,10 +1538,7 @@ int svr_draw_tex_image(SvrContext* ctx, SvrMesh mesh, uint32_t first_index, uint
   SvrStats st{};
   st.drawcall_count = 1;
   st.triangle_count = (int)(index_count / 3);
-  int e = run_pass(ctx, nullptr, draws);
-  ctx->stats = st;
-  if (out_stats) *out_stats = st;
-  return e;
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, nullptr, draws));
 }
 
 int svr_run_mesh_vert(SvrContext* ctx, SvrMesh mesh, uint32_t first_vertex, uint32_t n_vertices, const float world[16],
@@ -1847,21 +1816,12 @@ static int make_list_version(const DrawListRes& L, std::shared_ptr<const ListVer
   v->n_transparent = (uint32_t)(n - L.n_opaque);
   std::vector<uint32_t> order(L.n_opaque);
   std::iota(order.begin(), order.end(), 0u);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t ia, uint32_t ib) {
-    const SvrRenderObject& a = L.objs[ia];
-    const SvrRenderObject& b = L.objs[ib];
-    if (a.material == b.material) return a.mesh < b.mesh;
-    return a.material < b.material;
-  });
+  sort_draw_order(order, L.objs.data());
   std::vector<SvrRenderObject> sorted;
   sorted.reserve(n);
   for (uint32_t i : order) sorted.push_back(L.objs[i]);
   sorted.insert(sorted.end(), L.objs.begin() + L.n_opaque, L.objs.end());
-  for (const SvrRenderObject& o : sorted) {
-    const uint32_t t = o.index_count / 3u;
-    v->tris_max += t;
-    v->chunks_max += chunk_count(o.first_index, t);
-  }
+  add_object_bounds(sorted.data(), n, &v->tris_max, &v->chunks_max);
   if (n) {
     HIPCHK(hipMalloc((void**)&v->dev, n * sizeof(SvrRenderObject)));
     HIPCHK(hipMemcpy(v->dev, sorted.data(), n * sizeof(SvrRenderObject), hipMemcpyHostToDevice));
@@ -1875,14 +1835,12 @@ static int make_list_version(const DrawListRes& L, std::shared_ptr<const ListVer
   return SVR_OK;
 }
 
-constexpr size_t LIST_MAX_OBJECTS = 16384;  // the device flatten's bound (svr_draw_geometry's `fits`)
-
 int svr_create_draw_list(SvrContext* ctx, const SvrRenderObject* opaque, size_t n_opaque, const SvrRenderObject* transparent,
                          size_t n_transparent, SvrDrawList* out) {
   if (!ctx || !out || (!opaque && n_opaque) || (!transparent && n_transparent))
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_create_draw_list: null argument");
-  if (n_opaque > LIST_MAX_OBJECTS || n_transparent > LIST_MAX_OBJECTS - n_opaque)
-    return fail(SVR_ERR_UNSUPPORTED, "svr_create_draw_list: more than 16384 objects in one list");
+  if (n_opaque > FLATTEN_MAX_OBJECTS || n_transparent > FLATTEN_MAX_OBJECTS - n_opaque)
+    return fail(SVR_ERR_UNSUPPORTED, "svr_create_draw_list: more than " + std::to_string(FLATTEN_MAX_OBJECTS) + " objects in one list");
   DrawListRes L;
   L.n_opaque = (uint32_t)n_opaque;
   L.objs.reserve(n_opaque + n_transparent);
@@ -1929,7 +1887,7 @@ int svr_destroy_draw_list(SvrContext* ctx, SvrDrawList list) {
 }
 
 // Per pass the host checks the handle and the mesh epoch, and enqueues the pass of svr_draw_geometry's device
-// flatten with the list's current version (run_pass_flatten): no per-object loop.
+// flatten with the list's current version (enqueue_pass): no per-object loop.
 int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
   if (!ctx || !scene) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list: null argument");
   auto t0 = std::chrono::steady_clock::now();
@@ -1938,31 +1896,20 @@ int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, 
   if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, "svr_draw_list");  // a mesh was destroyed since
   if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list: the list is no longer valid (" + L->why + ")");
   if (int e = use_device(ctx)) return e;
-  if (owned_tile_rows(ctx) == 0) {  // as svr_draw_geometry: this context owns no tile row
-    ctx->pending_clear.valid = false;
-    ctx->stats = SvrStats{};
-    if (out_stats) *out_stats = ctx->stats;
-    return SVR_OK;
-  }
-  if (ctx->tex_slots != ctx->materials.size() + 1)
-    if (int e = upload_tex_table(ctx, nullptr)) return e;
-  const std::shared_ptr<const ListVersion>& v = L->cur;
-  const size_t n_objects = (size_t)v->n_opaque + v->n_transparent;
-  SvrStats st{};
-  int e;
-  if (n_objects == 0) {  // svr_draw_geometry's host path: a pass of no draws
-    std::vector<DrawDesc> draws;
-    e = run_pass(ctx, scene, draws, true);
-  } else {
+  if (owns_nothing(ctx, out_stats)) return SVR_OK;
+  if (int e = upload_tex_table(ctx, nullptr)) return e;
+  const ListVersion& v = *L->cur;
+  const size_t n_objects = (size_t)v.n_opaque + v.n_transparent;
+  SvrContext::LoggedOp in;  // no objects: svr_draw_geometry's host path, a pass of no draws
+  if (n_objects > 0) {
     if (n_objects > LIST_FUSED_MAX && (ctx->meshes.size() >= (1u << 20) || ctx->materials.size() >= (1u << 20)))
       return fail(SVR_ERR_UNSUPPORTED, "svr_draw_list: lists over 4096 objects need fewer than 2^20 meshes and materials");
-    e = run_pass_flatten(ctx, scene, nullptr, 0, nullptr, 0, v->tris_max, v->chunks_max, v);
+    in.input = SvrContext::PassInput::List;
+    in.list = L->cur;
+    in.n_opaque_obj = v.n_opaque;
+    in.n_transparent_obj = v.n_transparent;
   }
-  auto t1 = std::chrono::steady_clock::now();
-  st.mesh_draw_time = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  ctx->stats = st;
-  if (out_stats) *out_stats = st;
-  return e;
+  return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), v.tris_max, v.chunks_max, true), &t0);
 }
 
 int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void* chunks, size_t chunk_bytes, uint32_t* n_draws,
