@@ -90,7 +90,14 @@ DRAW_LIST_SYMBOLS = ["svr_create_draw_list", "svr_update_draw_list", "svr_destro
                      "svr_debug_read_records"]
 # include/svr_ids.h: the object and primitive ID target, HIP library only
 ID_SYMBOLS = ["svr_enable_ids", "svr_bind_id_target", "svr_get_id_target", "svr_read_ids", "svr_pick"]
+# include/svr_views.h: multiview passes, HIP library only
+VIEWS_SYMBOLS = ["svr_draw_geometry_views", "svr_draw_list_views"]
+MAX_VIEWS = 16
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
+
+
+class SvrViewTargets(C.Structure):  # include/svr_views.h
+    _fields_ = [("color", C.c_void_p), ("depth", C.c_void_p), ("ids", C.c_void_p), ("clear_rgba", C.POINTER(C.c_float))]
 
 
 class SvrError(RuntimeError):
@@ -163,6 +170,11 @@ class SvrLib:
             L.svr_destroy_draw_list.argtypes = [P, C.c_uint32]
             L.svr_draw_list.argtypes = [P, C.c_uint32, C.POINTER(SvrSceneData), C.POINTER(SvrStats)]
             L.svr_debug_read_records.argtypes = [P, P, C.c_size_t, P, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        self.has_views = hasattr(L, "svr_draw_geometry_views")
+        if self.has_views:
+            L.svr_draw_geometry_views.argtypes = [P, C.c_uint32, P, C.POINTER(SvrViewTargets), P, C.c_size_t, P, C.c_size_t,
+                                                  C.POINTER(SvrStats)]
+            L.svr_draw_list_views.argtypes = [P, C.c_uint32, C.c_uint32, P, C.POINTER(SvrViewTargets), C.POINTER(SvrStats)]
         self.has_ids = hasattr(L, "svr_enable_ids")
         if self.has_ids:
             L.svr_enable_ids.argtypes = [P, C.c_int]
@@ -357,6 +369,37 @@ class Renderer:
         st = SvrStats()
         handle = lst.handle if isinstance(lst, DrawList) else int(lst)
         self.lib.check(self.lib.lib.svr_draw_list(self.h, handle, C.byref(scene), C.byref(st)))
+        return st
+
+    # -- multiview passes (include/svr_views.h)
+    def _view_args(self, scenes, color_ptr, depth_ptr, ids_ptr, clear_rgba):
+        if not getattr(self.lib, "has_views", False):
+            raise SvrError(-5, f"{self.lib.backend} has no multiview (include/svr_views.h)")
+        scenes = list(scenes)
+        arr = (SvrSceneData * max(len(scenes), 1))(*scenes)
+        t = SvrViewTargets()
+        t.color, t.depth, t.ids = C.c_void_p(color_ptr or None), C.c_void_p(depth_ptr or None), C.c_void_p(ids_ptr or None)
+        if clear_rgba is not None:
+            t.clear_rgba = (C.c_float * 4)(*[float(v) for v in clear_rgba])
+        self._view_keep = (arr, t)  # alive for the duration of the call
+        return len(scenes), arr, t
+
+    def draw_views(self, scenes, color_ptr, depth_ptr, opaque, transparent=None, ids_ptr=None, clear_rgba=None):
+        """svr_draw_geometry_views: scenes[k] draws layer k of the device targets (colour [K, H, W, C], depth [K, H, W],
+        ids [K, H, W, 2] or None); clear_rgba None = colour LOAD"""
+        n, arr, t = self._view_args(scenes, color_ptr, depth_ptr, ids_ptr, clear_rgba)
+        op, n_op = self._objects(opaque)
+        tr, n_tr = self._objects(transparent)
+        st = SvrStats()
+        self.lib.check(self.lib.lib.svr_draw_geometry_views(self.h, n, C.addressof(arr), C.byref(t), op, n_op, tr, n_tr, C.byref(st)))
+        return st
+
+    def draw_list_views(self, scenes, lst, color_ptr, depth_ptr, ids_ptr=None, clear_rgba=None):
+        """svr_draw_list_views: draw_views over a retained list"""
+        n, arr, t = self._view_args(scenes, color_ptr, depth_ptr, ids_ptr, clear_rgba)
+        st = SvrStats()
+        handle = lst.handle if isinstance(lst, DrawList) else int(lst)
+        self.lib.check(self.lib.lib.svr_draw_list_views(self.h, handle, n, C.addressof(arr), C.byref(t), C.byref(st)))
         return st
 
     def read_records(self):

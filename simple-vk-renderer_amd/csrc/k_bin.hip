@@ -89,6 +89,7 @@ __device__ __forceinline__ void bin_one(const FrameParams& P, uint32_t r, int mi
 }
 
 // The triangles over 16 tiles the setup kernel queued instead of deciding their tiles lane by lane: one WAVE per record.
+template <bool MV>
 __device__ __forceinline__ void bin_big(const FrameParams& P, uint32_t first_wave, uint32_t n_waves) {
   const uint32_t n_big = min(P.counters->n_big, P.n_tris), n_setup = min(P.counters->n_pairs, P.bin_cap);
   for (uint32_t it = first_wave; it < n_big; it += n_waves) {
@@ -96,7 +97,7 @@ __device__ __forceinline__ void bin_big(const FrameParams& P, uint32_t first_wav
     const TriRec* rec = P.recs + r;
     RecBox b = load_box(rec);
     if (!b.valid) continue;  // wave-uniform
-    bin_one(P, r, b.minx, b.miny, b.maxx, b.maxy, (b.flags & F_TRANSPARENT) ? P.n_tiles : 0u, load_edges(rec), n_setup);
+    bin_one(P, r, b.minx, b.miny, b.maxx, b.maxy, bin_base<MV>(P, b.flags), load_edges(rec), n_setup);
   }
 }
 
@@ -115,7 +116,8 @@ struct ClipLds {
   TriGeom geom[CLIP_LANES];
 };
 // IDS: the pieces carry their parent's object and primitive (TriRec::object)
-template <bool IDS>
+// MV: transparent carries the piece's bin base (bin_base) instead of its transparency
+template <bool IDS, bool MV>
 __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, uint32_t block, uint32_t n_blocks) {
   const uint32_t lane = threadIdx.x;  // wave 0 of the block
   const uint32_t n = min(P.counters->n_clip, P.clip_cap), n_setup = min(P.counters->n_pairs, P.bin_cap);
@@ -172,7 +174,7 @@ __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, u
             made = true;
             used++;
             if (IDS) *reinterpret_cast<uint2*>(dst + REC_ID_PIECE) = make_uint2(d.pad, prim);
-            transparent = (d.flags & F_TRANSPARENT) ? 1u : 0u;
+            transparent = MV ? bin_base<true>(P, d.flags) : ((d.flags & F_TRANSPARENT) ? 1u : 0u);
             if (P.instrument) atomicAdd(&P.counters->binned, 1ull);
           }
         }
@@ -185,7 +187,7 @@ __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, u
         EdgeSet e;
         e.A0 = gm.A[0]; e.A1 = gm.A[1]; e.A2 = gm.A[2]; e.B0 = gm.B[0]; e.B1 = gm.B[1]; e.B2 = gm.B[2];
         e.C0 = gm.C[0]; e.C1 = gm.C[1]; e.C2 = gm.C[2];
-        bin_one(P, (uint32_t)__shfl((int)rec, l), gm.minx, gm.miny, gm.maxx, gm.maxy, __shfl((int)transparent, l) ? P.n_tiles : 0u, e, n_setup);
+        bin_one(P, (uint32_t)__shfl((int)rec, l), gm.minx, gm.miny, gm.maxx, gm.maxy, MV ? (uint32_t)__shfl((int)transparent, l) : (__shfl((int)transparent, l) ? P.n_tiles : 0u), e, n_setup);
       }
       __builtin_amdgcn_wave_barrier();  // ... before the next step's pieces overwrite them
     }
@@ -208,17 +210,18 @@ __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, u
 // atomic-bound), and its return value is the pair's position in its bin — kept, so the fill is a plain
 // scatter with no second round of atomics.
 // IDS: count_ids_kernel, for passes with an ID target (clip_and_bin); count_kernel is the kernel as it was
-template <bool IDS>
+// MV: a multiview pass (include/svr_views.h; count_mv_kernel, count_mv_ids_kernel)
+template <bool IDS, bool MV>
 __device__ __forceinline__ void count_main(const FrameParams& P, uint32_t big_blocks, uint32_t clip_blocks) {
   __shared__ ClipLds s_clip;
   if (P.counters->overflow) return;  // a queue overflowed: the pass is void, the host grows it and replays
   if (blockIdx.x < big_blocks) {
-    bin_big(P, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (big_blocks * blockDim.x) >> 6);
+    bin_big<MV>(P, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (big_blocks * blockDim.x) >> 6);
     return;
   }
   const uint32_t rest_blocks = big_blocks + clip_blocks;
   if (blockIdx.x < rest_blocks) {
-    if (threadIdx.x < 64u) clip_and_bin<IDS>(P, s_clip, blockIdx.x - big_blocks, clip_blocks);
+    if (threadIdx.x < 64u) clip_and_bin<IDS, MV>(P, s_clip, blockIdx.x - big_blocks, clip_blocks);
     return;
   }
   // Which lanes of the wave target the same bin is found through a small LDS hash table of the wave's own (128
@@ -262,10 +265,16 @@ __device__ __forceinline__ void count_main(const FrameParams& P, uint32_t big_bl
   }
 }
 __global__ __launch_bounds__(256, 4) void count_kernel(FrameParams P, uint32_t big_blocks, uint32_t clip_blocks) {
-  count_main<false>(P, big_blocks, clip_blocks);
+  count_main<false, false>(P, big_blocks, clip_blocks);
 }
 __global__ __launch_bounds__(256, 4) void count_ids_kernel(FrameParams P, uint32_t big_blocks, uint32_t clip_blocks) {
-  count_main<true>(P, big_blocks, clip_blocks);
+  count_main<true, false>(P, big_blocks, clip_blocks);
+}
+__global__ __launch_bounds__(256, 4) void count_mv_kernel(FrameParams P, uint32_t big_blocks, uint32_t clip_blocks) {
+  count_main<false, true>(P, big_blocks, clip_blocks);
+}
+__global__ __launch_bounds__(256, 4) void count_mv_ids_kernel(FrameParams P, uint32_t big_blocks, uint32_t clip_blocks) {
+  count_main<true, true>(P, big_blocks, clip_blocks);
 }
 
 // Bin offsets without a scan: bins need not lie in tile order, only be disjoint spans, so every wave
@@ -400,7 +409,9 @@ void launch_bin_count(const FrameParams& P, hipStream_t s) {
   // (128 blocks for the queued big triangles also in the 8K x16 frame: with 1024 the kernel is 246 us instead of 168 —
   // what bounds it there is the device atomics on the bins' counters, and more waves only queue up behind them)
   const uint32_t big_blocks = 128, clip_blocks = 512;
-  if (P.ids)
+  if (P.layer_rows)
+    hipLaunchKernelGGL(P.ids ? count_mv_ids_kernel : count_mv_kernel, dim3(big_blocks + clip_blocks + 1024u), dim3(256), 0, s, P, big_blocks, clip_blocks);
+  else if (P.ids)
     hipLaunchKernelGGL(count_ids_kernel, dim3(big_blocks + clip_blocks + 1024u), dim3(256), 0, s, P, big_blocks, clip_blocks);
   else
     hipLaunchKernelGGL(count_kernel, dim3(big_blocks + clip_blocks + 1024u), dim3(256), 0, s, P, big_blocks, clip_blocks);

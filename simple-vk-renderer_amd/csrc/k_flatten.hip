@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void chunks_kernel(FlattenParams F) {
 // make_draw stored column by column (the same bytes): a whole DrawDesc in registers beside the scans of list_kernel
 // does not fit its 128 VGPRs
 __device__ __forceinline__ void store_draw(const FlattenParams& F, const float* viewproj, uint32_t slot, const SvrRenderObject& o, uint32_t tri_base,
-                                           uint32_t object) {
+                                           uint32_t object, uint32_t view_flags = 0u) {
   const MeshEntry me = F.meshes[o.mesh - 1];
   const MatEntry ma = F.materials[o.material - 1];
   DrawDesc* d = F.draws + slot;
@@ -246,7 +246,7 @@ __device__ __forceinline__ void store_draw(const FlattenParams& F, const float* 
   d->tri_count = o.index_count / 3u;
   d->tri_base = tri_base;
   d->tex = o.material - 1u;
-  d->flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (ma.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u);
+  d->flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (ma.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u) | view_flags;
   d->groups = me.groups;
   d->first_index = o.first_index;
   d->pad = object;
@@ -260,15 +260,20 @@ __device__ __forceinline__ void store_draw(const FlattenParams& F, const float* 
 // (visible, triangles, wave chunks) over the workgroup through LDS, and every visible lane writes its DrawDesc and
 // WaveChunks at the bases it found.  Same records as the host path stages (and as the four kernels above).
 // IDS: list_ids_kernel, for passes with an ID target (DrawDesc::pad = object number); list_kernel is the kernel as it was
-template <bool IDS>
+// MV: list_views_kernel, a multiview pass (include/svr_views.h): the same walk once per view, each with the view's own
+// viewproj (cull and mvp) and the view in the records' flags; slots, triangle numbers and chunks run on across the views.
+template <bool IDS, bool MV = false>
 __device__ __forceinline__ void list_main(const FlattenParams& F) {
   __shared__ uint32_t s_sum[3][16];
   __shared__ float s_vp[16];  // viewproj from LDS: held in SGPRs for both of its uses it spilled 32 of them
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
   const uint32_t n_all = F.n_opaque + F.n_transparent;
-  if (tid < 16) s_vp[tid] = F.viewproj[tid];
+  const uint32_t n_views = MV ? F.n_views : 1u;
+  uint32_t base_v = 0, base_t = 0, base_c = 0;  // totals of the rounds (and views) before
+  for (uint32_t view = 0; view < n_views; view++) {
+  if (MV) __syncthreads();  // the previous view's last round is done with s_vp
+  if (tid < 16) s_vp[tid] = MV ? F.viewprojs[16u * view + tid] : F.viewproj[tid];
   __syncthreads();
-  uint32_t base_v = 0, base_t = 0, base_c = 0;  // totals of the rounds before
   for (uint32_t r0 = 0; r0 < n_all; r0 += 1024u) {
     const uint32_t i = r0 + tid;
     bool vis = false;
@@ -311,7 +316,7 @@ __device__ __forceinline__ void list_main(const FlattenParams& F) {
     __syncthreads();  // s_sum is rewritten by the next round
     if (vis) {
       const uint32_t slot = bv + iv - 1u, cb = bc + ic - chk;
-      store_draw(F, s_vp, slot, F.objects[i], bt + it - tri, (IDS && i < F.n_opaque) ? object_number(F, i) : 0u);
+      store_draw(F, s_vp, slot, F.objects[i], bt + it - tri, (IDS && i < F.n_opaque) ? object_number(F, i) : 0u, MV ? view << F_VIEW_SHIFT : 0u);
       for (uint32_t c = 0; c < chk; c++) {
         WaveChunk ch;
         ch.draw = slot;
@@ -320,15 +325,18 @@ __device__ __forceinline__ void list_main(const FlattenParams& F) {
       }
     }
   }
+  }
   if (tid == 0) {
     F.counters->flat_draws = base_v;
     F.counters->flat_tris = base_t;
     F.counters->flat_chunks = base_c;
-    F.counters->flat_culled = F.n_opaque - (base_v - F.n_transparent);
+    F.counters->flat_culled = n_views * F.n_opaque - (base_v - n_views * F.n_transparent);
   }
 }
 __global__ __launch_bounds__(1024) void list_kernel(FlattenParams F) { list_main<false>(F); }
 __global__ __launch_bounds__(1024) void list_ids_kernel(FlattenParams F) { list_main<true>(F); }
+__global__ __launch_bounds__(1024) void list_views_kernel(FlattenParams F) { list_main<false, true>(F); }
+__global__ __launch_bounds__(1024) void list_views_ids_kernel(FlattenParams F) { list_main<true, true>(F); }
 
 void launch_flatten(const FlattenParams& F, hipStream_t s) {
   const uint32_t n_all = F.n_opaque + F.n_transparent;
@@ -346,7 +354,10 @@ void launch_flatten(const FlattenParams& F, hipStream_t s) {
 void launch_list_flatten(const FlattenParams& F, hipStream_t s) {
   const uint32_t n_all = F.n_opaque + F.n_transparent;
   if (n_all == 0) return;
-  if (n_all <= LIST_FUSED_MAX && F.ids)
+  if (F.n_views) {  // multiview (svr_draw_list_views keeps such lists to LIST_FUSED_MAX objects)
+    if (F.ids) hipLaunchKernelGGL(list_views_ids_kernel, dim3(1), dim3(1024), 0, s, F);
+    else hipLaunchKernelGGL(list_views_kernel, dim3(1), dim3(1024), 0, s, F);
+  } else if (n_all <= LIST_FUSED_MAX && F.ids)
     hipLaunchKernelGGL(list_ids_kernel, dim3(1), dim3(1024), 0, s, F);
   else if (n_all <= LIST_FUSED_MAX)
     hipLaunchKernelGGL(list_kernel, dim3(1), dim3(1024), 0, s, F);

@@ -70,7 +70,8 @@ __device__ __forceinline__ bool chunk_can_be_seen(const FrameParams& P, const fl
 
 // IDS: the pass has an ID target (include/svr_ids.h); records carry their object and primitive (TriRec::object).
 // (A template kernel, not a body shared by two: that wrapper alone cost the instance without IDs two VGPRs.)
-template <bool IDS>
+// MV: a multiview pass (include/svr_views.h): the record's bins are its view's layer (bin_base)
+template <bool IDS, bool MV>
 __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
   // the wave's chunk and its draw are wave-uniform: held in SGPRs, so chunk -> draw record is two scalar round
   // trips (read as per-lane values they were a chain of six vector loads in front of the first index fetch)
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
   e.A0 = g.A[0]; e.A1 = g.A[1]; e.A2 = g.A[2]; e.B0 = g.B[0]; e.B1 = g.B[1]; e.B2 = g.B[2];
   e.C0 = g.C[0]; e.C1 = g.C[1]; e.C2 = g.C[2];
   emit_small_pairs(P, ok && tr.nt <= SMALL_MAX_TILES, tr, g.minx, g.miny, g.maxx, g.maxy,
-                   (d.flags & F_TRANSPARENT) ? P.n_tiles : 0u, e, seq, s_tot);
+                   bin_base<MV>(P, d.flags), e, seq, s_tot);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -307,10 +308,14 @@ __global__ __launch_bounds__(256) void vertex_shader_kernel(const SvrVertex* vtx
 void launch_setup(const FrameParams& P, hipStream_t s) {
   if (P.n_chunks == 0) return;
   uint32_t blocks = (P.n_chunks + 3) / 4;
-  if (P.ids)
-    hipLaunchKernelGGL(setup_kernel<true>, dim3(blocks), dim3(256), 0, s, P);
-  else
-    hipLaunchKernelGGL(setup_kernel<false>, dim3(blocks), dim3(256), 0, s, P);
+  if (P.layer_rows) {
+    if (P.ids) hipLaunchKernelGGL((setup_kernel<true, true>), dim3(blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((setup_kernel<false, true>), dim3(blocks), dim3(256), 0, s, P);
+  } else if (P.ids) {
+    hipLaunchKernelGGL((setup_kernel<true, false>), dim3(blocks), dim3(256), 0, s, P);
+  } else {
+    hipLaunchKernelGGL((setup_kernel<false, false>), dim3(blocks), dim3(256), 0, s, P);
+  }
 }
 // Pass prologue: pull the pass inputs (DrawDesc[] + WaveChunk[], ~100 KB) out of the pinned staging
 // buffer and zero the pass's counters, in one kernel.  A hipMemcpyAsync here is an SDMA packet with

@@ -1172,7 +1172,10 @@ __device__ __forceinline__ void store_row16(void* p, uint4 v) {
 // by blockIdx alone: sharing one body with run-time row ranges cost the whole-tile path 20-35 spilled
 // registers and 8-13 % of the frame, and choosing by a flag in tile_info put a dependent load in front of
 // every tile (+2 %).
-template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS>
+// MV: a multiview pass (include/svr_views.h): the tile's layer is its tile row / P.layer_rows; its pixel rows are
+// layer-local and its targets start at the layer's base, so rows past the layer's last (a partial last tile row: the next
+// layer's memory) are outside the scissor like any other
+template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV>
 __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, const uint4 i1, uint4* s_cov, uint32_t* s_idx, unsigned char* s_c,
                                           const uint32_t wv, const bool hiz_on, const uint32_t wg_start = 0) {
   typedef Codec<FMT> CD;
@@ -1205,7 +1208,12 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
   constexpr int nrows = 4 << lrpw;
   const uint32_t tx = tile % P.tiles_x, ty = tile / P.tiles_x;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const int tx0 = (int)(P.sx + tx * TILE), ty0 = tile_row_y(P, (int)ty);
+  const uint32_t layer = MV ? ty / P.layer_rows : 0u;  // workgroup-uniform (SGPRs)
+  const size_t lbase = MV ? (size_t)layer * P.W * P.H : 0u;
+  float* const depth = P.depth + lbase;
+  enc_t* const color = reinterpret_cast<enc_t*>(P.color) + lbase;
+  uint2* const ids = IDS ? P.ids + lbase : nullptr;
+  const int tx0 = (int)(P.sx + tx * TILE), ty0 = tile_row_y(P, (int)(ty - layer * (MV ? P.layer_rows : 0u)));
   const int x_end = (int)(P.sx + P.sw), y_end = (int)(P.sy + P.sh);
   const int sub_y0 = ty0 + row0;
   // pixel ownership: wave w the 16x16 quadrant w, lane l one pixel in each of its four 8x8 blocks; slot k of a
@@ -1351,7 +1359,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       uint4 lo = src[0], hi = src[1];
       z = make_uint4(lo.y, lo.w, hi.y, hi.w);
     }
-    store_row16(P.depth + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c), z);
+    store_row16(depth + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c), z);
     if (n_tr) *reinterpret_cast<uint4*>(s_z + row * TILE + c) = z;
   } else {
     int rx, ry;
@@ -1361,7 +1369,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
     for (int k = 0; k < 4; k++) {
       const uint32_t w = li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256);
       uint32_t z = n_op ? (uint32_t)(s_depth[w] >> 32) : 0u;
-      if (pix_ok[k]) P.depth[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = u2f(z);
+      if (pix_ok[k]) depth[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = u2f(z);
       if (n_tr) s_z[w] = z;
     }
   }
@@ -1384,13 +1392,13 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       __syncthreads();
       const uint32_t tid = tid_of(wv), row = tid >> 3, c = (tid & 7u) * 4u;
       const uint4* src = reinterpret_cast<const uint4*>(s_id + row * TILE + c);
-      uint2* dst = P.ids + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c);
+      uint2* dst = ids + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c);
       store_row16(dst, src[0]);
       store_row16(dst + 2, src[1]);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; k++)
-        if (pix_ok[k]) P.ids[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = id[k];
+        if (pix_ok[k]) ids[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = id[k];
     }
   }
   __syncthreads();  // the visibility tile is dead: its memory is the tile's colour from here on
@@ -1482,7 +1490,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
     for (int k = 0; k < 4; k++)  // colour loadOp LOAD for what neither the opaque pass nor a clear has written
       if (!dirty[k] && pix_ok[k])
         lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] =
-            reinterpret_cast<const enc_t*>(P.color)[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)];
+            color[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)];
     unsigned char* mine = s_c + LDS_C_OFF + wv * WAVE_C_BYTES;
     enc_t* col = lc + (uint32_t)(row0 + ((int)wv << lrpw)) * TILE;  // this wave's rows of the colour tile
     uint2* q = reinterpret_cast<uint2*>(mine);
@@ -1506,7 +1514,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
     for (uint32_t i = tid_of(wv); i < TILE * TILE / PX; i += 256u) {
       uint32_t row = i / (TILE / PX), c = (i % (TILE / PX)) * PX;
       uint4 v = *reinterpret_cast<const uint4*>(lc + row * TILE + c);
-      store_row16(reinterpret_cast<enc_t*>(P.color) + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c), v);
+      store_row16(color + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c), v);
     }
   } else {
     int rx, ry;
@@ -1515,7 +1523,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #pragma unroll
     for (int k = 0; k < 4; k++)
       if (pix_ok[k] && dirty[k])
-        reinterpret_cast<enc_t*>(P.color)[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] =
+        color[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] =
             lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)];
   }
   if (stamps) {
@@ -1551,7 +1559,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #define SVR_TILE_WAVES 5  // waves per SIMD (= workgroups per CU) the tile kernel is compiled for (A/B builds: tools/build_variant.sh)
 #endif
 // IDS: the pass writes an ID target (FrameParams::ids): tile_ids_kernel below; tile_kernel is the kernel as it was
-template <int FMT, bool INSTR, bool SPLIT, bool IDS>
+template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false>
 __device__ __forceinline__ void tile_main(const FrameParams& P) {
   __shared__ uint4 s_cov[BATCH * 8];
   __shared__ uint32_t s_idx[BATCH];
@@ -1613,18 +1621,23 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   } else if (SPLIT) {
     if (blockIdx.x < SPLIT_EXTRA) {  // the quarters of split tiles, as many as fill_kernel made
       if (blockIdx.x >= 4u * min(n_split, SPLIT_MAX)) return;
-      tile_body<FMT, INSTR, true, true, IDS>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, true, true, IDS, MV>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     } else {
-      tile_body<FMT, INSTR, false, true, IDS>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, false, true, IDS, MV>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     }
   } else {
-    tile_body<FMT, INSTR, false, false, IDS>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+    tile_body<FMT, INSTR, false, false, IDS, MV>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
   }
 }
 template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false>(P); }
 template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_ids_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, true>(P); }
+// multiview passes (include/svr_views.h)
+template <int FMT, bool INSTR, bool SPLIT>
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false, true>(P); }
+template <int FMT, bool INSTR, bool SPLIT>
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_ids_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, true, true>(P); }
 
 // Instrumented passes only: the counters go to the host (pinned, device-visible) by a one-wave kernel
 // behind the tile kernel.  (A D2H copy packet there costs ~15 us of stream time; a last-workgroup-
@@ -1666,8 +1679,10 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
 #endif
 #define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT)                                                                                          \
   do {                                                                                                                               \
-    if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);    \
-    else hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);              \
+    if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P); \
+    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_mv_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);  \
+    else if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);      \
+    else hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);                \
   } while (0)
   if (color_format == SVR_COLOR_RGBA16F) {
     if (count_fragments) {

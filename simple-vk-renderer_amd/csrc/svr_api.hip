@@ -24,6 +24,7 @@
 
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_ids.h"
+#include "../../include/svr_views.h"
 #include "svr_cull.h"
 #include "svr_launch.h"
 
@@ -197,6 +198,8 @@ struct SvrContext {
     uint32_t n_opaque_obj = 0, n_transparent_obj = 0;  // Objects and List
     // List: the version of a resident draw list it was enqueued with (svr_draw_list): the objects stay on the device
     std::shared_ptr<const ListVersion> list;
+    // List, multiview (svr_draw_list_views): the views' viewproj matrices, 16 floats each; empty = one view
+    std::vector<float> viewprojs;
     bool flattened() const { return input != PassInput::Draws; }
     // a fill: colour target, its format and extent, the rows it writes
     void* target = nullptr;
@@ -509,10 +512,11 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   // per-pass inputs: draws + chunks through pinned staging, one copy
   // (resident: the objects are a draw list's device copy, nothing to stage)
   const size_t n_objects = flatten ? (size_t)op.n_opaque_obj + op.n_transparent_obj : 0;
-  size_t draw_bytes = (flatten ? n_objects : draws.size()) * sizeof(DrawDesc), chunk_bytes = (size_t)P.n_chunks * sizeof(WaveChunk);
+  const size_t n_views = op.viewprojs.size() / 16u;  // a multiview list pass: one draw per object and view at most
+  size_t draw_bytes = (flatten ? n_objects * std::max<size_t>(n_views, 1) : draws.size()) * sizeof(DrawDesc), chunk_bytes = (size_t)P.n_chunks * sizeof(WaveChunk);
   if (int e = set.inputs.ensure(std::max<size_t>(draw_bytes + chunk_bytes + 16, 256))) return e;
   if (flatten)
-    if (int e = set.flat.ensure(n_objects * (16 + sizeof(SvrRenderObject)) + 128)) return e;
+    if (int e = set.flat.ensure(std::max(n_objects * (16 + sizeof(SvrRenderObject)), n_views * 64) + 128)) return e;
   if (int e = bind_pass_buffers(ctx, P, set_index)) return e;
   // How far stage 1 runs ahead.  A pass of few tiles (a band of a sharded frame: stage 1 56 us, tiles 50 us) is bounded
   // by stage 1, which then wants to run back to back: it only waits for its set, last read by the tile stage of
@@ -525,12 +529,13 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
     else if (set.used) HIPCHK(hipStreamWaitEvent(g, set.ev_tile, 0));
   }
   void* stage = nullptr;
-  if (int e = stage_buffer(ctx, op_slot, (flatten ? (resident ? 0 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
+  if (int e = stage_buffer(ctx, op_slot, (flatten ? (resident ? n_views * 64 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
   P.host_counters = &ctx->h_counters[op_slot];
   P.host_row_cost = ctx->h_row_cost + (size_t)op_slot * ROW_COST_MAX;
   P.op_seq = op.seq;
   if (flatten) {  // the objects themselves are the input; cull, sort, draw records and chunks happen on the device
     if (!resident) std::memcpy(stage, op.objects.data(), n_objects * sizeof(SvrRenderObject));
+    if (n_views) std::memcpy(stage, op.viewprojs.data(), n_views * 64);  // the prologue puts them at the head of set.flat
   } else {
     std::memcpy(stage, draws.data(), draw_bytes);
     WaveChunk* ch = reinterpret_cast<WaveChunk*>((char*)stage + draw_bytes);
@@ -554,8 +559,8 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
       if (!ctx->tev[ts][k]) HIPCHK(hipEventCreate(&ctx->tev[ts][k]));
   }
   // inputs out of the staging buffer + zero the counters, class counters and tile_count (adjacent)
-  launch_prologue(stage, set.inputs.p, flatten ? 0 : draw_bytes + chunk_bytes, P.counters,
-                  TILE_HEAD_BYTES + (size_t)P.n_tiles * 2 * sizeof(uint32_t), flatten ? 0u : (uint32_t)draws.size(), P.scene, g);
+  launch_prologue(stage, n_views ? set.flat.p : set.inputs.p, n_views ? n_views * 64 : (flatten ? 0 : draw_bytes + chunk_bytes), P.counters,
+                  TILE_HEAD_BYTES + (size_t)P.n_tiles * 2 * sizeof(uint32_t), (flatten || P.layer_rows) ? 0u : (uint32_t)draws.size(), P.scene, g);
   if (flatten) {
     FlattenParams F;
     std::memset(&F, 0, sizeof(F));
@@ -574,6 +579,8 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
     F.counters = P.counters;
     F.ids = P.ids ? 1u : 0u;
     F.obj_ids = (P.ids && resident) ? op.list->obj_ids : nullptr;
+    F.n_views = (uint32_t)n_views;
+    F.viewprojs = n_views ? (const float*)set.flat.p : nullptr;
     if (resident)
       launch_list_flatten(F, g);
     else
@@ -619,7 +626,8 @@ int retire_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, const Counters&
     ctx->stats.triangle_count = (int32_t)c.flat_tris;
     ctx->stats.culled_draws = c.flat_culled;
   }
-  // the tile rows' costs (posted by its tile kernel before anything else): svr_get_row_costs
+  // the tile rows' costs (posted by its tile kernel before anything else): svr_get_row_costs, of single-view passes
+  if (op.P.layer_rows) return SVR_OK;
   const uint32_t* src = ctx->h_row_cost + (size_t)op.slot * ROW_COST_MAX;
   ctx->row_cost.assign(src, src + std::min<uint32_t>(op.P.tiles_y, ROW_COST_MAX));
   ctx->row_cost_y0 = op.P.sy;
@@ -816,7 +824,8 @@ uint32_t owned_tile_rows(const SvrContext* ctx) {
   return all > ctx->roff ? (all - ctx->roff + ctx->rstride - 1) / ctx->rstride : 0u;
 }
 
-int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tris64, size_t n_chunks, FrameParams& P) {
+// take_clear: a deferred clear of the rows this pass covers may ride along (not for multiview passes: other targets)
+int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tris64, size_t n_chunks, FrameParams& P, bool take_clear = true) {
   if (n_tris64 >= 0x3ffffff0ull) return fail(SVR_ERR_UNSUPPORTED, "more than 2^30 triangles in one pass");
   std::memset(&P, 0, sizeof(P));
   P.color = ctx->color;
@@ -852,7 +861,7 @@ int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tri
   if (scene) P.scene = *scene;
   // a deferred clear of exactly the rows this pass covers rides along; any other one runs now
   const SvrContext::PendingClear& pc = ctx->pending_clear;
-  if (pc.valid && pc.target == ctx->color && pc.fmt == ctx->fmt && pc.y0 == ctx->sy && pc.rows == ctx->sh && ctx->sx == 0 &&
+  if (take_clear && pc.valid && pc.target == ctx->color && pc.fmt == ctx->fmt && pc.y0 == ctx->sy && pc.rows == ctx->sh && ctx->sx == 0 &&
       ctx->sw == ctx->W) {
     P.lazy_clear = 1u;
     P.clear_lo = (uint32_t)pc.packed;
@@ -893,15 +902,44 @@ int upload_flatten_tables(SvrContext* ctx) {
 // Enqueue one pass.  `in` holds its input (in.input and the draws, objects or list version it names), n_tris / n_chunks
 // bound what it draws; ids: a geometry pass, which writes the ID target if there is one (host draws' pad words then carry
 // object numbers).
-int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedOp&& in, uint64_t n_tris, size_t n_chunks, bool ids) {
+// A multiview pass (include/svr_views.h): its layered targets, and the clear its layers start from
+struct MultiView {
+  uint32_t n_views = 0;
+  void* color = nullptr;
+  float* depth = nullptr;
+  uint2* ids = nullptr;
+  bool clear = false;
+  uint64_t packed = 0;
+};
+
+int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedOp&& in, uint64_t n_tris, size_t n_chunks, bool ids,
+                 const MultiView* mv = nullptr) {
   if (int e = poll_pending(ctx)) return e;
   if (in.flattened())  // before fill_frame_params: it can fence, and so flush the deferred clear
     if (int e = upload_flatten_tables(ctx)) return e;
   FrameParams P;
   const SvrContext::PendingClear asked = ctx->pending_clear;  // folded into P.lazy_clear below: put back if the pass is not enqueued
-  if (int e = fill_frame_params(ctx, scene, n_tris, n_chunks, P)) return e;
+  if (int e = fill_frame_params(ctx, scene, n_tris, n_chunks, P, mv == nullptr)) return e;
   P.flatten = in.flattened() ? 1u : 0u;
-  if (ids) P.ids = ctx->ids;
+  if (mv) {  // every layer's tile rows, layer-major; the layers' own clear rides in the pass like a deferred one
+    P.color = mv->color;
+    P.depth = mv->depth;
+    P.ids = mv->ids;
+    P.layer_rows = (ctx->H + TILE - 1) / TILE;
+    P.tiles_y = mv->n_views * P.layer_rows;
+    P.n_tiles = P.tiles_x * P.tiles_y;
+    if (P.n_tiles > SPLIT_TILES_MAX) P.tuning |= TUNE_NO_SPLIT;
+    P.lazy_clear = mv->clear ? 1u : 0u;
+    P.clear_lo = mv->clear ? (uint32_t)mv->packed : 0u;
+    P.clear_hi = mv->clear ? (uint32_t)(mv->packed >> 32) : 0u;
+    if (P.tile_cycles) {
+      if (int e = ctx->d_tile_cycles.ensure((size_t)P.n_tiles * 16)) return e;
+      P.tile_cycles = (uint32_t*)ctx->d_tile_cycles.p;
+    }
+    P.trace_buf = nullptr;  // svr_debug_trace_pixel names a pixel of the context's target, not of a layer
+  } else if (ids) {
+    P.ids = ctx->ids;
+  }
   int slot = 0;
   int e = log_slot(ctx, &slot);
   if (e == SVR_OK) {
@@ -916,12 +954,12 @@ int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedO
     e = submit_pass(ctx, op, !(ctx->tuning & TUNE_NO_PIPELINE));
     if (e) ctx->log.pop_back();
   }
-  if (e && P.lazy_clear) ctx->pending_clear = asked;
+  if (e && P.lazy_clear && !mv) ctx->pending_clear = asked;
   return e;
 }
 
 // a pass of draw records built on the host: numbers their triangles and swaps them into the log
-int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false) {
+int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false, const MultiView* mv = nullptr) {
   uint64_t n_tris64 = 0;
   size_t n_chunks = 0;
   for (DrawDesc& d : draws) {
@@ -931,7 +969,7 @@ int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& 
   }
   SvrContext::LoggedOp in;
   in.draws.swap(draws);
-  return enqueue_pass(ctx, scene, std::move(in), n_tris64, n_chunks, ids);
+  return enqueue_pass(ctx, scene, std::move(in), n_tris64, n_chunks, ids, mv);
 }
 
 // the device flatten's bound on the objects of one pass, and so on those of a draw list (include/svr_draw_list.h)
@@ -1299,10 +1337,8 @@ int svr_write_material(SvrContext* ctx, int pass, const float color_factors[4], 
   return SVR_OK;
 }
 
-int svr_clear_color(SvrContext* ctx, const float rgba[4]) {
-  if (!ctx || !rgba) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_clear_color: null argument");
-  if (int e = use_device(ctx)) return e;
-  if (int e = poll_pending(ctx)) return e;
+// the texel a clear colour is stored as in the context's colour format
+static uint64_t encode_clear(const SvrContext* ctx, const float rgba[4]) {
   uint64_t packed;
   if (ctx->fmt == SVR_COLOR_RGBA16F) {
     packed = (uint64_t)host_f32_to_f16(rgba[0]) | ((uint64_t)host_f32_to_f16(rgba[1]) << 16) |
@@ -1316,6 +1352,14 @@ int svr_clear_color(SvrContext* ctx, const float rgba[4]) {
       packed |= (uint64_t)(uint32_t)std::nearbyintf(c * 255.0f) << (8 * k);
     }
   }
+  return packed;
+}
+
+int svr_clear_color(SvrContext* ctx, const float rgba[4]) {
+  if (!ctx || !rgba) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_clear_color: null argument");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  const uint64_t packed = encode_clear(ctx, rgba);
   // whole rows of the scissor (a rank of the multi-GPU path only owns its band); deferred (flush_clear)
   if (int e = flush_clear(ctx)) return e;  // an older deferred clear cannot be skipped in general
   ctx->pending_clear.valid = true;
@@ -1936,6 +1980,134 @@ int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void
     if (nc) HIPCHK(hipMemcpy(chunks, P.chunks, (size_t)nc * sizeof(WaveChunk), hipMemcpyDeviceToHost));
   }
   return SVR_OK;
+}
+
+// ---------------------------------------------------------------- multiview passes (include/svr_views.h)
+// the arguments every multiview call checks, in the order of the header's refusals; fills mv
+static int check_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* t, const char* who, MultiView* mv) {
+  const std::string fn(who);
+  if (!scenes || !t || !t->color || !t->depth) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
+  if (n_views == 0 || n_views > SVR_MAX_VIEWS) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": need 1 <= n_views <= 16");
+  if ((uint64_t)n_views * ((ctx->H + TILE - 1) / TILE) > ROW_COST_MAX)
+    return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": n_views * ceil(height / 32) exceeds 512 tile rows");
+  if (((uintptr_t)t->color | (uintptr_t)t->depth | (uintptr_t)t->ids) & 15u)
+    return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": targets must be 16-byte aligned");
+  if (ctx->sx != 0 || ctx->sy != 0 || ctx->sw != ctx->W || ctx->sh != ctx->H)
+    return fail(SVR_ERR_UNSUPPORTED, fn + ": a narrowed scissor has no multiview form");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, fn + ": interleaved rows (svr_set_row_interleave) have no multiview form");
+  for (uint32_t k = 1; k < n_views; k++)  // one UBO: only the matrices differ between the views
+    if (std::memcmp(scenes[k].ambient_color, scenes[0].ambient_color, 12 * sizeof(float)) != 0)
+      return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": ambient_color, sunlight_direction and sunlight_color must be equal in every view");
+  mv->n_views = n_views;
+  mv->color = t->color;
+  mv->depth = t->depth;
+  mv->ids = (uint2*)t->ids;
+  mv->clear = t->clear_rgba != nullptr;
+  mv->packed = t->clear_rgba ? encode_clear(ctx, t->clear_rgba) : 0u;
+  return SVR_OK;
+}
+
+// DrawDesc::mvp = viewproj * mat, column by column as prologue_kernel's matvec4 forms it (C0): the product then is the
+// one a single-view pass over this scene computes on the device
+static void host_mvp(const float* vp, const float* mat, float* out) {
+  for (int j = 0; j < 4; j++)
+    for (int r = 0; r < 4; r++) {
+      float acc = vp[0 + r] * mat[4 * j + 0];
+      acc = std::fmaf(vp[4 + r], mat[4 * j + 1], acc);
+      acc = std::fmaf(vp[8 + r], mat[4 * j + 2], acc);
+      acc = std::fmaf(vp[12 + r], mat[4 * j + 3], acc);
+      out[4 * j + r] = acc;
+    }
+}
+
+// The pass of svr_draw_geometry for every view: the opaque draw order is sorted once (a culled subset keeps its order), each
+// view culls with its own viewproj and gets its draws, view after view, with the view in the flags; triangle numbers and
+// wave chunks run on across the views (run_pass)
+static int draw_views(SvrContext* ctx, const MultiView& mv, const SvrSceneData* scenes, const SvrRenderObject* opaque, size_t n_opaque,
+                      const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats,
+                      const std::chrono::steady_clock::time_point& t0) {
+  if (int e = upload_tex_table(ctx, nullptr)) return e;
+  std::vector<uint32_t> sorted(n_opaque);
+  std::iota(sorted.begin(), sorted.end(), 0u);
+  sort_draw_order(sorted, opaque);
+  const bool ids = mv.ids != nullptr;
+  std::vector<DrawDesc> draws;
+  SvrStats st{};
+  for (uint32_t k = 0; k < mv.n_views; k++) {
+    const float* vp = scenes[k].viewproj;
+    auto push = [&](const SvrRenderObject& o, uint32_t object) {
+      const MeshRes& m = ctx->meshes[o.mesh - 1];
+      const MaterialRes& mat = ctx->materials[o.material - 1];
+      DrawDesc d;
+      std::memset(&d, 0, sizeof(d));
+      std::memcpy(d.mat, o.transform, 64);
+      host_mvp(vp, d.mat, d.mvp);
+      std::memcpy(d.color_factors, mat.cf, 16);
+      d.vtx = m.vtx;
+      d.idx = m.idx + o.first_index;
+      d.groups = m.groups;
+      d.first_index = o.first_index;
+      d.tri_count = o.index_count / 3;
+      d.tex = o.material - 1;
+      d.flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (mat.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u) | (k << F_VIEW_SHIFT);
+      d.pad = ids ? object : 0u;
+      draws.push_back(d);
+      st.drawcall_count++;
+      st.triangle_count += (int)(o.index_count / 3);
+    };
+    for (uint32_t i : sorted) {
+      if (is_visible(opaque[i], vp)) push(opaque[i], i + 1u);
+      else st.culled_draws++;
+    }
+    for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
+  }
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, &scenes[0], draws, true, &mv), &t0);
+}
+
+int svr_draw_geometry_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
+                            const SvrRenderObject* opaque, size_t n_opaque, const SvrRenderObject* transparent, size_t n_transparent,
+                            SvrStats* out_stats) {
+  if (!ctx || (!opaque && n_opaque) || (!transparent && n_transparent))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_geometry_views: null argument");
+  auto t0 = std::chrono::steady_clock::now();
+  MultiView mv;
+  if (int e = check_views(ctx, n_views, scenes, targets, "svr_draw_geometry_views", &mv)) return e;
+  for (size_t i = 0; i < n_opaque; i++)
+    if (int e = validate_object(ctx, opaque[i], false, "svr_draw_geometry_views")) return e;
+  for (size_t i = 0; i < n_transparent; i++)
+    if (int e = validate_object(ctx, transparent[i], true, "svr_draw_geometry_views")) return e;
+  if (int e = use_device(ctx)) return e;
+  return draw_views(ctx, mv, scenes, opaque, n_opaque, transparent, n_transparent, out_stats, t0);
+}
+
+int svr_draw_list_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
+                        SvrStats* out_stats) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list_views: null argument");
+  auto t0 = std::chrono::steady_clock::now();
+  DrawListRes* L = get_list(ctx, list);
+  if (!L) return fail(SVR_ERR_BAD_HANDLE, "svr_draw_list_views: bad list handle");
+  MultiView mv;
+  if (int e = check_views(ctx, n_views, scenes, targets, "svr_draw_list_views", &mv)) return e;
+  if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, "svr_draw_list_views");  // a mesh was destroyed since
+  if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list_views: the list is no longer valid (" + L->why + ")");
+  if (int e = use_device(ctx)) return e;
+  const ListVersion& v = *L->cur;
+  const size_t n_objects = (size_t)v.n_opaque + v.n_transparent;
+  if (n_objects > 0 && n_objects <= LIST_FUSED_MAX && ctx->device_flatten != 2) {
+    // the device copy in draw order, culled and turned into records view by view by one workgroup (list_views_kernel)
+    if (int e = upload_tex_table(ctx, nullptr)) return e;
+    SvrContext::LoggedOp in;
+    in.input = SvrContext::PassInput::List;
+    in.list = L->cur;
+    in.n_opaque_obj = v.n_opaque;
+    in.n_transparent_obj = v.n_transparent;
+    in.viewprojs.resize((size_t)n_views * 16);
+    for (uint32_t k = 0; k < n_views; k++) std::memcpy(&in.viewprojs[(size_t)k * 16], scenes[k].viewproj, 64);
+    return finish_draw(ctx, SvrStats{}, out_stats,
+                       enqueue_pass(ctx, &scenes[0], std::move(in), v.tris_max * n_views, v.chunks_max * n_views, true, &mv), &t0);
+  }
+  // larger lists, or SVR_OPT_DEVICE_FLATTEN = 2: the host path over the list's submission-order copy
+  return draw_views(ctx, mv, scenes, L->objs.data(), L->n_opaque, L->objs.data() + L->n_opaque, L->objs.size() - L->n_opaque, out_stats, t0);
 }
 
 // ---------------------------------------------------------------- the ID target (include/svr_ids.h)

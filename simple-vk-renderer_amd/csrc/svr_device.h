@@ -25,6 +25,8 @@ constexpr uint32_t F_T1 = 1u;            // edge 1 is not top-left (biased by -1
 constexpr uint32_t F_T2 = 2u;            // edge 2 is not top-left
 constexpr uint32_t F_KIND_SHIFT = 4;     // 2 bits
 constexpr uint32_t F_TRANSPARENT = 256u;
+constexpr uint32_t F_VIEW_SHIFT = 24;    // 4 bits: the draw's view of a multiview pass (include/svr_views.h); 0 otherwise
+constexpr uint32_t MAX_VIEWS = 16;
 
 // SVR_OPT_TUNING bits: switch an optimisation off at run time so it can be A/B-timed in one process
 constexpr uint32_t TUNE_NO_TILE_ORDER = 1u;   // tile kernel walks tiles row-major instead of heaviest-first
@@ -246,7 +248,8 @@ struct FrameParams {
   float* trace_buf;               // 64 floats or NULL
   uint32_t* tile_cycles;          // SVR_OPT_TILE_CYCLES: [n_tiles][4] shader-clock cycles of phases A..D
   uint32_t tuning;                // SVR_OPT_TUNING bits (A/B switches for benchmarking, default 0)
-  uint32_t pad_t;
+  uint32_t layer_rows;            // multiview passes (include/svr_views.h): tile rows per layer (ceil(H / 32)); tile row t is row
+                                  // t % layer_rows of layer t / layer_rows, at color/depth/ids + layer * W * H.  0: one view
   SvrSceneData scene;
   uint2* ids;                     // ID target (include/svr_ids.h): {object, primitive} per pixel; NULL = none (the kernels'
                                   // ID instances run only when it is set)
@@ -274,6 +277,8 @@ struct FlattenParams {
   uint32_t ids;              // 1: the pass has an ID target (the IDS instances: DrawDesc::pad = object number)
   const uint32_t* obj_ids;   // ... of each opaque object: a draw list's draw order -> its position as submitted, + 1;
                              // NULL: opaque object i is object i + 1
+  uint32_t n_views;          // multiview draw lists (list_views_kernel): the views, one after another, each with its own cull
+  const float* viewprojs;    // ... and their viewproj matrices, 16 floats each (device memory)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -291,6 +296,15 @@ __device__ __forceinline__ void local_tile_rows(const FrameParams& P, int miny, 
     l0 = (g0 - (int)P.roff + s - 1) / s;  // ceil; the dividend is never negative (roff < rstride)
     l1 = b < 0 ? -1 : b / s;
   }
+}
+
+// Multiview passes: every layer has its own ceil(H / 32) tile rows, layer-major, and a record's bins are those of its layer
+// (its view sits in the flags).  Opaque bins [0, n_tiles), transparent bins [n_tiles, 2 n_tiles) as in a single view.
+template <bool MV>
+__device__ __forceinline__ uint32_t bin_base(const FrameParams& P, uint32_t flags) {
+  uint32_t b = (flags & F_TRANSPARENT) ? P.n_tiles : 0u;
+  if (MV) b += (flags >> F_VIEW_SHIFT) * P.layer_rows * P.tiles_x;
+  return b;
 }
 
 __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }

@@ -4,6 +4,9 @@
 //
 //   svr_demo --lib <libsvr_*.so> --width 160 --height 90 --frames 2 --dump /tmp/prefix [--retained 1]
 //       --retained 1: the engine keeps its draw context in a draw list (include/svr_draw_list.h, HIP library only)
+//       --views N: N cameras at the camera's position, yaw stepped by 360/N, in one multiview pass (include/svr_views.h,
+//           HIP library only); prints "view k yaw Y" and dumps layer k as <prefix>.view<k>.color / .depth
+//       --yaw Y: the camera's yaw in radians (a single-camera run of view k: --yaw <its Y>)
 //       --select X,Y: after the last frame, print what won pixel (X, Y) (include/svr_ids.h, HIP library only):
 //           select X Y object N mesh <name> surface S primitive P   or   select X Y none
 //   svr_demo --lib libsvr_hip.so --dist libsvr_dist.so --ranks 2 [--transport shm|rccl] [--bounds 0,13,90] [--rebalance 1]
@@ -68,6 +71,9 @@ int main(int argc, char** argv) {
   int ranks = 1, rebalance = 0, queue_caps = 0, partition = 0, pick_partition = 0;
   uint32_t w = 160, h = 90;
   int frames = 2, background = 0, retained = 0;
+  uint32_t views = 0;
+  float yaw = 0.f;
+  bool set_yaw = false;
   bool select = false;
   uint32_t sel_x = 0, sel_y = 0;
   float cam[5] = {0, 0, 0, 0, 0};  // position, pitch, yaw
@@ -87,6 +93,8 @@ int main(int argc, char** argv) {
     else if (a == "--png") png = argv[i + 1];
     else if (a == "--background") background = atoi(argv[i + 1]);
     else if (a == "--retained") retained = atoi(argv[i + 1]);  // 1: draw through a draw list (include/svr_draw_list.h)
+    else if (a == "--views") views = (uint32_t)atoi(argv[i + 1]);  // N cameras in one multiview pass (include/svr_views.h)
+    else if (a == "--yaw") { yaw = (float)atof(argv[i + 1]); set_yaw = true; }  // the camera's yaw (radians), after the scene's own
     else if (a == "--select" && sscanf(argv[i + 1], "%u,%u", &sel_x, &sel_y) == 2) select = true;  // (--pick is the partition pick)
     else if (a == "--swapchain" && sscanf(argv[i + 1], "%ux%u", &sw, &sh) == 2) {}
     else if (a == "--camera" && sscanf(argv[i + 1], "%f,%f,%f,%f,%f", &cam[0], &cam[1], &cam[2], &cam[3], &cam[4]) == 5) {}
@@ -115,7 +123,7 @@ int main(int argc, char** argv) {
   if (lib.empty()) {
     fprintf(stderr, "usage: svr_demo --lib <shared library exporting svr.h> [--width W --height H --frames N --dump prefix]\n"
                     "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n"
-                    "                [--retained 1]\n");
+                    "                [--retained 1] [--views N] [--yaw radians]\n");
     return 2;
   }
   // the sharded frame: one process per rank, forked before anything touches the GPU; rank 0 makes the id
@@ -387,6 +395,8 @@ int main(int argc, char** argv) {
     g_exit_ok = true;
     return 0;
   }
+  if (set_yaw) eng.main_camera.yaw = yaw;
+  eng.views = views;
   if (select && !eng.enable_ids()) {
     fprintf(stderr, "--select: %s\n", eng.error.c_str());
     return 1;
@@ -398,7 +408,7 @@ int main(int argc, char** argv) {
       dump(prefix + ".opaque", eng.main_draw_context.opaque_surfaces.data(), eng.main_draw_context.opaque_surfaces.size());
       dump(prefix + ".transparent", eng.main_draw_context.transparent_surfaces.data(), eng.main_draw_context.transparent_surfaces.size());
     }
-    if (!eng.draw_background() || !eng.draw_geometry()) {
+    if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : eng.draw_geometry())) {
       fprintf(stderr, "draw failed: %s\n", eng.error.c_str());
       return 1;
     }
@@ -432,6 +442,22 @@ int main(int argc, char** argv) {
       return 1;
     }
     dump(prefix + ".swapchain", swap.data(), swap.size());
+  }
+  if (views) {  // --views: layer k is what a run with --yaw <view k's yaw> leaves in the colour and depth targets
+    std::vector<uint16_t> color;
+    std::vector<float> depth;
+    if (!eng.read_view_layers(color, depth)) {
+      fprintf(stderr, "readback failed: %s\n", eng.error.c_str());
+      return 1;
+    }
+    const size_t px = (size_t)w * h;
+    for (uint32_t k = 0; k < views; k++) {
+      printf("view %u yaw %.9g\n", k, (double)eng.view_yaw(k));
+      if (!prefix.empty()) {
+        dump(prefix + ".view" + std::to_string(k) + ".color", color.data() + px * 4 * k, px * 4);
+        dump(prefix + ".view" + std::to_string(k) + ".depth", depth.data() + px * k, px);
+      }
+    }
   }
   eng.cleanup();
   return 0;

@@ -36,6 +36,8 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_draw_list = reinterpret_cast<decltype(svr_draw_list)>(dlsym(handle, "svr_draw_list"));
   svr_enable_ids = reinterpret_cast<decltype(svr_enable_ids)>(dlsym(handle, "svr_enable_ids"));
   svr_pick = reinterpret_cast<decltype(svr_pick)>(dlsym(handle, "svr_pick"));
+  svr_draw_geometry_views = reinterpret_cast<decltype(svr_draw_geometry_views)>(dlsym(handle, "svr_draw_geometry_views"));
+  svr_draw_list_views = reinterpret_cast<decltype(svr_draw_list_views)>(dlsym(handle, "svr_draw_list_views"));
   return ok;
 }
 void SvrApi::unload() {
@@ -154,6 +156,7 @@ bool SvrEngine::init(const std::string& library_path, uint32_t w, uint32_t h) {
 }
 
 void SvrEngine::cleanup() {
+  release_views();
   if (ctx && draw_list && api.svr_destroy_draw_list) api.svr_destroy_draw_list(ctx, draw_list);
   draw_list = 0;
   if (ctx) api.svr_destroy(ctx);
@@ -364,4 +367,122 @@ bool SvrEngine::read_depth(std::vector<float>& out) {
   return true;
 }
 
+}  // namespace svrhost
+
+// ---------------------------------------------------------------- multiview (include/svr_views.h)
+namespace svrhost {
+namespace {
+// the device allocator and copies of the HIP runtime the product library already has loaded (this harness has no HIP
+// of its own): hipMalloc / hipFree / hipMemcpy by name
+struct HipRt {
+  int (*malloc_)(void**, size_t) = nullptr;
+  int (*free_)(void*) = nullptr;
+  int (*memcpy_)(void*, const void*, size_t, int) = nullptr;
+  bool load() {
+    if (malloc_) return true;
+    void* h = dlopen("libamdhip64.so", RTLD_NOW | RTLD_NOLOAD);
+    if (!h) h = dlopen("libamdhip64.so", RTLD_NOW);
+    if (!h) return false;
+    malloc_ = reinterpret_cast<decltype(malloc_)>(dlsym(h, "hipMalloc"));
+    free_ = reinterpret_cast<decltype(free_)>(dlsym(h, "hipFree"));
+    memcpy_ = reinterpret_cast<decltype(memcpy_)>(dlsym(h, "hipMemcpy"));
+    return malloc_ && free_ && memcpy_;
+  }
+};
+HipRt g_hip;
+constexpr int HIP_H2D = 1, HIP_D2H = 2;
+}  // namespace
+
+float SvrEngine::view_yaw(uint32_t k) const { return main_camera.yaw + (float)k * (svrm::radians(360.f) / (float)views); }
+
+bool SvrEngine::draw_geometry_views() {
+  if (!api.svr_draw_geometry_views || !api.svr_draw_list_views) {
+    error = "--views: the library has no multiview (include/svr_views.h)";
+    return false;
+  }
+  const size_t px = (size_t)width * height;
+  if (!view_color) {
+    if (!g_hip.load()) {
+      error = "--views: no HIP runtime to allocate the layers";
+      return false;
+    }
+    if (g_hip.malloc_(&view_color, px * 8 * views) || g_hip.malloc_((void**)&view_depth, px * 4 * views)) {
+      error = "--views: hipMalloc failed";
+      return false;
+    }
+  }
+  // every layer starts as the context's target after the background: what a single-camera frame loads
+  std::vector<uint16_t> bg(px * 4);
+  if (api.svr_read_color(ctx, bg.data(), bg.size() * 2, 0)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  for (uint32_t k = 0; k < views; k++)
+    if (g_hip.memcpy_((char*)view_color + px * 8 * k, bg.data(), px * 8, HIP_H2D)) {
+      error = "--views: hipMemcpy failed";
+      return false;
+    }
+  // the cameras: update_scene's matrices with the yaw of view k
+  std::vector<SvrSceneData> scenes(views, scene_data);
+  for (uint32_t k = 0; k < views; k++) {
+    Camera cam = main_camera;
+    cam.yaw = view_yaw(k);
+    mat4 view = cam.get_view_matrix();
+    mat4 proj = svrm::perspective(svrm::radians(70.f), (float)width / (float)height, 10000.f, 0.1f);
+    proj.m[1][1] *= -1;
+    mat4 viewproj = svrm::mul(proj, view);
+    std::memcpy(scenes[k].view, view.data(), 64);
+    std::memcpy(scenes[k].proj, proj.data(), 64);
+    std::memcpy(scenes[k].viewproj, viewproj.data(), 64);
+  }
+  SvrViewTargets t{};
+  t.color = view_color;
+  t.depth = view_depth;
+  SvrStats st{};
+  int rc;
+  if (retained) {
+    if (!sync_draw_list()) return false;
+    rc = api.svr_draw_list_views(ctx, draw_list, views, scenes.data(), &t, &st);
+  } else {
+    rc = api.svr_draw_geometry_views(ctx, views, scenes.data(), &t, main_draw_context.opaque_surfaces.data(),
+                                     main_draw_context.opaque_surfaces.size(), main_draw_context.transparent_surfaces.data(),
+                                     main_draw_context.transparent_surfaces.size(), &st);
+  }
+  if (rc) {
+    error = api.svr_last_error();
+    return false;
+  }
+  stats.drawcall_count = st.drawcall_count;
+  stats.triangle_count = st.triangle_count;
+  stats.mesh_draw_time = st.mesh_draw_time;
+  // as after draw_geometry: update_scene refills the opaque list only, the transparent one is emptied here
+  main_draw_context.opaque_surfaces.clear();
+  main_draw_context.transparent_surfaces.clear();
+  drawn_sources.swap(main_draw_context.opaque_sources);
+  main_draw_context.opaque_sources.clear();
+  return true;
+}
+
+void SvrEngine::release_views() {
+  if (ctx && view_color) api.svr_sync(ctx);  // passes in flight write the layers
+  if (view_color) g_hip.free_(view_color);
+  if (view_depth) g_hip.free_(view_depth);
+  view_color = nullptr;
+  view_depth = nullptr;
+}
+
+bool SvrEngine::read_view_layers(std::vector<uint16_t>& color, std::vector<float>& depth) {
+  const size_t px = (size_t)width * height;
+  if (api.svr_sync(ctx)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  color.resize(px * 4 * views);
+  depth.resize(px * views);
+  if (g_hip.memcpy_(color.data(), view_color, color.size() * 2, HIP_D2H) || g_hip.memcpy_(depth.data(), view_depth, depth.size() * 4, HIP_D2H)) {
+    error = "--views: hipMemcpy failed";
+    return false;
+  }
+  return true;
+}
 }  // namespace svrhost

@@ -18,6 +18,7 @@
 
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_ids.h"
+#include "../../include/svr_views.h"
 #include "svr_math.h"
 
 namespace svrhost {
@@ -37,6 +38,8 @@ struct SvrApi {
   SVR_FN(svr_create_draw_list) SVR_FN(svr_update_draw_list) SVR_FN(svr_destroy_draw_list) SVR_FN(svr_draw_list)
   // include/svr_ids.h: optional as well (HIP library only); needed by SvrEngine::pick
   SVR_FN(svr_enable_ids) SVR_FN(svr_pick)
+  // include/svr_views.h: optional (HIP library only), needed by SvrEngine::draw_views
+  SVR_FN(svr_draw_geometry_views) SVR_FN(svr_draw_list_views)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -152,6 +155,16 @@ struct SvrEngine {
   DrawContext list_context;  // what draw_list holds
   bool sync_draw_list();
   bool draw();  // update_scene -> draw_background -> draw_geometry (ImGui/present have no counterpart)
+  // Multiview (svr_demo --views N, include/svr_views.h): N cameras at main_camera's position, yaw stepped by 2 pi / N.
+  // The layers live in device memory of the HIP runtime the library runs on; each starts as the context's colour
+  // target (the background just drawn) and gets view k of the draw context, immediate or retained.
+  uint32_t views = 0;
+  void* view_color = nullptr;  // [views][height][width] RGBA16F texels
+  float* view_depth = nullptr;
+  float view_yaw(uint32_t k) const;
+  bool draw_geometry_views();
+  bool read_view_layers(std::vector<uint16_t>& color, std::vector<float>& depth);
+  void release_views();
   // the swapchain image of the frame just drawn: vkutil::copy_image at src/vk_engine.cpp:1277 (B8G8R8A8)
   bool read_swapchain(std::vector<uint8_t>& out);
   bool read_color_rgba16f(std::vector<uint16_t>& out);
