@@ -93,6 +93,8 @@ ID_SYMBOLS = ["svr_enable_ids", "svr_bind_id_target", "svr_get_id_target", "svr_
 # include/svr_views.h: multiview passes, HIP library only
 VIEWS_SYMBOLS = ["svr_draw_geometry_views", "svr_draw_list_views"]
 MAX_VIEWS = 16
+# include/svr_depth.h: depth-only passes, HIP library only
+DEPTH_SYMBOLS = ["svr_draw_depth", "svr_draw_list_depth", "svr_draw_depth_views", "svr_draw_list_depth_views"]
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -175,6 +177,12 @@ class SvrLib:
             L.svr_draw_geometry_views.argtypes = [P, C.c_uint32, P, C.POINTER(SvrViewTargets), P, C.c_size_t, P, C.c_size_t,
                                                   C.POINTER(SvrStats)]
             L.svr_draw_list_views.argtypes = [P, C.c_uint32, C.c_uint32, P, C.POINTER(SvrViewTargets), C.POINTER(SvrStats)]
+        self.has_depth = hasattr(L, "svr_draw_depth")
+        if self.has_depth:
+            L.svr_draw_depth.argtypes = [P, C.POINTER(SvrSceneData), P, C.c_size_t, C.POINTER(SvrStats)]
+            L.svr_draw_list_depth.argtypes = [P, C.c_uint32, C.POINTER(SvrSceneData), C.POINTER(SvrStats)]
+            L.svr_draw_depth_views.argtypes = [P, C.c_uint32, P, C.POINTER(SvrViewTargets), P, C.c_size_t, C.POINTER(SvrStats)]
+            L.svr_draw_list_depth_views.argtypes = [P, C.c_uint32, C.c_uint32, P, C.POINTER(SvrViewTargets), C.POINTER(SvrStats)]
         self.has_ids = hasattr(L, "svr_enable_ids")
         if self.has_ids:
             L.svr_enable_ids.argtypes = [P, C.c_int]
@@ -400,6 +408,45 @@ class Renderer:
         st = SvrStats()
         handle = lst.handle if isinstance(lst, DrawList) else int(lst)
         self.lib.check(self.lib.lib.svr_draw_list_views(self.h, handle, n, C.addressof(arr), C.byref(t), C.byref(st)))
+        return st
+
+    # -- depth-only passes (include/svr_depth.h)
+    def _need_depth(self):
+        if not getattr(self.lib, "has_depth", False):
+            raise SvrError(-5, f"{self.lib.backend} has no depth-only passes (include/svr_depth.h)")
+
+    def draw_depth(self, scene, opaque):
+        """svr_draw_depth: the depth (and bound ID) target of draw_geometry(scene, opaque), without shading; colour untouched"""
+        self._need_depth()
+        op, n_op = self._objects(opaque)
+        st = SvrStats()
+        self.lib.check(self.lib.lib.svr_draw_depth(self.h, C.byref(scene), op, n_op, C.byref(st)))
+        return st
+
+    def draw_list_depth(self, scene, lst):
+        """svr_draw_list_depth: draw_depth over a retained list's opaque objects"""
+        self._need_depth()
+        st = SvrStats()
+        handle = lst.handle if isinstance(lst, DrawList) else int(lst)
+        self.lib.check(self.lib.lib.svr_draw_list_depth(self.h, handle, C.byref(scene), C.byref(st)))
+        return st
+
+    def draw_depth_views(self, scenes, depth_ptr, opaque, ids_ptr=None):
+        """svr_draw_depth_views: scenes[k] draws layer k of the device targets (depth [K, H, W], ids [K, H, W, 2] or None)"""
+        self._need_depth()
+        n, arr, t = self._view_args(scenes, None, depth_ptr, ids_ptr, None)
+        op, n_op = self._objects(opaque)
+        st = SvrStats()
+        self.lib.check(self.lib.lib.svr_draw_depth_views(self.h, n, C.addressof(arr), C.byref(t), op, n_op, C.byref(st)))
+        return st
+
+    def draw_list_depth_views(self, scenes, lst, depth_ptr, ids_ptr=None):
+        """svr_draw_list_depth_views: draw_depth_views over a retained list's opaque objects"""
+        self._need_depth()
+        n, arr, t = self._view_args(scenes, None, depth_ptr, ids_ptr, None)
+        st = SvrStats()
+        handle = lst.handle if isinstance(lst, DrawList) else int(lst)
+        self.lib.check(self.lib.lib.svr_draw_list_depth_views(self.h, handle, n, C.addressof(arr), C.byref(t), C.byref(st)))
         return st
 
     def read_records(self):

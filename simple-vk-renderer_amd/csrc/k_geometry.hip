@@ -71,8 +71,21 @@ __device__ __forceinline__ bool chunk_can_be_seen(const FrameParams& P, const fl
 // IDS: the pass has an ID target (include/svr_ids.h); records carry their object and primitive (TriRec::object).
 // (A template kernel, not a body shared by two: that wrapper alone cost the instance without IDs two VGPRs.)
 // MV: a multiview pass (include/svr_views.h): the record's bins are its view's layer (bin_base)
+// DO (A/B builds with SVR_AB_DEPTH_SETUP only, tools/build_variant.sh): the instance of a depth-only pass
+// (include/svr_depth.h): gl_Position only, and of the record only what phase A reads — pieces 0-6 (k_tile.hip SREC), bit
+// for bit the colour instances' — plus, with IDS, the ID piece.  Built, measured, not kept (depth-only passes:
+// 7-11 % off a depth-only frame without IDs, 2 % slower with them): depth-only passes run the instances below.  In the
+// product beside them it would rename them (a third template parameter) or cost them two VGPRs (one body behind two
+// kernels, with or without the LDS passed in), and the colour instances keep their names and figures.
+#ifdef SVR_AB_DEPTH_SETUP
+template <bool IDS, bool MV, bool DO = false>
+#else
 template <bool IDS, bool MV>
+#endif
 __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
+#ifndef SVR_AB_DEPTH_SETUP
+  constexpr bool DO = false;
+#endif
   // the wave's chunk and its draw are wave-uniform: held in SGPRs, so chunk -> draw record is two scalar round
   // trips (read as per-lane values they were a chain of six vector loads in front of the first index fetch)
   const uint32_t gw = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
@@ -151,7 +164,7 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
       const uint32_t j = r * 64u + lane;
       if (j < v_count) {
         VOut o;
-        shade_corner(d, kind, d.mvp, v_first + j, o);
+        shade_corner<DO>(d, kind, d.mvp, v_first + j, o);
         s_v[j] = o;
       }
     }
@@ -175,9 +188,9 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
         v1 = s_v[i1 - v_first];
         v2 = s_v[i2 - v_first];
       } else {
-        shade_corner(d, kind, mvp, i0, v0);
-        shade_corner(d, kind, mvp, i1, v1);
-        shade_corner(d, kind, mvp, i2, v2);
+        shade_corner<DO>(d, kind, mvp, i0, v0);
+        shade_corner<DO>(d, kind, mvp, i1, v1);
+        shade_corner<DO>(d, kind, mvp, i2, v2);
       }
     }
     int c0 = outcode(v0.clip), c1 = outcode(v1.clip), c2 = outcode(v2.clip);
@@ -224,6 +237,7 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int half = 0; half < 2; half++) {
+      if (DO && !IDS && half == 1) continue;  // no shading half, no ID piece
 #pragma unroll
       for (uint32_t r = 0; r < 2u; r++) {  // records 32 r .. 32 r + 31
         __builtin_amdgcn_wave_barrier();   // (the wave's LDS operations retire in order; this pins the compiler's order)
@@ -237,6 +251,7 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
           const uint32_t tl = (uint32_t)k * 8u + (lane >> 3), i = lane & 7u, t = 32u * r + tl;
           uint4 v = sl[tl * 8u + (i ^ (tl & 7u))];
           bool header = half == 0 && i == 0u;
+          if (DO && (half == 0 ? i == 7u : i != REC_ID_PIECE - 8u)) continue;  // piece 7 (texture fields), the shading half
           if ((act >> t) & 1ull)
             if (header || ((okm >> t) & 1ull)) wave_recs[t * 16u + (uint32_t)half * 8u + i] = v;
         }
@@ -305,9 +320,18 @@ __global__ __launch_bounds__(256) void vertex_shader_kernel(const SvrVertex* vtx
   reinterpret_cast<float4*>(out_var)[2 * i + 1] = make_float4(o.attr[4], o.attr[5], o.attr[6], o.attr[7]);
 }
 
-void launch_setup(const FrameParams& P, hipStream_t s) {
+void launch_setup(const FrameParams& P, bool depth_only, hipStream_t s) {
   if (P.n_chunks == 0) return;
   uint32_t blocks = (P.n_chunks + 3) / 4;
+#ifdef SVR_AB_DEPTH_SETUP  // A/B builds only: depth-only passes through the DO instances
+  if (depth_only) {
+    if (P.layer_rows && P.ids) hipLaunchKernelGGL((setup_kernel<true, true, true>), dim3(blocks), dim3(256), 0, s, P);
+    else if (P.layer_rows) hipLaunchKernelGGL((setup_kernel<false, true, true>), dim3(blocks), dim3(256), 0, s, P);
+    else if (P.ids) hipLaunchKernelGGL((setup_kernel<true, false, true>), dim3(blocks), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((setup_kernel<false, false, true>), dim3(blocks), dim3(256), 0, s, P);
+    return;
+  }
+#endif
   if (P.layer_rows) {
     if (P.ids) hipLaunchKernelGGL((setup_kernel<true, true>), dim3(blocks), dim3(256), 0, s, P);
     else hipLaunchKernelGGL((setup_kernel<false, true>), dim3(blocks), dim3(256), 0, s, P);

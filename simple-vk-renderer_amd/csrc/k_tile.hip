@@ -1168,6 +1168,36 @@ __device__ __forceinline__ void store_row16(void* p, uint4 v) {
   __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
 }
 
+// The end of every tile workgroup: its phase cycles (SVR_OPT_TILE_CYCLES) and, instrumented, its counters.
+template <bool INSTR>
+__device__ __forceinline__ void tile_epilogue(const FrameParams& P, const bool stamps, const long long (&stamp)[5], const uint32_t tile, const int row0,
+                                              const uint32_t wv, const uint32_t wg_start, const uint32_t lane, uint32_t n_raster, uint32_t n_shaded,
+                                              const uint32_t n_hiz_bad) {
+  if (stamps) {
+    if (tid_of(wv) == 0 && row0 == 0) {  // of a split tile: its first quarter
+#ifdef SVR_DEBUG_WG_TIMES  // development build (tools/frames.py --wgtimes): when and where the workgroup ran, not its phases
+      P.tile_cycles[tile * 4u + 0] = wg_start;
+      P.tile_cycles[tile * 4u + 1] = (uint32_t)wall_clock64();
+      P.tile_cycles[tile * 4u + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
+      P.tile_cycles[tile * 4u + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
+#else
+      for (int k = 0; k < 4; k++) P.tile_cycles[tile * 4u + k] = (uint32_t)(stamp[k + 1] - stamp[k]);
+#endif
+    }
+  }
+  if (INSTR) {
+    for (int off = 32; off > 0; off >>= 1) {
+      n_raster += __shfl_down(n_raster, off);
+      n_shaded += __shfl_down(n_shaded, off);
+    }
+    if (lane == 0) {
+      atomicAdd(&P.counters->rasterized, (unsigned long long)n_raster);
+      atomicAdd(&P.counters->shaded, (unsigned long long)n_shaded);
+    }
+    if (__any(n_hiz_bad != 0u) && n_hiz_bad) atomicAdd(&P.counters->hiz_bad, n_hiz_bad);
+  }
+}
+
 // QUARTER: this workgroup renders 8 rows of a split tile (svr_device.h SPLIT_*).  Its own instantiation, chosen
 // by blockIdx alone: sharing one body with run-time row ranges cost the whole-tile path 20-35 spilled
 // registers and 8-13 % of the frame, and choosing by a flag in tile_info put a dependent load in front of
@@ -1175,7 +1205,9 @@ __device__ __forceinline__ void store_row16(void* p, uint4 v) {
 // MV: a multiview pass (include/svr_views.h): the tile's layer is its tile row / P.layer_rows; its pixel rows are
 // layer-local and its targets start at the layer's base, so rows past the layer's last (a partial last tile row: the next
 // layer's memory) are outside the scissor like any other
-template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV>
+// DO: a depth-only pass (include/svr_depth.h): phase A and the depth / ID store, then the workgroup is done.  Its s_c holds
+// the visibility tile and a quarter's (or a filter window's) list of LCAP entries, nothing of phases B to D.
+template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP>
 __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, const uint4 i1, uint4* s_cov, uint32_t* s_idx, unsigned char* s_c,
                                           const uint32_t wv, const bool hiz_on, const uint32_t wg_start = 0) {
   typedef Codec<FMT> CD;
@@ -1250,7 +1282,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       // A quarter of an opaque-heavy tile: most of the bin's triangles do not reach its 8 rows, and staging
       // them costs as much as in the whole tile.  One pass over the record headers (indices, then bounding
       // rows: two round trips per 1024 entries) leaves the quarter's own list in LDS, behind the depth tile.
-      // The bin is taken in windows of QUARTER_LIST_CAP entries (what the list holds if all of a window stay):
+      // The bin is taken in windows of LCAP entries (QUARTER_LIST_CAP: what the list holds if all of a window stay):
       // visibility is a maximum, so it may be found window by window.  (Bins beyond the capacity used to be
       // walked whole by each of the four quarters: configs[4]'s deepest tiles hold 12 000 triangles, and a
       // rank of eight was as slow as those tiles' quarters — 0.44 ms for an eighth of a 1.5-ms tile stage.)
@@ -1259,9 +1291,11 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       // (there a hidden triangle still costs its place in a batch: two barriers and a round trip per 64, and in the
       // 8K x16 frame nine of ten are hidden).  Windows of 1024 entries then, the sixteen block depths taken off the
       // visibility tile between two of them.  Instrumented passes keep everything and tag what would go (bit 31).
+      // (Visibility is a maximum: how the bin is cut into windows does not change what wins.)
       uint32_t* s_list = reinterpret_cast<uint32_t*>(s_c + LDS_Z_OFF);
       uint32_t* f_bm = s_idx + 48;  // [16] block depths of the filter (scan_columns has s_idx[16..47])
-      const uint32_t WIN = hiz_filter ? 1024u : QUARTER_LIST_CAP;
+      constexpr uint32_t FILTER_WIN = LCAP < 1024u ? LCAP : 1024u;
+      const uint32_t WIN = hiz_filter ? FILTER_WIN : LCAP;
       for (uint32_t win = 0; win < n_op; win += WIN) {
         const uint32_t n_win = min(n_op - win, WIN);
         const bool ftest = hiz_filter && win != 0u;
@@ -1360,7 +1394,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       z = make_uint4(lo.y, lo.w, hi.y, hi.w);
     }
     store_row16(depth + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c), z);
-    if (n_tr) *reinterpret_cast<uint4*>(s_z + row * TILE + c) = z;
+    if (!DO && n_tr) *reinterpret_cast<uint4*>(s_z + row * TILE + c) = z;
   } else {
     int rx, ry;
     uint32_t li;
@@ -1370,7 +1404,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       const uint32_t w = li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256);
       uint32_t z = n_op ? (uint32_t)(s_depth[w] >> 32) : 0u;
       if (pix_ok[k]) depth[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = u2f(z);
-      if (n_tr) s_z[w] = z;
+      if (!DO && n_tr) s_z[w] = z;
     }
   }
   // IDS: the ID target (include/svr_ids.h) leaves with the depth, {object, primitive} of the winner's record ({0, 0}: none),
@@ -1400,6 +1434,11 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       for (int k = 0; k < 4; k++)
         if (pix_ok[k]) ids[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = id[k];
     }
+  }
+  if constexpr (DO) {  // no phase B, C or D: their cycles are 0, and the pass shades nothing
+    if (stamps) stamp[1] = stamp[2] = stamp[3] = stamp[4] = clock64();
+    tile_epilogue<INSTR>(P, stamps, stamp, tile, row0, wv, wg_start, lane, n_raster, 0u, n_hiz_bad);
+    return;
   }
   __syncthreads();  // the visibility tile is dead: its memory is the tile's colour from here on
 
@@ -1526,30 +1565,8 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
         color[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] =
             lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)];
   }
-  if (stamps) {
-    stamp[4] = clock64();
-    if (tid_of(wv) == 0 && row0 == 0) {  // of a split tile: its first quarter
-#ifdef SVR_DEBUG_WG_TIMES  // development build (tools/frames.py --wgtimes): when and where the workgroup ran, not its phases
-      P.tile_cycles[tile * 4u + 0] = wg_start;
-      P.tile_cycles[tile * 4u + 1] = (uint32_t)wall_clock64();
-      P.tile_cycles[tile * 4u + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-      P.tile_cycles[tile * 4u + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-#else
-      for (int k = 0; k < 4; k++) P.tile_cycles[tile * 4u + k] = (uint32_t)(stamp[k + 1] - stamp[k]);
-#endif
-    }
-  }
-  if (INSTR) {
-    for (int off = 32; off > 0; off >>= 1) {
-      n_raster += __shfl_down(n_raster, off);
-      n_shaded += __shfl_down(n_shaded, off);
-    }
-    if (lane == 0) {
-      atomicAdd(&P.counters->rasterized, (unsigned long long)n_raster);
-      atomicAdd(&P.counters->shaded, (unsigned long long)n_shaded);
-    }
-    if (__any(n_hiz_bad != 0u) && n_hiz_bad) atomicAdd(&P.counters->hiz_bad, n_hiz_bad);
-  }
+  if (stamps) stamp[4] = clock64();
+  tile_epilogue<INSTR>(P, stamps, stamp, tile, row0, wv, wg_start, lane, n_raster, n_shaded, n_hiz_bad);
 }
 
 // SPLIT: the launch is headed by SPLIT_EXTRA slots for the quarters of split tiles.  A kernel of its own: the
@@ -1558,18 +1575,33 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #ifndef SVR_TILE_WAVES
 #define SVR_TILE_WAVES 5  // waves per SIMD (= workgroups per CU) the tile kernel is compiled for (A/B builds: tools/build_variant.sh)
 #endif
+#ifndef SVR_DEPTH_WAVES
+#define SVR_DEPTH_WAVES 5  // waves per SIMD (= workgroups per CU) of the depth-only tile kernels (A/B builds: tools/build_variant.sh)
+// (phase A alone needs 90-96 VGPRs: at 6 and more the depth-only instances spill, and 6 measured no faster: DESIGN §5)
+#endif
+// LDS of a depth-only workgroup: s_cov, s_idx, the visibility tile and a list of this many entries fill the workgroup's share
+// of gfx950's 128 granules of 1280 bytes at SVR_DEPTH_WAVES workgroups per CU (8: 928 entries, 6: 2528, 5: 3808)
+constexpr uint32_t depth_list_cap(uint32_t wgs) {
+  return (((128u / wgs) * 1280u - BATCH * 8 * 16 - BATCH * 4 - 64u - LDS_Z_OFF) / 4u) & ~31u;
+}
+constexpr uint32_t DEPTH_LIST_CAP = depth_list_cap(SVR_DEPTH_WAVES) < QUARTER_LIST_CAP ? depth_list_cap(SVR_DEPTH_WAVES) : QUARTER_LIST_CAP;
+static_assert(DEPTH_LIST_CAP >= BATCH, "a depth-only list window holds a batch");
+
 // IDS: the pass writes an ID target (FrameParams::ids): tile_ids_kernel below; tile_kernel is the kernel as it was
-template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false>
+// DO: a depth-only pass (tile_depth_kernel): s_c is the visibility tile and an LCAP-entry list only
+template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP>
 __device__ __forceinline__ void tile_main(const FrameParams& P) {
+  constexpr uint32_t SC_BYTES = DO ? LDS_Z_OFF + LCAP * 4 : PHASE_C_BYTES;
   __shared__ uint4 s_cov[BATCH * 8];
   __shared__ uint32_t s_idx[BATCH];
-  __shared__ __attribute__((aligned(16))) unsigned char s_c[PHASE_C_BYTES];  // phase A depth tile, phase C blocks
-  static_assert(LDS_Z_OFF + QUARTER_LIST_CAP * 4 <= PHASE_C_BYTES, "depth tile + a quarter's triangle list");
-  static_assert(SPLIT_SORT_MAX <= SORT_CAP && PHASE_C_BYTES - LDS_C_OFF >= SORT_CAP * 8 && PHASE_C_BYTES - LDS_C_OFF >= RANK_SORT_MAX * 8 &&
-                    PHASE_C_BYTES - LDS_C_OFF >= 4 * WAVE_C_BYTES, "sort scratch aliases the waves' phase-C blocks");
+  __shared__ __attribute__((aligned(16))) unsigned char s_c[SC_BYTES];  // phase A depth tile, phase C blocks
+  static_assert(LDS_Z_OFF + LCAP * 4 <= SC_BYTES, "depth tile + a quarter's triangle list");
+  static_assert(DO || (SPLIT_SORT_MAX <= SORT_CAP && PHASE_C_BYTES - LDS_C_OFF >= SORT_CAP * 8 && PHASE_C_BYTES - LDS_C_OFF >= RANK_SORT_MAX * 8 &&
+                    PHASE_C_BYTES - LDS_C_OFF >= 4 * WAVE_C_BYTES), "sort scratch aliases the waves' phase-C blocks");
   // gfx950 hands out its 160 KiB of LDS in granules of 1280 bytes (320 dwords): five workgroups per CU need 25 granules
   // each, 32 000 bytes — NOT 32 768 (at 32 064 bytes the kernel stayed at four per CU: tools/frames.py --wgtimes)
-  static_assert(sizeof(s_cov) + sizeof(s_idx) + PHASE_C_BYTES + 64 <= 25 * 1280, "five workgroups per CU: 25 LDS granules of 1280 B");
+  static_assert(DO || sizeof(s_cov) + sizeof(s_idx) + PHASE_C_BYTES + 64 <= 25 * 1280, "five workgroups per CU: 25 LDS granules of 1280 B");
+  static_assert(!DO || sizeof(s_cov) + sizeof(s_idx) + SC_BYTES + 64 <= (128 / SVR_DEPTH_WAVES) * 1280, "SVR_DEPTH_WAVES depth-only workgroups per CU");
   static_assert(TILE * TILE * 8 >= TILE * TILE * sizeof(uint2), "the colour tile aliases the visibility tile");
 
   // Everything the workgroup needs before it can start comes in ONE round of scalar loads: the failure flags
@@ -1621,12 +1653,12 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   } else if (SPLIT) {
     if (blockIdx.x < SPLIT_EXTRA) {  // the quarters of split tiles, as many as fill_kernel made
       if (blockIdx.x >= 4u * min(n_split, SPLIT_MAX)) return;
-      tile_body<FMT, INSTR, true, true, IDS, MV>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, true, true, IDS, MV, DO, LCAP>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     } else {
-      tile_body<FMT, INSTR, false, true, IDS, MV>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, false, true, IDS, MV, DO, LCAP>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     }
   } else {
-    tile_body<FMT, INSTR, false, false, IDS, MV>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+    tile_body<FMT, INSTR, false, false, IDS, MV, DO, LCAP>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
   }
 }
 template <int FMT, bool INSTR, bool SPLIT>
@@ -1638,6 +1670,12 @@ template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false, true>(P); }
 template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_ids_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, true, true>(P); }
+// depth-only passes (include/svr_depth.h): one instance for both colour formats (the colour target is not touched), IDS and
+// MV as above
+template <bool INSTR, bool SPLIT, bool IDS, bool MV>
+__global__ __launch_bounds__(256, SVR_DEPTH_WAVES) void tile_depth_kernel(FrameParams P) {
+  tile_main<SVR_COLOR_RGBA8, INSTR, SPLIT, IDS, MV, true, DEPTH_LIST_CAP>(P);
+}
 
 // Instrumented passes only: the counters go to the host (pinned, device-visible) by a one-wave kernel
 // behind the tile kernel.  (A D2H copy packet there costs ~15 us of stream time; a last-workgroup-
@@ -1653,7 +1691,7 @@ __global__ __launch_bounds__(64) void report_kernel(FrameParams P) {
 // start (may be null): signalled when the tile kernel starts.  done: signalled when the pass's last kernel has finished.  It rides on that kernel's
 // own dispatch packet (hipExtLaunchKernel's stopEvent): a separate hipEventRecord is one more packet
 // for the command processor between two tile kernels.
-void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, hipStream_t s, hipEvent_t start, hipEvent_t done) {
+void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, bool depth_only, hipStream_t s, hipEvent_t start, hipEvent_t done) {
   const bool split = !(P.tuning & (TUNE_NO_SPLIT | TUNE_NO_TILE_ORDER));
   dim3 grid(split ? P.n_tiles + SPLIT_EXTRA : P.n_tiles), block(256);
   const bool report = count_fragments || P.flatten;
@@ -1677,6 +1715,25 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
 #else
   const uint32_t pad = P.n_tiles <= SPLIT_TILES_MAX ? 1280u : 0u;
 #endif
+  if (depth_only) {  // no pad: the small-pass reasoning above is the shading kernel's (depth-only passes)
+#define SVR_LAUNCH_DEPTH(INSTR, SPLIT)                                                                                                         \
+  do {                                                                                                                                         \
+    if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, true>), grid, block, lds_pad, s, start, tile_done, 0, P);  \
+    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, true>), grid, block, lds_pad, s, start, tile_done, 0, P);    \
+    else if (P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, false>), grid, block, lds_pad, s, start, tile_done, 0, P);           \
+    else hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, false>), grid, block, lds_pad, s, start, tile_done, 0, P);                     \
+  } while (0)
+    if (count_fragments) {
+      if (split) SVR_LAUNCH_DEPTH(true, true);
+      else SVR_LAUNCH_DEPTH(true, false);
+    } else {
+      if (split) SVR_LAUNCH_DEPTH(false, true);
+      else SVR_LAUNCH_DEPTH(false, false);
+    }
+#undef SVR_LAUNCH_DEPTH
+    if (report) hipExtLaunchKernelGGL(report_kernel, dim3(1), dim3(64), 0, s, nullptr, done, 0, P);
+    return;
+  }
 #define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT)                                                                                          \
   do {                                                                                                                               \
     if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P); \

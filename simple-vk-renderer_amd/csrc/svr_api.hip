@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/svr_depth.h"
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_ids.h"
 #include "../../include/svr_views.h"
@@ -94,6 +95,8 @@ struct ListVersion {
   uint32_t n_opaque = 0, n_transparent = 0;
   uint64_t tris_max = 0;  // upper bounds that size the pass's buffers and grids (every object visible)
   size_t chunks_max = 0;
+  uint64_t tris_max_opaque = 0;  // ... of the opaque objects alone (depth-only passes: include/svr_depth.h)
+  size_t chunks_max_opaque = 0;
   uint32_t* obj_ids = nullptr;  // [n_opaque] draw order -> position in the opaque array as submitted, + 1 (ID passes: svr_ids.h)
   ~ListVersion() {
     if (dev) (void)hipFree(dev);
@@ -193,6 +196,8 @@ struct SvrContext {
     bool timed = false;  // op_start/op_done of the slot bracket the tile kernel: fold into the running mean at retirement
     FrameParams P{};  // parameters as recorded
     PassInput input = PassInput::Draws;
+    bool depth_only = false;  // a depth-only pass (include/svr_depth.h): set by enqueue_pass; the setup and tile kernels of
+                              // submit_pass, retire_pass and the replay all follow it
     std::vector<DrawDesc> draws;  // Draws: records built on the host
     std::vector<SvrRenderObject> objects;  // Objects: the caller's (opaque, then transparent), flattened on the device
     uint32_t n_opaque_obj = 0, n_transparent_obj = 0;  // Objects and List
@@ -588,7 +593,7 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   }
   const bool all_stages = ctx->kernel_timing >= 2;
   if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][0], g));
-  launch_setup(P, g);
+  launch_setup(P, op.depth_only, g);
   if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][1], g));
   launch_bin_count(P, g);
   launch_bin_scan(P, g);
@@ -597,7 +602,8 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   if (pipe) HIPCHK(hipStreamWaitEvent(s, set.ev_bin, 0));
   if (ts >= 0) HIPCHK(hipEventRecord(ctx->tev[ts][3], s));
   // op_done rides on the pass's last kernel; with kernel timing level 1 op_start rides on the tile kernel too
-  launch_tiles(P, ctx->fmt, P.instrument != 0, s, ctx->kernel_timing == 1 ? ctx->op_start[op_slot] : nullptr, ctx->op_done[op_slot]);
+  launch_tiles(P, ctx->fmt, P.instrument != 0, op.depth_only, s, ctx->kernel_timing == 1 ? ctx->op_start[op_slot] : nullptr,
+               ctx->op_done[op_slot]);
   if (ts >= 0) {
     HIPCHK(hipEventRecord(ctx->tev[ts][4], s));
     ctx->tev_used[ts] = true;
@@ -626,8 +632,8 @@ int retire_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, const Counters&
     ctx->stats.triangle_count = (int32_t)c.flat_tris;
     ctx->stats.culled_draws = c.flat_culled;
   }
-  // the tile rows' costs (posted by its tile kernel before anything else): svr_get_row_costs, of single-view passes
-  if (op.P.layer_rows) return SVR_OK;
+  // the tile rows' costs (posted by its tile kernel before anything else): svr_get_row_costs, of single-view colour passes
+  if (op.P.layer_rows || op.depth_only) return SVR_OK;
   const uint32_t* src = ctx->h_row_cost + (size_t)op.slot * ROW_COST_MAX;
   ctx->row_cost.assign(src, src + std::min<uint32_t>(op.P.tiles_y, ROW_COST_MAX));
   ctx->row_cost_y0 = op.P.sy;
@@ -824,8 +830,12 @@ uint32_t owned_tile_rows(const SvrContext* ctx) {
   return all > ctx->roff ? (all - ctx->roff + ctx->rstride - 1) / ctx->rstride : 0u;
 }
 
-// take_clear: a deferred clear of the rows this pass covers may ride along (not for multiview passes: other targets)
-int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tris64, size_t n_chunks, FrameParams& P, bool take_clear = true) {
+// What a pass does with a deferred svr_clear_color: Take — it rides along if it covers the pass's rows, else it runs now;
+// Flush — it runs now (multiview passes: other targets); Leave — it stays deferred (depth-only passes: the clear belongs
+// to the colour target, which they do not touch)
+enum class ClearMode { Take, Flush, Leave };
+int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tris64, size_t n_chunks, FrameParams& P,
+                      ClearMode clear = ClearMode::Take) {
   if (n_tris64 >= 0x3ffffff0ull) return fail(SVR_ERR_UNSUPPORTED, "more than 2^30 triangles in one pass");
   std::memset(&P, 0, sizeof(P));
   P.color = ctx->color;
@@ -860,8 +870,9 @@ int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tri
   }
   if (scene) P.scene = *scene;
   // a deferred clear of exactly the rows this pass covers rides along; any other one runs now
+  if (clear == ClearMode::Leave) return SVR_OK;
   const SvrContext::PendingClear& pc = ctx->pending_clear;
-  if (take_clear && pc.valid && pc.target == ctx->color && pc.fmt == ctx->fmt && pc.y0 == ctx->sy && pc.rows == ctx->sh && ctx->sx == 0 &&
+  if (clear == ClearMode::Take && pc.valid && pc.target == ctx->color && pc.fmt == ctx->fmt && pc.y0 == ctx->sy && pc.rows == ctx->sh && ctx->sx == 0 &&
       ctx->sw == ctx->W) {
     P.lazy_clear = 1u;
     P.clear_lo = (uint32_t)pc.packed;
@@ -873,10 +884,11 @@ int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tri
   return SVR_OK;
 }
 
-// (re)upload the handle -> resource tables the device flatten pass reads
-int upload_flatten_tables(SvrContext* ctx) {
+// (re)upload the handle -> resource tables the device flatten pass reads; keep_clear: the fence leaves a deferred clear
+// deferred (depth-only passes)
+int upload_flatten_tables(SvrContext* ctx, bool keep_clear = false) {
   if (ctx->mesh_table_n == ctx->meshes.size() && ctx->mat_table_n == ctx->materials.size()) return SVR_OK;
-  if (int e = finish_pending(ctx)) return e;  // a pass in flight may be reading the old tables
+  if (int e = keep_clear ? retire_ops(ctx, true) : finish_pending(ctx)) return e;  // a pass in flight may be reading the old tables
   std::vector<MeshEntry> me(ctx->meshes.size());
   for (size_t i = 0; i < me.size(); i++) {
     me[i].vtx = ctx->meshes[i].vtx;
@@ -901,7 +913,7 @@ int upload_flatten_tables(SvrContext* ctx) {
 
 // Enqueue one pass.  `in` holds its input (in.input and the draws, objects or list version it names), n_tris / n_chunks
 // bound what it draws; ids: a geometry pass, which writes the ID target if there is one (host draws' pad words then carry
-// object numbers).
+// object numbers); depth_only: a depth-only pass (include/svr_depth.h), whose input holds opaque objects only.
 // A multiview pass (include/svr_views.h): its layered targets, and the clear its layers start from
 struct MultiView {
   uint32_t n_views = 0;
@@ -913,13 +925,14 @@ struct MultiView {
 };
 
 int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedOp&& in, uint64_t n_tris, size_t n_chunks, bool ids,
-                 const MultiView* mv = nullptr) {
+                 const MultiView* mv = nullptr, bool depth_only = false) {
   if (int e = poll_pending(ctx)) return e;
   if (in.flattened())  // before fill_frame_params: it can fence, and so flush the deferred clear
-    if (int e = upload_flatten_tables(ctx)) return e;
+    if (int e = upload_flatten_tables(ctx, depth_only)) return e;
   FrameParams P;
   const SvrContext::PendingClear asked = ctx->pending_clear;  // folded into P.lazy_clear below: put back if the pass is not enqueued
-  if (int e = fill_frame_params(ctx, scene, n_tris, n_chunks, P, mv == nullptr)) return e;
+  const ClearMode clear = depth_only ? ClearMode::Leave : (mv ? ClearMode::Flush : ClearMode::Take);
+  if (int e = fill_frame_params(ctx, scene, n_tris, n_chunks, P, clear)) return e;
   P.flatten = in.flattened() ? 1u : 0u;
   if (mv) {  // every layer's tile rows, layer-major; the layers' own clear rides in the pass like a deferred one
     P.color = mv->color;
@@ -940,6 +953,10 @@ int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedO
   } else if (ids) {
     P.ids = ctx->ids;
   }
+  if (depth_only) {  // no colour address, and no fragment stage to trace
+    P.color = nullptr;
+    P.trace_buf = nullptr;
+  }
   int slot = 0;
   int e = log_slot(ctx, &slot);
   if (e == SVR_OK) {
@@ -949,6 +966,7 @@ int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedO
     if (ctx->next_seq == 0) ctx->next_seq = 1;
     op.slot = slot;
     op.timed = ctx->kernel_timing == 1;
+    op.depth_only = depth_only;
     op.P = P;
     std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
     e = submit_pass(ctx, op, !(ctx->tuning & TUNE_NO_PIPELINE));
@@ -959,7 +977,8 @@ int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedO
 }
 
 // a pass of draw records built on the host: numbers their triangles and swaps them into the log
-int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false, const MultiView* mv = nullptr) {
+int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false, const MultiView* mv = nullptr,
+             bool depth_only = false) {
   uint64_t n_tris64 = 0;
   size_t n_chunks = 0;
   for (DrawDesc& d : draws) {
@@ -969,7 +988,7 @@ int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& 
   }
   SvrContext::LoggedOp in;
   in.draws.swap(draws);
-  return enqueue_pass(ctx, scene, std::move(in), n_tris64, n_chunks, ids, mv);
+  return enqueue_pass(ctx, scene, std::move(in), n_tris64, n_chunks, ids, mv, depth_only);
 }
 
 // the device flatten's bound on the objects of one pass, and so on those of a draw list (include/svr_draw_list.h)
@@ -1006,9 +1025,10 @@ int finish_draw(SvrContext* ctx, SvrStats st, SvrStats* out_stats, int e,
 }
 
 // interleaved rows and more ranks than tile rows: this context owns no tile row, and a geometry pass draws nothing
-bool owns_nothing(SvrContext* ctx, SvrStats* out_stats) {
+// (a depth-only pass leaves a deferred clear of the colour target as it is)
+bool owns_nothing(SvrContext* ctx, SvrStats* out_stats, bool depth_only = false) {
   if (owned_tile_rows(ctx) != 0) return false;
-  ctx->pending_clear.valid = false;
+  if (!depth_only) ctx->pending_clear.valid = false;
   finish_draw(ctx, SvrStats{}, out_stats, SVR_OK);
   return true;
 }
@@ -1473,17 +1493,18 @@ static int validate_object(SvrContext* ctx, const SvrRenderObject& o, bool trans
   return SVR_OK;
 }
 
-int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque,
-                      const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats) {
+// svr_draw_geometry, and with depth_only svr_draw_depth (no transparent objects then): who names the entry point
+static int draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque,
+                         const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats, bool depth_only, const char* who) {
   if (!ctx || !scene || (!opaque && n_opaque) || (!transparent && n_transparent))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_geometry: null argument");
+    return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
   auto t0 = std::chrono::steady_clock::now();
   if (int e = use_device(ctx)) return e;
   for (size_t i = 0; i < n_opaque; i++)
-    if (int e = validate_object(ctx, opaque[i], false)) return e;
+    if (int e = validate_object(ctx, opaque[i], false, who)) return e;
   for (size_t i = 0; i < n_transparent; i++)
-    if (int e = validate_object(ctx, transparent[i], true)) return e;
-  if (owns_nothing(ctx, out_stats)) return SVR_OK;
+    if (int e = validate_object(ctx, transparent[i], true, who)) return e;
+  if (owns_nothing(ctx, out_stats, depth_only)) return SVR_OK;
   if (int e = upload_tex_table(ctx, nullptr)) return e;
   // Many objects: cull, sort and the per-object records run on the device (k_flatten.hip).  The three
   // counts of the stats then only exist after the pass (svr_get_stats); out_stats gets what the host knows.
@@ -1500,7 +1521,7 @@ int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRende
     uint64_t tris_max = 0;
     size_t chunks_max = 0;
     add_object_bounds(in.objects.data(), n_objects, &tris_max, &chunks_max);
-    return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), tris_max, chunks_max, true), &t0);
+    return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), tris_max, chunks_max, true, nullptr, depth_only), &t0);
   }
   // cull: opaque only (src/vk_engine.cpp:1361-1367)
   std::vector<uint32_t> order;
@@ -1534,7 +1555,12 @@ int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRende
   for (uint32_t i : order) push(opaque[i], i + 1u);
   for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
   st.culled_draws = (uint32_t)(n_opaque - order.size());
-  return finish_draw(ctx, st, out_stats, run_pass(ctx, scene, draws, true), &t0);
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, scene, draws, true, nullptr, depth_only), &t0);
+}
+
+int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque,
+                      const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats) {
+  return draw_geometry(ctx, scene, opaque, n_opaque, transparent, n_transparent, out_stats, false, "svr_draw_geometry");
 }
 
 int svr_draw_colored_triangle(SvrContext* ctx, SvrStats* out_stats) {
@@ -1866,6 +1892,7 @@ static int make_list_version(const DrawListRes& L, std::shared_ptr<const ListVer
   for (uint32_t i : order) sorted.push_back(L.objs[i]);
   sorted.insert(sorted.end(), L.objs.begin() + L.n_opaque, L.objs.end());
   add_object_bounds(sorted.data(), n, &v->tris_max, &v->chunks_max);
+  add_object_bounds(sorted.data(), L.n_opaque, &v->tris_max_opaque, &v->chunks_max_opaque);
   if (n) {
     HIPCHK(hipMalloc((void**)&v->dev, n * sizeof(SvrRenderObject)));
     HIPCHK(hipMemcpy(v->dev, sorted.data(), n * sizeof(SvrRenderObject), hipMemcpyHostToDevice));
@@ -1932,28 +1959,37 @@ int svr_destroy_draw_list(SvrContext* ctx, SvrDrawList list) {
 
 // Per pass the host checks the handle and the mesh epoch, and enqueues the pass of svr_draw_geometry's device
 // flatten with the list's current version (enqueue_pass): no per-object loop.
-int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
-  if (!ctx || !scene) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list: null argument");
+// svr_draw_list, and with depth_only svr_draw_list_depth: the flatten then walks the list's opaque objects only
+static int draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats, bool depth_only, const char* who) {
+  const std::string fn(who);
+  if (!ctx || !scene) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
   auto t0 = std::chrono::steady_clock::now();
   DrawListRes* L = get_list(ctx, list);
-  if (!L) return fail(SVR_ERR_BAD_HANDLE, "svr_draw_list: bad list handle");
+  if (!L) return fail(SVR_ERR_BAD_HANDLE, fn + ": bad list handle");
   if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, "svr_draw_list");  // a mesh was destroyed since
-  if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list: the list is no longer valid (" + L->why + ")");
+  if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": the list is no longer valid (" + L->why + ")");
   if (int e = use_device(ctx)) return e;
-  if (owns_nothing(ctx, out_stats)) return SVR_OK;
+  if (owns_nothing(ctx, out_stats, depth_only)) return SVR_OK;
   if (int e = upload_tex_table(ctx, nullptr)) return e;
   const ListVersion& v = *L->cur;
-  const size_t n_objects = (size_t)v.n_opaque + v.n_transparent;
+  const uint32_t n_transparent = depth_only ? 0u : v.n_transparent;
+  const size_t n_objects = (size_t)v.n_opaque + n_transparent;
   SvrContext::LoggedOp in;  // no objects: svr_draw_geometry's host path, a pass of no draws
   if (n_objects > 0) {
     if (n_objects > LIST_FUSED_MAX && (ctx->meshes.size() >= (1u << 20) || ctx->materials.size() >= (1u << 20)))
-      return fail(SVR_ERR_UNSUPPORTED, "svr_draw_list: lists over 4096 objects need fewer than 2^20 meshes and materials");
+      return fail(SVR_ERR_UNSUPPORTED, fn + ": lists over 4096 objects need fewer than 2^20 meshes and materials");
     in.input = SvrContext::PassInput::List;
     in.list = L->cur;
     in.n_opaque_obj = v.n_opaque;
-    in.n_transparent_obj = v.n_transparent;
+    in.n_transparent_obj = n_transparent;
   }
-  return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), v.tris_max, v.chunks_max, true), &t0);
+  const uint64_t tris_max = depth_only ? v.tris_max_opaque : v.tris_max;
+  const size_t chunks_max = depth_only ? v.chunks_max_opaque : v.chunks_max;
+  return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), tris_max, chunks_max, true, nullptr, depth_only), &t0);
+}
+
+int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
+  return draw_list(ctx, list, scene, out_stats, false, "svr_draw_list");
 }
 
 int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void* chunks, size_t chunk_bytes, uint32_t* n_draws,
@@ -1984,9 +2020,13 @@ int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void
 
 // ---------------------------------------------------------------- multiview passes (include/svr_views.h)
 // the arguments every multiview call checks, in the order of the header's refusals; fills mv
-static int check_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* t, const char* who, MultiView* mv) {
+// depth_only (include/svr_depth.h): no colour target and no clear; the views' lighting is not read, so it may differ
+static int check_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* t, const char* who, MultiView* mv,
+                       bool depth_only = false) {
   const std::string fn(who);
-  if (!scenes || !t || !t->color || !t->depth) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
+  if (!scenes || !t || (!depth_only && !t->color) || !t->depth) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
+  if (depth_only && (t->color || t->clear_rgba))
+    return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": a depth-only pass takes no colour target and no clear_rgba (both must be NULL)");
   if (n_views == 0 || n_views > SVR_MAX_VIEWS) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": need 1 <= n_views <= 16");
   if ((uint64_t)n_views * ((ctx->H + TILE - 1) / TILE) > ROW_COST_MAX)
     return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": n_views * ceil(height / 32) exceeds 512 tile rows");
@@ -1995,7 +2035,7 @@ static int check_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* sc
   if (ctx->sx != 0 || ctx->sy != 0 || ctx->sw != ctx->W || ctx->sh != ctx->H)
     return fail(SVR_ERR_UNSUPPORTED, fn + ": a narrowed scissor has no multiview form");
   if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, fn + ": interleaved rows (svr_set_row_interleave) have no multiview form");
-  for (uint32_t k = 1; k < n_views; k++)  // one UBO: only the matrices differ between the views
+  for (uint32_t k = 1; k < n_views && !depth_only; k++)  // one UBO: only the matrices differ between the views
     if (std::memcmp(scenes[k].ambient_color, scenes[0].ambient_color, 12 * sizeof(float)) != 0)
       return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": ambient_color, sunlight_direction and sunlight_color must be equal in every view");
   mv->n_views = n_views;
@@ -2025,7 +2065,7 @@ static void host_mvp(const float* vp, const float* mat, float* out) {
 // wave chunks run on across the views (run_pass)
 static int draw_views(SvrContext* ctx, const MultiView& mv, const SvrSceneData* scenes, const SvrRenderObject* opaque, size_t n_opaque,
                       const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats,
-                      const std::chrono::steady_clock::time_point& t0) {
+                      const std::chrono::steady_clock::time_point& t0, bool depth_only = false) {
   if (int e = upload_tex_table(ctx, nullptr)) return e;
   std::vector<uint32_t> sorted(n_opaque);
   std::iota(sorted.begin(), sorted.end(), 0u);
@@ -2061,7 +2101,7 @@ static int draw_views(SvrContext* ctx, const MultiView& mv, const SvrSceneData* 
     }
     for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
   }
-  return finish_draw(ctx, st, out_stats, run_pass(ctx, &scenes[0], draws, true, &mv), &t0);
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, &scenes[0], draws, true, &mv, depth_only), &t0);
 }
 
 int svr_draw_geometry_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
@@ -2080,19 +2120,22 @@ int svr_draw_geometry_views(SvrContext* ctx, uint32_t n_views, const SvrSceneDat
   return draw_views(ctx, mv, scenes, opaque, n_opaque, transparent, n_transparent, out_stats, t0);
 }
 
-int svr_draw_list_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
-                        SvrStats* out_stats) {
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list_views: null argument");
+// svr_draw_list_views, and with depth_only svr_draw_list_depth_views (the list's opaque objects only)
+static int draw_list_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
+                           SvrStats* out_stats, bool depth_only, const char* who) {
+  const std::string fn(who);
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
   auto t0 = std::chrono::steady_clock::now();
   DrawListRes* L = get_list(ctx, list);
-  if (!L) return fail(SVR_ERR_BAD_HANDLE, "svr_draw_list_views: bad list handle");
+  if (!L) return fail(SVR_ERR_BAD_HANDLE, fn + ": bad list handle");
   MultiView mv;
-  if (int e = check_views(ctx, n_views, scenes, targets, "svr_draw_list_views", &mv)) return e;
-  if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, "svr_draw_list_views");  // a mesh was destroyed since
-  if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_list_views: the list is no longer valid (" + L->why + ")");
+  if (int e = check_views(ctx, n_views, scenes, targets, who, &mv, depth_only)) return e;
+  if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, who);  // a mesh was destroyed since
+  if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": the list is no longer valid (" + L->why + ")");
   if (int e = use_device(ctx)) return e;
   const ListVersion& v = *L->cur;
-  const size_t n_objects = (size_t)v.n_opaque + v.n_transparent;
+  const uint32_t n_transparent = depth_only ? 0u : v.n_transparent;
+  const size_t n_objects = (size_t)v.n_opaque + n_transparent;
   if (n_objects > 0 && n_objects <= LIST_FUSED_MAX && ctx->device_flatten != 2) {
     // the device copy in draw order, culled and turned into records view by view by one workgroup (list_views_kernel)
     if (int e = upload_tex_table(ctx, nullptr)) return e;
@@ -2100,14 +2143,47 @@ int svr_draw_list_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, con
     in.input = SvrContext::PassInput::List;
     in.list = L->cur;
     in.n_opaque_obj = v.n_opaque;
-    in.n_transparent_obj = v.n_transparent;
+    in.n_transparent_obj = n_transparent;
     in.viewprojs.resize((size_t)n_views * 16);
     for (uint32_t k = 0; k < n_views; k++) std::memcpy(&in.viewprojs[(size_t)k * 16], scenes[k].viewproj, 64);
+    const uint64_t tris_max = depth_only ? v.tris_max_opaque : v.tris_max;
+    const size_t chunks_max = depth_only ? v.chunks_max_opaque : v.chunks_max;
     return finish_draw(ctx, SvrStats{}, out_stats,
-                       enqueue_pass(ctx, &scenes[0], std::move(in), v.tris_max * n_views, v.chunks_max * n_views, true, &mv), &t0);
+                       enqueue_pass(ctx, &scenes[0], std::move(in), tris_max * n_views, chunks_max * n_views, true, &mv, depth_only), &t0);
   }
   // larger lists, or SVR_OPT_DEVICE_FLATTEN = 2: the host path over the list's submission-order copy
-  return draw_views(ctx, mv, scenes, L->objs.data(), L->n_opaque, L->objs.data() + L->n_opaque, L->objs.size() - L->n_opaque, out_stats, t0);
+  return draw_views(ctx, mv, scenes, L->objs.data(), L->n_opaque, L->objs.data() + L->n_opaque, n_transparent, out_stats, t0, depth_only);
+}
+
+int svr_draw_list_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
+                        SvrStats* out_stats) {
+  return draw_list_views(ctx, list, n_views, scenes, targets, out_stats, false, "svr_draw_list_views");
+}
+
+// ---------------------------------------------------------------- depth-only passes (include/svr_depth.h)
+int svr_draw_depth(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque, SvrStats* out_stats) {
+  return draw_geometry(ctx, scene, opaque, n_opaque, nullptr, 0, out_stats, true, "svr_draw_depth");
+}
+
+int svr_draw_list_depth(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
+  return draw_list(ctx, list, scene, out_stats, true, "svr_draw_list_depth");
+}
+
+int svr_draw_depth_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
+                         const SvrRenderObject* opaque, size_t n_opaque, SvrStats* out_stats) {
+  if (!ctx || (!opaque && n_opaque)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_depth_views: null argument");
+  auto t0 = std::chrono::steady_clock::now();
+  MultiView mv;
+  if (int e = check_views(ctx, n_views, scenes, targets, "svr_draw_depth_views", &mv, true)) return e;
+  for (size_t i = 0; i < n_opaque; i++)
+    if (int e = validate_object(ctx, opaque[i], false, "svr_draw_depth_views")) return e;
+  if (int e = use_device(ctx)) return e;
+  return draw_views(ctx, mv, scenes, opaque, n_opaque, nullptr, 0, out_stats, t0, true);
+}
+
+int svr_draw_list_depth_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes,
+                              const SvrViewTargets* targets, SvrStats* out_stats) {
+  return draw_list_views(ctx, list, n_views, scenes, targets, out_stats, true, "svr_draw_list_depth_views");
 }
 
 // ---------------------------------------------------------------- the ID target (include/svr_ids.h)

@@ -6,12 +6,16 @@
 
 namespace svr {
 
+// POS_ONLY: gl_Position alone (depth-only passes): the varyings are left 0 and their arithmetic is dropped
+template <bool POS_ONLY = false>
 __device__ __forceinline__ void shade_corner(const DrawDesc& d, uint32_t kind, const float* mvp, uint32_t index, VOut& o) {
   VertexRaw v = load_vertex(d.vtx, index);
   if (kind == PIPE_MESH)
     mesh_vert(v, mvp, d.mat, d.color_factors, o);
   else
     colored_triangle_mesh_vert(v, d.mat, o);
+  if (POS_ONLY)
+    for (int k = 0; k < 8; k++) o.attr[k] = 0.0f;
 }
 
 __device__ __forceinline__ float plane_dist(int plane, const float* c) {

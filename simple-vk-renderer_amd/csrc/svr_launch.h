@@ -9,7 +9,8 @@ namespace svr {
 // n_draws: DrawDesc records at the head of the copy whose mvp the kernel fills in (viewproj * mat)
 void launch_prologue(const void* host_src, void* dst, size_t copy_bytes, void* zero, size_t zero_bytes, uint32_t n_draws,
                      const SvrSceneData& scene, hipStream_t s);
-void launch_setup(const FrameParams& P, hipStream_t s);
+// depth_only: a depth-only pass (include/svr_depth.h): the setup_kernel instances that store what phase A reads
+void launch_setup(const FrameParams& P, bool depth_only, hipStream_t s);
 void launch_mesh_vert(const SvrVertex* vtx, uint32_t first, uint32_t n, const float* world16,
                       const float* viewproj16, const float* color_factors4, float* out_clip,
                       float* out_varyings, hipStream_t s);
@@ -26,7 +27,8 @@ void launch_bin_count(const FrameParams& P, hipStream_t s);
 void launch_bin_scan(const FrameParams& P, hipStream_t s);
 void launch_bin_fill(const FrameParams& P, hipStream_t s, hipEvent_t done);  // done: signalled with the kernel (may be null)
 // k_tile.hip
-void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, hipStream_t s, hipEvent_t start, hipEvent_t done);
+// depth_only: a depth-only pass (include/svr_depth.h): the tile_depth_kernel instances, which touch no colour
+void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, bool depth_only, hipStream_t s, hipEvent_t start, hipEvent_t done);
 // k_image.hip
 // packed_pixel: the already encoded texel (RGBA16F: 4 halves, RGBA8: low 32 bits)
 // poison: the context's sticky overflow flag (the clear is void while it is raised)

@@ -7,6 +7,8 @@
 //       --views N: N cameras at the camera's position, yaw stepped by 360/N, in one multiview pass (include/svr_views.h,
 //           HIP library only); prints "view k yaw Y" and dumps layer k as <prefix>.view<k>.color / .depth
 //       --yaw Y: the camera's yaw in radians (a single-camera run of view k: --yaw <its Y>)
+//       --depth-only 1: every frame's geometry is a depth-only pass (include/svr_depth.h, HIP library only): the dumped
+//           depth is a normal run's, the colour the background's
 //       --select X,Y: after the last frame, print what won pixel (X, Y) (include/svr_ids.h, HIP library only):
 //           select X Y object N mesh <name> surface S primitive P   or   select X Y none
 //   svr_demo --lib libsvr_hip.so --dist libsvr_dist.so --ranks 2 [--transport shm|rccl] [--bounds 0,13,90] [--rebalance 1]
@@ -72,6 +74,7 @@ int main(int argc, char** argv) {
   uint32_t w = 160, h = 90;
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
+  bool depth_only = false;
   float yaw = 0.f;
   bool set_yaw = false;
   bool select = false;
@@ -93,6 +96,7 @@ int main(int argc, char** argv) {
     else if (a == "--png") png = argv[i + 1];
     else if (a == "--background") background = atoi(argv[i + 1]);
     else if (a == "--retained") retained = atoi(argv[i + 1]);  // 1: draw through a draw list (include/svr_draw_list.h)
+    else if (a == "--depth-only") depth_only = atoi(argv[i + 1]) != 0;  // depth-only passes (include/svr_depth.h)
     else if (a == "--views") views = (uint32_t)atoi(argv[i + 1]);  // N cameras in one multiview pass (include/svr_views.h)
     else if (a == "--yaw") { yaw = (float)atof(argv[i + 1]); set_yaw = true; }  // the camera's yaw (radians), after the scene's own
     else if (a == "--select" && sscanf(argv[i + 1], "%u,%u", &sel_x, &sel_y) == 2) select = true;  // (--pick is the partition pick)
@@ -123,7 +127,7 @@ int main(int argc, char** argv) {
   if (lib.empty()) {
     fprintf(stderr, "usage: svr_demo --lib <shared library exporting svr.h> [--width W --height H --frames N --dump prefix]\n"
                     "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n"
-                    "                [--retained 1] [--views N] [--yaw radians]\n");
+                    "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1]\n");
     return 2;
   }
   // the sharded frame: one process per rank, forked before anything touches the GPU; rank 0 makes the id
@@ -397,6 +401,10 @@ int main(int argc, char** argv) {
   }
   if (set_yaw) eng.main_camera.yaw = yaw;
   eng.views = views;
+  if (depth_only && views) {
+    fprintf(stderr, "--depth-only: not with --views\n");
+    return 1;
+  }
   if (select && !eng.enable_ids()) {
     fprintf(stderr, "--select: %s\n", eng.error.c_str());
     return 1;
@@ -408,7 +416,7 @@ int main(int argc, char** argv) {
       dump(prefix + ".opaque", eng.main_draw_context.opaque_surfaces.data(), eng.main_draw_context.opaque_surfaces.size());
       dump(prefix + ".transparent", eng.main_draw_context.transparent_surfaces.data(), eng.main_draw_context.transparent_surfaces.size());
     }
-    if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : eng.draw_geometry())) {
+    if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : (depth_only ? eng.draw_depth() : eng.draw_geometry()))) {
       fprintf(stderr, "draw failed: %s\n", eng.error.c_str());
       return 1;
     }

@@ -38,6 +38,8 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_pick = reinterpret_cast<decltype(svr_pick)>(dlsym(handle, "svr_pick"));
   svr_draw_geometry_views = reinterpret_cast<decltype(svr_draw_geometry_views)>(dlsym(handle, "svr_draw_geometry_views"));
   svr_draw_list_views = reinterpret_cast<decltype(svr_draw_list_views)>(dlsym(handle, "svr_draw_list_views"));
+  svr_draw_depth = reinterpret_cast<decltype(svr_draw_depth)>(dlsym(handle, "svr_draw_depth"));
+  svr_draw_list_depth = reinterpret_cast<decltype(svr_draw_list_depth)>(dlsym(handle, "svr_draw_list_depth"));
   return ok;
 }
 void SvrApi::unload() {
@@ -304,6 +306,33 @@ bool SvrEngine::draw_geometry() {  // src/vk_engine.cpp:1357-1477: the whole bod
   main_draw_context.opaque_surfaces.clear();
   main_draw_context.transparent_surfaces.clear();
   // the IDs of this pass count its opaque list as given (a draw list's too: sync_draw_list made it the list's order)
+  drawn_sources.swap(main_draw_context.opaque_sources);
+  main_draw_context.opaque_sources.clear();
+  return true;
+}
+
+bool SvrEngine::draw_depth() {  // draw_geometry without shading: a shadow or depth pass at the same call site
+  if (!api.svr_draw_depth || !api.svr_draw_list_depth) {
+    error = "--depth-only: the library has no depth-only passes (include/svr_depth.h)";
+    return false;
+  }
+  SvrStats st{};
+  int rc;
+  if (retained) {
+    if (!sync_draw_list()) return false;
+    rc = api.svr_draw_list_depth(ctx, draw_list, &scene_data, &st);
+  } else {
+    rc = api.svr_draw_depth(ctx, &scene_data, main_draw_context.opaque_surfaces.data(), main_draw_context.opaque_surfaces.size(), &st);
+  }
+  if (rc) {
+    error = api.svr_last_error();
+    return false;
+  }
+  stats.drawcall_count = st.drawcall_count;
+  stats.triangle_count = st.triangle_count;
+  stats.mesh_draw_time = st.mesh_draw_time;
+  main_draw_context.opaque_surfaces.clear();
+  main_draw_context.transparent_surfaces.clear();
   drawn_sources.swap(main_draw_context.opaque_sources);
   main_draw_context.opaque_sources.clear();
   return true;

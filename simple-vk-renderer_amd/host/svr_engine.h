@@ -18,6 +18,7 @@
 
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_ids.h"
+#include "../../include/svr_depth.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -40,6 +41,8 @@ struct SvrApi {
   SVR_FN(svr_enable_ids) SVR_FN(svr_pick)
   // include/svr_views.h: optional (HIP library only), needed by SvrEngine::draw_views
   SVR_FN(svr_draw_geometry_views) SVR_FN(svr_draw_list_views)
+  // include/svr_depth.h: optional (HIP library only), needed by SvrEngine::draw_depth
+  SVR_FN(svr_draw_depth) SVR_FN(svr_draw_list_depth)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -147,6 +150,9 @@ struct SvrEngine {
   uint32_t swapchain_width = 0, swapchain_height = 0;  // _swap_chain_extent; 0 = the draw extent
   bool draw_background();
   bool draw_geometry();
+  // Depth-only frames (svr_demo --depth-only 1, include/svr_depth.h): the draw context's opaque surfaces (or the draw
+  // list's, retained) into the depth target without shading; the colour target keeps the background just drawn.
+  bool draw_depth();
   // Retained mode (svr_demo --retained): the draw context goes to a draw list made once; the list is updated only
   // where the scene graph's output differs from what it holds (a changed run of objects), or made again when the
   // counts change, and every frame is one svr_draw_list.
