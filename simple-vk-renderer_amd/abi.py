@@ -95,11 +95,19 @@ VIEWS_SYMBOLS = ["svr_draw_geometry_views", "svr_draw_list_views"]
 MAX_VIEWS = 16
 # include/svr_depth.h: depth-only passes, HIP library only
 DEPTH_SYMBOLS = ["svr_draw_depth", "svr_draw_list_depth", "svr_draw_depth_views", "svr_draw_list_depth_views"]
+# include/svr_occlusion.h: occlusion culling against a depth pyramid, HIP library only
+OCCLUSION_SYMBOLS = ["svr_create_depth_pyramid", "svr_destroy_depth_pyramid", "svr_build_depth_pyramid",
+                     "svr_set_occlusion_pyramid", "svr_read_depth_pyramid", "svr_get_occlusion_stats",
+                     "svr_debug_read_occlusion"]
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
 class SvrViewTargets(C.Structure):  # include/svr_views.h
     _fields_ = [("color", C.c_void_p), ("depth", C.c_void_p), ("ids", C.c_void_p), ("clear_rgba", C.POINTER(C.c_float))]
+
+
+class SvrOcclusionStats(C.Structure):  # include/svr_occlusion.h
+    _fields_ = [("chunks_tested", C.c_uint64), ("chunks_culled", C.c_uint64), ("triangles_culled", C.c_uint64)]
 
 
 class SvrError(RuntimeError):
@@ -183,6 +191,15 @@ class SvrLib:
             L.svr_draw_list_depth.argtypes = [P, C.c_uint32, C.POINTER(SvrSceneData), C.POINTER(SvrStats)]
             L.svr_draw_depth_views.argtypes = [P, C.c_uint32, P, C.POINTER(SvrViewTargets), P, C.c_size_t, C.POINTER(SvrStats)]
             L.svr_draw_list_depth_views.argtypes = [P, C.c_uint32, C.c_uint32, P, C.POINTER(SvrViewTargets), C.POINTER(SvrStats)]
+        self.has_occlusion = hasattr(L, "svr_create_depth_pyramid")
+        if self.has_occlusion:
+            L.svr_create_depth_pyramid.argtypes = [P, C.POINTER(C.c_uint32)]
+            L.svr_destroy_depth_pyramid.argtypes = [P, C.c_uint32]
+            L.svr_build_depth_pyramid.argtypes = [P, C.c_uint32, P]
+            L.svr_set_occlusion_pyramid.argtypes = [P, C.c_uint32]
+            L.svr_read_depth_pyramid.argtypes = [P, C.c_uint32, C.c_uint32, P, C.c_size_t, C.POINTER(C.c_uint32)]
+            L.svr_get_occlusion_stats.argtypes = [P, C.POINTER(SvrOcclusionStats)]
+            L.svr_debug_read_occlusion.argtypes = [P, P, C.c_size_t, C.POINTER(C.c_uint32)]
         self.has_ids = hasattr(L, "svr_enable_ids")
         if self.has_ids:
             L.svr_enable_ids.argtypes = [P, C.c_int]
@@ -448,6 +465,66 @@ class Renderer:
         handle = lst.handle if isinstance(lst, DrawList) else int(lst)
         self.lib.check(self.lib.lib.svr_draw_list_depth_views(self.h, handle, n, C.addressof(arr), C.byref(t), C.byref(st)))
         return st
+
+    # -- occlusion culling (include/svr_occlusion.h)
+    def _need_occlusion(self):
+        if not getattr(self.lib, "has_occlusion", False):
+            raise SvrError(-5, f"{self.lib.backend} has no occlusion culling (include/svr_occlusion.h)")
+
+    def create_depth_pyramid(self):
+        """svr_create_depth_pyramid: a handle (int) of a pyramid sized for this context (all 0.0 until built)"""
+        self._need_occlusion()
+        h = C.c_uint32()
+        self.lib.check(self.lib.lib.svr_create_depth_pyramid(self.h, C.byref(h)))
+        return h.value
+
+    def destroy_depth_pyramid(self, pyr):
+        self._need_occlusion()
+        self.lib.check(self.lib.lib.svr_destroy_depth_pyramid(self.h, int(pyr)))
+
+    def build_depth_pyramid(self, pyr, depth_ptr=None):
+        """svr_build_depth_pyramid from a device W x H float buffer (an address), or the context's depth target (None)"""
+        self._need_occlusion()
+        self.lib.check(self.lib.lib.svr_build_depth_pyramid(self.h, int(pyr), depth_ptr))
+
+    def set_occlusion_pyramid(self, pyr):
+        """svr_set_occlusion_pyramid: later passes cull against pyr; 0 = off"""
+        self._need_occlusion()
+        self.lib.check(self.lib.lib.svr_set_occlusion_pyramid(self.h, int(pyr)))
+
+    def pyramid_levels(self, pyr):
+        self._need_occlusion()
+        n = C.c_uint32()
+        rc = self.lib.lib.svr_read_depth_pyramid(self.h, int(pyr), 0, None, 0, C.byref(n))
+        if rc not in (0, -1):
+            self.lib.check(rc)
+        return n.value
+
+    def read_depth_pyramid(self, pyr, level):
+        """level (1 ..) of pyr as uint32 bit patterns [ceil(H / 2^level), ceil(W / 2^level)] (fences)"""
+        self._need_occlusion()
+        lw, lh = -(-self.width // (1 << level)), -(-self.height // (1 << level))
+        out = np.zeros((lh, lw), dtype=np.uint32)
+        self.lib.check(self.lib.lib.svr_read_depth_pyramid(self.h, int(pyr), int(level), out.ctypes.data, out.nbytes, None))
+        return out
+
+    def occlusion_stats(self):
+        """svr_get_occlusion_stats: SvrOcclusionStats of the last instrumented pass"""
+        self._need_occlusion()
+        st = SvrOcclusionStats()
+        self.lib.check(self.lib.lib.svr_get_occlusion_stats(self.h, C.byref(st)))
+        return st
+
+    def read_occlusion(self):
+        """bool [n_chunks]: the chunks of the last pass that occlusion culling dropped, in read_records' order (fences)"""
+        self._need_occlusion()
+        n = C.c_uint32()
+        L = self.lib.lib
+        self.lib.check(L.svr_debug_read_occlusion(self.h, None, 0, C.byref(n)))
+        words = np.zeros(max(1, (n.value + 31) // 32), dtype=np.uint32)
+        self.lib.check(L.svr_debug_read_occlusion(self.h, words.ctypes.data, words.size, C.byref(n)))
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:n.value]
+        return bits.astype(bool)
 
     def read_records(self):
         """(DrawDesc records [n, 192] uint8, WaveChunk records [n, 2] uint32) the last pass ran with (fences)."""

@@ -68,6 +68,69 @@ __device__ __forceinline__ bool chunk_can_be_seen(const FrameParams& P, const fl
   return true;
 }
 
+// Occlusion culling (include/svr_occlusion.h; the margins: DESIGN.md §5, occlusion culling).  Is every fragment of the box
+// [lo, hi] under clip = mvp * (p, 1) strictly behind the pyramid P.pyr over the box's screen rectangle?  Lanes 0..7 take
+// one corner each, through the matvec4 the vertex stage uses (d.mvp): a vertex of the chunk lies in the box, so its exact
+// clip coordinates are a convex combination of the corners' and, with w > 0 at every corner, its exact z / w is at most
+// the corners' largest (z / w is linear-fractional: its maximum over a box in w > 0 sits at a corner).  Float bounds
+// carry the rest: ez, ew bound the error of a computed clip z, w — the corners', the vertices', the clipper's
+// interpolated ones — against the exact ones (4 terms of magnitude at most S: 4 2^-24 S for the transform, 3 2^-24 S
+// more for a clipper's lerp, taken as 2^-20 S); D = the largest (z + ez) / (w - ew) over the corners bounds the exact z / w
+// of every point of the box; a computed vertex then has z_v / w_v <= D + (ez + D ew) / (w_min - 2 ew).  The relative
+// 2^-17 covers the float steps of this bound, the vertex stage's divide (2 ulp) and the tile kernel's plane interpolation
+// (its own bound, k_tile.hip: (|z0| + |dz1| + |dz2|) 2^-21 <= 5 2^-21 of the largest vertex depth).  Fragment depths are
+// clamped to [0, 1], where bit order is float order, so bits(bound) < every texel over the rectangle means every
+// fragment is strictly behind it.  The rectangle: the corners' images, one pixel wider, clamped to the scissor; the
+// level: the smallest at which it spans at most 4 x 4 texels, lanes 0..15 one texel each.  Wave-uniform verdict; NaNs,
+// infinities, corners behind the eye or across the near or far plane never cull.
+__device__ __forceinline__ bool chunk_is_occluded(const FrameParams& P, const float* mvp, const float lo[3], const float hi[3], uint32_t lane) {
+  const float px = (lane & 4u) ? hi[0] : lo[0], py = (lane & 2u) ? hi[1] : lo[1], pz = (lane & 1u) ? hi[2] : lo[2];
+  float c[4];
+  matvec4(mvp, px, py, pz, 1.0f, c);
+  const float ax = fmaxf(fabsf(lo[0]), fabsf(hi[0])), ay = fmaxf(fabsf(lo[1]), fabsf(hi[1])), az = fmaxf(fabsf(lo[2]), fabsf(hi[2]));
+  const float ez = (fabsf(mvp[2]) * ax + fabsf(mvp[6]) * ay + fabsf(mvp[10]) * az + fabsf(mvp[14])) * 0x1p-20f;
+  const float ew = (fabsf(mvp[3]) * ax + fabsf(mvp[7]) * ay + fabsf(mvp[11]) * az + fabsf(mvp[15])) * 0x1p-20f;
+  const unsigned long long corners = 0xffull;
+  const bool fin = fabsf(c[0]) < INFINITY && fabsf(c[1]) < INFINITY && fabsf(c[2]) < INFINITY && fabsf(c[3]) < INFINITY &&
+                   ez < INFINITY && ew < INFINITY;
+  const bool good = fin && c[3] - ew > ew && c[2] - ez >= 0.0f && c[2] + ez <= c[3] - ew;
+  if ((__ballot(good) & corners) != corners) return false;
+  float dmax = (c[2] + ez) / (c[3] - ew), wmin = c[3];
+  float xlo = (c[0] / c[3] + 1.0f) * (0.5f * (float)P.W), ylo = (c[1] / c[3] + 1.0f) * (0.5f * (float)P.H);
+  float xhi = xlo, yhi = ylo;
+#pragma unroll
+  for (int m = 1; m < 8; m <<= 1) {  // lanes 0..7 hold the corners: their partners under xor 1, 2, 4 are corners too
+    dmax = fmaxf(dmax, __shfl_xor(dmax, m));
+    wmin = fminf(wmin, __shfl_xor(wmin, m));
+    xlo = fminf(xlo, __shfl_xor(xlo, m));
+    xhi = fmaxf(xhi, __shfl_xor(xhi, m));
+    ylo = fminf(ylo, __shfl_xor(ylo, m));
+    yhi = fmaxf(yhi, __shfl_xor(yhi, m));
+  }
+  const float bnd = dmax + (ez + dmax * ew) / (wmin - 2.0f * ew);
+  const float zb = __shfl(fminf(bnd + bnd * 0x1p-17f + 0x1p-126f, 1.0f), 0);
+  xlo = __shfl(xlo, 0);
+  xhi = __shfl(xhi, 0);
+  ylo = __shfl(ylo, 0);
+  yhi = __shfl(yhi, 0);
+  if (!(zb >= 0.0f) || !(fabsf(xlo) < 1.0e6f && fabsf(xhi) < 1.0e6f && fabsf(ylo) < 1.0e6f && fabsf(yhi) < 1.0e6f)) return false;
+  const int x0 = __builtin_amdgcn_readfirstlane(max((int)floorf(xlo) - 1, (int)P.sx));
+  const int x1 = __builtin_amdgcn_readfirstlane(min((int)ceilf(xhi) + 1, (int)(P.sx + P.sw) - 1));
+  const int y0 = __builtin_amdgcn_readfirstlane(max((int)floorf(ylo) - 1, (int)P.sy));
+  const int y1 = __builtin_amdgcn_readfirstlane(min((int)ceilf(yhi) + 1, (int)(P.sy + P.sh) - 1));
+  if (x0 > x1 || y0 > y1) return false;  // off the scissor: the frustum test's business, not this one's
+  uint32_t l = 1;
+  while (l < P.pyr_levels && (((uint32_t)x1 >> l) - ((uint32_t)x0 >> l) > 3u || ((uint32_t)y1 >> l) - ((uint32_t)y0 >> l) > 3u)) l++;
+  const uint32_t lw = ((P.W - 1u) >> l) + 1u;
+  const uint32_t tx = ((uint32_t)x0 >> l) + (lane & 3u), ty = ((uint32_t)y0 >> l) + ((lane >> 2) & 3u);
+  uint32_t t = 0xffffffffu;
+  if (lane < 16u && tx <= ((uint32_t)x1 >> l) && ty <= ((uint32_t)y1 >> l)) t = P.pyr[P.pyr_off[l] + ty * lw + tx];
+#pragma unroll
+  for (int m = 1; m < 16; m <<= 1) t = min(t, (uint32_t)__shfl_xor((int)t, m));
+  t = (uint32_t)__shfl((int)t, 0);
+  return f2u(zb) < t;
+}
+
 // IDS: the pass has an ID target (include/svr_ids.h); records carry their object and primitive (TriRec::object).
 // (A template kernel, not a body shared by two: that wrapper alone cost the instance without IDs two VGPRs.)
 // MV: a multiview pass (include/svr_views.h): the record's bins are its view's layer (bin_base)
@@ -114,6 +177,7 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
   // band of rows) above or below the band — are dropped before a single index is fetched: the box of the chunk's
   // vertices comes from the mesh's index-group table (svr_upload_mesh).
   uint32_t v_first = 0, v_count = 0;  // wave-uniform
+  bool occluded = false;              // wave-uniform: dropped by occlusion culling
   if (live && d.groups && kind != PIPE_COLORED_TRIANGLE) {
     const uint32_t first = d.first_index + 3u * ch.first_tri, last = first + 3u * chunk_len(d.first_index, d.tri_count, ch.first_tri) - 1u;
     typedef const __attribute__((address_space(4))) float* const_floats;
@@ -136,7 +200,20 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
       hi[k] = fmaxf(a[3 + k], b[3 + k]);
     }
     if (boxes_ok) live = chunk_can_be_seen(P, d.mvp, lo, hi, lane);
+    if (P.pyr && boxes_ok && live) {  // occlusion culling: only when the pass carries a pyramid (a runtime branch)
+      occluded = chunk_is_occluded(P, d.mvp, lo, hi, lane);
+      live = !occluded;
+      if (P.instrument && lane == 0) {
+        atomicAdd(&P.counters->occl_tested, 1u);
+        if (occluded) {
+          atomicAdd(&P.counters->occl_culled, 1u);
+          atomicAdd(&P.counters->occl_tris, chunk_len(d.first_index, d.tri_count, ch.first_tri));
+        }
+      }
+    }
   }
+  // every chunk's wave writes its flag, so the flags need no zeroing
+  if (P.pyr && gw < n_chunks && lane == 0) P.occl_flags[gw] = occluded ? 1u : 0u;
   // (a chunk ends at the next line of the mesh's index-group grid: svr_device.h chunk_len)
   uint32_t tri = (live && lane < chunk_len(d.first_index, d.tri_count, ch.first_tri)) ? ch.first_tri + lane : 0xffffffffu;
   uint32_t seq = d.tri_base + tri;

@@ -25,6 +25,7 @@
 #include "../../include/svr_depth.h"
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_ids.h"
+#include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
 #include "svr_cull.h"
 #include "svr_launch.h"
@@ -113,6 +114,20 @@ struct DrawListRes {
   bool alive = false;
 };
 
+// A depth pyramid (include/svr_occlusion.h).  The handle, every logged build of it and every logged pass that culls
+// against it share its memory; the last to let go frees it (stream-ordered destruction, like a draw list's version).
+struct PyramidMem {
+  uint32_t* p = nullptr;  // levels 1 .. levels back to back, level l at word off[l]
+  uint32_t levels = 0;
+  uint32_t off[PYR_MAX_LEVELS + 1] = {};
+  size_t words = 0;
+  hipEvent_t ev_built = nullptr;  // recorded behind the last build enqueued (the context's stream): stage 1 of a culling pass waits for it
+  ~PyramidMem() {
+    if (p) (void)hipFree(p);
+    if (ev_built) (void)hipEventDestroy(ev_built);
+  }
+};
+
 // software fp32 -> fp16 (RTE) for the one clear colour the host encodes
 uint16_t host_f32_to_f16(float f) {
   uint32_t x;
@@ -156,6 +171,9 @@ struct SvrContext {
   std::vector<SvrSamplerDesc> samplers;
   std::vector<MaterialRes> materials;
   std::vector<DrawListRes> lists;  // svr_create_draw_list
+  std::vector<std::shared_ptr<PyramidMem>> pyramids;  // svr_create_depth_pyramid (handle - 1; null once destroyed)
+  uint32_t occl_bound = 0;                            // svr_set_occlusion_pyramid: the handle passes cull against, 0 = none
+  SvrOcclusionStats occl_stats{};                     // of the last instrumented pass
   uint64_t mesh_epoch = 0;         // counts svr_destroy_mesh calls: a draw list re-validates when it has moved
   // Texel arena: every image of the context lives in ONE allocation, so a texel's address is a 32-bit byte
   // offset from one wave-uniform base (FrameParams::tex_arena): the fragment stage's eight gathers per pixel
@@ -176,7 +194,7 @@ struct SvrContext {
   // internal stream `gstream` while the tile stage of pass N still reads set N on the caller's
   // stream.  ev_bin: set filled (recorded on gstream); ev_tile: set consumed (the pass's op_done event).
   struct PassSet {
-    DevBuf inputs, recs, clipq, bigq, tiles, bins, pairs, flat, sorta;  // flat: keys / triangle counts / chunk bases of k_flatten  // inputs = DrawDesc[] then WaveChunk[] (one H2D copy)
+    DevBuf inputs, recs, clipq, bigq, tiles, bins, pairs, flat, sorta, occl;  // occl: a culling pass's flag per chunk  // flat: keys / triangle counts / chunk bases of k_flatten  // inputs = DrawDesc[] then WaveChunk[] (one H2D copy)
     hipEvent_t ev_bin = nullptr;
     hipEvent_t ev_tile = nullptr;  // not owned: op_done of the pass that used the set last
     bool used = false;
@@ -186,7 +204,7 @@ struct SvrContext {
   PassSet sets[NSETS];
   int set_pos = 0;
   // operation log (see "the operation log" below): a pass, or a fill of the colour target (every other operation)
-  enum class OpKind { Pass, Clear, Background, Blit };
+  enum class OpKind { Pass, Clear, Background, Blit, Pyramid };  // Pyramid: svr_build_depth_pyramid (logged like a clear)
   enum class PassInput { Draws, Objects, List };  // what a pass reads: the one place that says so (P.flatten follows it)
   struct LoggedOp {
     OpKind kind = OpKind::Pass;
@@ -205,6 +223,9 @@ struct SvrContext {
     std::shared_ptr<const ListVersion> list;
     // List, multiview (svr_draw_list_views): the views' viewproj matrices, 16 floats each; empty = one view
     std::vector<float> viewprojs;
+    // a pass: the pyramid it culls against (include/svr_occlusion.h), or none; Pyramid: the one it builds, from pyr_src
+    std::shared_ptr<PyramidMem> pyr;
+    const float* pyr_src = nullptr;
     bool flattened() const { return input != PassInput::Draws; }
     // a fill: colour target, its format and extent, the rows it writes
     void* target = nullptr;
@@ -523,6 +544,17 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   if (flatten)
     if (int e = set.flat.ensure(std::max(n_objects * (16 + sizeof(SvrRenderObject)), n_views * 64) + 128)) return e;
   if (int e = bind_pass_buffers(ctx, P, set_index)) return e;
+  if (op.pyr) {  // occlusion culling (include/svr_occlusion.h)
+    if (int e = set.occl.ensure(std::max<size_t>(P.n_chunks, 16))) return e;
+    P.pyr = op.pyr->p;
+    P.pyr_levels = op.pyr->levels;
+    std::memcpy(P.pyr_off, op.pyr->off, sizeof(P.pyr_off));
+    P.occl_flags = (uint8_t*)set.occl.p;
+    // Stage 1 reads the pyramid: it waits for the last build enqueued before this pass (on the caller's stream; without
+    // the pipeline, stream order does it).  The other way round needs nothing: a later build of this pyramid runs on the
+    // caller's stream behind this pass's tile kernel, which waits for this pass's stage 1 (ev_bin).
+    if (pipe) HIPCHK(hipStreamWaitEvent(g, op.pyr->ev_built, 0));
+  }
   // How far stage 1 runs ahead.  A pass of few tiles (a band of a sharded frame: stage 1 56 us, tiles 50 us) is bounded
   // by stage 1, which then wants to run back to back: it only waits for its set, last read by the tile stage of
   // NSETS passes ago (a band of an eight-way split: -16 % per frame against two sets, with the priority above).  A 4K
@@ -625,6 +657,9 @@ int retire_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, const Counters&
     ctx->stats.rasterized_fragments = c.rasterized;
     ctx->stats.shaded_fragments = c.shaded;
     ctx->stats.binned_triangles = c.binned;
+    ctx->occl_stats.chunks_tested = c.occl_tested;
+    ctx->occl_stats.chunks_culled = c.occl_culled;
+    ctx->occl_stats.triangles_culled = c.occl_tris;
     if (c.hiz_bad) return fail(SVR_ERR_DEVICE, "internal check failed: the hierarchical depth test dropped a fragment that wins (" + std::to_string(c.hiz_bad) + ")");
   }
   if (op.flattened()) {  // device-flattened passes learn these late
@@ -661,6 +696,9 @@ int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying 
     const size_t px_bytes = op.target_fmt == SVR_COLOR_RGBA16F ? 8 : 4;
     launch_fill_color((char*)op.target + (size_t)op.y_first * op.tw * px_bytes, op.tw * op.n_rows, op.target_fmt, op.clear_packed,
                       ctx->d_poison, ctx->stream);
+  } else if (op.kind == SvrContext::OpKind::Pyramid) {  // (writes nothing while the poison flag is up)
+    launch_pyramid(op.pyr_src, op.tw, op.th, op.pyr->p, op.pyr->off, op.pyr->levels, ctx->d_poison, ctx->stream);
+    HIPCHK(hipEventRecord(op.pyr->ev_built, ctx->stream));
   } else if (op.kind == SvrContext::OpKind::Background) {
     launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison, ctx->stream);
   } else {
@@ -968,6 +1006,7 @@ int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedO
     op.timed = ctx->kernel_timing == 1;
     op.depth_only = depth_only;
     op.P = P;
+    if (ctx->occl_bound && !mv) op.pyr = ctx->pyramids[ctx->occl_bound - 1];  // (multiview passes refuse a bound pyramid)
     std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
     e = submit_pass(ctx, op, !(ctx->tuning & TUNE_NO_PIPELINE));
     if (e) ctx->log.pop_back();
@@ -1109,7 +1148,7 @@ void svr_destroy(SvrContext* ctx) {
   if (ctx->tex_arena) (void)hipFree(ctx->tex_arena);
   DevBuf* bufs[] = {&ctx->tex_table, &ctx->d_cvt, &ctx->d_trace, &ctx->d_tile_cycles, &ctx->mesh_table, &ctx->mat_table};
   for (auto& set : ctx->sets) {
-    DevBuf* sb[] = {&set.inputs, &set.recs, &set.clipq, &set.bigq, &set.tiles, &set.bins, &set.pairs, &set.flat, &set.sorta};
+    DevBuf* sb[] = {&set.inputs, &set.recs, &set.clipq, &set.bigq, &set.tiles, &set.bins, &set.pairs, &set.flat, &set.sorta, &set.occl};
     for (DevBuf* b : sb) b->release();
     if (set.ev_bin) (void)hipEventDestroy(set.ev_bin);
   }
@@ -1130,6 +1169,8 @@ void svr_destroy(SvrContext* ctx) {
   for (int i = 0; i < SvrContext::TRING; i++)
     for (int k = 0; k < 5; k++)
       if (ctx->tev[i][k]) (void)hipEventDestroy(ctx->tev[i][k]);
+  ctx->log.clear();  // the pyramids' memory goes with the last reference to it
+  ctx->pyramids.clear();
   if (ctx->color_own) (void)hipFree(ctx->color_own);
   if (ctx->depth_own) (void)hipFree(ctx->depth_own);
   if (ctx->ids_own) (void)hipFree(ctx->ids_own);
@@ -2035,6 +2076,7 @@ static int check_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* sc
   if (ctx->sx != 0 || ctx->sy != 0 || ctx->sw != ctx->W || ctx->sh != ctx->H)
     return fail(SVR_ERR_UNSUPPORTED, fn + ": a narrowed scissor has no multiview form");
   if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, fn + ": interleaved rows (svr_set_row_interleave) have no multiview form");
+  if (ctx->occl_bound) return fail(SVR_ERR_UNSUPPORTED, fn + ": occlusion culling (svr_set_occlusion_pyramid) has no multiview form");
   for (uint32_t k = 1; k < n_views && !depth_only; k++)  // one UBO: only the matrices differ between the views
     if (std::memcmp(scenes[k].ambient_color, scenes[0].ambient_color, 12 * sizeof(float)) != 0)
       return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": ambient_color, sunlight_direction and sunlight_color must be equal in every view");
@@ -2184,6 +2226,102 @@ int svr_draw_depth_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* 
 int svr_draw_list_depth_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes,
                               const SvrViewTargets* targets, SvrStats* out_stats) {
   return draw_list_views(ctx, list, n_views, scenes, targets, out_stats, true, "svr_draw_list_depth_views");
+}
+
+// ---------------------------------------------------------------- occlusion culling (include/svr_occlusion.h)
+static std::shared_ptr<PyramidMem> get_pyramid(SvrContext* ctx, SvrDepthPyramid h) {
+  if (h == 0 || h > ctx->pyramids.size()) return nullptr;
+  return ctx->pyramids[h - 1];
+}
+
+int svr_create_depth_pyramid(SvrContext* ctx, SvrDepthPyramid* out) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_create_depth_pyramid: null argument");
+  if (int e = use_device(ctx)) return e;
+  auto m = std::make_shared<PyramidMem>();
+  m->levels = pyramid_levels(ctx->W, ctx->H);
+  m->words = pyramid_offsets(ctx->W, ctx->H, m->off);
+  HIPCHK(hipMalloc((void**)&m->p, m->words * sizeof(uint32_t)));
+  HIPCHK(hipEventCreateWithFlags(&m->ev_built, hipEventDisableTiming));
+  // all texels 0.0 until the first build: a pass culls nothing against it
+  HIPCHK(hipMemsetAsync(m->p, 0, m->words * sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipEventRecord(m->ev_built, ctx->stream));
+  ctx->pyramids.push_back(m);
+  *out = (SvrDepthPyramid)ctx->pyramids.size();
+  return SVR_OK;
+}
+
+int svr_destroy_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_destroy_depth_pyramid: null context");
+  if (!get_pyramid(ctx, pyr)) return fail(SVR_ERR_BAD_HANDLE, "svr_destroy_depth_pyramid: bad pyramid handle");
+  if (int e = use_device(ctx)) return e;
+  ctx->pyramids[pyr - 1].reset();  // the memory goes with the last logged operation that holds it
+  if (ctx->occl_bound == pyr) ctx->occl_bound = 0;
+  return SVR_OK;
+}
+
+int svr_build_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr, const float* depth_dev) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_build_depth_pyramid: null context");
+  std::shared_ptr<PyramidMem> m = get_pyramid(ctx, pyr);
+  if (!m) return fail(SVR_ERR_BAD_HANDLE, "svr_build_depth_pyramid: bad pyramid handle");
+  const float* src = depth_dev ? depth_dev : ctx->depth;
+  if (!src) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_build_depth_pyramid: no depth target");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Pyramid, nullptr, 0, 0, ctx->H, &op)) return e;
+  op->pyr = m;
+  op->pyr_src = src;
+  return submit_fill(ctx, *op);
+}
+
+int svr_set_occlusion_pyramid(SvrContext* ctx, SvrDepthPyramid pyr) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_set_occlusion_pyramid: null context");
+  if (pyr != 0 && !get_pyramid(ctx, pyr)) return fail(SVR_ERR_BAD_HANDLE, "svr_set_occlusion_pyramid: bad pyramid handle");
+  ctx->occl_bound = pyr;
+  return SVR_OK;
+}
+
+int svr_read_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr, uint32_t level, void* dst, size_t bytes, uint32_t* n_levels) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: null context");
+  std::shared_ptr<PyramidMem> m = get_pyramid(ctx, pyr);
+  if (!m) return fail(SVR_ERR_BAD_HANDLE, "svr_read_depth_pyramid: bad pyramid handle");
+  if (n_levels) *n_levels = m->levels;
+  if (level < 1 || level > m->levels)
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: level out of range (1.." + std::to_string(m->levels) + ")");
+  const size_t need = (size_t)(((ctx->W - 1u) >> level) + 1u) * (((ctx->H - 1u) >> level) + 1u) * sizeof(uint32_t);
+  if (!dst || bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: destination too small");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst, m->p + m->off[level], need, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+int svr_get_occlusion_stats(SvrContext* ctx, SvrOcclusionStats* out) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_occlusion_stats: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  *out = ctx->occl_stats;
+  return SVR_OK;
+}
+
+int svr_debug_read_occlusion(SvrContext* ctx, uint32_t* bits, size_t capacity, uint32_t* n_chunks) {
+  if (!ctx || !n_chunks) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  const FrameParams& P = ctx->last;
+  if (!P.draws) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: no pass yet");
+  uint32_t nc = P.n_chunks;
+  if (P.flatten) {  // the device knows the count
+    Counters c;
+    HIPCHK(hipMemcpy(&c, P.counters, sizeof(Counters), hipMemcpyDeviceToHost));
+    nc = c.flat_chunks;
+  }
+  *n_chunks = nc;
+  if (!bits) return SVR_OK;
+  if (capacity < ((size_t)nc + 31u) / 32u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: bit buffer too small");
+  std::vector<uint8_t> flags(nc, 0);
+  if (P.occl_flags && nc) HIPCHK(hipMemcpy(flags.data(), P.occl_flags, nc, hipMemcpyDeviceToHost));
+  std::memset(bits, 0, ((size_t)nc + 31u) / 32u * sizeof(uint32_t));
+  for (uint32_t i = 0; i < nc; i++)
+    if (flags[i]) bits[i / 32u] |= 1u << (i % 32u);
+  return SVR_OK;
 }
 
 // ---------------------------------------------------------------- the ID target (include/svr_ids.h)

@@ -182,8 +182,10 @@ struct Counters {
   uint32_t flat_chunks;    // their wave chunks: the setup kernel's real grid
   uint32_t flat_culled;    // opaque objects rejected by is_visible
   uint32_t hiz_bad;        // instrumented passes: fragments the hierarchical depth test would have dropped although they win (must stay 0)
-  uint32_t pad1;
-  unsigned long long pad2;  // 96 bytes: the counters head the tile-counter allocation (zeroed by the prologue)
+  // occlusion culling (include/svr_occlusion.h), instrumented passes only: chunks that reached the test, culled, their triangles
+  uint32_t occl_tested;
+  uint32_t occl_culled;
+  uint32_t occl_tris;      // 96 bytes: the counters head the tile-counter allocation (zeroed by the prologue)
 };
 static_assert(sizeof(Counters) == 96, "Counters layout");
 
@@ -199,6 +201,8 @@ struct MatEntry {
   uint32_t pass;
   uint32_t pad[3];
 };
+
+constexpr uint32_t PYR_MAX_LEVELS = 14;  // a depth pyramid's levels 1 .. : targets up to 16384 = 2^14 pixels wide or high
 
 struct FrameParams {
   // targets
@@ -253,6 +257,13 @@ struct FrameParams {
   SvrSceneData scene;
   uint2* ids;                     // ID target (include/svr_ids.h): {object, primitive} per pixel; NULL = none (the kernels'
                                   // ID instances run only when it is set)
+  // occlusion culling (include/svr_occlusion.h): the bound pyramid's levels 1 .. pyr_levels back to back, level l at word
+  // pyr_off[l] (ceil(W / 2^l) x ceil(H / 2^l) bit patterns, row-major); NULL = no culling (a runtime branch of the setup
+  // kernel, not an instance of its own)
+  const uint32_t* pyr;
+  uint32_t pyr_levels;
+  uint32_t pyr_off[PYR_MAX_LEVELS + 1];
+  uint8_t* occl_flags;            // [n_chunks] with pyr: 1 = the chunk was culled, written by every chunk's wave (no zeroing)
 };
 
 // Largest resident draw list flattened by the single-workgroup list_kernel: four rounds of 1024 lanes.  Each round is

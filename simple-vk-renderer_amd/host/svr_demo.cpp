@@ -9,6 +9,9 @@
 //       --yaw Y: the camera's yaw in radians (a single-camera run of view k: --yaw <its Y>)
 //       --depth-only 1: every frame's geometry is a depth-only pass (include/svr_depth.h, HIP library only): the dumped
 //           depth is a normal run's, the colour the background's
+//       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
+//           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
+//           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
 //       --select X,Y: after the last frame, print what won pixel (X, Y) (include/svr_ids.h, HIP library only):
 //           select X Y object N mesh <name> surface S primitive P   or   select X Y none
 //   svr_demo --lib libsvr_hip.so --dist libsvr_dist.so --ranks 2 [--transport shm|rccl] [--bounds 0,13,90] [--rebalance 1]
@@ -75,6 +78,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false;
+  std::string occlusion = "off";
   float yaw = 0.f;
   bool set_yaw = false;
   bool select = false;
@@ -97,6 +101,7 @@ int main(int argc, char** argv) {
     else if (a == "--background") background = atoi(argv[i + 1]);
     else if (a == "--retained") retained = atoi(argv[i + 1]);  // 1: draw through a draw list (include/svr_draw_list.h)
     else if (a == "--depth-only") depth_only = atoi(argv[i + 1]) != 0;  // depth-only passes (include/svr_depth.h)
+    else if (a == "--occlusion") occlusion = argv[i + 1];  // off | last | prepass (include/svr_occlusion.h)
     else if (a == "--views") views = (uint32_t)atoi(argv[i + 1]);  // N cameras in one multiview pass (include/svr_views.h)
     else if (a == "--yaw") { yaw = (float)atof(argv[i + 1]); set_yaw = true; }  // the camera's yaw (radians), after the scene's own
     else if (a == "--select" && sscanf(argv[i + 1], "%u,%u", &sel_x, &sel_y) == 2) select = true;  // (--pick is the partition pick)
@@ -127,7 +132,8 @@ int main(int argc, char** argv) {
   if (lib.empty()) {
     fprintf(stderr, "usage: svr_demo --lib <shared library exporting svr.h> [--width W --height H --frames N --dump prefix]\n"
                     "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n"
-                    "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1]\n");
+                    "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1]\n"
+                    "                [--occlusion off|last|prepass]\n");
     return 2;
   }
   // the sharded frame: one process per rank, forked before anything touches the GPU; rank 0 makes the id
@@ -196,6 +202,12 @@ int main(int argc, char** argv) {
 
   eng.current_background_effect = background;
   eng.retained = retained != 0;
+  if (occlusion == "last") eng.occlusion = SvrEngine::Occlusion::Last;
+  else if (occlusion == "prepass") eng.occlusion = SvrEngine::Occlusion::Prepass;
+  else if (occlusion != "off") {
+    fprintf(stderr, "--occlusion: off, last or prepass\n");
+    return 2;
+  }
   eng.swapchain_width = sw;
   eng.swapchain_height = sh;
   if (!gltf.empty()) {  // VulkanEngine::init: load_gltf_meshes(this, path) -> loaded_scenes["structure"] (src/vk_engine.cpp:192-198)
@@ -213,6 +225,8 @@ int main(int argc, char** argv) {
     printf("gltf %s: %zu meshes %zu surfaces %zu nodes %zu top nodes %zu materials %zu images %zu samplers\n", gltf.c_str(),
            loaded->meshes.size(), surfaces, loaded->nodes.size(), loaded->top_nodes.size(), loaded->materials.size(),
            loaded->images.size(), loaded->samplers.size());
+    for (auto& m : loaded->materials)
+      if (m->pass_type == SVR_PASS_MAIN_COLOR) eng.occluder_materials.push_back(m->handle);
   } else {
   // "load_gltf_meshes" by hand: one mesh with two primitives (two cubes' worth of geometry in one buffer)
   auto mesh = std::make_shared<MeshAsset>();
@@ -222,6 +236,7 @@ int main(int argc, char** argv) {
   const float tint[4] = {0.4f, 0.3f, 0.2f, 1.f};
   auto transparent = eng.write_material(SVR_PASS_TRANSPARENT, tint, eng.error_checkerboard_image, eng.default_sampler_nearest);
   auto opaque = std::make_shared<MaterialInstance>(eng.default_data);
+  eng.occluder_materials.push_back(opaque->handle);  // --occlusion prepass: the opaque cubes are the occluders
   for (int prim = 0; prim < 2; prim++) {
     size_t initial_vtx = vtx.size();
     std::vector<uint32_t> ci;
@@ -403,6 +418,10 @@ int main(int argc, char** argv) {
   eng.views = views;
   if (depth_only && views) {
     fprintf(stderr, "--depth-only: not with --views\n");
+    return 1;
+  }
+  if (eng.occlusion != SvrEngine::Occlusion::Off && views) {
+    fprintf(stderr, "--occlusion: not with --views (multiview passes do not cull)\n");
     return 1;
   }
   if (select && !eng.enable_ids()) {

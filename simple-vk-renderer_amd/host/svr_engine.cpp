@@ -40,6 +40,10 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_draw_list_views = reinterpret_cast<decltype(svr_draw_list_views)>(dlsym(handle, "svr_draw_list_views"));
   svr_draw_depth = reinterpret_cast<decltype(svr_draw_depth)>(dlsym(handle, "svr_draw_depth"));
   svr_draw_list_depth = reinterpret_cast<decltype(svr_draw_list_depth)>(dlsym(handle, "svr_draw_list_depth"));
+  svr_create_depth_pyramid = reinterpret_cast<decltype(svr_create_depth_pyramid)>(dlsym(handle, "svr_create_depth_pyramid"));
+  svr_destroy_depth_pyramid = reinterpret_cast<decltype(svr_destroy_depth_pyramid)>(dlsym(handle, "svr_destroy_depth_pyramid"));
+  svr_build_depth_pyramid = reinterpret_cast<decltype(svr_build_depth_pyramid)>(dlsym(handle, "svr_build_depth_pyramid"));
+  svr_set_occlusion_pyramid = reinterpret_cast<decltype(svr_set_occlusion_pyramid)>(dlsym(handle, "svr_set_occlusion_pyramid"));
   return ok;
 }
 void SvrApi::unload() {
@@ -161,6 +165,8 @@ void SvrEngine::cleanup() {
   release_views();
   if (ctx && draw_list && api.svr_destroy_draw_list) api.svr_destroy_draw_list(ctx, draw_list);
   draw_list = 0;
+  if (ctx && pyramid && api.svr_destroy_depth_pyramid) api.svr_destroy_depth_pyramid(ctx, pyramid);
+  pyramid = 0;
   if (ctx) api.svr_destroy(ctx);
   ctx = nullptr;
   api.unload();
@@ -285,9 +291,52 @@ bool SvrEngine::sync_draw_list() {
   return true;
 }
 
+bool SvrEngine::occlusion_begin() {
+  if (occlusion == Occlusion::Off) return true;
+  if (!api.svr_create_depth_pyramid || !api.svr_destroy_depth_pyramid || !api.svr_build_depth_pyramid ||
+      !api.svr_set_occlusion_pyramid) {
+    error = "--occlusion: the library has no occlusion culling (include/svr_occlusion.h)";
+    return false;
+  }
+  if (!pyramid && api.svr_create_depth_pyramid(ctx, &pyramid)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  if (occlusion == Occlusion::Prepass) {  // the occluders' depth, with this frame's camera, then its pyramid
+    std::vector<SvrRenderObject> occ;
+    for (const SvrRenderObject& o : main_draw_context.opaque_surfaces)
+      for (SvrMaterial m : occluder_materials)
+        if (o.material == m) {
+          occ.push_back(o);
+          break;
+        }
+    SvrStats st{};
+    if (api.svr_set_occlusion_pyramid(ctx, 0) || api.svr_draw_depth(ctx, &scene_data, occ.data(), occ.size(), &st) ||
+        api.svr_build_depth_pyramid(ctx, pyramid, nullptr)) {
+      error = api.svr_last_error();
+      return false;
+    }
+  }
+  if (api.svr_set_occlusion_pyramid(ctx, pyramid)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::occlusion_end() {
+  if (occlusion != Occlusion::Last) return true;
+  if (api.svr_build_depth_pyramid(ctx, pyramid, nullptr)) {  // this frame's depth: the next frame culls against it
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
 bool SvrEngine::draw_geometry() {  // src/vk_engine.cpp:1357-1477: the whole body is one call
   SvrStats st{};
   int rc;
+  if (!occlusion_begin()) return false;
   if (retained) {
     if (!sync_draw_list()) return false;
     rc = api.svr_draw_list(ctx, draw_list, &scene_data, &st);  // the three counts arrive with the pass (svr_get_stats)
@@ -300,6 +349,7 @@ bool SvrEngine::draw_geometry() {  // src/vk_engine.cpp:1357-1477: the whole bod
     error = api.svr_last_error();
     return false;
   }
+  if (!occlusion_end()) return false;
   stats.drawcall_count = st.drawcall_count;
   stats.triangle_count = st.triangle_count;
   stats.mesh_draw_time = st.mesh_draw_time;
@@ -318,6 +368,7 @@ bool SvrEngine::draw_depth() {  // draw_geometry without shading: a shadow or de
   }
   SvrStats st{};
   int rc;
+  if (!occlusion_begin()) return false;
   if (retained) {
     if (!sync_draw_list()) return false;
     rc = api.svr_draw_list_depth(ctx, draw_list, &scene_data, &st);
@@ -328,6 +379,7 @@ bool SvrEngine::draw_depth() {  // draw_geometry without shading: a shadow or de
     error = api.svr_last_error();
     return false;
   }
+  if (!occlusion_end()) return false;
   stats.drawcall_count = st.drawcall_count;
   stats.triangle_count = st.triangle_count;
   stats.mesh_draw_time = st.mesh_draw_time;

@@ -19,6 +19,7 @@
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_ids.h"
 #include "../../include/svr_depth.h"
+#include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -43,6 +44,9 @@ struct SvrApi {
   SVR_FN(svr_draw_geometry_views) SVR_FN(svr_draw_list_views)
   // include/svr_depth.h: optional (HIP library only), needed by SvrEngine::draw_depth
   SVR_FN(svr_draw_depth) SVR_FN(svr_draw_list_depth)
+  // include/svr_occlusion.h: optional (HIP library only), needed by SvrEngine::occlusion
+  SVR_FN(svr_create_depth_pyramid) SVR_FN(svr_destroy_depth_pyramid) SVR_FN(svr_build_depth_pyramid)
+  SVR_FN(svr_set_occlusion_pyramid)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -153,6 +157,17 @@ struct SvrEngine {
   // Depth-only frames (svr_demo --depth-only 1, include/svr_depth.h): the draw context's opaque surfaces (or the draw
   // list's, retained) into the depth target without shading; the colour target keeps the background just drawn.
   bool draw_depth();
+  // Occlusion culling (svr_demo --occlusion off|last|prepass, include/svr_occlusion.h).  Last: each frame's geometry
+  // culls against the pyramid of the previous frame's depth (built behind every frame; before the first it is all 0.0
+  // and culls nothing).  Prepass: each frame first draws the opaque objects whose material is in occluder_materials
+  // (walls, floors) as a depth-only pass, builds the pyramid from it and culls the frame against that.  Either way the
+  // frames are bit for bit those without culling, for a static camera (last) or always (prepass).
+  enum class Occlusion { Off, Last, Prepass };
+  Occlusion occlusion = Occlusion::Off;
+  std::vector<SvrMaterial> occluder_materials;
+  SvrDepthPyramid pyramid = 0;
+  bool occlusion_begin();  // in front of a frame's geometry pass
+  bool occlusion_end();    // behind it
   // Retained mode (svr_demo --retained): the draw context goes to a draw list made once; the list is updated only
   // where the scene graph's output differs from what it holds (a changed run of objects), or made again when the
   // counts change, and every frame is one svr_draw_list.
