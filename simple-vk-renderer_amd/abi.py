@@ -90,6 +90,10 @@ DRAW_LIST_SYMBOLS = ["svr_create_draw_list", "svr_update_draw_list", "svr_destro
                      "svr_debug_read_records"]
 # include/svr_ids.h: the object and primitive ID target, HIP library only
 ID_SYMBOLS = ["svr_enable_ids", "svr_bind_id_target", "svr_get_id_target", "svr_read_ids", "svr_pick"]
+# include/svr_attributes.h: attribute targets (barycentrics, UV, normal, albedo per pixel), HIP library only
+ATTRIBUTE_SYMBOLS = ["svr_enable_attributes", "svr_bind_attribute_target", "svr_get_attribute_target", "svr_read_attribute"]
+ATTR_BARY, ATTR_UV, ATTR_NORMAL, ATTR_ALBEDO, ATTR_ALL = 1, 2, 4, 8, 15
+ATTR_FLOATS = {ATTR_BARY: 4, ATTR_UV: 2, ATTR_NORMAL: 4, ATTR_ALBEDO: 4}  # floats per texel
 # include/svr_views.h: multiview passes, HIP library only
 VIEWS_SYMBOLS = ["svr_draw_geometry_views", "svr_draw_list_views"]
 MAX_VIEWS = 16
@@ -207,6 +211,12 @@ class SvrLib:
             L.svr_get_id_target.argtypes = [P, C.POINTER(P)]
             L.svr_read_ids.argtypes = [P, P, C.c_size_t]
             L.svr_pick.argtypes = [P, C.c_uint32, C.c_uint32, P]
+        self.has_attributes = hasattr(L, "svr_enable_attributes")
+        if self.has_attributes:
+            L.svr_enable_attributes.argtypes = [P, C.c_uint32]
+            L.svr_bind_attribute_target.argtypes = [P, C.c_int, P]
+            L.svr_get_attribute_target.argtypes = [P, C.c_int, C.POINTER(P)]
+            L.svr_read_attribute.argtypes = [P, C.c_int, P, C.c_size_t]
 
     @property
     def backend(self):
@@ -661,6 +671,34 @@ class Renderer:
         out = (C.c_uint32 * 2)()
         self.lib.check(self.lib.lib.svr_pick(self.h, int(x), int(y), out))
         return None if out[0] == 0 else (int(out[0]), int(out[1]))
+
+    # ---- attribute targets (include/svr_attributes.h)
+    def _need_attributes(self):
+        if not getattr(self.lib, "has_attributes", False):
+            raise SvrError(-5, f"{self.lib.backend} has no attribute targets (include/svr_attributes.h)")
+
+    def enable_attributes(self, mask=ATTR_ALL):
+        """the context-owned planes are those of `mask` (ATTR_* bits) from here on; 0 frees them all"""
+        self._need_attributes()
+        self.lib.check(self.lib.lib.svr_enable_attributes(self.h, int(mask)))
+
+    def bind_attribute_target(self, attr, ptr):
+        """caller-owned device memory (width * height texels) as the plane of one attribute; None/0 = back to the context's"""
+        self._need_attributes()
+        self.lib.check(self.lib.lib.svr_bind_attribute_target(self.h, int(attr), C.c_void_p(ptr or None)))
+
+    def get_attribute_target(self, attr):
+        self._need_attributes()
+        p = C.c_void_p()
+        self.lib.check(self.lib.lib.svr_get_attribute_target(self.h, int(attr), C.byref(p)))
+        return p.value
+
+    def read_attribute(self, attr):
+        """(H, W, 4) float32, UV: (H, W, 2): the plane of one attribute (all-zero texels: no opaque fragment won)"""
+        self._need_attributes()
+        out = np.empty((self.height, self.width, ATTR_FLOATS.get(int(attr), 4)), dtype=np.float32)
+        self.lib.check(self.lib.lib.svr_read_attribute(self.h, int(attr), out.ctypes.data, out.nbytes))
+        return out
 
 
 class DrawList:

@@ -130,6 +130,12 @@ __device__ __forceinline__ float interp3(float a0, float da1, float da2, float b
   return fmaf(b2, da2, fmaf(b1, da1, a0)) * r;
 }
 
+// What an attribute pass (include/svr_attributes.h) keeps of a fragment-shader invocation: trace slots 1-5 and 15-21 of
+// the pixel, out of the registers that made its colour.  won: 1.0f, the ALBEDO texel's last word (0: no opaque fragment).
+struct FragAttr {
+  float b1, b2, r, u, v, nx, ny, nz, light, cr, cg, cb, won;
+};
+
 // The quad partners' u,v by DPP: lanes ^1 / ^8 of an 8x8 block hold the pixel's horizontal / vertical quad partner.
 // Where every quad of the block is of one triangle (QUADS, wave-uniform: 42 % of a 4K frame's pixels, 77 % of the 8K x16
 // frame's) the partner's own u,v ARE the values this lane would extrapolate for it — the edge functions are exact
@@ -140,8 +146,10 @@ __device__ __forceinline__ float quad_partner_y(float v) { return u2f((uint32_t)
 // COMMON: the caller knows (key bit 1) that this is mesh.frag with a LINEAR/LINEAR/MIPMAP_LINEAR sampler
 // on an image with power-of-two extents:
 // pipeline kind, filter and mip-mode selections fold away (same arithmetic on the surviving path).
-template <bool TRACE, bool COMMON = false>
-__device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec, int px, int py, float* trace, const bool quads = false) {
+// ATTR: the invocation's attribute values go to *fa (a compile-time flag: the other instances carry nothing of it)
+template <bool TRACE, bool COMMON = false, bool ATTR = false>
+__device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec, int px, int py, float* trace, const bool quads = false,
+                                              FragAttr* fa = nullptr) {
   const TriRec* tr = P.recs + rec;
   const uint4* q4 = reinterpret_cast<const uint4*>(tr);
   const float4* f4 = reinterpret_cast<const float4*>(tr);
@@ -193,8 +201,10 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   float cr = interp3(s1.z, s3.z, s5.z, b1, b2, r);
   float cg = interp3(s1.w, s3.w, s5.w, b1, b2, r);
   float cb = interp3(s2.x, s4.x, s6.x, b1, b2, r);
+  if (ATTR) { fa->b1 = b1; fa->b2 = b2; fa->r = r; fa->won = 1.0f; }
   if (kind == PIPE_COLORED_TRIANGLE) return make_float4(cr, cg, cb, 1.0f);  // shaders/colored_triangle.frag:9-12
   float u = interp3(s2.y, s4.y, s6.y, b1, b2, r), v = interp3(s2.z, s4.z, s6.z, b1, b2, r);
+  if (ATTR) { fa->u = u; fa->v = v; }
   if (!COMMON) {
     hr = rcp_ieee(hq);
     vr = rcp_ieee(vq);
@@ -291,6 +301,7 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
     trace[15] = nx; trace[16] = ny; trace[17] = nz; trace[18] = cr; trace[19] = cg; trace[20] = cb;
     trace[21] = light; trace[22] = o.x; trace[23] = o.y; trace[24] = o.z; trace[25] = o.w;
   }
+  if (ATTR) { fa->nx = nx; fa->ny = ny; fa->nz = nz; fa->light = light; fa->cr = cr; fa->cg = cg; fa->cb = cb; }
   return o;
 }
 
@@ -1168,6 +1179,27 @@ __device__ __forceinline__ void store_row16(void* p, uint4 v) {
   __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
 }
 
+// Attribute passes (include/svr_attributes.h): one pixel's texels leave for the planes that are bound (a run-time test per
+// plane, pass-uniform), straight from the registers shade_pixel handed back; `a` is all zero where no opaque fragment won.
+// Nothing is staged: slot k of a wave is one 8x8 block, eight lanes are eight neighbouring pixels of a row, so a store
+// instruction of a float4 plane writes eight whole 128-byte pieces of rows (whole lines, where the plane's base and row
+// pitch are multiples of 128 bytes) — the shape the colour tile only gets by going through LDS, because its texels are a
+// quarter or half as wide.  The UV plane's texels are 8 bytes, a block's rows 64-byte half lines; collecting whole tiles
+// of them in s_cov and writing whole rows behind phase B, as the ID target does, was built and measured SLOWER than these
+// stores (two barriers more per tile: DESIGN.md "Attribute targets").
+__device__ __forceinline__ void store_attr(const FrameParams& P, const FragAttr& a, const bool ok, const int px, const int py) {
+  if (!ok) return;
+  const size_t at = (size_t)py * P.W + (size_t)px;
+  if (P.attr[0]) store_row16(reinterpret_cast<float4*>(P.attr[0]) + at, make_uint4(f2u(a.b1), f2u(a.b2), f2u(a.r), 0u));
+  if (P.attr[1]) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 t = {f2u(a.u), f2u(a.v)};
+    __builtin_nontemporal_store(t, reinterpret_cast<u32x2*>(P.attr[1]) + at);
+  }
+  if (P.attr[2]) store_row16(reinterpret_cast<float4*>(P.attr[2]) + at, make_uint4(f2u(a.nx), f2u(a.ny), f2u(a.nz), f2u(a.light)));
+  if (P.attr[3]) store_row16(reinterpret_cast<float4*>(P.attr[3]) + at, make_uint4(f2u(a.cr), f2u(a.cg), f2u(a.cb), f2u(a.won)));
+}
+
 // The end of every tile workgroup: its phase cycles (SVR_OPT_TILE_CYCLES) and, instrumented, its counters.
 template <bool INSTR>
 __device__ __forceinline__ void tile_epilogue(const FrameParams& P, const bool stamps, const long long (&stamp)[5], const uint32_t tile, const int row0,
@@ -1207,7 +1239,9 @@ __device__ __forceinline__ void tile_epilogue(const FrameParams& P, const bool s
 // layer's memory) are outside the scissor like any other
 // DO: a depth-only pass (include/svr_depth.h): phase A and the depth / ID store, then the workgroup is done.  Its s_c holds
 // the visibility tile and a quarter's (or a filter window's) list of LCAP entries, nothing of phases B to D.
-template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP>
+// ATTR: an attribute pass (include/svr_attributes.h): phase B also stores what shade_pixel computed for the winners into
+// the planes of P.attr that are bound; the ID target (IDS is set in these instances) is then a run-time matter, P.ids.
+template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false>
 __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, const uint4 i1, uint4* s_cov, uint32_t* s_idx, unsigned char* s_c,
                                           const uint32_t wv, const bool hiz_on, const uint32_t wg_start = 0) {
   typedef Codec<FMT> CD;
@@ -1409,7 +1443,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
   }
   // IDS: the ID target (include/svr_ids.h) leaves with the depth, {object, primitive} of the winner's record ({0, 0}: none),
   // over exactly the pixels the depth store wrote.  Whole rows go through s_cov (8 KiB, idle between phases A and C).
-  if (IDS) {
+  if (IDS && (!ATTR || P.ids)) {
     int rx, ry;
     uint32_t li;
     lane_pixel(wv, rx, ry, li);
@@ -1456,14 +1490,20 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
     if (__all(!dirty[k] || (recs[k] & REC_COMMON))) {
       // every quad of this 8x8 block of one triangle (or empty): lane ^ 1 is the pixel to the left or right, lane ^ 8 above or below
       const int rk = (int)recs[k];
-      const bool quads = __all(!dirty[k] || (__builtin_amdgcn_mov_dpp(rk, 0xB1, 0xf, 0xf, true) == rk && __builtin_amdgcn_mov_dpp(rk, 0x128, 0xf, 0xf, true) == rk));
+      // (ATTR: only where the tile's origin is even.  Lanes ^ 1 and ^ 8 are the pixel's quad partners — px ^ 1, py ^ 1 —
+      // only then; under a scissor with an odd origin they are the neighbours on the other side, whose u, v give slightly
+      // other derivatives than the contract's.  The other instances take the shortcut there too, and are left as they
+      // are: DESIGN.md "Attribute targets".)
+      const bool quads = (!ATTR || ((tx0 | ty0) & 1) == 0) && __all(!dirty[k] || (__builtin_amdgcn_mov_dpp(rk, 0xB1, 0xf, 0xf, true) == rk && __builtin_amdgcn_mov_dpp(rk, 0x128, 0xf, 0xf, true) == rk));
+      FragAttr fa = {};  // (ATTR only)
       if (dirty[k]) {
-        lc[(uint32_t)qy * TILE + (uint32_t)qx] = CD::encode(shade_pixel<false, true>(P, recs[k] & ~REC_COMMON, px, py, nullptr, quads));
+        lc[(uint32_t)qy * TILE + (uint32_t)qx] = CD::encode(shade_pixel<false, true, ATTR>(P, recs[k] & ~REC_COMMON, px, py, nullptr, quads, ATTR ? &fa : nullptr));
         if (INSTR) {
           n_shaded++;
           if (P.trace_buf && px == P.trace_x && py == P.trace_y) (void)shade_pixel<true>(P, recs[k] & ~REC_COMMON, px, py, P.trace_buf);
         }
       }
+      if (ATTR) store_attr(P, fa, pix_ok[k], px, py);
     } else {
       generic_slots |= 1u << k;
     }
@@ -1481,12 +1521,17 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       uint32_t li;
       lane_pixel(wv, rx, ry, li);
       int px = tx0 + rx + (k & 1) * 8, py = ty0 + ry + (k >> 1) * 8;
+      FragAttr fa = {};  // (ATTR only)
       if (d) {
-        lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] = CD::encode(shade_pixel<false>(P, rec, px, py, nullptr));
+        lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] = CD::encode(shade_pixel<false, false, ATTR>(P, rec, px, py, nullptr, false, ATTR ? &fa : nullptr));
         if (INSTR) {
           n_shaded++;
           if (P.trace_buf && px == P.trace_x && py == P.trace_y) (void)shade_pixel<true>(P, rec, px, py, P.trace_buf);
         }
+      }
+      if (ATTR) {
+        const bool ok = k == 0 ? pix_ok[0] : (k == 1 ? pix_ok[1] : (k == 2 ? pix_ok[2] : pix_ok[3]));
+        store_attr(P, fa, ok, px, py);
       }
     }
   }
@@ -1589,7 +1634,8 @@ static_assert(DEPTH_LIST_CAP >= BATCH, "a depth-only list window holds a batch")
 
 // IDS: the pass writes an ID target (FrameParams::ids): tile_ids_kernel below; tile_kernel is the kernel as it was
 // DO: a depth-only pass (tile_depth_kernel): s_c is the visibility tile and an LCAP-entry list only
-template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP>
+// ATTR: an attribute pass (tile_attr_kernel)
+template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false>
 __device__ __forceinline__ void tile_main(const FrameParams& P) {
   constexpr uint32_t SC_BYTES = DO ? LDS_Z_OFF + LCAP * 4 : PHASE_C_BYTES;
   __shared__ uint4 s_cov[BATCH * 8];
@@ -1653,12 +1699,12 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   } else if (SPLIT) {
     if (blockIdx.x < SPLIT_EXTRA) {  // the quarters of split tiles, as many as fill_kernel made
       if (blockIdx.x >= 4u * min(n_split, SPLIT_MAX)) return;
-      tile_body<FMT, INSTR, true, true, IDS, MV, DO, LCAP>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, true, true, IDS, MV, DO, LCAP, ATTR>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     } else {
-      tile_body<FMT, INSTR, false, true, IDS, MV, DO, LCAP>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, false, true, IDS, MV, DO, LCAP, ATTR>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     }
   } else {
-    tile_body<FMT, INSTR, false, false, IDS, MV, DO, LCAP>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+    tile_body<FMT, INSTR, false, false, IDS, MV, DO, LCAP, ATTR>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
   }
 }
 template <int FMT, bool INSTR, bool SPLIT>
@@ -1670,6 +1716,17 @@ template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false, true>(P); }
 template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_ids_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, true, true>(P); }
+// attribute passes (include/svr_attributes.h): one instance whatever planes are bound, and with or without an ID target
+// (both tested at run time).  SVR_ATTR_WAVES workgroups per CU (A/B builds: tools/build_variant.sh): five, like the
+// other instances — the uninstrumented ones fit 96 VGPRs without a spilled VGPR or a scratch frame.  At four per CU the
+// same stores measured 10-13 us per 4K frame slower (DESIGN.md "Attribute targets").
+#ifndef SVR_ATTR_WAVES
+#define SVR_ATTR_WAVES 5
+#endif
+template <int FMT, bool INSTR, bool SPLIT>
+__global__ __launch_bounds__(256, SVR_ATTR_WAVES) void tile_attr_kernel(FrameParams P) {
+  tile_main<FMT, INSTR, SPLIT, true, false, false, QUARTER_LIST_CAP, true>(P);
+}
 // depth-only passes (include/svr_depth.h): one instance for both colour formats (the colour target is not touched), IDS and
 // MV as above
 template <bool INSTR, bool SPLIT, bool IDS, bool MV>
@@ -1734,9 +1791,12 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
     if (report) hipExtLaunchKernelGGL(report_kernel, dim3(1), dim3(64), 0, s, nullptr, done, 0, P);
     return;
   }
+  // (enqueue_pass binds attribute planes to single-view shading passes only)
+  const bool attr = P.attr[0] || P.attr[1] || P.attr[2] || P.attr[3];
 #define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT)                                                                                          \
   do {                                                                                                                               \
-    if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P); \
+    if (attr) hipExtLaunchKernelGGL((tile_attr_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);              \
+    else if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P); \
     else if (P.layer_rows) hipExtLaunchKernelGGL((tile_mv_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);  \
     else if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);      \
     else hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);                \

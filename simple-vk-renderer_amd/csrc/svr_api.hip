@@ -24,6 +24,7 @@
 
 #include "../../include/svr_depth.h"
 #include "../../include/svr_draw_list.h"
+#include "../../include/svr_attributes.h"
 #include "../../include/svr_ids.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
@@ -162,6 +163,9 @@ struct SvrContext {
   uint2* ids_own = nullptr;  // svr_enable_ids
   uint2* ids = nullptr;      // the ID target (include/svr_ids.h): a caller's (svr_bind_id_target), ids_own or none
   bool ids_bound = false;    // ... it is the caller's
+  void* attr_own[4] = {};    // svr_enable_attributes: the context's planes, by bit number (include/svr_attributes.h)
+  void* attr[4] = {};        // the attribute targets: a caller's (svr_bind_attribute_target), attr_own or none
+  bool attr_bound[4] = {};   // ... it is the caller's
   uint32_t sx = 0, sy = 0, sw = 0, sh = 0;
   uint32_t rstride = 1, roff = 0;      // svr_set_row_interleave
   uint32_t* present_status = nullptr;  // svr_set_present_status
@@ -990,6 +994,8 @@ int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedO
     P.trace_buf = nullptr;  // svr_debug_trace_pixel names a pixel of the context's target, not of a layer
   } else if (ids) {
     P.ids = ctx->ids;
+    if (!depth_only)  // attribute planes (include/svr_attributes.h): of single-view shading passes; logged and replayed with P
+      for (int i = 0; i < 4; i++) P.attr[i] = ctx->attr[i];
   }
   if (depth_only) {  // no colour address, and no fragment stage to trace
     P.color = nullptr;
@@ -1174,6 +1180,8 @@ void svr_destroy(SvrContext* ctx) {
   if (ctx->color_own) (void)hipFree(ctx->color_own);
   if (ctx->depth_own) (void)hipFree(ctx->depth_own);
   if (ctx->ids_own) (void)hipFree(ctx->ids_own);
+  for (void* p : ctx->attr_own)
+    if (p) (void)hipFree(p);
   delete ctx;
 }
 
@@ -2384,6 +2392,89 @@ int svr_pick(SvrContext* ctx, uint32_t x, uint32_t y, uint32_t out[2]) {
   if (!ctx->ids) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_pick: no ID target (svr_enable_ids / svr_bind_id_target)");
   if (int e = svr_sync(ctx)) return e;
   HIPCHK(hipMemcpy(out, ctx->ids + (size_t)y * ctx->W + x, sizeof(uint2), hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- attribute targets (include/svr_attributes.h)
+namespace {
+// the plane's index (bit number) of a single attribute bit, or -1
+int attr_index(int attr) {
+  switch (attr) {
+    case SVR_ATTR_BARY: return 0;
+    case SVR_ATTR_UV: return 1;
+    case SVR_ATTR_NORMAL: return 2;
+    case SVR_ATTR_ALBEDO: return 3;
+    default: return -1;
+  }
+}
+size_t attr_bytes(const SvrContext* ctx, int i) { return (size_t)ctx->W * ctx->H * (i == 1 ? 8u : 16u); }
+}  // namespace
+
+int svr_enable_attributes(SvrContext* ctx, uint32_t mask) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  if (mask & ~(uint32_t)SVR_ATTR_ALL) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_enable_attributes: unknown attribute bit");
+  if (int e = use_device(ctx)) return e;
+  bool change = false;
+  for (int i = 0; i < 4; i++) change = change || ((mask >> i) & 1u) != (ctx->attr_own[i] ? 1u : 0u);
+  if (!change) return SVR_OK;
+  // the zeroing below runs outside the stream; passes in flight (and their replays) may still write a plane that goes
+  if (int e = finish_pending(ctx)) return e;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  // all or nothing: the planes the mask adds are allocated and zeroed first, and a failure frees them again
+  void* fresh[4] = {};
+  for (int i = 0; i < 4; i++) {
+    if (!((mask >> i) & 1u) || ctx->attr_own[i]) continue;
+    hipError_t r = hipMalloc(&fresh[i], attr_bytes(ctx, i));
+    if (r != hipSuccess) fresh[i] = nullptr;
+    if (r == hipSuccess) r = hipMemset(fresh[i], 0, attr_bytes(ctx, i));
+    if (r != hipSuccess) {
+      for (void* p : fresh)
+        if (p) (void)hipFree(p);
+      return fail(r == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE, std::string("svr_enable_attributes: ") + hipGetErrorString(r));
+    }
+  }
+  for (int i = 0; i < 4; i++) {
+    if ((mask >> i) & 1u) {
+      if (fresh[i]) ctx->attr_own[i] = fresh[i];
+      if (!ctx->attr_bound[i]) ctx->attr[i] = ctx->attr_own[i];
+    } else if (ctx->attr_own[i]) {
+      if (ctx->attr[i] == ctx->attr_own[i]) ctx->attr[i] = nullptr;
+      (void)hipFree(ctx->attr_own[i]);
+      ctx->attr_own[i] = nullptr;
+    }
+  }
+  return SVR_OK;
+}
+
+int svr_bind_attribute_target(SvrContext* ctx, int attr, void* dev) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  const int i = attr_index(attr);
+  if (i < 0) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_bind_attribute_target: not one attribute bit");
+  if (((uintptr_t)dev & 15u) != 0u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_bind_attribute_target: the target must be 16-byte aligned");
+  if (int e = use_device(ctx)) return e;
+  // no fence: passes already enqueued carry their own planes (also for a replay), as with svr_bind_id_target
+  if (int e = poll_pending(ctx)) return e;
+  ctx->attr_bound[i] = dev != nullptr;
+  ctx->attr[i] = dev ? dev : ctx->attr_own[i];
+  return SVR_OK;
+}
+
+int svr_get_attribute_target(SvrContext* ctx, int attr, void** dev) {
+  if (!ctx || !dev) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_attribute_target: null argument");
+  const int i = attr_index(attr);
+  if (i < 0) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_attribute_target: not one attribute bit");
+  *dev = ctx->attr[i];
+  return SVR_OK;
+}
+
+int svr_read_attribute(SvrContext* ctx, int attr, void* dst_host, size_t bytes) {
+  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_attribute: null argument");
+  const int i = attr_index(attr);
+  if (i < 0) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_attribute: not one attribute bit");
+  if (!ctx->attr[i]) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_attribute: no such plane (svr_enable_attributes / svr_bind_attribute_target)");
+  if (bytes != attr_bytes(ctx, i)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_attribute: the size is not the plane's");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst_host, ctx->attr[i], bytes, hipMemcpyDeviceToHost));
   return SVR_OK;
 }
 

@@ -264,6 +264,9 @@ struct FrameParams {
   uint32_t pyr_levels;
   uint32_t pyr_off[PYR_MAX_LEVELS + 1];
   uint8_t* occl_flags;            // [n_chunks] with pyr: 1 = the chunk was culled, written by every chunk's wave (no zeroing)
+  // attribute planes (include/svr_attributes.h) by bit number: BARY (float4), UV (float2), NORMAL (float4), ALBEDO (float4)
+  // per pixel; NULL = none.  Any of them set: the tile kernel's attribute instance runs (single-view shading passes only)
+  void* attr[4];
 };
 
 // Largest resident draw list flattened by the single-workgroup list_kernel: four rounds of 1024 lanes.  Each round is

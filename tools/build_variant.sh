@@ -10,7 +10,7 @@ out=$root/build_ab/obj_$name
 mkdir -p "$out"
 flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wextra -Wno-unused-parameter $*"
 pids=()
-for f in svr_api k_geometry k_flatten k_bin k_tile k_image; do
+for f in svr_api k_geometry k_flatten k_bin k_tile k_image k_pyramid; do
   /opt/rocm/bin/hipcc $flags -c "$src/$f.hip" -o "$out/$f.o" &
   pids+=($!)
 done
