@@ -276,8 +276,10 @@ int svr_run_vertex_shader(SvrContext* ctx, int shader, SvrMesh mesh, uint32_t fi
 /* Implementation switches (the reference has compile-time flags only).
  * SVR_OPT_COUNT_FRAGMENTS: 1 = count rasterized/shaded fragments and binned triangles with device
  * atomics (instrumented kernels; keep 0 for timed runs).
- * SVR_OPT_KERNEL_TIMING: 1 = time the tile kernel of every pass with the start/stop events of its own
- * dispatch (no extra packets in the stream), averaged into SvrStats.tile_ms as passes are validated;
+ * SVR_OPT_KERNEL_TIMING: 1 = time the tile kernel of every pass by its own stamps of the 100 MHz wall clock — the
+ * start of its first workgroup, the end of the workgroup that ends last, stored to pinned host memory — with no event
+ * and no packet in the stream (a start event on the kernel's launch is a packet of its own: 5 us per pass), averaged
+ * into SvrStats.tile_ms as passes are validated;
  * 2 = hipEvent records around geometry, binning and tiles (five more packets per pass, a few
  * microseconds of stream bubbles each: for profiling, not for timed runs) -> SvrStats.{geometry,
  * binning,tile}_ms; setting the option (to 0, 1 or 2) resets the averages.

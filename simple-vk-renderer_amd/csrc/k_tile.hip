@@ -1639,7 +1639,7 @@ template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false, bool DO = 
 __device__ __forceinline__ void tile_main(const FrameParams& P) {
   constexpr uint32_t SC_BYTES = DO ? LDS_Z_OFF + LCAP * 4 : PHASE_C_BYTES;
   __shared__ uint4 s_cov[BATCH * 8];
-  __shared__ uint32_t s_idx[BATCH];
+  __shared__ __attribute__((aligned(16))) uint32_t s_idx[BATCH];  // s_idx + 16 and + 48 are read as uint4 (scan_columns, tile_body's filter)
   __shared__ __attribute__((aligned(16))) unsigned char s_c[SC_BYTES];  // phase A depth tile, phase C blocks
   static_assert(LDS_Z_OFF + LCAP * 4 <= SC_BYTES, "depth tile + a quarter's triangle list");
   static_assert(DO || (SPLIT_SORT_MAX <= SORT_CAP && PHASE_C_BYTES - LDS_C_OFF >= SORT_CAP * 8 && PHASE_C_BYTES - LDS_C_OFF >= RANK_SORT_MAX * 8 &&
@@ -1679,9 +1679,12 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   // total is the pass's own (offsets_kernel), so the choice is the same for every workgroup.
   const bool hiz_on = !(P.tuning & TUNE_NO_HIZ) && ((P.tuning & TUNE_HIZ) || entries >= HIZ_AVG_ENTRIES * P.n_tiles);
 
-  if (blockIdx.x == 0)  // the pass's cost per tile row, for the host (nobody waits for it)
+  if (blockIdx.x == 0) {  // the pass's cost per tile row, for the host (nobody waits for it)
     for (uint32_t r = threadIdx.x; r < min(P.tiles_y, ROW_COST_MAX); r += blockDim.x)
       __hip_atomic_store(P.host_row_cost + r, P.row_cost[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // SVR_OPT_KERNEL_TIMING level 1: the kernel's start, by its own clock (a start event is a packet in front of the kernel)
+    if (P.host_clock && threadIdx.x == 0) __hip_atomic_store(P.host_clock, wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
   // A pass that overflowed a queue is void, and so is everything after it until the host has replayed
   // it (svr_api.hip "the operation log"): the targets stay as they were before the failed pass.
   if (overflow | poison) {
@@ -1706,6 +1709,17 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   } else {
     tile_body<FMT, INSTR, false, false, IDS, MV, DO, LCAP, ATTR>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
   }
+  // ... and every workgroup's end, one of 64 words each: plain stores, the last one into a word stays (an atomic maximum on
+  // pinned host memory is not an operation the host link carries: it would become a compare-and-swap loop of round trips
+  // that holds the workgroup's slot).  Stores of workgroups that end within the link's reordering of each other may land
+  // the wrong way round, and the last workgroup to end need not be one that stores: the largest of the 64 words is the
+  // kernel's end to within that.  Measured as a whole at 4K: 171.1 us by the stamps where the kernel trace has 174.2 from
+  // dispatch to completion, so less than 3.1 us, launch and completion overheads included.  Stores
+  // to one line of host memory go one at a time: with every one of a 4K frame's 16 000 workgroups storing into eight
+  // lines the kernel took 0.33-0.47 ms instead of 0.17.  So every word has a line of its own, and of a large pass
+  // every eighth workgroup stores (32 a line; its workgroups end a hundred a microsecond, so one of the last few does).
+  if (P.host_clock && threadIdx.x == 0 && (P.n_tiles <= SPLIT_TILES_MAX || (blockIdx.x & 7u) == 0u))
+    __hip_atomic_store(P.host_clock + (1u + ((blockIdx.x >> 3) & 63u)) * CLOCK_STRIDE, wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false>(P); }
@@ -1745,10 +1759,10 @@ __global__ __launch_bounds__(64) void report_kernel(FrameParams P) {
                        reinterpret_cast<const uint32_t*>(P.counters)[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// start (may be null): signalled when the tile kernel starts.  done: signalled when the pass's last kernel has finished.  It rides on that kernel's
+// done: signalled when the pass's last kernel has finished.  It rides on that kernel's
 // own dispatch packet (hipExtLaunchKernel's stopEvent): a separate hipEventRecord is one more packet
 // for the command processor between two tile kernels.
-void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, bool depth_only, hipStream_t s, hipEvent_t start, hipEvent_t done) {
+void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, bool depth_only, hipStream_t s, hipEvent_t done) {
   const bool split = !(P.tuning & (TUNE_NO_SPLIT | TUNE_NO_TILE_ORDER));
   dim3 grid(split ? P.n_tiles + SPLIT_EXTRA : P.n_tiles), block(256);
   const bool report = count_fragments || P.flatten;
@@ -1775,10 +1789,10 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
   if (depth_only) {  // no pad: the small-pass reasoning above is the shading kernel's (depth-only passes)
 #define SVR_LAUNCH_DEPTH(INSTR, SPLIT)                                                                                                         \
   do {                                                                                                                                         \
-    if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, true>), grid, block, lds_pad, s, start, tile_done, 0, P);  \
-    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, true>), grid, block, lds_pad, s, start, tile_done, 0, P);    \
-    else if (P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, false>), grid, block, lds_pad, s, start, tile_done, 0, P);           \
-    else hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, false>), grid, block, lds_pad, s, start, tile_done, 0, P);                     \
+    if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, true>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);  \
+    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, true>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);    \
+    else if (P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, false>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);           \
+    else hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, false>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);                     \
   } while (0)
     if (count_fragments) {
       if (split) SVR_LAUNCH_DEPTH(true, true);
@@ -1795,11 +1809,11 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
   const bool attr = P.attr[0] || P.attr[1] || P.attr[2] || P.attr[3];
 #define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT)                                                                                          \
   do {                                                                                                                               \
-    if (attr) hipExtLaunchKernelGGL((tile_attr_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);              \
-    else if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P); \
-    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_mv_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);  \
-    else if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);      \
-    else hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, start, tile_done, 0, P);                \
+    if (attr) hipExtLaunchKernelGGL((tile_attr_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);              \
+    else if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P); \
+    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_mv_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);  \
+    else if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);      \
+    else hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);                \
   } while (0)
   if (color_format == SVR_COLOR_RGBA16F) {
     if (count_fragments) {

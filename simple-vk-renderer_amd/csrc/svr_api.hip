@@ -215,7 +215,7 @@ struct SvrContext {
     int slot = 0;  // index into h_counters / op_done
     // a pass
     uint32_t seq = 0;  // running number, reported by the device if the pass overflows
-    bool timed = false;  // op_start/op_done of the slot bracket the tile kernel: fold into the running mean at retirement
+    bool timed = false;  // the tile kernel stamps its start and end into the slot's h_clock words: fold into the running mean at retirement
     FrameParams P{};  // parameters as recorded
     PassInput input = PassInput::Draws;
     bool depth_only = false;  // a depth-only pass (include/svr_depth.h): set by enqueue_pass; the setup and tile kernels of
@@ -246,7 +246,6 @@ struct SvrContext {
   };
   std::deque<LoggedOp> log;
   hipEvent_t op_done[MAX_OPS] = {};
-  hipEvent_t op_start[MAX_OPS] = {};  // SVR_OPT_KERNEL_TIMING level 1: start of the slot's tile kernel (rides on its dispatch)
   int op_pos = 0;
   uint32_t replayed = 0;         // passes re-run by recover_from_overflow
   // svr_clear_color deferred into the next pass (the attachment's loadOp CLEAR): see flush_clear
@@ -272,6 +271,7 @@ struct SvrContext {
   size_t h_stage_cap[MAX_OPS] = {};
   Counters* h_counters = nullptr;  // pinned, [MAX_OPS]
   uint32_t* h_row_cost = nullptr;  // pinned, [MAX_OPS][ROW_COST_MAX]: tile-row costs posted by every pass's tile kernel
+  unsigned long long* h_clock = nullptr;  // pinned, [MAX_OPS][CLOCK_WORDS]: SVR_OPT_KERNEL_TIMING level 1 (FrameParams::host_clock)
   std::vector<uint32_t> row_cost;  // ... of the pass validated last (svr_get_row_costs), with its scissor rows
   uint32_t row_cost_y0 = 0, row_cost_rows = 0;
 
@@ -281,7 +281,7 @@ struct SvrContext {
   bool tev_used[TRING] = {};
   bool tev_all[TRING] = {};  // the slot holds all five events (level 2), not just the tile pair
   int tev_pos = 0;
-  int kernel_timing = 0;  // 0 off, 1 tile kernel only (two events on the caller's stream), 2 all three stages
+  int kernel_timing = 0;  // 0 off, 1 tile kernel only (it stamps the clock itself: no events), 2 all three stages
   double acc_ms[3] = {0, 0, 0};
   uint32_t acc_n = 0;
   FrameParams last{};        // parameters of the pass enqueued last (debug read-backs)
@@ -573,6 +573,11 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   if (int e = stage_buffer(ctx, op_slot, (flatten ? (resident ? n_views * 64 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
   P.host_counters = &ctx->h_counters[op_slot];
   P.host_row_cost = ctx->h_row_cost + (size_t)op_slot * ROW_COST_MAX;
+  P.host_clock = nullptr;
+  if (op.timed) {  // (the slot is free: its previous pass has been retired)
+    P.host_clock = ctx->h_clock + (size_t)op_slot * CLOCK_WORDS;
+    std::memset(P.host_clock, 0, sizeof(unsigned long long) * CLOCK_WORDS);
+  }
   P.op_seq = op.seq;
   if (flatten) {  // the objects themselves are the input; cull, sort, draw records and chunks happen on the device
     if (!resident) std::memcpy(stage, op.objects.data(), n_objects * sizeof(SvrRenderObject));
@@ -637,9 +642,9 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][2], g));
   if (pipe) HIPCHK(hipStreamWaitEvent(s, set.ev_bin, 0));
   if (ts >= 0) HIPCHK(hipEventRecord(ctx->tev[ts][3], s));
-  // op_done rides on the pass's last kernel; with kernel timing level 1 op_start rides on the tile kernel too
-  launch_tiles(P, ctx->fmt, P.instrument != 0, op.depth_only, s, ctx->kernel_timing == 1 ? ctx->op_start[op_slot] : nullptr,
-               ctx->op_done[op_slot]);
+  // op_done rides on the pass's last kernel (a start event would be a packet of its own in front of the tile kernel:
+  // with kernel timing level 1 the kernel stamps the clock itself, P.host_clock)
+  launch_tiles(P, ctx->fmt, P.instrument != 0, op.depth_only, s, ctx->op_done[op_slot]);
   if (ts >= 0) {
     HIPCHK(hipEventRecord(ctx->tev[ts][4], s));
     ctx->tev_used[ts] = true;
@@ -786,10 +791,16 @@ int retire_ops(SvrContext* ctx, bool blocking) {
       ctx->log.erase(ctx->log.begin(), ctx->log.begin() + (long)k);
       return recover_from_overflow(ctx);
     }
-    if (ctx->log[k].timed) {  // both events belong to the tile kernel's dispatch: its duration, no extra packets
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ctx->op_start[slot], ctx->op_done[slot]) == hipSuccess) {
-        ctx->acc_ms[2] += ms;
+    if (ctx->log[k].timed) {  // the kernel's own stamps of the 100 MHz wall clock: first workgroup's start, last workgroup's end
+      const volatile unsigned long long* w = ctx->h_clock + (size_t)slot * CLOCK_WORDS;
+      unsigned long long t_end = 0;
+      const unsigned long long t_start = w[0];
+      for (uint32_t i = 1; i <= 64; i++) {
+        const unsigned long long t = w[i * CLOCK_STRIDE];
+        if (t > t_end) t_end = t;
+      }
+      if (t_start != 0 && t_end >= t_start) {  // (a void pass stamps too; a pass whose kernel never ran does not count)
+        ctx->acc_ms[2] += (double)(t_end - t_start) * 1e-5;
         ctx->acc_n++;
       }
     }
@@ -1128,10 +1139,13 @@ int svr_create(const SvrConfig* cfg, SvrContext** out) {
   if ((r = hipHostMalloc((void**)&ctx->h_counters, sizeof(Counters) * SvrContext::MAX_OPS, hipHostMallocDefault)) != hipSuccess)
     return bail(r, "hipHostMalloc");
   for (int i = 0; i < SvrContext::MAX_OPS; i++)
-    if ((r = hipEventCreate(&ctx->op_done[i])) != hipSuccess || (r = hipEventCreate(&ctx->op_start[i])) != hipSuccess) return bail(r, "hipEventCreate");
+    if ((r = hipEventCreate(&ctx->op_done[i])) != hipSuccess) return bail(r, "hipEventCreate");
   if ((r = hipHostMalloc((void**)&ctx->h_row_cost, sizeof(uint32_t) * ROW_COST_MAX * SvrContext::MAX_OPS, hipHostMallocDefault)) != hipSuccess)
     return bail(r, "hipHostMalloc");
   std::memset(ctx->h_row_cost, 0, sizeof(uint32_t) * ROW_COST_MAX * SvrContext::MAX_OPS);
+  if ((r = hipHostMalloc((void**)&ctx->h_clock, sizeof(unsigned long long) * CLOCK_WORDS * SvrContext::MAX_OPS, hipHostMallocDefault)) != hipSuccess)
+    return bail(r, "hipHostMalloc");
+  std::memset(ctx->h_clock, 0, sizeof(unsigned long long) * CLOCK_WORDS * SvrContext::MAX_OPS);
   if ((r = hipHostMalloc((void**)&ctx->h_failed_seq, 64, hipHostMallocDefault)) != hipSuccess) return bail(r, "hipHostMalloc");
   *ctx->h_failed_seq = 0;
   if ((r = hipMalloc((void**)&ctx->d_poison, 256)) != hipSuccess) return bail(r, "hipMalloc");
@@ -1166,10 +1180,9 @@ void svr_destroy(SvrContext* ctx) {
     if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]);
   if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
   if (ctx->h_row_cost) (void)hipHostFree(ctx->h_row_cost);
+  if (ctx->h_clock) (void)hipHostFree(ctx->h_clock);
   for (int i = 0; i < SvrContext::MAX_OPS; i++)
     if (ctx->op_done[i]) (void)hipEventDestroy(ctx->op_done[i]);
-  for (int i = 0; i < SvrContext::MAX_OPS; i++)
-    if (ctx->op_start[i]) (void)hipEventDestroy(ctx->op_start[i]);
   if (ctx->d_poison) (void)hipFree(ctx->d_poison);
   if (ctx->h_failed_seq) (void)hipHostFree(ctx->h_failed_seq);
   for (int i = 0; i < SvrContext::TRING; i++)

@@ -267,7 +267,14 @@ struct FrameParams {
   // attribute planes (include/svr_attributes.h) by bit number: BARY (float4), UV (float2), NORMAL (float4), ALBEDO (float4)
   // per pixel; NULL = none.  Any of them set: the tile kernel's attribute instance runs (single-view shading passes only)
   void* attr[4];
+  // SVR_OPT_KERNEL_TIMING level 1 (pinned host memory; NULL = off): the tile kernel stamps the 100 MHz wall clock itself.
+  // Word 0: the start of the workgroup with launch index 0; word (1 + ((blockIdx.x >> 3) & 63)) * CLOCK_STRIDE: the end of the
+  // workgroup that stored there last — every workgroup of a pass of up to SPLIT_TILES_MAX tiles, every eighth of a larger
+  // one.  The host takes the largest of the 64 at retirement (svr_api.hip retire_ops).
+  unsigned long long* host_clock;
 };
+constexpr uint32_t CLOCK_STRIDE = 16;                 // one 128-byte line per word: stores to one line of host memory go one at a time
+constexpr uint32_t CLOCK_WORDS = 65 * CLOCK_STRIDE;  // of FrameParams::host_clock
 
 // Largest resident draw list flattened by the single-workgroup list_kernel: four rounds of 1024 lanes.  Each round is
 // one is_visible per lane and a workgroup scan, back to back on one CU; longer lists go to the four kernels of

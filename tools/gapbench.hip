@@ -100,6 +100,28 @@ int main() {
     }
     CHECK(hipStreamSynchronize(s));
     report("one stream, hipEventRecord behind every kernel", now_us() - t, 100.0, LINKS);
+    // 2c. a start event and a stop event on every kernel's launch (SVR_OPT_KERNEL_TIMING level 1 until this row was measured)
+    {
+      static std::vector<hipEvent_t> ev_start;
+      if (ev_start.empty()) {
+        ev_start.resize(RING);
+        for (int i = 0; i < RING; i++) CHECK(hipEventCreate(&ev_start[i]));
+      }
+      t = now_us();
+      for (int i = 0; i < LINKS; i++) hipExtLaunchKernelGGL(spin, grid, block, 0, s, ev_start[i % RING], ev_tile[i % RING], 0, T_LONG, nullptr);
+      CHECK(hipStreamSynchronize(s));
+      report("one stream, start and stop event on every kernel", now_us() - t, 100.0, LINKS);
+      CHECK(hipDeviceSynchronize());
+      t = now_us();
+      for (int i = 0; i < LINKS; i++) {
+        if (i >= 2) CHECK(hipStreamWaitEvent(g, ev_tile[(i - 2) % RING], 0));
+        hipExtLaunchKernelGGL(spin, dim3(256), block, 0, g, nullptr, ev_bin[i % RING], 0, T_SHORT, nullptr);
+        CHECK(hipStreamWaitEvent(s, ev_bin[i % RING], 0));
+        hipExtLaunchKernelGGL(spin, grid, block, 0, s, ev_start[i % RING], ev_tile[i % RING], 0, T_LONG, nullptr);
+      }
+      CHECK(hipDeviceSynchronize());
+      report("two streams: pipeline as in submit_pass, start event on the tile kernel too", now_us() - t, 100.0, LINKS);
+    }
     // 3. scratch-using kernels
     t = now_us();
     for (int i = 0; i < LINKS; i++) hipLaunchKernelGGL(spin_scratch, grid, block, 0, s, T_LONG, nullptr);
@@ -206,6 +228,45 @@ int main() {
                  : variant == 1 ? "two streams: wait as a one-wave gate kernel on a device word"
                                 : "two streams: no wait, a publish kernel behind stage 1 (timing only)",
                  now_us() - t, 100.0, LINKS);
+      }
+    }
+    // 5c. the tile kernels on two alternating internal streams t[0], t[1]: tile i waits for its bins and for tile i-1
+    //     on t[i & 1], whose previous packet (tile i-2) retired long ago, so its queue looks at the barrier while
+    //     tile i-1 still runs.  Variant 0 keeps no order with the caller's stream s (timing only: not a correct
+    //     program).  Variant 1 is the correct program: work the caller enqueued on s before the pass precedes the tile
+    //     kernel (an event recorded on s, which stands behind s's wait for tile i-1 and so covers that too) and work
+    //     enqueued on s after the pass follows it (s waits for the tile event).  Variant 2: as 1, and tile i waits for
+    //     tile i-1 directly as well as through s.
+    {
+      static hipStream_t t[2] = {nullptr, nullptr};
+      static std::vector<hipEvent_t> ev_c;
+      if (!t[0]) {
+        CHECK(hipStreamCreateWithFlags(&t[0], hipStreamNonBlocking));
+        CHECK(hipStreamCreateWithFlags(&t[1], hipStreamNonBlocking));
+        ev_c.resize(RING);
+        for (int i = 0; i < RING; i++) CHECK(hipEventCreateWithFlags(&ev_c[i], hipEventDisableTiming));
+      }
+      for (int variant = 0; variant < 3; variant++) {
+        CHECK(hipDeviceSynchronize());
+        double t0 = now_us();
+        for (int i = 0; i < LINKS; i++) {
+          hipStream_t T = t[i & 1];
+          if (i >= 2) CHECK(hipStreamWaitEvent(g, ev_tile[(i - 2) % RING], 0));
+          hipExtLaunchKernelGGL(spin, dim3(256), block, 0, g, nullptr, ev_bin[i % RING], 0, T_SHORT, nullptr);
+          if (variant >= 1) {
+            CHECK(hipEventRecord(ev_c[i % RING], s));
+            CHECK(hipStreamWaitEvent(T, ev_c[i % RING], 0));
+          }
+          CHECK(hipStreamWaitEvent(T, ev_bin[i % RING], 0));
+          if (variant != 1 && i >= 1) CHECK(hipStreamWaitEvent(T, ev_tile[(i - 1) % RING], 0));
+          hipExtLaunchKernelGGL(spin, grid, block, 0, T, nullptr, ev_tile[i % RING], 0, T_LONG, nullptr);
+          if (variant >= 1) CHECK(hipStreamWaitEvent(s, ev_tile[i % RING], 0));
+        }
+        CHECK(hipDeviceSynchronize());
+        report(variant == 0   ? "four streams: tiles on two alternating streams, no order with the caller's (timing only)"
+               : variant == 1 ? "four streams: tiles on two alternating streams, ordered through the caller's stream"
+                              : "four streams: ... and tile i also waits for tile i-1 directly",
+               now_us() - t0, 100.0, LINKS);
       }
     }
     // 6. the same with stage 1 as six short kernels (5 us each)

@@ -19,9 +19,11 @@ CMD="python3 $root/bench.py --steps 60 --warmup 5 --no-cpu-baseline"
 failed=""
 pass() {  # pass NAME [--pmc counters...] -- program...
   local name=$1; shift
-  if ! timeout -k 10 240 rocprofv3 --kernel-trace "$@" > $out/$name.log 2>&1; then
+  timeout -k 10 240 rocprofv3 --kernel-trace "$@" > $out/$name.log 2>&1
+  local rc=$?  # (124 / 137: the time limit — a hung profiler; anything else: rocprofv3's or the program's own)
+  if [ $rc -ne 0 ]; then
     failed="$failed $name"
-    echo "profile_round: pass $name FAILED (rc $?)" | tee -a $out/failed.txt
+    echo "profile_round: pass $name FAILED (rc $rc)" | tee -a $out/failed.txt
   fi
 }
 pass kt -d $out/kt -o kt -- $CMD
