@@ -103,6 +103,9 @@ DEPTH_SYMBOLS = ["svr_draw_depth", "svr_draw_list_depth", "svr_draw_depth_views"
 OCCLUSION_SYMBOLS = ["svr_create_depth_pyramid", "svr_destroy_depth_pyramid", "svr_build_depth_pyramid",
                      "svr_set_occlusion_pyramid", "svr_read_depth_pyramid", "svr_get_occlusion_stats",
                      "svr_debug_read_occlusion"]
+# include/svr_lighting.h: the deferred lighting pass, HIP library only
+LIGHTING_SYMBOLS = ["svr_light_pass", "svr_debug_read_light_tiles"]
+MAX_LIGHTS = 4096
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -112,6 +115,21 @@ class SvrViewTargets(C.Structure):  # include/svr_views.h
 
 class SvrOcclusionStats(C.Structure):  # include/svr_occlusion.h
     _fields_ = [("chunks_tested", C.c_uint64), ("chunks_culled", C.c_uint64), ("triangles_culled", C.c_uint64)]
+
+
+class SvrPointLight(C.Structure):  # include/svr_lighting.h
+    _fields_ = [("position", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 3), ("intensity", C.c_float)]
+
+
+class SvrLightPass(C.Structure):  # include/svr_lighting.h
+    _fields_ = [("inv_viewproj", C.c_float * 16), ("ambient_color", C.c_float * 4), ("sunlight_direction", C.c_float * 4),
+                ("sunlight_color", C.c_float * 4), ("lights", C.c_void_p), ("n_lights", C.c_uint32),
+                ("shadow_depth", C.c_void_p), ("shadow_width", C.c_uint32), ("shadow_height", C.c_uint32),
+                ("shadow_viewproj", C.c_float * 16), ("shadow_bias", C.c_float)]
+
+
+POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("intensity", "<f4")])
+assert POINT_LIGHT_DTYPE.itemsize == C.sizeof(SvrPointLight) == 32
 
 
 class SvrError(RuntimeError):
@@ -217,6 +235,10 @@ class SvrLib:
             L.svr_bind_attribute_target.argtypes = [P, C.c_int, P]
             L.svr_get_attribute_target.argtypes = [P, C.c_int, C.POINTER(P)]
             L.svr_read_attribute.argtypes = [P, C.c_int, P, C.c_size_t]
+        self.has_lighting = hasattr(L, "svr_light_pass")
+        if self.has_lighting:
+            L.svr_light_pass.argtypes = [P, C.POINTER(SvrLightPass)]
+            L.svr_debug_read_light_tiles.argtypes = [P, P, C.c_size_t, C.POINTER(C.c_uint32)]
 
     @property
     def backend(self):
@@ -698,6 +720,40 @@ class Renderer:
         self._need_attributes()
         out = np.empty((self.height, self.width, ATTR_FLOATS.get(int(attr), 4)), dtype=np.float32)
         self.lib.check(self.lib.lib.svr_read_attribute(self.h, int(attr), out.ctypes.data, out.nbytes))
+        return out
+
+    # ---- the deferred lighting pass (include/svr_lighting.h)
+    def _need_lighting(self):
+        if not getattr(self.lib, "has_lighting", False):
+            raise SvrError(-5, f"{self.lib.backend} has no lighting pass (include/svr_lighting.h)")
+
+    def light_pass(self, inv_viewproj, ambient, sun_dir, sun_color, lights=None, shadow_ptr=None, shadow_size=(0, 0),
+                   shadow_viewproj=None, shadow_bias=0.0):
+        """svr_light_pass: relight the opaque winners of the colour target from the depth target and the NORMAL and ALBEDO
+        planes.  lights: POINT_LIGHT_DTYPE array or None; shadow_ptr: a device depth map of shadow_size = (width, height)
+        drawn with shadow_viewproj, or None"""
+        self._need_lighting()
+        p = SvrLightPass()
+        p.inv_viewproj = _f16m(inv_viewproj)
+        p.ambient_color, p.sunlight_direction, p.sunlight_color = _f4(ambient), _f4(sun_dir), _f4(sun_color)
+        arr = np.ascontiguousarray(lights if lights is not None else np.zeros(0, POINT_LIGHT_DTYPE), dtype=POINT_LIGHT_DTYPE).reshape(-1)
+        p.lights, p.n_lights = (arr.ctypes.data if arr.size else None), arr.size
+        if shadow_ptr:
+            p.shadow_depth = C.c_void_p(shadow_ptr)
+            p.shadow_width, p.shadow_height = int(shadow_size[0]), int(shadow_size[1])
+            p.shadow_viewproj = _f16m(shadow_viewproj)
+            p.shadow_bias = float(shadow_bias)
+        self.lib.check(self.lib.lib.svr_light_pass(self.h, C.byref(p)))
+
+    def read_light_tiles(self):
+        """uint32 [n_tiles]: the lights each 32x32 tile of the last lighting pass kept, row-major over its tile grid (fences)"""
+        self._need_lighting()
+        n = C.c_uint32()
+        L = self.lib.lib
+        self.lib.check(L.svr_debug_read_light_tiles(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self.lib.check(L.svr_debug_read_light_tiles(self.h, out.ctypes.data, out.size, C.byref(n)))
         return out
 
 

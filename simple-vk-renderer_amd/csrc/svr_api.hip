@@ -26,6 +26,7 @@
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_attributes.h"
 #include "../../include/svr_ids.h"
+#include "../../include/svr_lighting.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
 #include "svr_cull.h"
@@ -208,7 +209,7 @@ struct SvrContext {
   PassSet sets[NSETS];
   int set_pos = 0;
   // operation log (see "the operation log" below): a pass, or a fill of the colour target (every other operation)
-  enum class OpKind { Pass, Clear, Background, Blit, Pyramid };  // Pyramid: svr_build_depth_pyramid (logged like a clear)
+  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass
   enum class PassInput { Draws, Objects, List };  // what a pass reads: the one place that says so (P.flatten follows it)
   struct LoggedOp {
     OpKind kind = OpKind::Pass;
@@ -230,6 +231,10 @@ struct SvrContext {
     // a pass: the pyramid it culls against (include/svr_occlusion.h), or none; Pyramid: the one it builds, from pyr_src
     std::shared_ptr<PyramidMem> pyr;
     const float* pyr_src = nullptr;
+    // Light (include/svr_lighting.h): the kernel's parameters as recorded, its owned tile rows and the caller's lights
+    LightLaunch light{};
+    uint32_t light_tiles_y = 0;
+    std::vector<SvrPointLight> lights;
     bool flattened() const { return input != PassInput::Draws; }
     // a fill: colour target, its format and extent, the rows it writes
     void* target = nullptr;
@@ -291,6 +296,11 @@ struct SvrContext {
   uint32_t tuning = 0;
   int trace_x = -1, trace_y = -1;
   DevBuf d_trace, d_tile_cycles;
+  // svr_light_pass: the device copy of a pass's lights (SVR_MAX_LIGHTS records, refilled in stream order in front of
+  // every lighting pass) and the kept-light count per tile of the last one; both allocated once, by the first pass
+  SvrPointLight* d_lights = nullptr;
+  uint32_t* d_light_tiles = nullptr;
+  uint32_t light_tiles_n = 0;
   SvrStats stats{};
 };
 
@@ -708,6 +718,15 @@ int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying 
   } else if (op.kind == SvrContext::OpKind::Pyramid) {  // (writes nothing while the poison flag is up)
     launch_pyramid(op.pyr_src, op.tw, op.th, op.pyr->p, op.pyr->off, op.pyr->levels, ctx->d_poison, ctx->stream);
     HIPCHK(hipEventRecord(op.pyr->ev_built, ctx->stream));
+  } else if (op.kind == SvrContext::OpKind::Light) {  // (writes nothing while the poison flag is up)
+    if (!op.lights.empty()) {
+      const size_t bytes = op.lights.size() * sizeof(SvrPointLight);
+      void* stage = nullptr;
+      if (int e = stage_buffer(ctx, op.slot, bytes, &stage)) return e;
+      std::memcpy(stage, op.lights.data(), bytes);
+      HIPCHK(hipMemcpyAsync(ctx->d_lights, stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    launch_light(op.light, op.target_fmt, op.light_tiles_y, ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Background) {
     launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison, ctx->stream);
   } else {
@@ -1184,6 +1203,8 @@ void svr_destroy(SvrContext* ctx) {
   for (int i = 0; i < SvrContext::MAX_OPS; i++)
     if (ctx->op_done[i]) (void)hipEventDestroy(ctx->op_done[i]);
   if (ctx->d_poison) (void)hipFree(ctx->d_poison);
+  if (ctx->d_lights) (void)hipFree(ctx->d_lights);
+  if (ctx->d_light_tiles) (void)hipFree(ctx->d_light_tiles);
   if (ctx->h_failed_seq) (void)hipHostFree(ctx->h_failed_seq);
   for (int i = 0; i < SvrContext::TRING; i++)
     for (int k = 0; k < 5; k++)
@@ -2488,6 +2509,75 @@ int svr_read_attribute(SvrContext* ctx, int attr, void* dst_host, size_t bytes) 
   if (bytes != attr_bytes(ctx, i)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_attribute: the size is not the plane's");
   if (int e = svr_sync(ctx)) return e;
   HIPCHK(hipMemcpy(dst_host, ctx->attr[i], bytes, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- the deferred lighting pass (include/svr_lighting.h)
+int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: null argument");
+  if (pass->n_lights > SVR_MAX_LIGHTS) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: more than SVR_MAX_LIGHTS lights");
+  if (pass->n_lights && !pass->lights) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: null light array");
+  for (uint32_t i = 0; i < pass->n_lights; i++)
+    if (!(std::isfinite(pass->lights[i].radius) && pass->lights[i].radius > 0.0f))
+      return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: light " + std::to_string(i) + ": the radius must be finite and greater than 0");
+  if (pass->shadow_depth && (pass->shadow_width == 0 || pass->shadow_height == 0 || pass->shadow_width > (1u << 24) || pass->shadow_height > (1u << 24)))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: the shadow map's extent must be 1 .. 2^24 each way");
+  if (!ctx->attr[2] || !ctx->attr[3])
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: needs the SVR_ATTR_NORMAL and SVR_ATTR_ALBEDO planes (svr_enable_attributes / svr_bind_attribute_target)");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  if (!ctx->d_lights) HIPCHK(hipMalloc((void**)&ctx->d_lights, SVR_MAX_LIGHTS * sizeof(SvrPointLight)));
+  if (!ctx->d_light_tiles) HIPCHK(hipMalloc((void**)&ctx->d_light_tiles, (size_t)((ctx->W + TILE - 1) / TILE) * ((ctx->H + TILE - 1) / TILE) * sizeof(uint32_t)));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Light, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
+  op->lights.assign(pass->lights, pass->lights + pass->n_lights);
+  op->light_tiles_y = owned_tile_rows(ctx);
+  LightLaunch& L = op->light;
+  L.color = ctx->color;
+  L.depth = ctx->depth;
+  L.normal = (const float4*)ctx->attr[2];
+  L.albedo = (const float4*)ctx->attr[3];
+  L.W = ctx->W;
+  L.H = ctx->H;
+  L.sx = ctx->sx;
+  L.sy = ctx->sy;
+  L.sw = ctx->sw;
+  L.sh = ctx->sh;
+  L.tiles_x = (ctx->sw + TILE - 1) / TILE;
+  L.rstride = ctx->rstride;
+  L.roff = ctx->roff;
+  L.two_over_w = 2.0f / (float)ctx->W;
+  L.two_over_h = 2.0f / (float)ctx->H;
+  std::memcpy(L.inv_viewproj, pass->inv_viewproj, sizeof(L.inv_viewproj));
+  std::memcpy(L.ambient_color, pass->ambient_color, sizeof(L.ambient_color));
+  std::memcpy(L.sunlight_direction, pass->sunlight_direction, sizeof(L.sunlight_direction));
+  std::memcpy(L.sunlight_color, pass->sunlight_color, sizeof(L.sunlight_color));
+  L.lights = ctx->d_lights;
+  L.n_lights = pass->n_lights;
+  L.shadow_depth = pass->shadow_depth;
+  if (pass->shadow_depth) {
+    L.shadow_w = pass->shadow_width;
+    L.shadow_h = pass->shadow_height;
+    L.shadow_half_w = (float)pass->shadow_width * 0.5f;
+    L.shadow_half_h = (float)pass->shadow_height * 0.5f;
+    std::memcpy(L.shadow_viewproj, pass->shadow_viewproj, sizeof(L.shadow_viewproj));
+    L.shadow_bias = pass->shadow_bias;
+  }
+  L.tile_counts = ctx->d_light_tiles;
+  L.poison = ctx->d_poison;
+  ctx->light_tiles_n = L.tiles_x * op->light_tiles_y;
+  return submit_fill(ctx, *op);
+}
+
+int svr_debug_read_light_tiles(SvrContext* ctx, uint32_t* counts, size_t capacity, uint32_t* n_tiles) {
+  if (!ctx || !n_tiles) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  *n_tiles = ctx->light_tiles_n;
+  if (!counts) return SVR_OK;
+  if (!ctx->d_light_tiles) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: no lighting pass yet");
+  if (capacity < ctx->light_tiles_n) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: buffer too small");
+  if (ctx->light_tiles_n) HIPCHK(hipMemcpy(counts, ctx->d_light_tiles, (size_t)ctx->light_tiles_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return SVR_OK;
 }
 

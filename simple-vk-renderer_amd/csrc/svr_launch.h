@@ -1,5 +1,6 @@
 // svr_launch.h — host-callable launchers of the HIP kernels (one per kernel file).
 #pragma once
+#include "../../include/svr_lighting.h"
 #include "svr_device.h"
 
 namespace svr {
@@ -49,6 +50,29 @@ uint32_t pyramid_levels(uint32_t W, uint32_t H);
 size_t pyramid_offsets(uint32_t W, uint32_t H, uint32_t* off);  // off[1 .. levels]: word offset of each level; returns the words
 void launch_pyramid(const float* depth, uint32_t W, uint32_t H, uint32_t* pyr, const uint32_t* off, uint32_t n_levels,
                     const uint32_t* poison, hipStream_t s);
+// k_light.hip: the deferred lighting pass (include/svr_lighting.h)
+struct LightLaunch {
+  void* color;                  // the colour target (W x H), written where the albedo texel names an opaque winner
+  const float* depth;           // W x H
+  const float4* normal;         // the SVR_ATTR_NORMAL plane
+  const float4* albedo;         // the SVR_ATTR_ALBEDO plane
+  uint32_t W, H;
+  uint32_t sx, sy, sw, sh;      // the scissor
+  uint32_t tiles_x, rstride, roff;  // tile (x, y) of the grid is tile row y * rstride + roff of the scissor
+  float two_over_w, two_over_h; // C17: 2.0f / float(W), 2.0f / float(H), divided on the host
+  float inv_viewproj[16];
+  float ambient_color[4], sunlight_direction[4], sunlight_color[4];
+  const SvrPointLight* lights;  // device copy
+  uint32_t n_lights;
+  const float* shadow_depth;    // null: unshadowed
+  uint32_t shadow_w, shadow_h;
+  float shadow_half_w, shadow_half_h;  // C18: Ws / 2, Hs / 2 (exact)
+  float shadow_viewproj[16];
+  float shadow_bias;
+  uint32_t* tile_counts;        // [tiles_x * tiles_y]: the lights each tile kept (svr_debug_read_light_tiles)
+  const uint32_t* poison;
+};
+void launch_light(const LightLaunch& L, int color_format, uint32_t tiles_y, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr
