@@ -20,6 +20,8 @@
 #include <memory>
 #include <numeric>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/svr_depth.h"
@@ -41,22 +43,74 @@ int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      return fail(e_ == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE,                  \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                                  \
+// a failed runtime call: "<what>: <the runtime's text>"
+int hip_fail(hipError_t e, const char* what) {
+  return fail(e == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+// HIPCHK names the failed call by its own text.  HIPCHK_AS: by the text given — where the call goes through one of the
+// owners' helpers below, the runtime call it makes, as a caller has always read it in svr_last_error
+#define HIPCHK_AS(expr, text)                        \
+  do {                                               \
+    hipError_t e_ = (expr);                          \
+    if (e_ != hipSuccess) return hip_fail(e_, text); \
   } while (0)
+#define HIPCHK(expr) HIPCHK_AS(expr, #expr)
+// hipMalloc of `bytes` into the DevPtr `owner`
+#define DEV_ALLOC(owner, bytes) HIPCHK_AS(dev_alloc(owner, bytes), "hipMalloc((void**)&" #owner ", " #bytes ")")
 
+// Everything the runtime hands out is held by a move-only owner that gives it back: a device allocation, a pinned host
+// block, an event, a stream.  Nothing below frees by hand; an early return frees what the call had got so far.
+struct DevFree {
+  void operator()(void* p) const { (void)hipFree(p); }
+};
+struct PinnedFree {
+  void operator()(void* p) const { (void)hipHostFree(p); }
+};
+struct EventDestroy {
+  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+struct StreamDestroy {
+  void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+};
+template <class T> using DevPtr = std::unique_ptr<T, DevFree>;
+template <class T> using PinnedPtr = std::unique_ptr<T, PinnedFree>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
+
+template <class T> hipError_t dev_alloc(DevPtr<T>& out, size_t bytes) {
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e == hipSuccess) out.reset(static_cast<T*>(p));
+  return e;
+}
+template <class T> hipError_t pinned_alloc(PinnedPtr<T>& out, size_t bytes) {
+  void* p = nullptr;
+  const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+  if (e == hipSuccess) out.reset(static_cast<typename PinnedPtr<T>::pointer>(p));
+  return e;
+}
+hipError_t make_event(Event& out, unsigned flags) {
+  hipEvent_t ev = nullptr;
+  const hipError_t e = hipEventCreateWithFlags(&ev, flags);
+  if (e == hipSuccess) out.reset(ev);
+  return e;
+}
+
+// a device buffer that only grows
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int ensure(size_t bytes) {  // contents are NOT preserved
     if (bytes <= cap) return SVR_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     size_t want = bytes + bytes / 4;
     HIPCHK(hipMalloc(&p, want));
     cap = want;
@@ -70,9 +124,9 @@ struct DevBuf {
 };
 
 struct MeshRes {
-  SvrVertex* vtx = nullptr;
-  uint32_t* idx = nullptr;
-  float* groups = nullptr;  // float[6] per 192 indices: box of the vertices they name (setup kernel's chunk culling)
+  DevPtr<SvrVertex> vtx;
+  DevPtr<uint32_t> idx;
+  DevPtr<float> groups;  // float[6] per 192 indices: box of the vertices they name (setup kernel's chunk culling)
   size_t n_vtx = 0, n_idx = 0;
   bool alive = false;
 };
@@ -94,17 +148,13 @@ struct MaterialRes {
 // new one, and the list and every logged pass that was enqueued with this one share it; the last to let go frees it
 // (a pass lets go when it is validated, after its completion event — or after its replay).
 struct ListVersion {
-  SvrRenderObject* dev = nullptr;  // DRAW ORDER: opaque objects sorted by (material, mesh, submission index), then the transparent ones
+  DevPtr<SvrRenderObject> dev;  // DRAW ORDER: opaque objects sorted by (material, mesh, submission index), then the transparent ones
   uint32_t n_opaque = 0, n_transparent = 0;
   uint64_t tris_max = 0;  // upper bounds that size the pass's buffers and grids (every object visible)
   size_t chunks_max = 0;
   uint64_t tris_max_opaque = 0;  // ... of the opaque objects alone (depth-only passes: include/svr_depth.h)
   size_t chunks_max_opaque = 0;
-  uint32_t* obj_ids = nullptr;  // [n_opaque] draw order -> position in the opaque array as submitted, + 1 (ID passes: svr_ids.h)
-  ~ListVersion() {
-    if (dev) (void)hipFree(dev);
-    if (obj_ids) (void)hipFree(obj_ids);
-  }
+  DevPtr<uint32_t> obj_ids;  // [n_opaque] draw order -> position in the opaque array as submitted, + 1 (ID passes: svr_ids.h)
 };
 struct DrawListRes {
   std::vector<SvrRenderObject> objs;  // submission order: opaque list, then transparent list
@@ -119,15 +169,11 @@ struct DrawListRes {
 // A depth pyramid (include/svr_occlusion.h).  The handle, every logged build of it and every logged pass that culls
 // against it share its memory; the last to let go frees it (stream-ordered destruction, like a draw list's version).
 struct PyramidMem {
-  uint32_t* p = nullptr;  // levels 1 .. levels back to back, level l at word off[l]
+  DevPtr<uint32_t> p;  // levels 1 .. levels back to back, level l at word off[l]
   uint32_t levels = 0;
   uint32_t off[PYR_MAX_LEVELS + 1] = {};
   size_t words = 0;
-  hipEvent_t ev_built = nullptr;  // recorded behind the last build enqueued (the context's stream): stage 1 of a culling pass waits for it
-  ~PyramidMem() {
-    if (p) (void)hipFree(p);
-    if (ev_built) (void)hipEventDestroy(ev_built);
-  }
+  Event ev_built;  // recorded behind the last build enqueued (the context's stream): stage 1 of a culling pass waits for it
 };
 
 // software fp32 -> fp16 (RTE) for the one clear colour the host encodes
@@ -157,14 +203,14 @@ struct SvrContext {
   uint32_t W = 0, H = 0;
   int fmt = SVR_COLOR_RGBA16F;
   hipStream_t stream = nullptr;
-  void* color_own = nullptr;
-  float* depth_own = nullptr;
+  DevPtr<void> color_own;
+  DevPtr<float> depth_own;
   void* color = nullptr;
   float* depth = nullptr;
-  uint2* ids_own = nullptr;  // svr_enable_ids
+  DevPtr<uint2> ids_own;     // svr_enable_ids
   uint2* ids = nullptr;      // the ID target (include/svr_ids.h): a caller's (svr_bind_id_target), ids_own or none
   bool ids_bound = false;    // ... it is the caller's
-  void* attr_own[4] = {};    // svr_enable_attributes: the context's planes, by bit number (include/svr_attributes.h)
+  DevPtr<void> attr_own[4];  // svr_enable_attributes: the context's planes, by bit number (include/svr_attributes.h)
   void* attr[4] = {};        // the attribute targets: a caller's (svr_bind_attribute_target), attr_own or none
   bool attr_bound[4] = {};   // ... it is the caller's
   uint32_t sx = 0, sy = 0, sw = 0, sh = 0;
@@ -185,7 +231,7 @@ struct SvrContext {
   // are global loads with an SGPR base and a 32-bit VGPR offset instead of 64-bit pointer arithmetic per tap,
   // and records carry 4 bytes per texture, not a pointer.  Grows by reallocation (device copy, after a
   // fence); offsets never change.  Bound: 4 GiB of texels per context.
-  uint8_t* tex_arena = nullptr;
+  DevPtr<uint8_t> tex_arena;
   size_t tex_arena_cap = 0, tex_arena_top = 0;
   std::vector<std::pair<size_t, size_t>> tex_holes;  // (offset, bytes) of destroyed images, sorted by offset
   DevBuf tex_table;  // TexBinding[materials + 1]; last slot = scratch binding of svr_draw_tex_image
@@ -200,7 +246,7 @@ struct SvrContext {
   // stream.  ev_bin: set filled (recorded on gstream); ev_tile: set consumed (the pass's op_done event).
   struct PassSet {
     DevBuf inputs, recs, clipq, bigq, tiles, bins, pairs, flat, sorta, occl;  // occl: a culling pass's flag per chunk  // flat: keys / triangle counts / chunk bases of k_flatten  // inputs = DrawDesc[] then WaveChunk[] (one H2D copy)
-    hipEvent_t ev_bin = nullptr;
+    Event ev_bin;
     hipEvent_t ev_tile = nullptr;  // not owned: op_done of the pass that used the set last
     bool used = false;
   };
@@ -219,8 +265,12 @@ struct SvrContext {
     bool timed = false;  // the tile kernel stamps its start and end into the slot's h_clock words: fold into the running mean at retirement
     FrameParams P{};  // parameters as recorded
     PassInput input = PassInput::Draws;
-    bool depth_only = false;  // a depth-only pass (include/svr_depth.h): set by enqueue_pass; the setup and tile kernels of
-                              // submit_pass, retire_pass and the replay all follow it
+    // what the pass is, as enqueue_pass took it from its PassRequest: the one place submit_pass, retire_pass and the
+    // replay read it from.  depth_only: include/svr_depth.h (the setup and tile kernels' depth instances);
+    // multiview: include/svr_views.h (P.layer_rows is the kernels' copy of it)
+    struct PassShape {
+      bool depth_only = false, multiview = false;
+    } shape;
     std::vector<DrawDesc> draws;  // Draws: records built on the host
     std::vector<SvrRenderObject> objects;  // Objects: the caller's (opaque, then transparent), flattened on the device
     uint32_t n_opaque_obj = 0, n_transparent_obj = 0;  // Objects and List
@@ -249,8 +299,7 @@ struct SvrContext {
     uint32_t blit_rstride = 1, blit_roff = 0, blit_row_end = 0;  // identity blits of an interleaved pass: its tile rows only
     uint32_t* blit_status = nullptr;
   };
-  std::deque<LoggedOp> log;
-  hipEvent_t op_done[MAX_OPS] = {};
+  Event op_done[MAX_OPS];
   int op_pos = 0;
   uint32_t replayed = 0;         // passes re-run by recover_from_overflow
   // svr_clear_color deferred into the next pass (the attachment's loadOp CLEAR): see flush_clear
@@ -262,27 +311,27 @@ struct SvrContext {
     uint64_t packed = 0;
   } pending_clear;
   uint32_t next_seq = 1;
-  uint32_t* h_failed_seq = nullptr;  // pinned; written by the tile kernel of the first failing pass
-  uint32_t* d_poison = nullptr;  // sticky device flag: a pass overflowed, later target writes are void
-  hipStream_t gstream = nullptr;
-  hipStream_t gstream_hi = nullptr;   // the same at the highest priority: stage 1 of small passes (submit_pass)
-  hipStream_t last_g = nullptr;       // the one the previous pass used
-  hipEvent_t ev_gswitch = nullptr;
+  PinnedPtr<uint32_t> h_failed_seq;  // written by the tile kernel of the first failing pass
+  DevPtr<uint32_t> d_poison;  // sticky device flag: a pass overflowed, later target writes are void
+  Stream gstream;
+  Stream gstream_hi;                  // the same at the highest priority: stage 1 of small passes (submit_pass)
+  hipStream_t last_g = nullptr;       // the one the previous pass used (not owned)
+  Event ev_gswitch;
   DevBuf d_cvt;
   uint32_t clip_cap = 0, extra_cap = 0, bin_cap = 0;
   uint32_t debug_caps = 0;  // SVR_OPT_QUEUE_CAPS
   // pinned host staging + read-back, one of each per operation-log slot
-  void* h_stage[MAX_OPS] = {};  // per log slot
+  PinnedPtr<void> h_stage[MAX_OPS];  // per log slot
   size_t h_stage_cap[MAX_OPS] = {};
-  Counters* h_counters = nullptr;  // pinned, [MAX_OPS]
-  uint32_t* h_row_cost = nullptr;  // pinned, [MAX_OPS][ROW_COST_MAX]: tile-row costs posted by every pass's tile kernel
-  unsigned long long* h_clock = nullptr;  // pinned, [MAX_OPS][CLOCK_WORDS]: SVR_OPT_KERNEL_TIMING level 1 (FrameParams::host_clock)
+  PinnedPtr<Counters[]> h_counters;  // [MAX_OPS]
+  PinnedPtr<uint32_t> h_row_cost;  // [MAX_OPS][ROW_COST_MAX]: tile-row costs posted by every pass's tile kernel
+  PinnedPtr<unsigned long long> h_clock;  // [MAX_OPS][CLOCK_WORDS]: SVR_OPT_KERNEL_TIMING level 1 (FrameParams::host_clock)
   std::vector<uint32_t> row_cost;  // ... of the pass validated last (svr_get_row_costs), with its scissor rows
   uint32_t row_cost_y0 = 0, row_cost_rows = 0;
 
   // SVR_OPT_KERNEL_TIMING: ring of event quadruples (before setup, after clip, after fill, after tiles)
   static const int TRING = 16;
-  hipEvent_t tev[TRING][5] = {};  // geometry start, after clip, after fill (gstream) | tile start, tile end (stream)
+  Event tev[TRING][5];  // geometry start, after clip, after fill (gstream) | tile start, tile end (stream)
   bool tev_used[TRING] = {};
   bool tev_all[TRING] = {};  // the slot holds all five events (level 2), not just the tile pair
   int tev_pos = 0;
@@ -298,10 +347,20 @@ struct SvrContext {
   DevBuf d_trace, d_tile_cycles;
   // svr_light_pass: the device copy of a pass's lights (SVR_MAX_LIGHTS records, refilled in stream order in front of
   // every lighting pass) and the kept-light count per tile of the last one; both allocated once, by the first pass
-  SvrPointLight* d_lights = nullptr;
-  uint32_t* d_light_tiles = nullptr;
+  DevPtr<SvrPointLight> d_lights;
+  DevPtr<uint32_t> d_light_tiles;
   uint32_t light_tiles_n = 0;
   SvrStats stats{};
+  // Declared last, so it goes first: its entries hold draw-list versions and pyramids, and name the memory above.
+  std::deque<LoggedOp> log;
+
+  // Every member gives back what it holds, after this: nothing is freed before the device has finished with it.
+  ~SvrContext() {
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    if (gstream) (void)hipStreamSynchronize(gstream.get());
+    if (gstream_hi) (void)hipStreamSynchronize(gstream_hi.get());
+  }
 };
 
 namespace {
@@ -358,17 +417,13 @@ int arena_alloc(SvrContext* ctx, size_t bytes, uint32_t* off) {
     want = std::min(ARENA_MAX, (want + ((size_t)64 << 20) - 1) & ~(((size_t)64 << 20) - 1));
     if (int e = finish_pending(ctx)) return e;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    uint8_t* grown = nullptr;
-    HIPCHK(hipMalloc((void**)&grown, want));
+    DevPtr<uint8_t> grown;
+    DEV_ALLOC(grown, want);
     if (ctx->tex_arena_top) {
-      hipError_t r = hipMemcpy(grown, ctx->tex_arena, ctx->tex_arena_top, hipMemcpyDeviceToDevice);
-      if (r != hipSuccess) {
-        (void)hipFree(grown);
-        return fail(SVR_ERR_DEVICE, std::string("hipMemcpy(texel arena): ") + hipGetErrorString(r));
-      }
+      hipError_t r = hipMemcpy(grown.get(), ctx->tex_arena.get(), ctx->tex_arena_top, hipMemcpyDeviceToDevice);
+      if (r != hipSuccess) return fail(SVR_ERR_DEVICE, std::string("hipMemcpy(texel arena): ") + hipGetErrorString(r));
     }
-    if (ctx->tex_arena) (void)hipFree(ctx->tex_arena);
-    ctx->tex_arena = grown;
+    ctx->tex_arena = std::move(grown);
     ctx->tex_arena_cap = want;
   }
   *off = (uint32_t)ctx->tex_arena_top;
@@ -425,25 +480,24 @@ int upload_tex_table(SvrContext* ctx, const TexBinding* scratch) {
 // pinned staging buffer of a log slot (free: the slot's previous operation has been retired)
 int stage_buffer(SvrContext* ctx, int slot, size_t bytes, void** out) {
   if (ctx->h_stage_cap[slot] < bytes) {
-    if (ctx->h_stage[slot]) (void)hipHostFree(ctx->h_stage[slot]);
-    ctx->h_stage[slot] = nullptr;
+    ctx->h_stage[slot].reset();
     ctx->h_stage_cap[slot] = 0;
     size_t want = bytes + bytes / 2 + 4096;
-    HIPCHK(hipHostMalloc(&ctx->h_stage[slot], want, hipHostMallocDefault));
+    HIPCHK_AS(pinned_alloc(ctx->h_stage[slot], want), "hipHostMalloc(&ctx->h_stage[slot], want, hipHostMallocDefault)");
     ctx->h_stage_cap[slot] = want;
   }
-  *out = ctx->h_stage[slot];
+  *out = ctx->h_stage[slot].get();
   return SVR_OK;
 }
 
 // fold one finished slot of the timing ring into the running means
 int harvest_timing(SvrContext* ctx, int slot) {
   if (!ctx->tev_used[slot]) return SVR_OK;
-  HIPCHK(hipEventSynchronize(ctx->tev[slot][4]));
+  HIPCHK(hipEventSynchronize(ctx->tev[slot][4].get()));
   const int from[3] = {0, 1, 3}, to[3] = {1, 2, 4};
   for (int k = ctx->tev_all[slot] ? 0 : 2; k < 3; k++) {
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->tev[slot][from[k]], ctx->tev[slot][to[k]]));
+    HIPCHK(hipEventElapsedTime(&ms, ctx->tev[slot][from[k]].get(), ctx->tev[slot][to[k]].get()));
     ctx->acc_ms[k] += ms;
   }
   ctx->acc_n++;
@@ -483,8 +537,8 @@ int bind_pass_buffers(SvrContext* ctx, FrameParams& P, int set_index) {
   P.bin_cap = ctx->bin_cap;
   P.sort_arena = (unsigned long long*)set.sorta.p;
   P.sort_cap = ctx->bin_cap * 2u;  // a sorted bin needs at most twice its entries (power-of-two padding)
-  P.poison = ctx->d_poison;
-  P.host_failed_seq = ctx->h_failed_seq;
+  P.poison = ctx->d_poison.get();
+  P.host_failed_seq = ctx->h_failed_seq.get();
   return SVR_OK;
 }
 
@@ -526,26 +580,24 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
 #else
     const bool hi = P.n_tiles <= SPLIT_TILES_MAX;
 #endif
-    hipStream_t& slot = hi ? ctx->gstream_hi : ctx->gstream;
+    Stream& slot = hi ? ctx->gstream_hi : ctx->gstream;
     if (!slot) {
-      if (hi) {
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (hipStreamCreateWithPriority(&slot, hipStreamNonBlocking, greatest) != hipSuccess) {
-          (void)hipGetLastError();  // no priorities here: an ordinary stream does the job, a little later
-          slot = nullptr;
-          HIPCHK(hipStreamCreateWithFlags(&slot, hipStreamNonBlocking));
-        }
-      } else {
-        HIPCHK(hipStreamCreateWithFlags(&slot, hipStreamNonBlocking));
+      hipStream_t made = nullptr;
+      int least = 0, greatest = 0;
+      if (hi) (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+      if (!hi || hipStreamCreateWithPriority(&made, hipStreamNonBlocking, greatest) != hipSuccess) {
+        if (hi) (void)hipGetLastError();  // no priorities here: an ordinary stream does the job, a little later
+        made = nullptr;
+        HIPCHK(hipStreamCreateWithFlags(&made, hipStreamNonBlocking));
       }
+      slot.reset(made);
     }
-    g = slot;
+    g = slot.get();
   }
   if (pipe) {
     if (ctx->last_g && ctx->last_g != g) {  // keep stage 1 of consecutive passes in order across the two streams
-      HIPCHK(hipEventRecord(ctx->ev_gswitch, ctx->last_g));
-      HIPCHK(hipStreamWaitEvent(g, ctx->ev_gswitch, 0));
+      HIPCHK(hipEventRecord(ctx->ev_gswitch.get(), ctx->last_g));
+      HIPCHK(hipStreamWaitEvent(g, ctx->ev_gswitch.get(), 0));
     }
     ctx->last_g = g;
   }
@@ -560,14 +612,14 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   if (int e = bind_pass_buffers(ctx, P, set_index)) return e;
   if (op.pyr) {  // occlusion culling (include/svr_occlusion.h)
     if (int e = set.occl.ensure(std::max<size_t>(P.n_chunks, 16))) return e;
-    P.pyr = op.pyr->p;
+    P.pyr = op.pyr->p.get();
     P.pyr_levels = op.pyr->levels;
     std::memcpy(P.pyr_off, op.pyr->off, sizeof(P.pyr_off));
     P.occl_flags = (uint8_t*)set.occl.p;
     // Stage 1 reads the pyramid: it waits for the last build enqueued before this pass (on the caller's stream; without
     // the pipeline, stream order does it).  The other way round needs nothing: a later build of this pyramid runs on the
     // caller's stream behind this pass's tile kernel, which waits for this pass's stage 1 (ev_bin).
-    if (pipe) HIPCHK(hipStreamWaitEvent(g, op.pyr->ev_built, 0));
+    if (pipe) HIPCHK(hipStreamWaitEvent(g, op.pyr->ev_built.get(), 0));
   }
   // How far stage 1 runs ahead.  A pass of few tiles (a band of a sharded frame: stage 1 56 us, tiles 50 us) is bounded
   // by stage 1, which then wants to run back to back: it only waits for its set, last read by the tile stage of
@@ -582,10 +634,10 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
   void* stage = nullptr;
   if (int e = stage_buffer(ctx, op_slot, (flatten ? (resident ? n_views * 64 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
   P.host_counters = &ctx->h_counters[op_slot];
-  P.host_row_cost = ctx->h_row_cost + (size_t)op_slot * ROW_COST_MAX;
+  P.host_row_cost = ctx->h_row_cost.get() + (size_t)op_slot * ROW_COST_MAX;
   P.host_clock = nullptr;
   if (op.timed) {  // (the slot is free: its previous pass has been retired)
-    P.host_clock = ctx->h_clock + (size_t)op_slot * CLOCK_WORDS;
+    P.host_clock = ctx->h_clock.get() + (size_t)op_slot * CLOCK_WORDS;
     std::memset(P.host_clock, 0, sizeof(unsigned long long) * CLOCK_WORDS);
   }
   P.op_seq = op.seq;
@@ -612,15 +664,15 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
     ctx->tev_pos = (ctx->tev_pos + 1) % SvrContext::TRING;
     if (int e = harvest_timing(ctx, ts)) return e;
     for (int k = 0; k < 5; k++)
-      if (!ctx->tev[ts][k]) HIPCHK(hipEventCreate(&ctx->tev[ts][k]));
+      if (!ctx->tev[ts][k]) HIPCHK_AS(make_event(ctx->tev[ts][k], hipEventDefault), "hipEventCreate(&ctx->tev[ts][k])");
   }
   // inputs out of the staging buffer + zero the counters, class counters and tile_count (adjacent)
   launch_prologue(stage, n_views ? set.flat.p : set.inputs.p, n_views ? n_views * 64 : (flatten ? 0 : draw_bytes + chunk_bytes), P.counters,
-                  TILE_HEAD_BYTES + (size_t)P.n_tiles * 2 * sizeof(uint32_t), (flatten || P.layer_rows) ? 0u : (uint32_t)draws.size(), P.scene, g);
+                  TILE_HEAD_BYTES + (size_t)P.n_tiles * 2 * sizeof(uint32_t), (flatten || op.shape.multiview) ? 0u : (uint32_t)draws.size(), P.scene, g);
   if (flatten) {
     FlattenParams F;
     std::memset(&F, 0, sizeof(F));
-    F.objects = resident ? op.list->dev : (const SvrRenderObject*)stage;
+    F.objects = resident ? op.list->dev.get() : (const SvrRenderObject*)stage;
     F.n_opaque = op.n_opaque_obj;
     F.n_transparent = op.n_transparent_obj;
     std::memcpy(F.viewproj, P.scene.viewproj, 64);
@@ -634,7 +686,7 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
     F.chunks = (WaveChunk*)((char*)set.inputs.p + draw_bytes);
     F.counters = P.counters;
     F.ids = P.ids ? 1u : 0u;
-    F.obj_ids = (P.ids && resident) ? op.list->obj_ids : nullptr;
+    F.obj_ids = (P.ids && resident) ? op.list->obj_ids.get() : nullptr;
     F.n_views = (uint32_t)n_views;
     F.viewprojs = n_views ? (const float*)set.flat.p : nullptr;
     if (resident)
@@ -643,26 +695,26 @@ int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
       launch_flatten(F, g);
   }
   const bool all_stages = ctx->kernel_timing >= 2;
-  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][0], g));
-  launch_setup(P, op.depth_only, g);
-  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][1], g));
+  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][0].get(), g));
+  launch_setup(P, op.shape.depth_only, g);
+  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][1].get(), g));
   launch_bin_count(P, g);
   launch_bin_scan(P, g);
-  launch_bin_fill(P, g, pipe ? set.ev_bin : nullptr);  // ev_bin rides on the fill kernel's dispatch
-  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][2], g));
-  if (pipe) HIPCHK(hipStreamWaitEvent(s, set.ev_bin, 0));
-  if (ts >= 0) HIPCHK(hipEventRecord(ctx->tev[ts][3], s));
+  launch_bin_fill(P, g, pipe ? set.ev_bin.get() : nullptr);  // ev_bin rides on the fill kernel's dispatch
+  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][2].get(), g));
+  if (pipe) HIPCHK(hipStreamWaitEvent(s, set.ev_bin.get(), 0));
+  if (ts >= 0) HIPCHK(hipEventRecord(ctx->tev[ts][3].get(), s));
   // op_done rides on the pass's last kernel (a start event would be a packet of its own in front of the tile kernel:
   // with kernel timing level 1 the kernel stamps the clock itself, P.host_clock)
-  launch_tiles(P, ctx->fmt, P.instrument != 0, op.depth_only, s, ctx->op_done[op_slot]);
+  launch_tiles(P, ctx->fmt, P.instrument != 0, op.shape.depth_only, s, ctx->op_done[op_slot].get());
   if (ts >= 0) {
-    HIPCHK(hipEventRecord(ctx->tev[ts][4], s));
+    HIPCHK(hipEventRecord(ctx->tev[ts][4].get(), s));
     ctx->tev_used[ts] = true;
     ctx->tev_all[ts] = all_stages;
   }
   HIPCHK(hipGetLastError());
   // the one event of the pass: its counters are on the host, its set and staging buffer are free
-  set.ev_tile = ctx->op_done[op_slot];
+  set.ev_tile = ctx->op_done[op_slot].get();
   set.used = true;
   ctx->last = P;
   ctx->last_n_draws = flatten ? 0u : (uint32_t)draws.size();
@@ -687,8 +739,8 @@ int retire_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, const Counters&
     ctx->stats.culled_draws = c.flat_culled;
   }
   // the tile rows' costs (posted by its tile kernel before anything else): svr_get_row_costs, of single-view colour passes
-  if (op.P.layer_rows || op.depth_only) return SVR_OK;
-  const uint32_t* src = ctx->h_row_cost + (size_t)op.slot * ROW_COST_MAX;
+  if (op.shape.multiview || op.shape.depth_only) return SVR_OK;
+  const uint32_t* src = ctx->h_row_cost.get() + (size_t)op.slot * ROW_COST_MAX;
   ctx->row_cost.assign(src, src + std::min<uint32_t>(op.P.tiles_y, ROW_COST_MAX));
   ctx->row_cost_y0 = op.P.sy;
   ctx->row_cost_rows = op.P.sh;
@@ -714,23 +766,23 @@ int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying 
   if (op.kind == SvrContext::OpKind::Clear) {
     const size_t px_bytes = op.target_fmt == SVR_COLOR_RGBA16F ? 8 : 4;
     launch_fill_color((char*)op.target + (size_t)op.y_first * op.tw * px_bytes, op.tw * op.n_rows, op.target_fmt, op.clear_packed,
-                      ctx->d_poison, ctx->stream);
+                      ctx->d_poison.get(), ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Pyramid) {  // (writes nothing while the poison flag is up)
-    launch_pyramid(op.pyr_src, op.tw, op.th, op.pyr->p, op.pyr->off, op.pyr->levels, ctx->d_poison, ctx->stream);
-    HIPCHK(hipEventRecord(op.pyr->ev_built, ctx->stream));
+    launch_pyramid(op.pyr_src, op.tw, op.th, op.pyr->p.get(), op.pyr->off, op.pyr->levels, ctx->d_poison.get(), ctx->stream);
+    HIPCHK(hipEventRecord(op.pyr->ev_built.get(), ctx->stream));
   } else if (op.kind == SvrContext::OpKind::Light) {  // (writes nothing while the poison flag is up)
     if (!op.lights.empty()) {
       const size_t bytes = op.lights.size() * sizeof(SvrPointLight);
       void* stage = nullptr;
       if (int e = stage_buffer(ctx, op.slot, bytes, &stage)) return e;
       std::memcpy(stage, op.lights.data(), bytes);
-      HIPCHK(hipMemcpyAsync(ctx->d_lights, stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(ctx->d_lights.get(), stage, bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     launch_light(op.light, op.target_fmt, op.light_tiles_y, ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Background) {
-    launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison, ctx->stream);
+    launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison.get(), ctx->stream);
   } else {
-    launch_blit(op.target, op.target_fmt, op.tw, op.th, op.blit_dst, op.blit_w, op.blit_h, op.y_first, op.n_rows, op.blit_fmt, ctx->d_poison,
+    launch_blit(op.target, op.target_fmt, op.tw, op.th, op.blit_dst, op.blit_w, op.blit_h, op.y_first, op.n_rows, op.blit_fmt, ctx->d_poison.get(),
                 op.blit_rstride, op.blit_roff, op.blit_row_end, op.blit_status, replaying ? 2u : 0u, ctx->stream);
   }
   HIPCHK(hipGetLastError());
@@ -739,13 +791,13 @@ int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying 
 
 int recover_from_overflow(SvrContext* ctx) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->gstream) HIPCHK(hipStreamSynchronize(ctx->gstream));
-  if (ctx->gstream_hi) HIPCHK(hipStreamSynchronize(ctx->gstream_hi));
-  const uint32_t failed_seq = *(volatile uint32_t*)ctx->h_failed_seq;
+  if (ctx->gstream) HIPCHK(hipStreamSynchronize(ctx->gstream.get()));
+  if (ctx->gstream_hi) HIPCHK(hipStreamSynchronize(ctx->gstream_hi.get()));
+  const uint32_t failed_seq = *(volatile uint32_t*)ctx->h_failed_seq.get();
   *ctx->h_failed_seq = 0;
   for (SvrContext::LoggedOp& op : ctx->log) {
     if (op.kind != SvrContext::OpKind::Pass) {
-      HIPCHK(hipMemsetAsync(ctx->d_poison, 0, sizeof(uint32_t), ctx->stream));
+      HIPCHK(hipMemsetAsync(ctx->d_poison.get(), 0, sizeof(uint32_t), ctx->stream));
       if (int e = submit_fill(ctx, op, true)) return e;
       continue;
     }
@@ -762,7 +814,7 @@ int recover_from_overflow(SvrContext* ctx) {
         uint32_t need = std::max(c.total_entries, c.n_pairs + c.n_pairs_rest);
         ctx->bin_cap = std::max<uint32_t>(ctx->bin_cap * 2u, need + need / 4u);
       }
-      HIPCHK(hipMemsetAsync(ctx->d_poison, 0, sizeof(uint32_t), ctx->stream));
+      HIPCHK(hipMemsetAsync(ctx->d_poison.get(), 0, sizeof(uint32_t), ctx->stream));
       if (int e = submit_pass(ctx, op, false)) return e;
       HIPCHK(hipStreamSynchronize(ctx->stream));
       HIPCHK(hipMemcpy(&c, ctx->last.counters, sizeof(Counters), hipMemcpyDeviceToHost));
@@ -776,7 +828,7 @@ int recover_from_overflow(SvrContext* ctx) {
     if (int e = retire_pass(ctx, op, c)) return e;
     ctx->replayed++;
   }
-  HIPCHK(hipMemsetAsync(ctx->d_poison, 0, sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_poison.get(), 0, sizeof(uint32_t), ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->log.clear();
   return SVR_OK;
@@ -797,21 +849,21 @@ int retire_ops(SvrContext* ctx, bool blocking) {
     }
     const int slot = ctx->log[k].slot;
     if (blocking) {
-      HIPCHK(hipEventSynchronize(ctx->op_done[slot]));
+      HIPCHK(hipEventSynchronize(ctx->op_done[slot].get()));
     } else {
-      hipError_t q = hipEventQuery(ctx->op_done[slot]);
+      hipError_t q = hipEventQuery(ctx->op_done[slot].get());
       if (q == hipErrorNotReady) return SVR_OK;
       HIPCHK(q);
     }
     // the device names the first pass that overflowed (tile_kernel); everything from it on is void
-    const uint32_t failed = *(volatile uint32_t*)ctx->h_failed_seq;
+    const uint32_t failed = *(volatile uint32_t*)ctx->h_failed_seq.get();
     if (failed != 0 && failed == ctx->log[k].seq) {
       // the clears in front of the failed pass did land: only it and what follows is replayed
       ctx->log.erase(ctx->log.begin(), ctx->log.begin() + (long)k);
       return recover_from_overflow(ctx);
     }
     if (ctx->log[k].timed) {  // the kernel's own stamps of the 100 MHz wall clock: first workgroup's start, last workgroup's end
-      const volatile unsigned long long* w = ctx->h_clock + (size_t)slot * CLOCK_WORDS;
+      const volatile unsigned long long* w = ctx->h_clock.get() + (size_t)slot * CLOCK_WORDS;
       unsigned long long t_end = 0;
       const unsigned long long t_start = w[0];
       for (uint32_t i = 1; i <= 64; i++) {
@@ -840,7 +892,7 @@ int log_slot(SvrContext* ctx, int* slot) {
       if (any_pass) {
         for (const SvrContext::LoggedOp& op : ctx->log)
           if (op.kind == SvrContext::OpKind::Pass) {
-            HIPCHK(hipEventSynchronize(ctx->op_done[op.slot]));
+            HIPCHK(hipEventSynchronize(ctx->op_done[op.slot].get()));
             break;
           }
         if (int e = retire_ops(ctx, false)) return e;
@@ -902,16 +954,58 @@ uint32_t owned_tile_rows(const SvrContext* ctx) {
   return all > ctx->roff ? (all - ctx->roff + ctx->rstride - 1) / ctx->rstride : 0u;
 }
 
+// A multiview pass (include/svr_views.h): its layered targets, and the clear its layers start from
+struct MultiView {
+  uint32_t n_views = 0;
+  void* color = nullptr;
+  float* depth = nullptr;
+  uint2* ids = nullptr;
+  bool clear = false;
+  uint64_t packed = 0;
+};
+
+// What a drawing call asks for.  The entry point makes it (who it is, and whether it draws depth only); check_views
+// completes it for a multiview call; whoever learns what the pass draws — run_pass, list_pass, the device flatten of
+// draw_geometry — sets the bounds.  From enqueue_pass down it is read only, and nothing takes its parts one by one.
+struct PassRequest {
+  const char* who = "";                // the entry point: the texts name it
+  const SvrSceneData* scene = nullptr;  // the first view's, of a multiview pass; none: svr_draw_colored_triangle / _tex_image
+  uint64_t n_tris = 0;                 // bounds on the triangles and wave chunks the pass draws
+  size_t n_chunks = 0;
+  bool ids = false;         // a geometry pass: it writes the ID and attribute targets that there are
+  bool depth_only = false;  // include/svr_depth.h: opaque objects only, no colour
+  const MultiView* mv = nullptr;
+};
+PassRequest geometry_request(const char* who, const SvrSceneData* scene, bool depth_only) {
+  PassRequest rq;
+  rq.who = who;
+  rq.scene = scene;
+  rq.ids = true;
+  rq.depth_only = depth_only;
+  return rq;
+}
+
 // What a pass does with a deferred svr_clear_color: Take — it rides along if it covers the pass's rows, else it runs now;
 // Flush — it runs now (multiview passes: other targets); Leave — it stays deferred (depth-only passes: the clear belongs
 // to the colour target, which they do not touch)
 enum class ClearMode { Take, Flush, Leave };
-int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tris64, size_t n_chunks, FrameParams& P,
-                      ClearMode clear = ClearMode::Take) {
-  if (n_tris64 >= 0x3ffffff0ull) return fail(SVR_ERR_UNSUPPORTED, "more than 2^30 triangles in one pass");
+ClearMode clear_mode(const PassRequest& rq) { return rq.depth_only ? ClearMode::Leave : (rq.mv ? ClearMode::Flush : ClearMode::Take); }
+
+// the ID target a pass writes, or none; host records carry object numbers exactly when there is one
+uint2* id_target(const SvrContext* ctx, const PassRequest& rq) { return !rq.ids ? nullptr : (rq.mv ? rq.mv->ids : ctx->ids); }
+
+// Every parameter of the pass that the request and the context decide, final: the buffers of its set, the log slot and
+// the pyramid are submit_pass's.  A multiview pass has every layer's tile rows, layer-major, and its layers' own clear
+// rides in it like a deferred one.
+int fill_frame_params(SvrContext* ctx, const PassRequest& rq, SvrContext::PassInput input, FrameParams& P) {
+  if (rq.n_tris >= 0x3ffffff0ull) return fail(SVR_ERR_UNSUPPORTED, "more than 2^30 triangles in one pass");
+  const MultiView* mv = rq.mv;
   std::memset(&P, 0, sizeof(P));
-  P.color = ctx->color;
-  P.depth = ctx->depth;
+  P.color = rq.depth_only ? nullptr : (mv ? mv->color : ctx->color);
+  P.depth = mv ? mv->depth : ctx->depth;
+  P.ids = id_target(ctx, rq);
+  if (rq.ids && !mv && !rq.depth_only)  // attribute planes (include/svr_attributes.h): of single-view shading passes
+    for (int i = 0; i < 4; i++) P.attr[i] = ctx->attr[i];
   P.W = ctx->W;
   P.H = ctx->H;
   P.sx = ctx->sx;
@@ -921,27 +1015,38 @@ int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tri
   P.tiles_x = (ctx->sw + TILE - 1) / TILE;
   P.rstride = ctx->rstride;
   P.roff = ctx->roff;
-  P.tiles_y = owned_tile_rows(ctx);
+  P.layer_rows = mv ? (ctx->H + TILE - 1) / TILE : 0u;
+  P.tiles_y = mv ? mv->n_views * P.layer_rows : owned_tile_rows(ctx);
   P.n_tiles = P.tiles_x * P.tiles_y;
-  P.n_tris = (uint32_t)n_tris64;
-  P.n_chunks = (uint32_t)n_chunks;
+  P.n_tris = (uint32_t)rq.n_tris;
+  P.n_chunks = (uint32_t)rq.n_chunks;
+  P.flatten = input != SvrContext::PassInput::Draws ? 1u : 0u;
   P.tex = (const TexBinding*)ctx->tex_table.p;
-  P.tex_arena = ctx->tex_arena;
+  P.tex_arena = ctx->tex_arena.get();
   P.instrument = ctx->instrument ? 1u : 0u;
   P.trace_x = ctx->trace_x;
   P.trace_y = ctx->trace_y;
-  P.trace_buf = (ctx->instrument && ctx->trace_x >= 0) ? (float*)ctx->d_trace.p : nullptr;
+  // svr_debug_trace_pixel names a pixel of the context's colour target: not one of a layer, and no depth-only pass shades
+  P.trace_buf = (ctx->instrument && ctx->trace_x >= 0 && !mv && !rq.depth_only) ? (float*)ctx->d_trace.p : nullptr;
   P.tuning = ctx->tuning;
-#ifndef SVR_AB_SPLIT_ALL  // A/B builds only (tools/build_variant.sh): the quarter path for passes of any size
-  if (P.n_tiles > SPLIT_TILES_MAX) P.tuning |= TUNE_NO_SPLIT;  // svr_device.h: no tile of such a pass is worth splitting
+#ifdef SVR_AB_SPLIT_ALL  // A/B builds only (tools/build_variant.sh): the quarter path for single-view passes of any size
+  const bool may_split = !mv || P.n_tiles <= SPLIT_TILES_MAX;
+#else
+  const bool may_split = P.n_tiles <= SPLIT_TILES_MAX;  // svr_device.h: no tile of a larger pass is worth splitting
 #endif
-  P.tile_cycles = nullptr;
+  if (!may_split) P.tuning |= TUNE_NO_SPLIT;
   if (ctx->tile_cycles) {
     if (int e = ctx->d_tile_cycles.ensure((size_t)P.n_tiles * 16)) return e;
     P.tile_cycles = (uint32_t*)ctx->d_tile_cycles.p;
   }
-  if (scene) P.scene = *scene;
+  if (rq.scene) P.scene = *rq.scene;
+  if (mv && mv->clear) {
+    P.lazy_clear = 1u;
+    P.clear_lo = (uint32_t)mv->packed;
+    P.clear_hi = (uint32_t)(mv->packed >> 32);
+  }
   // a deferred clear of exactly the rows this pass covers rides along; any other one runs now
+  const ClearMode clear = clear_mode(rq);
   if (clear == ClearMode::Leave) return SVR_OK;
   const SvrContext::PendingClear& pc = ctx->pending_clear;
   if (clear == ClearMode::Take && pc.valid && pc.target == ctx->color && pc.fmt == ctx->fmt && pc.y0 == ctx->sy && pc.rows == ctx->sh && ctx->sx == 0 &&
@@ -956,16 +1061,16 @@ int fill_frame_params(SvrContext* ctx, const SvrSceneData* scene, uint64_t n_tri
   return SVR_OK;
 }
 
-// (re)upload the handle -> resource tables the device flatten pass reads; keep_clear: the fence leaves a deferred clear
-// deferred (depth-only passes)
-int upload_flatten_tables(SvrContext* ctx, bool keep_clear = false) {
+// (re)upload the handle -> resource tables the device flatten pass reads; its fence leaves a deferred clear deferred
+// where the pass does (ClearMode::Leave)
+int upload_flatten_tables(SvrContext* ctx, ClearMode clear) {
   if (ctx->mesh_table_n == ctx->meshes.size() && ctx->mat_table_n == ctx->materials.size()) return SVR_OK;
-  if (int e = keep_clear ? retire_ops(ctx, true) : finish_pending(ctx)) return e;  // a pass in flight may be reading the old tables
+  if (int e = clear == ClearMode::Leave ? retire_ops(ctx, true) : finish_pending(ctx)) return e;  // a pass in flight may be reading the old tables
   std::vector<MeshEntry> me(ctx->meshes.size());
   for (size_t i = 0; i < me.size(); i++) {
-    me[i].vtx = ctx->meshes[i].vtx;
-    me[i].idx = ctx->meshes[i].idx;
-    me[i].groups = ctx->meshes[i].groups;
+    me[i].vtx = ctx->meshes[i].vtx.get();
+    me[i].idx = ctx->meshes[i].idx.get();
+    me[i].groups = ctx->meshes[i].groups.get();
     me[i].pad = 0;
   }
   std::vector<MatEntry> ma(ctx->materials.size());
@@ -983,54 +1088,14 @@ int upload_flatten_tables(SvrContext* ctx, bool keep_clear = false) {
   return SVR_OK;
 }
 
-// Enqueue one pass.  `in` holds its input (in.input and the draws, objects or list version it names), n_tris / n_chunks
-// bound what it draws; ids: a geometry pass, which writes the ID target if there is one (host draws' pad words then carry
-// object numbers); depth_only: a depth-only pass (include/svr_depth.h), whose input holds opaque objects only.
-// A multiview pass (include/svr_views.h): its layered targets, and the clear its layers start from
-struct MultiView {
-  uint32_t n_views = 0;
-  void* color = nullptr;
-  float* depth = nullptr;
-  uint2* ids = nullptr;
-  bool clear = false;
-  uint64_t packed = 0;
-};
-
-int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedOp&& in, uint64_t n_tris, size_t n_chunks, bool ids,
-                 const MultiView* mv = nullptr, bool depth_only = false) {
+// Enqueue the pass rq asks for.  `in` holds its input (in.input and the draws, objects or list version it names).
+int enqueue_pass(SvrContext* ctx, const PassRequest& rq, SvrContext::LoggedOp&& in) {
   if (int e = poll_pending(ctx)) return e;
   if (in.flattened())  // before fill_frame_params: it can fence, and so flush the deferred clear
-    if (int e = upload_flatten_tables(ctx, depth_only)) return e;
+    if (int e = upload_flatten_tables(ctx, clear_mode(rq))) return e;
   FrameParams P;
   const SvrContext::PendingClear asked = ctx->pending_clear;  // folded into P.lazy_clear below: put back if the pass is not enqueued
-  const ClearMode clear = depth_only ? ClearMode::Leave : (mv ? ClearMode::Flush : ClearMode::Take);
-  if (int e = fill_frame_params(ctx, scene, n_tris, n_chunks, P, clear)) return e;
-  P.flatten = in.flattened() ? 1u : 0u;
-  if (mv) {  // every layer's tile rows, layer-major; the layers' own clear rides in the pass like a deferred one
-    P.color = mv->color;
-    P.depth = mv->depth;
-    P.ids = mv->ids;
-    P.layer_rows = (ctx->H + TILE - 1) / TILE;
-    P.tiles_y = mv->n_views * P.layer_rows;
-    P.n_tiles = P.tiles_x * P.tiles_y;
-    if (P.n_tiles > SPLIT_TILES_MAX) P.tuning |= TUNE_NO_SPLIT;
-    P.lazy_clear = mv->clear ? 1u : 0u;
-    P.clear_lo = mv->clear ? (uint32_t)mv->packed : 0u;
-    P.clear_hi = mv->clear ? (uint32_t)(mv->packed >> 32) : 0u;
-    if (P.tile_cycles) {
-      if (int e = ctx->d_tile_cycles.ensure((size_t)P.n_tiles * 16)) return e;
-      P.tile_cycles = (uint32_t*)ctx->d_tile_cycles.p;
-    }
-    P.trace_buf = nullptr;  // svr_debug_trace_pixel names a pixel of the context's target, not of a layer
-  } else if (ids) {
-    P.ids = ctx->ids;
-    if (!depth_only)  // attribute planes (include/svr_attributes.h): of single-view shading passes; logged and replayed with P
-      for (int i = 0; i < 4; i++) P.attr[i] = ctx->attr[i];
-  }
-  if (depth_only) {  // no colour address, and no fragment stage to trace
-    P.color = nullptr;
-    P.trace_buf = nullptr;
-  }
+  if (int e = fill_frame_params(ctx, rq, in.input, P)) return e;
   int slot = 0;
   int e = log_slot(ctx, &slot);
   if (e == SVR_OK) {
@@ -1040,30 +1105,30 @@ int enqueue_pass(SvrContext* ctx, const SvrSceneData* scene, SvrContext::LoggedO
     if (ctx->next_seq == 0) ctx->next_seq = 1;
     op.slot = slot;
     op.timed = ctx->kernel_timing == 1;
-    op.depth_only = depth_only;
+    op.shape.depth_only = rq.depth_only;
+    op.shape.multiview = rq.mv != nullptr;
     op.P = P;
-    if (ctx->occl_bound && !mv) op.pyr = ctx->pyramids[ctx->occl_bound - 1];  // (multiview passes refuse a bound pyramid)
+    if (ctx->occl_bound && !rq.mv) op.pyr = ctx->pyramids[ctx->occl_bound - 1];  // (multiview passes refuse a bound pyramid)
     std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
     e = submit_pass(ctx, op, !(ctx->tuning & TUNE_NO_PIPELINE));
     if (e) ctx->log.pop_back();
   }
-  if (e && P.lazy_clear && !mv) ctx->pending_clear = asked;
+  if (e && P.lazy_clear && !rq.mv) ctx->pending_clear = asked;
   return e;
 }
 
 // a pass of draw records built on the host: numbers their triangles and swaps them into the log
-int run_pass(SvrContext* ctx, const SvrSceneData* scene, std::vector<DrawDesc>& draws, bool ids = false, const MultiView* mv = nullptr,
-             bool depth_only = false) {
-  uint64_t n_tris64 = 0;
-  size_t n_chunks = 0;
+int run_pass(SvrContext* ctx, PassRequest& rq, std::vector<DrawDesc>& draws) {
+  rq.n_tris = 0;
+  rq.n_chunks = 0;
   for (DrawDesc& d : draws) {
-    d.tri_base = (uint32_t)n_tris64;
-    n_tris64 += d.tri_count;
-    n_chunks += chunk_count(d.first_index, d.tri_count);
+    d.tri_base = (uint32_t)rq.n_tris;
+    rq.n_tris += d.tri_count;
+    rq.n_chunks += chunk_count(d.first_index, d.tri_count);
   }
   SvrContext::LoggedOp in;
   in.draws.swap(draws);
-  return enqueue_pass(ctx, scene, std::move(in), n_tris64, n_chunks, ids, mv, depth_only);
+  return enqueue_pass(ctx, rq, std::move(in));
 }
 
 // the device flatten's bound on the objects of one pass, and so on those of a draw list (include/svr_draw_list.h)
@@ -1080,13 +1145,14 @@ void add_object_bounds(const SvrRenderObject* objs, size_t n, uint64_t* tris, si
 }
 
 // draw order of opaque objects (src/vk_engine.cpp:1369-1378): indices into objs, sorted by the deterministic key
-// (material, mesh, submission index)
+// (material, mesh, submission index).  The index is part of the key, so the order is a stable sort's without its buffer
 void sort_draw_order(std::vector<uint32_t>& order, const SvrRenderObject* objs) {
-  std::stable_sort(order.begin(), order.end(), [objs](uint32_t ia, uint32_t ib) {
+  std::sort(order.begin(), order.end(), [objs](uint32_t ia, uint32_t ib) {
     const SvrRenderObject& a = objs[ia];
     const SvrRenderObject& b = objs[ib];
-    if (a.material == b.material) return a.mesh < b.mesh;
-    return a.material < b.material;
+    if (a.material != b.material) return a.material < b.material;
+    if (a.mesh != b.mesh) return a.mesh < b.mesh;
+    return ia < ib;
   });
 }
 
@@ -1101,9 +1167,9 @@ int finish_draw(SvrContext* ctx, SvrStats st, SvrStats* out_stats, int e,
 
 // interleaved rows and more ranks than tile rows: this context owns no tile row, and a geometry pass draws nothing
 // (a depth-only pass leaves a deferred clear of the colour target as it is)
-bool owns_nothing(SvrContext* ctx, SvrStats* out_stats, bool depth_only = false) {
+bool owns_nothing(SvrContext* ctx, SvrStats* out_stats, const PassRequest& rq) {
   if (owned_tile_rows(ctx) != 0) return false;
-  if (!depth_only) ctx->pending_clear.valid = false;
+  if (clear_mode(rq) != ClearMode::Leave) ctx->pending_clear.valid = false;
   finish_draw(ctx, SvrStats{}, out_stats, SVR_OK);
   return true;
 }
@@ -1129,7 +1195,7 @@ int svr_create(const SvrConfig* cfg, SvrContext** out) {
                                     "); this library has no CPU fallback");
   if (cfg->device < 0 || cfg->device >= n_dev) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_create: bad device ordinal");
   HIPCHK(hipSetDevice(cfg->device));
-  SvrContext* ctx = new SvrContext();
+  std::unique_ptr<SvrContext> ctx(new SvrContext());  // a failure below gives back what the context has got so far
   ctx->device = cfg->device;
   ctx->W = cfg->width;
   ctx->H = cfg->height;
@@ -1138,86 +1204,32 @@ int svr_create(const SvrConfig* cfg, SvrContext** out) {
   ctx->sh = ctx->H;
   size_t n = (size_t)ctx->W * ctx->H;
   size_t cbytes = n * (ctx->fmt == SVR_COLOR_RGBA16F ? 8 : 4);
-  auto bail = [&](hipError_t err, const char* what) {
-    std::string msg = std::string(what) + ": " + hipGetErrorString(err);
-    svr_destroy(ctx);
-    return fail(err == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE, msg);
-  };
-  hipError_t r;
-  if ((r = hipMalloc(&ctx->color_own, cbytes)) != hipSuccess) return bail(r, "hipMalloc(color)");
-  if ((r = hipMalloc((void**)&ctx->depth_own, n * 4)) != hipSuccess) return bail(r, "hipMalloc(depth)");
-  if ((r = hipMemset(ctx->color_own, 0, cbytes)) != hipSuccess) return bail(r, "hipMemset(color)");
-  if ((r = hipMemset(ctx->depth_own, 0, n * 4)) != hipSuccess) return bail(r, "hipMemset(depth)");
-  ctx->color = ctx->color_own;
-  ctx->depth = ctx->depth_own;
+  HIPCHK_AS(dev_alloc(ctx->color_own, cbytes), "hipMalloc(color)");
+  HIPCHK_AS(dev_alloc(ctx->depth_own, n * 4), "hipMalloc(depth)");
+  HIPCHK_AS(hipMemset(ctx->color_own.get(), 0, cbytes), "hipMemset(color)");
+  HIPCHK_AS(hipMemset(ctx->depth_own.get(), 0, n * 4), "hipMemset(depth)");
+  ctx->color = ctx->color_own.get();
+  ctx->depth = ctx->depth_own.get();
   // (the internal streams are made by the first pass that needs them: submit_pass)
-  if ((r = hipEventCreateWithFlags(&ctx->ev_gswitch, hipEventDisableTiming)) != hipSuccess) return bail(r, "hipEventCreate");
-  for (int i = 0; i < SvrContext::NSETS; i++) {
-    if ((r = hipEventCreateWithFlags(&ctx->sets[i].ev_bin, hipEventDisableTiming)) != hipSuccess) return bail(r, "hipEventCreate");
-  }
-  if ((r = hipHostMalloc((void**)&ctx->h_counters, sizeof(Counters) * SvrContext::MAX_OPS, hipHostMallocDefault)) != hipSuccess)
-    return bail(r, "hipHostMalloc");
-  for (int i = 0; i < SvrContext::MAX_OPS; i++)
-    if ((r = hipEventCreate(&ctx->op_done[i])) != hipSuccess) return bail(r, "hipEventCreate");
-  if ((r = hipHostMalloc((void**)&ctx->h_row_cost, sizeof(uint32_t) * ROW_COST_MAX * SvrContext::MAX_OPS, hipHostMallocDefault)) != hipSuccess)
-    return bail(r, "hipHostMalloc");
-  std::memset(ctx->h_row_cost, 0, sizeof(uint32_t) * ROW_COST_MAX * SvrContext::MAX_OPS);
-  if ((r = hipHostMalloc((void**)&ctx->h_clock, sizeof(unsigned long long) * CLOCK_WORDS * SvrContext::MAX_OPS, hipHostMallocDefault)) != hipSuccess)
-    return bail(r, "hipHostMalloc");
-  std::memset(ctx->h_clock, 0, sizeof(unsigned long long) * CLOCK_WORDS * SvrContext::MAX_OPS);
-  if ((r = hipHostMalloc((void**)&ctx->h_failed_seq, 64, hipHostMallocDefault)) != hipSuccess) return bail(r, "hipHostMalloc");
+  HIPCHK_AS(make_event(ctx->ev_gswitch, hipEventDisableTiming), "hipEventCreate");
+  for (SvrContext::PassSet& set : ctx->sets)
+    HIPCHK_AS(make_event(set.ev_bin, hipEventDisableTiming), "hipEventCreate");
+  HIPCHK_AS(pinned_alloc(ctx->h_counters, sizeof(Counters) * SvrContext::MAX_OPS), "hipHostMalloc");
+  for (Event& ev : ctx->op_done)
+    HIPCHK_AS(make_event(ev, hipEventDefault), "hipEventCreate");
+  HIPCHK_AS(pinned_alloc(ctx->h_row_cost, sizeof(uint32_t) * ROW_COST_MAX * SvrContext::MAX_OPS), "hipHostMalloc");
+  std::memset(ctx->h_row_cost.get(), 0, sizeof(uint32_t) * ROW_COST_MAX * SvrContext::MAX_OPS);
+  HIPCHK_AS(pinned_alloc(ctx->h_clock, sizeof(unsigned long long) * CLOCK_WORDS * SvrContext::MAX_OPS), "hipHostMalloc");
+  std::memset(ctx->h_clock.get(), 0, sizeof(unsigned long long) * CLOCK_WORDS * SvrContext::MAX_OPS);
+  HIPCHK_AS(pinned_alloc(ctx->h_failed_seq, 64), "hipHostMalloc");
   *ctx->h_failed_seq = 0;
-  if ((r = hipMalloc((void**)&ctx->d_poison, 256)) != hipSuccess) return bail(r, "hipMalloc");
-  if ((r = hipMemset(ctx->d_poison, 0, 256)) != hipSuccess) return bail(r, "hipMemset");
-  *out = ctx;
+  HIPCHK_AS(dev_alloc(ctx->d_poison, 256), "hipMalloc");
+  HIPCHK_AS(hipMemset(ctx->d_poison.get(), 0, 256), "hipMemset");
+  *out = ctx.release();
   return SVR_OK;
 }
 
-void svr_destroy(SvrContext* ctx) {
-  if (!ctx) return;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->gstream) (void)hipStreamSynchronize(ctx->gstream);
-  if (ctx->gstream_hi) (void)hipStreamSynchronize(ctx->gstream_hi);
-  for (auto& m : ctx->meshes) {
-    if (m.vtx) (void)hipFree(m.vtx);
-    if (m.idx) (void)hipFree(m.idx);
-    if (m.groups) (void)hipFree(m.groups);
-  }
-  if (ctx->tex_arena) (void)hipFree(ctx->tex_arena);
-  DevBuf* bufs[] = {&ctx->tex_table, &ctx->d_cvt, &ctx->d_trace, &ctx->d_tile_cycles, &ctx->mesh_table, &ctx->mat_table};
-  for (auto& set : ctx->sets) {
-    DevBuf* sb[] = {&set.inputs, &set.recs, &set.clipq, &set.bigq, &set.tiles, &set.bins, &set.pairs, &set.flat, &set.sorta, &set.occl};
-    for (DevBuf* b : sb) b->release();
-    if (set.ev_bin) (void)hipEventDestroy(set.ev_bin);
-  }
-  if (ctx->gstream) (void)hipStreamDestroy(ctx->gstream);
-  if (ctx->gstream_hi) (void)hipStreamDestroy(ctx->gstream_hi);
-  if (ctx->ev_gswitch) (void)hipEventDestroy(ctx->ev_gswitch);
-  for (DevBuf* b : bufs) b->release();
-  for (int i = 0; i < SvrContext::MAX_OPS; i++)
-    if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]);
-  if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
-  if (ctx->h_row_cost) (void)hipHostFree(ctx->h_row_cost);
-  if (ctx->h_clock) (void)hipHostFree(ctx->h_clock);
-  for (int i = 0; i < SvrContext::MAX_OPS; i++)
-    if (ctx->op_done[i]) (void)hipEventDestroy(ctx->op_done[i]);
-  if (ctx->d_poison) (void)hipFree(ctx->d_poison);
-  if (ctx->d_lights) (void)hipFree(ctx->d_lights);
-  if (ctx->d_light_tiles) (void)hipFree(ctx->d_light_tiles);
-  if (ctx->h_failed_seq) (void)hipHostFree(ctx->h_failed_seq);
-  for (int i = 0; i < SvrContext::TRING; i++)
-    for (int k = 0; k < 5; k++)
-      if (ctx->tev[i][k]) (void)hipEventDestroy(ctx->tev[i][k]);
-  ctx->log.clear();  // the pyramids' memory goes with the last reference to it
-  ctx->pyramids.clear();
-  if (ctx->color_own) (void)hipFree(ctx->color_own);
-  if (ctx->depth_own) (void)hipFree(ctx->depth_own);
-  if (ctx->ids_own) (void)hipFree(ctx->ids_own);
-  for (void* p : ctx->attr_own)
-    if (p) (void)hipFree(p);
-  delete ctx;
-}
+void svr_destroy(SvrContext* ctx) { delete ctx; }  // ~SvrContext: the fence, then every member lets go
 
 int svr_set_stream(SvrContext* ctx, void* hip_stream) {
   if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
@@ -1236,8 +1248,8 @@ int svr_bind_targets(SvrContext* ctx, void* color_dev, void* depth_dev) {
   // can alternate between target sets while earlier ones are still in flight
   if (int e = poll_pending(ctx)) return e;
   if (int e = flush_clear(ctx)) return e;  // a deferred clear belongs to the targets it was asked for
-  ctx->color = color_dev ? color_dev : ctx->color_own;
-  ctx->depth = depth_dev ? (float*)depth_dev : ctx->depth_own;
+  ctx->color = color_dev ? color_dev : ctx->color_own.get();
+  ctx->depth = depth_dev ? (float*)depth_dev : ctx->depth_own.get();
   return SVR_OK;
 }
 
@@ -1261,14 +1273,11 @@ int svr_upload_mesh(SvrContext* ctx, const uint32_t* indices, size_t n_indices, 
   if (int e = use_device(ctx)) return e;
   MeshRes m;
   // device-local vertex + index buffers, blocking staged copy (src/vk_engine.cpp:345-381)
-  HIPCHK(hipMalloc((void**)&m.vtx, std::max<size_t>(n_vertices * sizeof(SvrVertex), 64)));
-  hipError_t r = hipMalloc((void**)&m.idx, std::max<size_t>(n_indices * 4, 64));
-  if (r != hipSuccess) {
-    (void)hipFree(m.vtx);
-    return fail(SVR_ERR_OUT_OF_MEMORY, std::string("hipMalloc(indices): ") + hipGetErrorString(r));
-  }
-  if (n_vertices) HIPCHK(hipMemcpy(m.vtx, vertices, n_vertices * sizeof(SvrVertex), hipMemcpyHostToDevice));
-  if (n_indices) HIPCHK(hipMemcpy(m.idx, indices, n_indices * 4, hipMemcpyHostToDevice));
+  DEV_ALLOC(m.vtx, std::max<size_t>(n_vertices * sizeof(SvrVertex), 64));
+  hipError_t r = dev_alloc(m.idx, std::max<size_t>(n_indices * 4, 64));
+  if (r != hipSuccess) return fail(SVR_ERR_OUT_OF_MEMORY, std::string("hipMalloc(indices): ") + hipGetErrorString(r));
+  if (n_vertices) HIPCHK(hipMemcpy(m.vtx.get(), vertices, n_vertices * sizeof(SvrVertex), hipMemcpyHostToDevice));
+  if (n_indices) HIPCHK(hipMemcpy(m.idx.get(), indices, n_indices * 4, hipMemcpyHostToDevice));
   // Index-group boxes: min / max position of the vertices named by every 192 consecutive indices.  A wave of the
   // setup kernel handles 64 consecutive triangles of a draw, i.e. at most two such groups, and skips them when
   // their box cannot reach the scissor.  (The bounds a caller attaches to a RenderObject are the loader's —
@@ -1297,19 +1306,14 @@ int svr_upload_mesh(SvrContext* ctx, const uint32_t* indices, size_t n_indices, 
       std::memcpy(&boxes[g * GROUP_WORDS + 6], &vmin, 4);
       std::memcpy(&boxes[g * GROUP_WORDS + 7], &vmax, 4);
     }
-    hipError_t rg = hipMalloc((void**)&m.groups, boxes.size() * sizeof(float));
-    if (rg == hipSuccess) rg = hipMemcpy(m.groups, boxes.data(), boxes.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (rg != hipSuccess) {
-      (void)hipFree(m.vtx);
-      (void)hipFree(m.idx);
-      if (m.groups) (void)hipFree(m.groups);
-      return fail(SVR_ERR_OUT_OF_MEMORY, std::string("svr_upload_mesh: index-group boxes: ") + hipGetErrorString(rg));
-    }
+    hipError_t rg = dev_alloc(m.groups, boxes.size() * sizeof(float));
+    if (rg == hipSuccess) rg = hipMemcpy(m.groups.get(), boxes.data(), boxes.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (rg != hipSuccess) return fail(SVR_ERR_OUT_OF_MEMORY, std::string("svr_upload_mesh: index-group boxes: ") + hipGetErrorString(rg));
   }
   m.n_vtx = n_vertices;
   m.n_idx = n_indices;
   m.alive = true;
-  ctx->meshes.push_back(m);
+  ctx->meshes.push_back(std::move(m));
   *out = (SvrMesh)ctx->meshes.size();
   return SVR_OK;
 }
@@ -1319,12 +1323,9 @@ int svr_destroy_mesh(SvrContext* ctx, SvrMesh mesh) {
   if (!m) return fail(SVR_ERR_BAD_HANDLE, "svr_destroy_mesh: bad handle");
   if (int e = use_device(ctx)) return e;
   if (int e = finish_pending(ctx)) return e;
-  (void)hipFree(m->vtx);
-  (void)hipFree(m->idx);
-  (void)hipFree(m->groups);
-  m->vtx = nullptr;
-  m->idx = nullptr;
-  m->groups = nullptr;
+  m->vtx.reset();
+  m->idx.reset();
+  m->groups.reset();
   m->alive = false;
   ctx->mesh_epoch++;  // draw lists that name it fail at their next svr_draw_list
   return SVR_OK;
@@ -1358,7 +1359,7 @@ int svr_create_image(SvrContext* ctx, const void* rgba8, uint32_t width, uint32_
   if (im.lw + im.lh > 28) return fail(SVR_ERR_UNSUPPORTED, "svr_create_image: image larger than 1 GiB");
   im.bytes = std::max<size_t>(total, 256);
   if (int e = arena_alloc(ctx, im.bytes, &im.arena_off)) return e;
-  uint8_t* base = ctx->tex_arena + im.arena_off;
+  uint8_t* base = ctx->tex_arena.get() + im.arena_off;
   hipError_t r = hipMemcpy(base, rgba8, (size_t)width * height * 4, hipMemcpyHostToDevice);
   if (r != hipSuccess) {
     arena_free(ctx, im.arena_off, im.bytes);
@@ -1403,7 +1404,7 @@ int svr_read_image_level(SvrContext* ctx, SvrImage image, uint32_t level, void* 
     size_t need = (size_t)lw * lh * 4;
     if (bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_image_level: buffer too small");
     if (int e = use_device(ctx)) return e;
-    HIPCHK(hipMemcpy(dst, ctx->tex_arena + im->arena_off + im->off[level], need, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dst, ctx->tex_arena.get() + im->arena_off + im->off[level], need, hipMemcpyDeviceToHost));
   }
   return SVR_OK;
 }
@@ -1525,7 +1526,7 @@ int svr_read_swapchain(SvrContext* ctx, uint32_t dw, uint32_t dh, int fmt, void*
   if (int e = use_device(ctx)) return e;
   if (int e = finish_pending(ctx)) return e;  // the read-back is a fence
   if (int e = ctx->d_cvt.ensure((size_t)dw * dh * 4)) return e;
-  launch_blit(ctx->color, ctx->fmt, ctx->W, ctx->H, ctx->d_cvt.p, dw, dh, 0, dh, fmt, ctx->d_poison, 1u, 0u, dh, nullptr, 0u, ctx->stream);
+  launch_blit(ctx->color, ctx->fmt, ctx->W, ctx->H, ctx->d_cvt.p, dw, dh, 0, dh, fmt, ctx->d_poison.get(), 1u, 0u, dh, nullptr, 0u, ctx->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(dst_host, ctx->d_cvt.p, (size_t)dw * dh * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1576,18 +1577,90 @@ static int validate_object(SvrContext* ctx, const SvrRenderObject& o, bool trans
   return SVR_OK;
 }
 
-// svr_draw_geometry, and with depth_only svr_draw_depth (no transparent objects then): who names the entry point
-static int draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque,
-                         const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats, bool depth_only, const char* who) {
-  if (!ctx || !scene || (!opaque && n_opaque) || (!transparent && n_transparent))
-    return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+// DrawDesc::mvp = viewproj * mat, column by column as prologue_kernel's matvec4 forms it (C0): the product then is the
+// one a single-view pass over this scene computes on the device
+static void host_mvp(const float* vp, const float* mat, float* out) {
+  for (int j = 0; j < 4; j++)
+    for (int r = 0; r < 4; r++) {
+      float acc = vp[0 + r] * mat[4 * j + 0];
+      acc = std::fmaf(vp[4 + r], mat[4 * j + 1], acc);
+      acc = std::fmaf(vp[8 + r], mat[4 * j + 2], acc);
+      acc = std::fmaf(vp[12 + r], mat[4 * j + 3], acc);
+      out[4 * j + r] = acc;
+    }
+}
+
+// what every record that draws from a mesh holds: its matrix, buffers and index range, a slot of the binding table, flags
+static DrawDesc mesh_record(const MeshRes& m, const float mat[16], uint32_t first_index, uint32_t index_count, uint32_t tex, uint32_t flags) {
+  DrawDesc d;
+  std::memset(&d, 0, sizeof(d));
+  std::memcpy(d.mat, mat, 64);
+  d.vtx = m.vtx.get();
+  d.idx = m.idx.get() + first_index;
+  d.groups = m.groups.get();
+  d.first_index = first_index;
+  d.tri_count = index_count / 3;
+  d.tex = tex;
+  d.flags = flags;
+  return d;
+}
+
+// The record of one mesh object (the push constants + bound buffers of the record lambda, src/vk_engine.cpp:1412-1457).
+// object: its number for the ID target (include/svr_ids.h), 0 = none.  viewproj: the view's, of a multiview pass, whose
+// mvp the host computes; null: a single-view pass leaves DrawDesc::mvp to the prologue kernel (n_draws of launch_prologue)
+static DrawDesc object_record(const SvrContext* ctx, const SvrRenderObject& o, uint32_t object, uint32_t view, const float* viewproj) {
+  const MaterialRes& mat = ctx->materials[o.material - 1];
+  DrawDesc d = mesh_record(ctx->meshes[o.mesh - 1], o.transform, o.first_index, o.index_count, o.material - 1,
+                           ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (mat.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u) | (view << F_VIEW_SHIFT));
+  if (viewproj) host_mvp(viewproj, d.mat, d.mvp);
+  std::memcpy(d.color_factors, mat.cf, 16);
+  d.pad = object;
+  return d;
+}
+
+// The host path of every geometry call, for the one view of rq.scene or the views of a multiview request (scenes[k]):
+// each view culls its opaque objects (src/vk_engine.cpp:1361-1367) and sorts the visible ones into draw order, then gets
+// its draws, opaque before transparent, view after view; triangle numbers and wave chunks run on across the views (run_pass)
+static int draw_objects(SvrContext* ctx, PassRequest& rq, const SvrSceneData* scenes, const SvrRenderObject* opaque, size_t n_opaque,
+                        const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats,
+                        const std::chrono::steady_clock::time_point& t0) {
+  const uint32_t n_views = rq.mv ? rq.mv->n_views : 1u;
+  const bool ids = id_target(ctx, rq) != nullptr;  // DrawDesc::pad = the opaque object's number
+  std::vector<uint32_t> order;
+  order.reserve(n_opaque);
+  std::vector<DrawDesc> draws;
+  SvrStats st{};
+  for (uint32_t k = 0; k < n_views; k++) {
+    const float* vp = scenes[k].viewproj;
+    order.clear();
+    for (size_t i = 0; i < n_opaque; i++)
+      if (is_visible(opaque[i], vp)) order.push_back((uint32_t)i);
+    sort_draw_order(order, opaque);
+    if (k == 0) draws.reserve((order.size() + n_transparent) * n_views);
+    auto push = [&](const SvrRenderObject& o, uint32_t object) {
+      draws.push_back(object_record(ctx, o, object, k, rq.mv ? vp : nullptr));
+      st.drawcall_count++;
+      st.triangle_count += (int)(o.index_count / 3);
+    };
+    for (uint32_t i : order) push(opaque[i], ids ? i + 1u : 0u);
+    for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
+    st.culled_draws += (uint32_t)(n_opaque - order.size());
+  }
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, rq, draws), &t0);
+}
+
+// svr_draw_geometry and svr_draw_depth (no transparent objects then)
+static int draw_geometry(SvrContext* ctx, PassRequest rq, const SvrRenderObject* opaque, size_t n_opaque, const SvrRenderObject* transparent,
+                         size_t n_transparent, SvrStats* out_stats) {
+  if (!ctx || !rq.scene || (!opaque && n_opaque) || (!transparent && n_transparent))
+    return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
   auto t0 = std::chrono::steady_clock::now();
   if (int e = use_device(ctx)) return e;
   for (size_t i = 0; i < n_opaque; i++)
-    if (int e = validate_object(ctx, opaque[i], false, who)) return e;
+    if (int e = validate_object(ctx, opaque[i], false, rq.who)) return e;
   for (size_t i = 0; i < n_transparent; i++)
-    if (int e = validate_object(ctx, transparent[i], true, who)) return e;
-  if (owns_nothing(ctx, out_stats, depth_only)) return SVR_OK;
+    if (int e = validate_object(ctx, transparent[i], true, rq.who)) return e;
+  if (owns_nothing(ctx, out_stats, rq)) return SVR_OK;
   if (int e = upload_tex_table(ctx, nullptr)) return e;
   // Many objects: cull, sort and the per-object records run on the device (k_flatten.hip).  The three
   // counts of the stats then only exist after the pass (svr_get_stats); out_stats gets what the host knows.
@@ -1601,49 +1674,15 @@ static int draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRe
     in.objects.insert(in.objects.end(), transparent, transparent + n_transparent);
     in.n_opaque_obj = (uint32_t)n_opaque;
     in.n_transparent_obj = (uint32_t)n_transparent;
-    uint64_t tris_max = 0;
-    size_t chunks_max = 0;
-    add_object_bounds(in.objects.data(), n_objects, &tris_max, &chunks_max);
-    return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), tris_max, chunks_max, true, nullptr, depth_only), &t0);
+    add_object_bounds(in.objects.data(), n_objects, &rq.n_tris, &rq.n_chunks);
+    return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, rq, std::move(in)), &t0);
   }
-  // cull: opaque only (src/vk_engine.cpp:1361-1367)
-  std::vector<uint32_t> order;
-  order.reserve(n_opaque);
-  for (size_t i = 0; i < n_opaque; i++)
-    if (is_visible(opaque[i], scene->viewproj)) order.push_back((uint32_t)i);
-  sort_draw_order(order, opaque);
-  std::vector<DrawDesc> draws;
-  draws.reserve(order.size() + n_transparent);
-  SvrStats st{};
-  const bool ids = ctx->ids != nullptr;  // DrawDesc::pad = the opaque object's number (include/svr_ids.h)
-  auto push = [&](const SvrRenderObject& o, uint32_t object) {
-    const MeshRes& m = ctx->meshes[o.mesh - 1];
-    const MaterialRes& mat = ctx->materials[o.material - 1];
-    DrawDesc d;
-    std::memset(&d, 0, sizeof(d));
-    std::memcpy(d.mat, o.transform, 64);
-    std::memcpy(d.color_factors, mat.cf, 16);
-    d.vtx = m.vtx;
-    d.idx = m.idx + o.first_index;
-    d.groups = m.groups;
-    d.first_index = o.first_index;
-    d.tri_count = o.index_count / 3;
-    d.tex = o.material - 1;
-    d.flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (mat.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u);
-    d.pad = ids ? object : 0u;
-    draws.push_back(d);
-    st.drawcall_count++;
-    st.triangle_count += (int)(o.index_count / 3);
-  };
-  for (uint32_t i : order) push(opaque[i], i + 1u);
-  for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
-  st.culled_draws = (uint32_t)(n_opaque - order.size());
-  return finish_draw(ctx, st, out_stats, run_pass(ctx, scene, draws, true, nullptr, depth_only), &t0);
+  return draw_objects(ctx, rq, rq.scene, opaque, n_opaque, transparent, n_transparent, out_stats, t0);
 }
 
 int svr_draw_geometry(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque,
                       const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats) {
-  return draw_geometry(ctx, scene, opaque, n_opaque, transparent, n_transparent, out_stats, false, "svr_draw_geometry");
+  return draw_geometry(ctx, geometry_request("svr_draw_geometry", scene, false), opaque, n_opaque, transparent, n_transparent, out_stats);
 }
 
 int svr_draw_colored_triangle(SvrContext* ctx, SvrStats* out_stats) {
@@ -1658,7 +1697,9 @@ int svr_draw_colored_triangle(SvrContext* ctx, SvrStats* out_stats) {
   SvrStats st{};
   st.drawcall_count = 1;
   st.triangle_count = 1;
-  return finish_draw(ctx, st, out_stats, run_pass(ctx, nullptr, draws));
+  PassRequest rq;
+  rq.who = "svr_draw_colored_triangle";
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, rq, draws));
 }
 
 int svr_draw_tex_image(SvrContext* ctx, SvrMesh mesh, uint32_t first_index, uint32_t index_count,
@@ -1677,21 +1718,15 @@ int svr_draw_tex_image(SvrContext* ctx, SvrMesh mesh, uint32_t first_index, uint
   TexBinding tb = make_binding(*im, ctx->samplers[sampler - 1]);
   if (int e = upload_tex_table(ctx, &tb)) return e;
   ctx->tex_slots = 0;  // scratch slot is in use: rebuild before the next mesh pass
-  std::vector<DrawDesc> draws(1);
-  DrawDesc& d = draws[0];
-  std::memset(&d, 0, sizeof(d));
-  std::memcpy(d.mat, render_matrix, 64);
-  d.vtx = m->vtx;
-  d.idx = m->idx + first_index;
-  d.groups = m->groups;
-  d.first_index = first_index;
-  d.tri_count = index_count / 3;
-  d.tex = (uint32_t)ctx->materials.size();
-  d.flags = (uint32_t)PIPE_TEX_IMAGE << F_KIND_SHIFT;
+  // a mesh record without colour factors, of kind PIPE_TEX_IMAGE, whose texture is the scratch slot
+  std::vector<DrawDesc> draws(1, mesh_record(*m, render_matrix, first_index, index_count, (uint32_t)ctx->materials.size(),
+                                             (uint32_t)PIPE_TEX_IMAGE << F_KIND_SHIFT));
   SvrStats st{};
   st.drawcall_count = 1;
   st.triangle_count = (int)(index_count / 3);
-  return finish_draw(ctx, st, out_stats, run_pass(ctx, nullptr, draws));
+  PassRequest rq;
+  rq.who = "svr_draw_tex_image";
+  return finish_draw(ctx, st, out_stats, run_pass(ctx, rq, draws));
 }
 
 int svr_run_mesh_vert(SvrContext* ctx, SvrMesh mesh, uint32_t first_vertex, uint32_t n_vertices, const float world[16],
@@ -1709,27 +1744,17 @@ int svr_run_mesh_vert(SvrContext* ctx, SvrMesh mesh, uint32_t first_vertex, uint
   std::memcpy(consts, world, 64);
   std::memcpy(consts + 16, scene->viewproj, 64);
   std::memcpy(consts + 32, ctx->materials[material - 1].cf, 16);
-  float* d_consts = nullptr;
-  float* d_out = nullptr;
-  HIPCHK(hipMalloc((void**)&d_consts, sizeof(consts)));
-  hipError_t r = hipMalloc((void**)&d_out, (size_t)n_vertices * 12 * sizeof(float));
-  if (r != hipSuccess) {
-    (void)hipFree(d_consts);
-    return fail(SVR_ERR_OUT_OF_MEMORY, "svr_run_mesh_vert: hipMalloc failed");
-  }
-  int rc = SVR_OK;
-  do {
-    if (hipMemcpy(d_consts, consts, sizeof(consts), hipMemcpyHostToDevice) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "hipMemcpy"); break; }
-    float* d_clip = d_out;
-    float* d_var = d_out + (size_t)n_vertices * 4;
-    launch_mesh_vert(m->vtx, first_vertex, n_vertices, d_consts, d_consts + 16, d_consts + 32, d_clip, d_var, ctx->stream);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "mesh_vert kernel failed"); break; }
-    if (hipMemcpy(out_clip, d_clip, (size_t)n_vertices * 16, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "hipMemcpy"); break; }
-    if (hipMemcpy(out_varyings, d_var, (size_t)n_vertices * 32, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "hipMemcpy"); break; }
-  } while (0);
-  (void)hipFree(d_consts);
-  (void)hipFree(d_out);
-  return rc;
+  DevPtr<float> d_consts, d_out;
+  DEV_ALLOC(d_consts, sizeof(consts));
+  if (dev_alloc(d_out, (size_t)n_vertices * 12 * sizeof(float)) != hipSuccess) return fail(SVR_ERR_OUT_OF_MEMORY, "svr_run_mesh_vert: hipMalloc failed");
+  if (hipMemcpy(d_consts.get(), consts, sizeof(consts), hipMemcpyHostToDevice) != hipSuccess) return fail(SVR_ERR_DEVICE, "hipMemcpy");
+  float* d_clip = d_out.get();
+  float* d_var = d_clip + (size_t)n_vertices * 4;
+  launch_mesh_vert(m->vtx.get(), first_vertex, n_vertices, d_consts.get(), d_consts.get() + 16, d_consts.get() + 32, d_clip, d_var, ctx->stream);
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(SVR_ERR_DEVICE, "mesh_vert kernel failed");
+  if (hipMemcpy(out_clip, d_clip, (size_t)n_vertices * 16, hipMemcpyDeviceToHost) != hipSuccess) return fail(SVR_ERR_DEVICE, "hipMemcpy");
+  if (hipMemcpy(out_varyings, d_var, (size_t)n_vertices * 32, hipMemcpyDeviceToHost) != hipSuccess) return fail(SVR_ERR_DEVICE, "hipMemcpy");
+  return SVR_OK;
 }
 
 int svr_run_vertex_shader(SvrContext* ctx, int shader, SvrMesh mesh, uint32_t first_vertex, uint32_t n_vertices,
@@ -1749,22 +1774,18 @@ int svr_run_vertex_shader(SvrContext* ctx, int shader, SvrMesh mesh, uint32_t fi
   }
   if (n_vertices == 0) return SVR_OK;
   if (int e = use_device(ctx)) return e;
-  float* d_buf = nullptr;  // 16 floats of matrix, then clip, then varyings
-  if (hipMalloc((void**)&d_buf, (16 + (size_t)n_vertices * 12) * sizeof(float)) != hipSuccess)
+  DevPtr<float> d_buf;  // 16 floats of matrix, then clip, then varyings
+  if (dev_alloc(d_buf, (16 + (size_t)n_vertices * 12) * sizeof(float)) != hipSuccess)
     return fail(SVR_ERR_OUT_OF_MEMORY, "svr_run_vertex_shader: hipMalloc failed");
-  int rc = SVR_OK;
-  do {
-    float zero[16] = {0};
-    if (hipMemcpy(d_buf, render_matrix ? render_matrix : zero, 64, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "hipMemcpy"); break; }
-    float* d_clip = d_buf + 16;
-    float* d_var = d_clip + (size_t)n_vertices * 4;
-    launch_vertex_shader(m ? m->vtx : nullptr, first_vertex, n_vertices, d_buf, d_clip, d_var, ctx->stream);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "vertex shader kernel failed"); break; }
-    if (hipMemcpy(out_clip, d_clip, (size_t)n_vertices * 16, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "hipMemcpy"); break; }
-    if (hipMemcpy(out_varyings, d_var, (size_t)n_vertices * 32, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(SVR_ERR_DEVICE, "hipMemcpy"); break; }
-  } while (0);
-  (void)hipFree(d_buf);
-  return rc;
+  const float zero[16] = {0};
+  if (hipMemcpy(d_buf.get(), render_matrix ? render_matrix : zero, 64, hipMemcpyHostToDevice) != hipSuccess) return fail(SVR_ERR_DEVICE, "hipMemcpy");
+  float* d_clip = d_buf.get() + 16;
+  float* d_var = d_clip + (size_t)n_vertices * 4;
+  launch_vertex_shader(m ? m->vtx.get() : nullptr, first_vertex, n_vertices, d_buf.get(), d_clip, d_var, ctx->stream);
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(SVR_ERR_DEVICE, "vertex shader kernel failed");
+  if (hipMemcpy(out_clip, d_clip, (size_t)n_vertices * 16, hipMemcpyDeviceToHost) != hipSuccess) return fail(SVR_ERR_DEVICE, "hipMemcpy");
+  if (hipMemcpy(out_varyings, d_var, (size_t)n_vertices * 32, hipMemcpyDeviceToHost) != hipSuccess) return fail(SVR_ERR_DEVICE, "hipMemcpy");
+  return SVR_OK;
 }
 
 int svr_set_option(SvrContext* ctx, int option, int64_t value) {
@@ -1872,16 +1893,15 @@ int svr_debug_rcp_sweep(SvrContext* ctx, int variant, uint64_t first, uint64_t c
   if (!ctx || !mismatches) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_rcp_sweep: null argument");
   if (variant < 0 || variant > 2 || first + count > (1ull << 32)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_rcp_sweep: bad range or variant");
   if (int e = use_device(ctx)) return e;
-  unsigned long long* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, 19 * 8));
+  DevPtr<unsigned long long> d;
+  DEV_ALLOC(d, 19 * 8);
   unsigned long long h[19] = {};
-  hipError_t r = hipMemset(d, 0, 19 * 8);
+  hipError_t r = hipMemset(d.get(), 0, 19 * 8);
   if (r == hipSuccess) {
-    launch_rcp_sweep(variant, first, count, d, ctx->stream);
+    launch_rcp_sweep(variant, first, count, d.get(), ctx->stream);
     r = hipStreamSynchronize(ctx->stream);
   }
-  if (r == hipSuccess) r = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
+  if (r == hipSuccess) r = hipMemcpy(h, d.get(), sizeof(h), hipMemcpyDeviceToHost);
   if (r != hipSuccess) return fail(SVR_ERR_DEVICE, std::string("svr_debug_rcp_sweep: ") + hipGetErrorString(r));
   *mismatches = h[0];
   if (refined) *refined = h[1];
@@ -1977,13 +1997,13 @@ static int make_list_version(const DrawListRes& L, std::shared_ptr<const ListVer
   add_object_bounds(sorted.data(), n, &v->tris_max, &v->chunks_max);
   add_object_bounds(sorted.data(), L.n_opaque, &v->tris_max_opaque, &v->chunks_max_opaque);
   if (n) {
-    HIPCHK(hipMalloc((void**)&v->dev, n * sizeof(SvrRenderObject)));
-    HIPCHK(hipMemcpy(v->dev, sorted.data(), n * sizeof(SvrRenderObject), hipMemcpyHostToDevice));
+    DEV_ALLOC(v->dev, n * sizeof(SvrRenderObject));
+    HIPCHK(hipMemcpy(v->dev.get(), sorted.data(), n * sizeof(SvrRenderObject), hipMemcpyHostToDevice));
   }
   if (L.n_opaque) {  // object numbers for ID passes (include/svr_ids.h)
     for (uint32_t& i : order) i += 1u;
-    HIPCHK(hipMalloc((void**)&v->obj_ids, order.size() * sizeof(uint32_t)));
-    HIPCHK(hipMemcpy(v->obj_ids, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    DEV_ALLOC(v->obj_ids, order.size() * sizeof(uint32_t));
+    HIPCHK(hipMemcpy(v->obj_ids.get(), order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   *out = std::move(v);
   return SVR_OK;
@@ -2040,41 +2060,6 @@ int svr_destroy_draw_list(SvrContext* ctx, SvrDrawList list) {
   return SVR_OK;
 }
 
-// Per pass the host checks the handle and the mesh epoch, and enqueues the pass of svr_draw_geometry's device
-// flatten with the list's current version (enqueue_pass): no per-object loop.
-// svr_draw_list, and with depth_only svr_draw_list_depth: the flatten then walks the list's opaque objects only
-static int draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats, bool depth_only, const char* who) {
-  const std::string fn(who);
-  if (!ctx || !scene) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
-  auto t0 = std::chrono::steady_clock::now();
-  DrawListRes* L = get_list(ctx, list);
-  if (!L) return fail(SVR_ERR_BAD_HANDLE, fn + ": bad list handle");
-  if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, "svr_draw_list");  // a mesh was destroyed since
-  if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": the list is no longer valid (" + L->why + ")");
-  if (int e = use_device(ctx)) return e;
-  if (owns_nothing(ctx, out_stats, depth_only)) return SVR_OK;
-  if (int e = upload_tex_table(ctx, nullptr)) return e;
-  const ListVersion& v = *L->cur;
-  const uint32_t n_transparent = depth_only ? 0u : v.n_transparent;
-  const size_t n_objects = (size_t)v.n_opaque + n_transparent;
-  SvrContext::LoggedOp in;  // no objects: svr_draw_geometry's host path, a pass of no draws
-  if (n_objects > 0) {
-    if (n_objects > LIST_FUSED_MAX && (ctx->meshes.size() >= (1u << 20) || ctx->materials.size() >= (1u << 20)))
-      return fail(SVR_ERR_UNSUPPORTED, fn + ": lists over 4096 objects need fewer than 2^20 meshes and materials");
-    in.input = SvrContext::PassInput::List;
-    in.list = L->cur;
-    in.n_opaque_obj = v.n_opaque;
-    in.n_transparent_obj = n_transparent;
-  }
-  const uint64_t tris_max = depth_only ? v.tris_max_opaque : v.tris_max;
-  const size_t chunks_max = depth_only ? v.chunks_max_opaque : v.chunks_max;
-  return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, scene, std::move(in), tris_max, chunks_max, true, nullptr, depth_only), &t0);
-}
-
-int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
-  return draw_list(ctx, list, scene, out_stats, false, "svr_draw_list");
-}
-
 int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void* chunks, size_t chunk_bytes, uint32_t* n_draws,
                            uint32_t* n_chunks) {
   if (!ctx || !n_draws || !n_chunks) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_records: null argument");
@@ -2102,16 +2087,25 @@ int svr_debug_read_records(SvrContext* ctx, void* draws, size_t draw_bytes, void
 }
 
 // ---------------------------------------------------------------- multiview passes (include/svr_views.h)
-// the arguments every multiview call checks, in the order of the header's refusals; fills mv
-// depth_only (include/svr_depth.h): no colour target and no clear; the views' lighting is not read, so it may differ
-static int check_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* t, const char* who, MultiView* mv,
-                       bool depth_only = false) {
-  const std::string fn(who);
-  if (!scenes || !t || (!depth_only && !t->color) || !t->depth) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
+// the arguments of a multiview call
+struct ViewArgs {
+  uint32_t n_views;
+  const SvrSceneData* scenes;
+  const SvrViewTargets* targets;
+};
+
+// What every multiview call checks of them, in the order of the header's refusals; completes the request: fills mv and
+// makes it rq's, with the first view's scene.  A depth-only pass (include/svr_depth.h) takes no colour target and no
+// clear; the views' lighting is not read, so it may differ
+static int check_views(SvrContext* ctx, PassRequest& rq, const ViewArgs& va, MultiView* mv) {
+  const std::string fn(rq.who);
+  const SvrViewTargets* t = va.targets;
+  const bool depth_only = rq.depth_only;
+  if (!va.scenes || !t || (!depth_only && !t->color) || !t->depth) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
   if (depth_only && (t->color || t->clear_rgba))
     return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": a depth-only pass takes no colour target and no clear_rgba (both must be NULL)");
-  if (n_views == 0 || n_views > SVR_MAX_VIEWS) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": need 1 <= n_views <= 16");
-  if ((uint64_t)n_views * ((ctx->H + TILE - 1) / TILE) > ROW_COST_MAX)
+  if (va.n_views == 0 || va.n_views > SVR_MAX_VIEWS) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": need 1 <= n_views <= 16");
+  if ((uint64_t)va.n_views * ((ctx->H + TILE - 1) / TILE) > ROW_COST_MAX)
     return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": n_views * ceil(height / 32) exceeds 512 tile rows");
   if (((uintptr_t)t->color | (uintptr_t)t->depth | (uintptr_t)t->ids) & 15u)
     return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": targets must be 16-byte aligned");
@@ -2119,155 +2113,143 @@ static int check_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* sc
     return fail(SVR_ERR_UNSUPPORTED, fn + ": a narrowed scissor has no multiview form");
   if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, fn + ": interleaved rows (svr_set_row_interleave) have no multiview form");
   if (ctx->occl_bound) return fail(SVR_ERR_UNSUPPORTED, fn + ": occlusion culling (svr_set_occlusion_pyramid) has no multiview form");
-  for (uint32_t k = 1; k < n_views && !depth_only; k++)  // one UBO: only the matrices differ between the views
-    if (std::memcmp(scenes[k].ambient_color, scenes[0].ambient_color, 12 * sizeof(float)) != 0)
+  for (uint32_t k = 1; k < va.n_views && !depth_only; k++)  // one UBO: only the matrices differ between the views
+    if (std::memcmp(va.scenes[k].ambient_color, va.scenes[0].ambient_color, 12 * sizeof(float)) != 0)
       return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": ambient_color, sunlight_direction and sunlight_color must be equal in every view");
-  mv->n_views = n_views;
+  mv->n_views = va.n_views;
   mv->color = t->color;
   mv->depth = t->depth;
   mv->ids = (uint2*)t->ids;
   mv->clear = t->clear_rgba != nullptr;
   mv->packed = t->clear_rgba ? encode_clear(ctx, t->clear_rgba) : 0u;
+  rq.scene = va.scenes;
+  rq.mv = mv;
   return SVR_OK;
 }
 
-// DrawDesc::mvp = viewproj * mat, column by column as prologue_kernel's matvec4 forms it (C0): the product then is the
-// one a single-view pass over this scene computes on the device
-static void host_mvp(const float* vp, const float* mat, float* out) {
-  for (int j = 0; j < 4; j++)
-    for (int r = 0; r < 4; r++) {
-      float acc = vp[0 + r] * mat[4 * j + 0];
-      acc = std::fmaf(vp[4 + r], mat[4 * j + 1], acc);
-      acc = std::fmaf(vp[8 + r], mat[4 * j + 2], acc);
-      acc = std::fmaf(vp[12 + r], mat[4 * j + 3], acc);
-      out[4 * j + r] = acc;
-    }
-}
-
-// The pass of svr_draw_geometry for every view: the opaque draw order is sorted once (a culled subset keeps its order), each
-// view culls with its own viewproj and gets its draws, view after view, with the view in the flags; triangle numbers and
-// wave chunks run on across the views (run_pass)
-static int draw_views(SvrContext* ctx, const MultiView& mv, const SvrSceneData* scenes, const SvrRenderObject* opaque, size_t n_opaque,
-                      const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats,
-                      const std::chrono::steady_clock::time_point& t0, bool depth_only = false) {
+// svr_draw_geometry_views and svr_draw_depth_views (no transparent objects then): the host path for every view
+static int draw_geometry_views(SvrContext* ctx, PassRequest rq, const ViewArgs& va, const SvrRenderObject* opaque, size_t n_opaque,
+                               const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats) {
+  if (!ctx || (!opaque && n_opaque) || (!transparent && n_transparent)) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
+  auto t0 = std::chrono::steady_clock::now();
+  MultiView mv;
+  if (int e = check_views(ctx, rq, va, &mv)) return e;
+  for (size_t i = 0; i < n_opaque; i++)
+    if (int e = validate_object(ctx, opaque[i], false, rq.who)) return e;
+  for (size_t i = 0; i < n_transparent; i++)
+    if (int e = validate_object(ctx, transparent[i], true, rq.who)) return e;
+  if (int e = use_device(ctx)) return e;
   if (int e = upload_tex_table(ctx, nullptr)) return e;
-  std::vector<uint32_t> sorted(n_opaque);
-  std::iota(sorted.begin(), sorted.end(), 0u);
-  sort_draw_order(sorted, opaque);
-  const bool ids = mv.ids != nullptr;
-  std::vector<DrawDesc> draws;
-  SvrStats st{};
-  for (uint32_t k = 0; k < mv.n_views; k++) {
-    const float* vp = scenes[k].viewproj;
-    auto push = [&](const SvrRenderObject& o, uint32_t object) {
-      const MeshRes& m = ctx->meshes[o.mesh - 1];
-      const MaterialRes& mat = ctx->materials[o.material - 1];
-      DrawDesc d;
-      std::memset(&d, 0, sizeof(d));
-      std::memcpy(d.mat, o.transform, 64);
-      host_mvp(vp, d.mat, d.mvp);
-      std::memcpy(d.color_factors, mat.cf, 16);
-      d.vtx = m.vtx;
-      d.idx = m.idx + o.first_index;
-      d.groups = m.groups;
-      d.first_index = o.first_index;
-      d.tri_count = o.index_count / 3;
-      d.tex = o.material - 1;
-      d.flags = ((uint32_t)PIPE_MESH << F_KIND_SHIFT) | (mat.pass == SVR_PASS_TRANSPARENT ? F_TRANSPARENT : 0u) | (k << F_VIEW_SHIFT);
-      d.pad = ids ? object : 0u;
-      draws.push_back(d);
-      st.drawcall_count++;
-      st.triangle_count += (int)(o.index_count / 3);
-    };
-    for (uint32_t i : sorted) {
-      if (is_visible(opaque[i], vp)) push(opaque[i], i + 1u);
-      else st.culled_draws++;
-    }
-    for (size_t i = 0; i < n_transparent; i++) push(transparent[i], 0u);
-  }
-  return finish_draw(ctx, st, out_stats, run_pass(ctx, &scenes[0], draws, true, &mv, depth_only), &t0);
+  return draw_objects(ctx, rq, va.scenes, opaque, n_opaque, transparent, n_transparent, out_stats, t0);
 }
 
 int svr_draw_geometry_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
                             const SvrRenderObject* opaque, size_t n_opaque, const SvrRenderObject* transparent, size_t n_transparent,
                             SvrStats* out_stats) {
-  if (!ctx || (!opaque && n_opaque) || (!transparent && n_transparent))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_geometry_views: null argument");
-  auto t0 = std::chrono::steady_clock::now();
-  MultiView mv;
-  if (int e = check_views(ctx, n_views, scenes, targets, "svr_draw_geometry_views", &mv)) return e;
-  for (size_t i = 0; i < n_opaque; i++)
-    if (int e = validate_object(ctx, opaque[i], false, "svr_draw_geometry_views")) return e;
-  for (size_t i = 0; i < n_transparent; i++)
-    if (int e = validate_object(ctx, transparent[i], true, "svr_draw_geometry_views")) return e;
-  if (int e = use_device(ctx)) return e;
-  return draw_views(ctx, mv, scenes, opaque, n_opaque, transparent, n_transparent, out_stats, t0);
+  return draw_geometry_views(ctx, geometry_request("svr_draw_geometry_views", nullptr, false), {n_views, scenes, targets}, opaque, n_opaque,
+                             transparent, n_transparent, out_stats);
 }
 
-// svr_draw_list_views, and with depth_only svr_draw_list_depth_views (the list's opaque objects only)
-static int draw_list_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
-                           SvrStats* out_stats, bool depth_only, const char* who) {
-  const std::string fn(who);
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
-  auto t0 = std::chrono::steady_clock::now();
+// ---------------------------------------------------------------- drawing a retained list (include/svr_draw_list.h)
+// what a multiview list call adds to a single-view one: its arguments, the MultiView made of them, and the list itself
+// (its host path walks the submission-order copy)
+struct ListViews {
+  ViewArgs va;
+  MultiView mv;
+  const DrawListRes* list = nullptr;
+};
+
+// The head of the four calls that draw a list: the handle, the checks of a multiview call (views: of those), the list's
+// validity — looked at again if a mesh was destroyed since — and the device.  Then the pass over the list's current
+// version: `in` names it as the List input, unless the pass draws no object, and rq gets the bounds of one view (a
+// depth-only pass: of the opaque objects alone, the only ones its flatten walks).
+static int list_pass(SvrContext* ctx, SvrDrawList list, PassRequest& rq, ListViews* views, SvrContext::LoggedOp& in) {
+  const std::string fn(rq.who);
   DrawListRes* L = get_list(ctx, list);
   if (!L) return fail(SVR_ERR_BAD_HANDLE, fn + ": bad list handle");
-  MultiView mv;
-  if (int e = check_views(ctx, n_views, scenes, targets, who, &mv, depth_only)) return e;
-  if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, who);  // a mesh was destroyed since
+  if (views)
+    if (int e = check_views(ctx, rq, views->va, &views->mv)) return e;
+  // a mesh was destroyed since: the single-view calls have always revalidated as svr_draw_list, the others by their name
+  if (L->mesh_epoch != ctx->mesh_epoch) (void)check_list_objects(ctx, *L, views ? rq.who : "svr_draw_list");
   if (!L->valid) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": the list is no longer valid (" + L->why + ")");
   if (int e = use_device(ctx)) return e;
   const ListVersion& v = *L->cur;
-  const uint32_t n_transparent = depth_only ? 0u : v.n_transparent;
-  const size_t n_objects = (size_t)v.n_opaque + n_transparent;
-  if (n_objects > 0 && n_objects <= LIST_FUSED_MAX && ctx->device_flatten != 2) {
-    // the device copy in draw order, culled and turned into records view by view by one workgroup (list_views_kernel)
-    if (int e = upload_tex_table(ctx, nullptr)) return e;
-    SvrContext::LoggedOp in;
+  const uint32_t n_transparent = rq.depth_only ? 0u : v.n_transparent;
+  if (v.n_opaque + (size_t)n_transparent > 0) {
     in.input = SvrContext::PassInput::List;
     in.list = L->cur;
     in.n_opaque_obj = v.n_opaque;
     in.n_transparent_obj = n_transparent;
-    in.viewprojs.resize((size_t)n_views * 16);
-    for (uint32_t k = 0; k < n_views; k++) std::memcpy(&in.viewprojs[(size_t)k * 16], scenes[k].viewproj, 64);
-    const uint64_t tris_max = depth_only ? v.tris_max_opaque : v.tris_max;
-    const size_t chunks_max = depth_only ? v.chunks_max_opaque : v.chunks_max;
-    return finish_draw(ctx, SvrStats{}, out_stats,
-                       enqueue_pass(ctx, &scenes[0], std::move(in), tris_max * n_views, chunks_max * n_views, true, &mv, depth_only), &t0);
+  }
+  rq.n_tris = rq.depth_only ? v.tris_max_opaque : v.tris_max;
+  rq.n_chunks = rq.depth_only ? v.chunks_max_opaque : v.chunks_max;
+  if (views) views->list = L;
+  return SVR_OK;
+}
+
+// Per pass the host checks the handle and the mesh epoch, and enqueues the pass of svr_draw_geometry's device
+// flatten with the list's current version (enqueue_pass): no per-object loop.
+// svr_draw_list and svr_draw_list_depth
+static int draw_list(SvrContext* ctx, SvrDrawList list, PassRequest rq, SvrStats* out_stats) {
+  if (!ctx || !rq.scene) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
+  auto t0 = std::chrono::steady_clock::now();
+  SvrContext::LoggedOp in;  // no objects: svr_draw_geometry's host path, a pass of no draws
+  if (int e = list_pass(ctx, list, rq, nullptr, in)) return e;
+  if (owns_nothing(ctx, out_stats, rq)) return SVR_OK;
+  if (int e = upload_tex_table(ctx, nullptr)) return e;
+  if ((size_t)in.n_opaque_obj + in.n_transparent_obj > LIST_FUSED_MAX && (ctx->meshes.size() >= (1u << 20) || ctx->materials.size() >= (1u << 20)))
+    return fail(SVR_ERR_UNSUPPORTED, std::string(rq.who) + ": lists over 4096 objects need fewer than 2^20 meshes and materials");
+  return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, rq, std::move(in)), &t0);
+}
+
+int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
+  return draw_list(ctx, list, geometry_request("svr_draw_list", scene, false), out_stats);
+}
+
+// svr_draw_list_views and svr_draw_list_depth_views
+static int draw_list_views(SvrContext* ctx, SvrDrawList list, PassRequest rq, const ViewArgs& va, SvrStats* out_stats) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
+  auto t0 = std::chrono::steady_clock::now();
+  ListViews views{va, MultiView{}, nullptr};
+  SvrContext::LoggedOp in;
+  if (int e = list_pass(ctx, list, rq, &views, in)) return e;
+  const DrawListRes* L = views.list;
+  if (int e = upload_tex_table(ctx, nullptr)) return e;
+  if (in.input == SvrContext::PassInput::List && (size_t)in.n_opaque_obj + in.n_transparent_obj <= LIST_FUSED_MAX && ctx->device_flatten != 2) {
+    // the device copy in draw order, culled and turned into records view by view by one workgroup (list_views_kernel)
+    in.viewprojs.resize((size_t)va.n_views * 16);
+    for (uint32_t k = 0; k < va.n_views; k++) std::memcpy(&in.viewprojs[(size_t)k * 16], va.scenes[k].viewproj, 64);
+    rq.n_tris *= va.n_views;
+    rq.n_chunks *= va.n_views;
+    return finish_draw(ctx, SvrStats{}, out_stats, enqueue_pass(ctx, rq, std::move(in)), &t0);
   }
   // larger lists, or SVR_OPT_DEVICE_FLATTEN = 2: the host path over the list's submission-order copy
-  return draw_views(ctx, mv, scenes, L->objs.data(), L->n_opaque, L->objs.data() + L->n_opaque, n_transparent, out_stats, t0, depth_only);
+  return draw_objects(ctx, rq, va.scenes, L->objs.data(), L->n_opaque, L->objs.data() + L->n_opaque, in.n_transparent_obj, out_stats, t0);
 }
 
 int svr_draw_list_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
                         SvrStats* out_stats) {
-  return draw_list_views(ctx, list, n_views, scenes, targets, out_stats, false, "svr_draw_list_views");
+  return draw_list_views(ctx, list, geometry_request("svr_draw_list_views", nullptr, false), {n_views, scenes, targets}, out_stats);
 }
 
 // ---------------------------------------------------------------- depth-only passes (include/svr_depth.h)
 int svr_draw_depth(SvrContext* ctx, const SvrSceneData* scene, const SvrRenderObject* opaque, size_t n_opaque, SvrStats* out_stats) {
-  return draw_geometry(ctx, scene, opaque, n_opaque, nullptr, 0, out_stats, true, "svr_draw_depth");
+  return draw_geometry(ctx, geometry_request("svr_draw_depth", scene, true), opaque, n_opaque, nullptr, 0, out_stats);
 }
 
 int svr_draw_list_depth(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, SvrStats* out_stats) {
-  return draw_list(ctx, list, scene, out_stats, true, "svr_draw_list_depth");
+  return draw_list(ctx, list, geometry_request("svr_draw_list_depth", scene, true), out_stats);
 }
 
 int svr_draw_depth_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* scenes, const SvrViewTargets* targets,
                          const SvrRenderObject* opaque, size_t n_opaque, SvrStats* out_stats) {
-  if (!ctx || (!opaque && n_opaque)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_draw_depth_views: null argument");
-  auto t0 = std::chrono::steady_clock::now();
-  MultiView mv;
-  if (int e = check_views(ctx, n_views, scenes, targets, "svr_draw_depth_views", &mv, true)) return e;
-  for (size_t i = 0; i < n_opaque; i++)
-    if (int e = validate_object(ctx, opaque[i], false, "svr_draw_depth_views")) return e;
-  if (int e = use_device(ctx)) return e;
-  return draw_views(ctx, mv, scenes, opaque, n_opaque, nullptr, 0, out_stats, t0, true);
+  return draw_geometry_views(ctx, geometry_request("svr_draw_depth_views", nullptr, true), {n_views, scenes, targets}, opaque, n_opaque, nullptr, 0,
+                             out_stats);
 }
 
 int svr_draw_list_depth_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes,
                               const SvrViewTargets* targets, SvrStats* out_stats) {
-  return draw_list_views(ctx, list, n_views, scenes, targets, out_stats, true, "svr_draw_list_depth_views");
+  return draw_list_views(ctx, list, geometry_request("svr_draw_list_depth_views", nullptr, true), {n_views, scenes, targets}, out_stats);
 }
 
 // ---------------------------------------------------------------- occlusion culling (include/svr_occlusion.h)
@@ -2282,11 +2264,11 @@ int svr_create_depth_pyramid(SvrContext* ctx, SvrDepthPyramid* out) {
   auto m = std::make_shared<PyramidMem>();
   m->levels = pyramid_levels(ctx->W, ctx->H);
   m->words = pyramid_offsets(ctx->W, ctx->H, m->off);
-  HIPCHK(hipMalloc((void**)&m->p, m->words * sizeof(uint32_t)));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_built, hipEventDisableTiming));
+  DEV_ALLOC(m->p, m->words * sizeof(uint32_t));
+  HIPCHK_AS(make_event(m->ev_built, hipEventDisableTiming), "hipEventCreateWithFlags(&m->ev_built, hipEventDisableTiming)");
   // all texels 0.0 until the first build: a pass culls nothing against it
-  HIPCHK(hipMemsetAsync(m->p, 0, m->words * sizeof(uint32_t), ctx->stream));
-  HIPCHK(hipEventRecord(m->ev_built, ctx->stream));
+  HIPCHK(hipMemsetAsync(m->p.get(), 0, m->words * sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipEventRecord(m->ev_built.get(), ctx->stream));
   ctx->pyramids.push_back(m);
   *out = (SvrDepthPyramid)ctx->pyramids.size();
   return SVR_OK;
@@ -2333,7 +2315,7 @@ int svr_read_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr, uint32_t level,
   const size_t need = (size_t)(((ctx->W - 1u) >> level) + 1u) * (((ctx->H - 1u) >> level) + 1u) * sizeof(uint32_t);
   if (!dst || bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: destination too small");
   if (int e = svr_sync(ctx)) return e;
-  HIPCHK(hipMemcpy(dst, m->p + m->off[level], need, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(dst, m->p.get() + m->off[level], need, hipMemcpyDeviceToHost));
   return SVR_OK;
 }
 
@@ -2374,22 +2356,19 @@ int svr_enable_ids(SvrContext* ctx, int on) {
     if (!ctx->ids_own) {
       const size_t bytes = (size_t)ctx->W * ctx->H * sizeof(uint2);
       if (int e = finish_pending(ctx)) return e;  // the zeroing below runs outside the stream
-      hipError_t r = hipMalloc((void**)&ctx->ids_own, bytes);
-      if (r != hipSuccess) {
-        ctx->ids_own = nullptr;
+      hipError_t r = dev_alloc(ctx->ids_own, bytes);
+      if (r != hipSuccess)
         return fail(r == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE, std::string("svr_enable_ids: ") + hipGetErrorString(r));
-      }
-      HIPCHK(hipMemset(ctx->ids_own, 0, bytes));
+      HIPCHK(hipMemset(ctx->ids_own.get(), 0, bytes));
     }
-    if (!ctx->ids_bound) ctx->ids = ctx->ids_own;
+    if (!ctx->ids_bound) ctx->ids = ctx->ids_own.get();
     return SVR_OK;
   }
   if (!ctx->ids_own) return SVR_OK;
   if (int e = finish_pending(ctx)) return e;  // passes in flight (and their replays) may still write the plane
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->ids == ctx->ids_own) ctx->ids = nullptr;
-  (void)hipFree(ctx->ids_own);
-  ctx->ids_own = nullptr;
+  if (ctx->ids == ctx->ids_own.get()) ctx->ids = nullptr;
+  ctx->ids_own.reset();
   return SVR_OK;
 }
 
@@ -2400,7 +2379,7 @@ int svr_bind_id_target(SvrContext* ctx, void* ids_dev) {
   // no fence: passes already enqueued carry their own ID target (also for a replay), as with svr_bind_targets
   if (int e = poll_pending(ctx)) return e;
   ctx->ids_bound = ids_dev != nullptr;
-  ctx->ids = ids_dev ? (uint2*)ids_dev : ctx->ids_own;
+  ctx->ids = ids_dev ? (uint2*)ids_dev : ctx->ids_own.get();
   return SVR_OK;
 }
 
@@ -2455,26 +2434,21 @@ int svr_enable_attributes(SvrContext* ctx, uint32_t mask) {
   if (int e = finish_pending(ctx)) return e;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   // all or nothing: the planes the mask adds are allocated and zeroed first, and a failure frees them again
-  void* fresh[4] = {};
+  DevPtr<void> fresh[4];
   for (int i = 0; i < 4; i++) {
     if (!((mask >> i) & 1u) || ctx->attr_own[i]) continue;
-    hipError_t r = hipMalloc(&fresh[i], attr_bytes(ctx, i));
-    if (r != hipSuccess) fresh[i] = nullptr;
-    if (r == hipSuccess) r = hipMemset(fresh[i], 0, attr_bytes(ctx, i));
-    if (r != hipSuccess) {
-      for (void* p : fresh)
-        if (p) (void)hipFree(p);
+    hipError_t r = dev_alloc(fresh[i], attr_bytes(ctx, i));
+    if (r == hipSuccess) r = hipMemset(fresh[i].get(), 0, attr_bytes(ctx, i));
+    if (r != hipSuccess)
       return fail(r == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE, std::string("svr_enable_attributes: ") + hipGetErrorString(r));
-    }
   }
   for (int i = 0; i < 4; i++) {
     if ((mask >> i) & 1u) {
-      if (fresh[i]) ctx->attr_own[i] = fresh[i];
-      if (!ctx->attr_bound[i]) ctx->attr[i] = ctx->attr_own[i];
+      if (fresh[i]) ctx->attr_own[i] = std::move(fresh[i]);
+      if (!ctx->attr_bound[i]) ctx->attr[i] = ctx->attr_own[i].get();
     } else if (ctx->attr_own[i]) {
-      if (ctx->attr[i] == ctx->attr_own[i]) ctx->attr[i] = nullptr;
-      (void)hipFree(ctx->attr_own[i]);
-      ctx->attr_own[i] = nullptr;
+      if (ctx->attr[i] == ctx->attr_own[i].get()) ctx->attr[i] = nullptr;
+      ctx->attr_own[i].reset();
     }
   }
   return SVR_OK;
@@ -2489,7 +2463,7 @@ int svr_bind_attribute_target(SvrContext* ctx, int attr, void* dev) {
   // no fence: passes already enqueued carry their own planes (also for a replay), as with svr_bind_id_target
   if (int e = poll_pending(ctx)) return e;
   ctx->attr_bound[i] = dev != nullptr;
-  ctx->attr[i] = dev ? dev : ctx->attr_own[i];
+  ctx->attr[i] = dev ? dev : ctx->attr_own[i].get();
   return SVR_OK;
 }
 
@@ -2526,8 +2500,8 @@ int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: needs the SVR_ATTR_NORMAL and SVR_ATTR_ALBEDO planes (svr_enable_attributes / svr_bind_attribute_target)");
   if (int e = use_device(ctx)) return e;
   if (int e = poll_pending(ctx)) return e;
-  if (!ctx->d_lights) HIPCHK(hipMalloc((void**)&ctx->d_lights, SVR_MAX_LIGHTS * sizeof(SvrPointLight)));
-  if (!ctx->d_light_tiles) HIPCHK(hipMalloc((void**)&ctx->d_light_tiles, (size_t)((ctx->W + TILE - 1) / TILE) * ((ctx->H + TILE - 1) / TILE) * sizeof(uint32_t)));
+  if (!ctx->d_lights) DEV_ALLOC(ctx->d_lights, SVR_MAX_LIGHTS * sizeof(SvrPointLight));
+  if (!ctx->d_light_tiles) DEV_ALLOC(ctx->d_light_tiles, (size_t)((ctx->W + TILE - 1) / TILE) * ((ctx->H + TILE - 1) / TILE) * sizeof(uint32_t));
   if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
   SvrContext::LoggedOp* op = nullptr;
   if (int e = log_fill(ctx, SvrContext::OpKind::Light, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
@@ -2553,7 +2527,7 @@ int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
   std::memcpy(L.ambient_color, pass->ambient_color, sizeof(L.ambient_color));
   std::memcpy(L.sunlight_direction, pass->sunlight_direction, sizeof(L.sunlight_direction));
   std::memcpy(L.sunlight_color, pass->sunlight_color, sizeof(L.sunlight_color));
-  L.lights = ctx->d_lights;
+  L.lights = ctx->d_lights.get();
   L.n_lights = pass->n_lights;
   L.shadow_depth = pass->shadow_depth;
   if (pass->shadow_depth) {
@@ -2564,8 +2538,8 @@ int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
     std::memcpy(L.shadow_viewproj, pass->shadow_viewproj, sizeof(L.shadow_viewproj));
     L.shadow_bias = pass->shadow_bias;
   }
-  L.tile_counts = ctx->d_light_tiles;
-  L.poison = ctx->d_poison;
+  L.tile_counts = ctx->d_light_tiles.get();
+  L.poison = ctx->d_poison.get();
   ctx->light_tiles_n = L.tiles_x * op->light_tiles_y;
   return submit_fill(ctx, *op);
 }
@@ -2577,7 +2551,7 @@ int svr_debug_read_light_tiles(SvrContext* ctx, uint32_t* counts, size_t capacit
   if (!counts) return SVR_OK;
   if (!ctx->d_light_tiles) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: no lighting pass yet");
   if (capacity < ctx->light_tiles_n) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: buffer too small");
-  if (ctx->light_tiles_n) HIPCHK(hipMemcpy(counts, ctx->d_light_tiles, (size_t)ctx->light_tiles_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (ctx->light_tiles_n) HIPCHK(hipMemcpy(counts, ctx->d_light_tiles.get(), (size_t)ctx->light_tiles_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return SVR_OK;
 }
 

@@ -667,3 +667,75 @@ def test_bound_targets_and_stream(hip, oracle):
     assert np.array_equal(color.cpu().numpy().view(np.uint16), ref["color"])
     assert np.array_equal(depth.cpu().numpy(), ref["depth"])
     r.close()
+
+
+def teardown_drift(lib, iterations=20):
+    """Create, use and destroy a context `iterations` times; every kind of resource and pass once per iteration, not all
+    fenced.  -> (free before the first, footprint F of one live iteration, free after iteration 2, free after the last)"""
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda", 0)
+    W, H = 64, 48
+    color2 = torch.zeros((2, H, W, 4), dtype=torch.float16, device=dev)  # the callers' tensors outlive every context
+    depth2 = torch.zeros((2, H, W), dtype=torch.float32, device=dev)
+    ids2 = torch.zeros((2, H, W, 2), dtype=torch.int32, device=dev)
+    cube = S.cube_mesh()
+    texels = np.random.default_rng(5).integers(0, 256, (8, 8, 4), dtype=np.uint8)
+    scenes = [S.scene_data_struct((0.0, 0.3, 2.5), -0.1, yaw, W, H) for yaw in (0.0, 0.25)]
+    lights = np.zeros(2, dtype=A.POINT_LIGHT_DTYPE)
+    lights["position"], lights["radius"], lights["color"], lights["intensity"] = [(1, 1, 1), (-1, 0.5, 1)], 3.0, (1, 0.8, 0.6), 2.0
+
+    def free():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(dev)[0]
+
+    marks = {"before": free()}
+    for it in range(1, iterations + 1):
+        r = lib.create(W, H)
+        mesh = r.upload_mesh(cube.indices, cube.vertices)
+        img = r.create_image(texels, mipmapped=True)
+        smp = r.create_sampler(**S.SAMPLER_LINEAR)
+        mo = r.write_material(A.PASS_MAIN_COLOR, (1, 1, 1, 1), img, smp)
+        mt = r.write_material(A.PASS_TRANSPARENT, (0.5, 0.5, 0.5, 0.5), img, smp)
+        n = cube.indices.size
+        opaque = SC.objs([SC.render_object(mesh, mo, 0, n, transform=GL.translate(GL.identity(), (0.2 * (k % 8) - 0.7, 0.3 * (k // 8) - 0.4, -0.3 * (k % 8))),
+                                           extents=(0.5, 0.5, 0.5)) for k in range(32)])
+        transparent = SC.objs([SC.render_object(mesh, mt, 0, n, transform=GL.translate(GL.identity(), (0.4, 0.2, 0.8)), extents=(0.5, 0.5, 0.5))])
+        lst = r.create_draw_list(opaque, transparent)
+        pyr = r.create_depth_pyramid()
+        r.enable_ids(True)
+        r.enable_attributes(A.ATTR_ALL)
+        r.set_option(A.OPT_QUEUE_CAPS, 64)  # the pass below overflows its queues: get_stats retires it, and so replays it
+        r.clear_color((1, 1, 1, 1))
+        r.draw_geometry(scenes[0], opaque, transparent)
+        assert r.get_stats().replayed_passes >= 1
+        r.set_option(A.OPT_QUEUE_CAPS, 0)  # the capacities of every other context; nothing below is fenced
+        r.clear_color((1, 1, 1, 1))
+        r.draw_geometry(scenes[0], opaque, transparent)  # host records
+        r.set_option(A.OPT_DEVICE_FLATTEN, 1)
+        r.draw_geometry(scenes[0], opaque, transparent)  # device flatten
+        r.set_option(A.OPT_DEVICE_FLATTEN, 0)
+        r.draw_list(scenes[0], lst)
+        r.draw_list_views(scenes, lst, color2.data_ptr(), depth2.data_ptr(), ids_ptr=ids2.data_ptr(), clear_rgba=(0, 0, 0, 1))
+        r.draw_depth(scenes[0], opaque)
+        r.build_depth_pyramid(pyr)
+        r.set_occlusion_pyramid(pyr)
+        r.draw_geometry(scenes[0], opaque, transparent)  # culled against the pyramid
+        r.set_occlusion_pyramid(0)
+        r.light_pass(np.linalg.inv(np.asarray(scenes[0].viewproj, np.float64).reshape(4, 4)), (0.1,) * 4, (0, 1, 0.5, 1), (1,) * 4, lights=lights)
+        if it == 1:
+            marks["live"] = free()  # (waits for the device: the only iteration whose passes are done before svr_destroy)
+        r.close()  # svr_destroy, with passes in flight
+        if it == 2:
+            marks["after2"] = free()
+    marks["after_last"] = free()
+    return marks["before"], marks["before"] - marks["live"], marks["after2"], marks["after_last"]
+
+
+def test_destroy_gives_back_what_a_context_took(hip):
+    """svr_destroy frees everything a context allocated: 20 contexts, each with every kind of resource and pass, leave the
+    device's free memory where two of them left it.  A context that leaked would lose about 18 footprints; one footprint
+    of slack is the runtime's own (allocation granules, its caches)."""
+    before, footprint, after2, after_last = teardown_drift(hip)
+    print(f"free before {before}, footprint {footprint}, after 2 iterations {after2}, after 20 {after_last}, drift {after2 - after_last}")
+    assert footprint > 0
+    assert after2 - after_last < footprint
