@@ -44,9 +44,12 @@
  * Out of scope
  *   - Multiview layers: the pass lights the context's own targets only.
  *   - Exchange in the sharded frame (svr_dist.h): a rank lights its own rows only; nothing is exchanged.
- *   - Transparent objects over deferred lighting: the pass replaces what was blended over an opaque winner.
+ *   - Transparent objects in the same pass as the G-buffer: the lighting pass replaces what was blended over an opaque
+ *     winner.  Draw them behind it under SVR_DEPTH_LOAD instead (include/svr_load.h): they are tested against the
+ *     opaque depth and blended over the lit colour, and the planes survive the pass.
  *   - PCF or otherwise filtered shadows: one nearest texel per pixel.
- *   - The C++ harness (host/) does not call it.
+ *   - The C++ harness (host/) calls it with the scene's sun and ambient only (svr_demo --deferred 1): no point lights,
+ *     no shadow map.
  *
  * HIP library only: the CPU oracle has no lighting pass.
  */

@@ -106,6 +106,9 @@ OCCLUSION_SYMBOLS = ["svr_create_depth_pyramid", "svr_destroy_depth_pyramid", "s
 # include/svr_lighting.h: the deferred lighting pass, HIP library only
 LIGHTING_SYMBOLS = ["svr_light_pass", "svr_debug_read_light_tiles"]
 MAX_LIGHTS = 4096
+# include/svr_load.h: the depth loadOp of geometry passes, HIP library only
+LOAD_SYMBOLS = ["svr_set_depth_load_op", "svr_get_depth_load_op"]
+DEPTH_CLEAR, DEPTH_LOAD = 0, 1
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -239,6 +242,10 @@ class SvrLib:
         if self.has_lighting:
             L.svr_light_pass.argtypes = [P, C.POINTER(SvrLightPass)]
             L.svr_debug_read_light_tiles.argtypes = [P, P, C.c_size_t, C.POINTER(C.c_uint32)]
+        self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
+        if self.has_depth_load:
+            L.svr_set_depth_load_op.argtypes = [P, C.c_int]
+            L.svr_get_depth_load_op.argtypes = [P, C.POINTER(C.c_int)]
 
     @property
     def backend(self):
@@ -755,6 +762,23 @@ class Renderer:
         if n.value:
             self.lib.check(L.svr_debug_read_light_tiles(self.h, out.ctypes.data, out.size, C.byref(n)))
         return out
+
+    # ---- the depth loadOp (include/svr_load.h)
+    def _need_depth_load(self):
+        if not getattr(self.lib, "has_depth_load", False):
+            raise SvrError(-5, f"{self.lib.backend} has no depth loadOp (include/svr_load.h)")
+
+    def set_depth_load_op(self, op):
+        """DEPTH_CLEAR (the default) or DEPTH_LOAD: later draw_geometry / draw_list passes start from the depth target as it
+        stands, leave the ID target and the attribute planes alone, and write max(loaded, drawn) depth"""
+        self._need_depth_load()
+        self.lib.check(self.lib.lib.svr_set_depth_load_op(self.h, int(op)))
+
+    def get_depth_load_op(self):
+        self._need_depth_load()
+        op = C.c_int()
+        self.lib.check(self.lib.lib.svr_get_depth_load_op(self.h, C.byref(op)))
+        return op.value
 
 
 class DrawList:

@@ -1241,7 +1241,12 @@ __device__ __forceinline__ void tile_epilogue(const FrameParams& P, const bool s
 // the visibility tile and a quarter's (or a filter window's) list of LCAP entries, nothing of phases B to D.
 // ATTR: an attribute pass (include/svr_attributes.h): phase B also stores what shade_pixel computed for the winners into
 // the planes of P.attr that are bound; the ID target (IDS is set in these instances) is then a run-time matter, P.ids.
-template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false>
+// LOAD: a pass under SVR_DEPTH_LOAD (include/svr_load.h): the visibility tile starts from the depth target's own words
+// instead of 0 — a loaded pixel enters as (depth bits << 32 | key 0), below every fragment of its depth and above every
+// farther one, so the maximum over (depth, key) IS GREATER_OR_EQUAL against the loaded depth — and a tile without an opaque
+// bin stores no depth.  The loaded word is only ever compared and stored back: it never forms an address.
+template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false,
+          bool LOAD = false>
 __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, const uint4 i1, uint4* s_cov, uint32_t* s_idx, unsigned char* s_c,
                                           const uint32_t wv, const bool hiz_on, const uint32_t wg_start = 0) {
   typedef Codec<FMT> CD;
@@ -1289,6 +1294,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
   // the whole tile lies inside the scissor (every pixel of it is this workgroup's to write): wave-uniform
   const bool inside = !QUARTER && tx0 + TILE <= x_end && ty0 + TILE <= y_end;
   const bool aligned = ((P.W | P.sx) & 3u) == 0u;
+  static_assert(!LOAD || (!MV && !DO && !IDS && !ATTR), "depth LOAD: single-view colour passes, the plain instances");
 
   bool pix_ok[4];
   uint32_t recs[4];
@@ -1310,7 +1316,24 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 
   // ---- phase A: opaque visibility
   if (n_op) {
-    for (uint32_t i = threadIdx.x; i < TILE * TILE; i += 256u) s_depth[i] = 0ull;  // ordered by scan_columns' first barrier
+    if constexpr (LOAD) {  // the tile's own depth words: whole rows where the write-back stores whole rows, else pixel by pixel
+      if (inside && aligned) {
+        const uint32_t row = threadIdx.x >> 3, c = (threadIdx.x & 7u) * 4u;
+        const uint4 z = *reinterpret_cast<const uint4*>(depth + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c));
+        uint4* dst = reinterpret_cast<uint4*>(s_depth + row * TILE + c);
+        dst[0] = make_uint4(0u, z.x, 0u, z.y);
+        dst[1] = make_uint4(0u, z.z, 0u, z.w);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {  // pixels outside the scissor or the quarter's rows enter as 0: they are never written back
+          uint32_t z = 0u;
+          if (pix_ok[k]) z = f2u(depth[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)]);
+          s_depth[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] = (unsigned long long)z << 32;
+        }
+      }
+    } else {
+      for (uint32_t i = threadIdx.x; i < TILE * TILE; i += 256u) s_depth[i] = 0ull;  // ordered by scan_columns' first barrier
+    }
     const bool hiz_filter = hiz_on && n_op > HIZ_FILTER_MIN;
     if ((QUARTER && n_op > 2u * BATCH) || hiz_filter) {
       // A quarter of an opaque-heavy tile: most of the bin's triangles do not reach its 8 rows, and staging
@@ -1419,6 +1442,44 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
   // The depth target is final here (transparent fragments test but do not write, src/vk_engine.cpp:1673-1674):
   // it leaves now, straight from the visibility tile, as whole rows where the tile lies inside the scissor (16
   // bytes per lane, full 128-byte lines), and phase C's copy of the opaque depth is taken on the way.
+  // LOAD: the visibility tile holds max(loaded, drawn) and goes out the same way; a tile without an opaque bin stores
+  // nothing and, where it has transparent triangles, takes phase C's copy from memory; one with neither bin does nothing
+  // to depth.  (A branch of its own: the other instances' code is what it was.)
+  if constexpr (LOAD) {
+    if (n_op || n_tr) {
+      if (inside && aligned) {
+        const uint32_t tid = tid_of(wv), row = tid >> 3, c = (tid & 7u) * 4u;
+        float* const at = depth + (size_t)(ty0 + (int)row) * P.W + (size_t)(tx0 + (int)c);
+        uint4 z;
+        if (n_op) {
+          const uint4* src = reinterpret_cast<const uint4*>(s_depth + row * TILE + c);
+          uint4 lo = src[0], hi = src[1];
+          z = make_uint4(lo.y, lo.w, hi.y, hi.w);
+          store_row16(at, z);
+        } else {
+          z = *reinterpret_cast<const uint4*>(at);
+        }
+        if (n_tr) *reinterpret_cast<uint4*>(s_z + row * TILE + c) = z;
+      } else {
+        int rx, ry;
+        uint32_t li;
+        lane_pixel(wv, rx, ry, li);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const uint32_t w = li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256);
+          float* const at = depth + (size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8);
+          uint32_t z = 0u;  // (pixels outside the scissor or the quarter's rows: no fragment reaches them)
+          if (n_op) {
+            z = (uint32_t)(s_depth[w] >> 32);
+            if (pix_ok[k]) *at = u2f(z);
+          } else if (pix_ok[k]) {
+            z = f2u(*at);
+          }
+          if (n_tr) s_z[w] = z;
+        }
+      }
+    }
+  } else
   if (inside && aligned) {
     const uint32_t tid = tid_of(wv), row = tid >> 3, c = (tid & 7u) * 4u;
     uint4 z = make_uint4(0u, 0u, 0u, 0u);  // depth CLEAR 0.0
@@ -1635,7 +1696,8 @@ static_assert(DEPTH_LIST_CAP >= BATCH, "a depth-only list window holds a batch")
 // IDS: the pass writes an ID target (FrameParams::ids): tile_ids_kernel below; tile_kernel is the kernel as it was
 // DO: a depth-only pass (tile_depth_kernel): s_c is the visibility tile and an LCAP-entry list only
 // ATTR: an attribute pass (tile_attr_kernel)
-template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false>
+// LOAD: a pass under SVR_DEPTH_LOAD (tile_load_kernel)
+template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false, bool LOAD = false>
 __device__ __forceinline__ void tile_main(const FrameParams& P) {
   constexpr uint32_t SC_BYTES = DO ? LDS_Z_OFF + LCAP * 4 : PHASE_C_BYTES;
   __shared__ uint4 s_cov[BATCH * 8];
@@ -1702,12 +1764,12 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   } else if (SPLIT) {
     if (blockIdx.x < SPLIT_EXTRA) {  // the quarters of split tiles, as many as fill_kernel made
       if (blockIdx.x >= 4u * min(n_split, SPLIT_MAX)) return;
-      tile_body<FMT, INSTR, true, true, IDS, MV, DO, LCAP, ATTR>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, true, true, IDS, MV, DO, LCAP, ATTR, LOAD>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     } else {
-      tile_body<FMT, INSTR, false, true, IDS, MV, DO, LCAP, ATTR>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<FMT, INSTR, false, true, IDS, MV, DO, LCAP, ATTR, LOAD>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     }
   } else {
-    tile_body<FMT, INSTR, false, false, IDS, MV, DO, LCAP, ATTR>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+    tile_body<FMT, INSTR, false, false, IDS, MV, DO, LCAP, ATTR, LOAD>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
   }
   // ... and every workgroup's end, one of 64 words each: plain stores, the last one into a word stays (an atomic maximum on
   // pinned host memory is not an operation the host link carries: it would become a compare-and-swap loop of round trips
@@ -1740,6 +1802,12 @@ __global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_ids_kernel(FrameP
 template <int FMT, bool INSTR, bool SPLIT>
 __global__ __launch_bounds__(256, SVR_ATTR_WAVES) void tile_attr_kernel(FrameParams P) {
   tile_main<FMT, INSTR, SPLIT, true, false, false, QUARTER_LIST_CAP, true>(P);
+}
+// passes under SVR_DEPTH_LOAD (include/svr_load.h): the plain colour instance over the depth the target holds; they write
+// no ID target and no attribute plane, so there is one per colour format whatever is bound
+template <int FMT, bool INSTR, bool SPLIT>
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_load_kernel(FrameParams P) {
+  tile_main<FMT, INSTR, SPLIT, false, false, false, QUARTER_LIST_CAP, false, true>(P);
 }
 // depth-only passes (include/svr_depth.h): one instance for both colour formats (the colour target is not touched), IDS and
 // MV as above
@@ -1805,11 +1873,13 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
     if (report) hipExtLaunchKernelGGL(report_kernel, dim3(1), dim3(64), 0, s, nullptr, done, 0, P);
     return;
   }
-  // (enqueue_pass binds attribute planes to single-view shading passes only)
+  // (enqueue_pass binds attribute planes to single-view shading passes only, and neither planes nor an ID target to a
+  // pass under SVR_DEPTH_LOAD: P.depth_load, include/svr_load.h)
   const bool attr = P.attr[0] || P.attr[1] || P.attr[2] || P.attr[3];
 #define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT)                                                                                          \
   do {                                                                                                                               \
-    if (attr) hipExtLaunchKernelGGL((tile_attr_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);              \
+    if (P.depth_load) hipExtLaunchKernelGGL((tile_load_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);     \
+    else if (attr) hipExtLaunchKernelGGL((tile_attr_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);         \
     else if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P); \
     else if (P.layer_rows) hipExtLaunchKernelGGL((tile_mv_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);  \
     else if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);      \

@@ -29,6 +29,7 @@
 #include "../../include/svr_attributes.h"
 #include "../../include/svr_ids.h"
 #include "../../include/svr_lighting.h"
+#include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
 #include "svr_cull.h"
@@ -215,6 +216,7 @@ struct SvrContext {
   bool attr_bound[4] = {};   // ... it is the caller's
   uint32_t sx = 0, sy = 0, sw = 0, sh = 0;
   uint32_t rstride = 1, roff = 0;      // svr_set_row_interleave
+  int depth_load_op = SVR_DEPTH_CLEAR;  // svr_set_depth_load_op (include/svr_load.h)
   uint32_t* present_status = nullptr;  // svr_set_present_status
 
   std::vector<MeshRes> meshes;
@@ -267,9 +269,10 @@ struct SvrContext {
     PassInput input = PassInput::Draws;
     // what the pass is, as enqueue_pass took it from its PassRequest: the one place submit_pass, retire_pass and the
     // replay read it from.  depth_only: include/svr_depth.h (the setup and tile kernels' depth instances);
-    // multiview: include/svr_views.h (P.layer_rows is the kernels' copy of it)
+    // multiview: include/svr_views.h (P.layer_rows is the kernels' copy of it); depth_load: include/svr_load.h (P.depth_load
+    // is the tile launch's copy of it)
     struct PassShape {
-      bool depth_only = false, multiview = false;
+      bool depth_only = false, multiview = false, depth_load = false;
     } shape;
     std::vector<DrawDesc> draws;  // Draws: records built on the host
     std::vector<SvrRenderObject> objects;  // Objects: the caller's (opaque, then transparent), flattened on the device
@@ -974,6 +977,7 @@ struct PassRequest {
   size_t n_chunks = 0;
   bool ids = false;         // a geometry pass: it writes the ID and attribute targets that there are
   bool depth_only = false;  // include/svr_depth.h: opaque objects only, no colour
+  bool depth_load = false;  // include/svr_load.h: the pass starts from the depth target's contents (take_depth_load_op)
   const MultiView* mv = nullptr;
 };
 PassRequest geometry_request(const char* who, const SvrSceneData* scene, bool depth_only) {
@@ -991,8 +995,22 @@ PassRequest geometry_request(const char* who, const SvrSceneData* scene, bool de
 enum class ClearMode { Take, Flush, Leave };
 ClearMode clear_mode(const PassRequest& rq) { return rq.depth_only ? ClearMode::Leave : (rq.mv ? ClearMode::Flush : ClearMode::Take); }
 
-// the ID target a pass writes, or none; host records carry object numbers exactly when there is one
-uint2* id_target(const SvrContext* ctx, const PassRequest& rq) { return !rq.ids ? nullptr : (rq.mv ? rq.mv->ids : ctx->ids); }
+// The depth loadOp of a geometry call (include/svr_load.h), decided here and nowhere else, as the context holds it when the
+// call is made: single-view colour passes load; multiview and depth-only calls (views: the call is one of the *_views
+// entry points) are refused while LOAD is set, before they change anything; svr_draw_colored_triangle and
+// svr_draw_tex_image never come here and keep clearing.
+int take_depth_load_op(const SvrContext* ctx, PassRequest& rq, bool views) {
+  rq.depth_load = false;
+  if (ctx->depth_load_op != SVR_DEPTH_LOAD) return SVR_OK;
+  if (views || rq.depth_only)
+    return fail(SVR_ERR_UNSUPPORTED, std::string(rq.who) + ": " + (views ? "multiview" : "depth-only") + " passes have no SVR_DEPTH_LOAD form (svr_set_depth_load_op)");
+  rq.depth_load = true;
+  return SVR_OK;
+}
+
+// the ID target a pass writes, or none; host records carry object numbers exactly when there is one (a pass under
+// SVR_DEPTH_LOAD writes neither IDs nor attribute planes: the G-buffer survives it)
+uint2* id_target(const SvrContext* ctx, const PassRequest& rq) { return (!rq.ids || rq.depth_load) ? nullptr : (rq.mv ? rq.mv->ids : ctx->ids); }
 
 // Every parameter of the pass that the request and the context decide, final: the buffers of its set, the log slot and
 // the pyramid are submit_pass's.  A multiview pass has every layer's tile rows, layer-major, and its layers' own clear
@@ -1004,7 +1022,8 @@ int fill_frame_params(SvrContext* ctx, const PassRequest& rq, SvrContext::PassIn
   P.color = rq.depth_only ? nullptr : (mv ? mv->color : ctx->color);
   P.depth = mv ? mv->depth : ctx->depth;
   P.ids = id_target(ctx, rq);
-  if (rq.ids && !mv && !rq.depth_only)  // attribute planes (include/svr_attributes.h): of single-view shading passes
+  P.depth_load = rq.depth_load ? 1u : 0u;
+  if (rq.ids && !mv && !rq.depth_only && !rq.depth_load)  // attribute planes (include/svr_attributes.h): of single-view shading passes
     for (int i = 0; i < 4; i++) P.attr[i] = ctx->attr[i];
   P.W = ctx->W;
   P.H = ctx->H;
@@ -1107,6 +1126,7 @@ int enqueue_pass(SvrContext* ctx, const PassRequest& rq, SvrContext::LoggedOp&& 
     op.timed = ctx->kernel_timing == 1;
     op.shape.depth_only = rq.depth_only;
     op.shape.multiview = rq.mv != nullptr;
+    op.shape.depth_load = rq.depth_load;
     op.P = P;
     if (ctx->occl_bound && !rq.mv) op.pyr = ctx->pyramids[ctx->occl_bound - 1];  // (multiview passes refuse a bound pyramid)
     std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
@@ -1544,6 +1564,20 @@ int svr_set_scissor(SvrContext* ctx, uint32_t x, uint32_t y, uint32_t w, uint32_
   return SVR_OK;
 }
 
+// include/svr_load.h
+int svr_set_depth_load_op(SvrContext* ctx, int op) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  if (op != SVR_DEPTH_CLEAR && op != SVR_DEPTH_LOAD) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_set_depth_load_op: op must be SVR_DEPTH_CLEAR or SVR_DEPTH_LOAD");
+  ctx->depth_load_op = op;
+  return SVR_OK;
+}
+
+int svr_get_depth_load_op(SvrContext* ctx, int* op) {
+  if (!ctx || !op) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_depth_load_op: null argument");
+  *op = ctx->depth_load_op;
+  return SVR_OK;
+}
+
 int svr_set_row_interleave(SvrContext* ctx, uint32_t stride, uint32_t offset) {
   if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
   if (stride == 0 || stride > 64 || offset >= stride) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_set_row_interleave: need 1 <= stride <= 64, offset < stride");
@@ -1654,6 +1688,7 @@ static int draw_geometry(SvrContext* ctx, PassRequest rq, const SvrRenderObject*
                          size_t n_transparent, SvrStats* out_stats) {
   if (!ctx || !rq.scene || (!opaque && n_opaque) || (!transparent && n_transparent))
     return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
+  if (int e = take_depth_load_op(ctx, rq, false)) return e;
   auto t0 = std::chrono::steady_clock::now();
   if (int e = use_device(ctx)) return e;
   for (size_t i = 0; i < n_opaque; i++)
@@ -2131,6 +2166,7 @@ static int check_views(SvrContext* ctx, PassRequest& rq, const ViewArgs& va, Mul
 static int draw_geometry_views(SvrContext* ctx, PassRequest rq, const ViewArgs& va, const SvrRenderObject* opaque, size_t n_opaque,
                                const SvrRenderObject* transparent, size_t n_transparent, SvrStats* out_stats) {
   if (!ctx || (!opaque && n_opaque) || (!transparent && n_transparent)) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
+  if (int e = take_depth_load_op(ctx, rq, true)) return e;
   auto t0 = std::chrono::steady_clock::now();
   MultiView mv;
   if (int e = check_views(ctx, rq, va, &mv)) return e;
@@ -2192,6 +2228,7 @@ static int list_pass(SvrContext* ctx, SvrDrawList list, PassRequest& rq, ListVie
 // svr_draw_list and svr_draw_list_depth
 static int draw_list(SvrContext* ctx, SvrDrawList list, PassRequest rq, SvrStats* out_stats) {
   if (!ctx || !rq.scene) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
+  if (int e = take_depth_load_op(ctx, rq, false)) return e;
   auto t0 = std::chrono::steady_clock::now();
   SvrContext::LoggedOp in;  // no objects: svr_draw_geometry's host path, a pass of no draws
   if (int e = list_pass(ctx, list, rq, nullptr, in)) return e;
@@ -2209,6 +2246,7 @@ int svr_draw_list(SvrContext* ctx, SvrDrawList list, const SvrSceneData* scene, 
 // svr_draw_list_views and svr_draw_list_depth_views
 static int draw_list_views(SvrContext* ctx, SvrDrawList list, PassRequest rq, const ViewArgs& va, SvrStats* out_stats) {
   if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
+  if (int e = take_depth_load_op(ctx, rq, true)) return e;
   auto t0 = std::chrono::steady_clock::now();
   ListViews views{va, MultiView{}, nullptr};
   SvrContext::LoggedOp in;

@@ -213,6 +213,9 @@ struct FrameParams {
   uint32_t tiles_x, tiles_y, n_tiles;
   uint32_t rstride, roff;         // svr_set_row_interleave: of the scissor's 32-row tile rows this pass owns those with
                                   // index % rstride == roff; tiles_y, bins and row costs count the owned rows only
+  uint32_t depth_load;            // 1: a pass under SVR_DEPTH_LOAD (include/svr_load.h): launch_tiles runs the tile_load_kernel
+                                  // instances, which start from the depth target's contents; ids and attr are NULL then
+                                  // (in what was padding in front of `draws`: no other field moves)
   // geometry
   const DrawDesc* draws;
   const WaveChunk* chunks;

@@ -9,6 +9,9 @@
 //       --yaw Y: the camera's yaw in radians (a single-camera run of view k: --yaw <its Y>)
 //       --depth-only 1: every frame's geometry is a depth-only pass (include/svr_depth.h, HIP library only): the dumped
 //           depth is a normal run's, the colour the background's
+//       --deferred 1: every frame is the opaque objects with normal and albedo planes, a lighting pass, then the transparent
+//           objects under SVR_DEPTH_LOAD (include/svr_attributes.h, svr_lighting.h, svr_load.h; HIP library only): the
+//           dumps are a normal run's
 //       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
 //           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
 //           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
@@ -77,7 +80,7 @@ int main(int argc, char** argv) {
   uint32_t w = 160, h = 90;
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
-  bool depth_only = false;
+  bool depth_only = false, deferred = false;
   std::string occlusion = "off";
   float yaw = 0.f;
   bool set_yaw = false;
@@ -101,6 +104,7 @@ int main(int argc, char** argv) {
     else if (a == "--background") background = atoi(argv[i + 1]);
     else if (a == "--retained") retained = atoi(argv[i + 1]);  // 1: draw through a draw list (include/svr_draw_list.h)
     else if (a == "--depth-only") depth_only = atoi(argv[i + 1]) != 0;  // depth-only passes (include/svr_depth.h)
+    else if (a == "--deferred") deferred = atoi(argv[i + 1]) != 0;  // G-buffer pass, lighting pass, transparent objects under LOAD
     else if (a == "--occlusion") occlusion = argv[i + 1];  // off | last | prepass (include/svr_occlusion.h)
     else if (a == "--views") views = (uint32_t)atoi(argv[i + 1]);  // N cameras in one multiview pass (include/svr_views.h)
     else if (a == "--yaw") { yaw = (float)atof(argv[i + 1]); set_yaw = true; }  // the camera's yaw (radians), after the scene's own
@@ -132,7 +136,7 @@ int main(int argc, char** argv) {
   if (lib.empty()) {
     fprintf(stderr, "usage: svr_demo --lib <shared library exporting svr.h> [--width W --height H --frames N --dump prefix]\n"
                     "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n"
-                    "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1]\n"
+                    "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1] [--deferred 1]\n"
                     "                [--occlusion off|last|prepass]\n");
     return 2;
   }
@@ -424,6 +428,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--occlusion: not with --views (multiview passes do not cull)\n");
     return 1;
   }
+  if (deferred && (views || depth_only || retained || eng.occlusion != SvrEngine::Occlusion::Off)) {
+    fprintf(stderr, "--deferred: not with --views, --depth-only, --retained or --occlusion\n");
+    return 1;
+  }
   if (select && !eng.enable_ids()) {
     fprintf(stderr, "--select: %s\n", eng.error.c_str());
     return 1;
@@ -435,7 +443,7 @@ int main(int argc, char** argv) {
       dump(prefix + ".opaque", eng.main_draw_context.opaque_surfaces.data(), eng.main_draw_context.opaque_surfaces.size());
       dump(prefix + ".transparent", eng.main_draw_context.transparent_surfaces.data(), eng.main_draw_context.transparent_surfaces.size());
     }
-    if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : (depth_only ? eng.draw_depth() : eng.draw_geometry()))) {
+    if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : (depth_only ? eng.draw_depth() : (deferred ? eng.draw_deferred() : eng.draw_geometry())))) {
       fprintf(stderr, "draw failed: %s\n", eng.error.c_str());
       return 1;
     }

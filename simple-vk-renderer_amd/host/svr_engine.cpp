@@ -44,6 +44,9 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_destroy_depth_pyramid = reinterpret_cast<decltype(svr_destroy_depth_pyramid)>(dlsym(handle, "svr_destroy_depth_pyramid"));
   svr_build_depth_pyramid = reinterpret_cast<decltype(svr_build_depth_pyramid)>(dlsym(handle, "svr_build_depth_pyramid"));
   svr_set_occlusion_pyramid = reinterpret_cast<decltype(svr_set_occlusion_pyramid)>(dlsym(handle, "svr_set_occlusion_pyramid"));
+  svr_enable_attributes = reinterpret_cast<decltype(svr_enable_attributes)>(dlsym(handle, "svr_enable_attributes"));
+  svr_light_pass = reinterpret_cast<decltype(svr_light_pass)>(dlsym(handle, "svr_light_pass"));
+  svr_set_depth_load_op = reinterpret_cast<decltype(svr_set_depth_load_op)>(dlsym(handle, "svr_set_depth_load_op"));
   return ok;
 }
 void SvrApi::unload() {
@@ -383,6 +386,48 @@ bool SvrEngine::draw_depth() {  // draw_geometry without shading: a shadow or de
   stats.drawcall_count = st.drawcall_count;
   stats.triangle_count = st.triangle_count;
   stats.mesh_draw_time = st.mesh_draw_time;
+  main_draw_context.opaque_surfaces.clear();
+  main_draw_context.transparent_surfaces.clear();
+  drawn_sources.swap(main_draw_context.opaque_sources);
+  main_draw_context.opaque_sources.clear();
+  return true;
+}
+
+bool SvrEngine::draw_deferred() {  // draw_geometry in three steps: G-buffer pass, lighting pass, transparent objects over it
+  if (!api.svr_enable_attributes || !api.svr_light_pass || !api.svr_set_depth_load_op) {
+    error = "--deferred: the library has no attribute targets, lighting pass or depth loadOp (include/svr_attributes.h, svr_lighting.h, svr_load.h)";
+    return false;
+  }
+  if (!gbuffer && api.svr_enable_attributes(ctx, SVR_ATTR_NORMAL | SVR_ATTR_ALBEDO)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  gbuffer = true;
+  const DrawContext& dc = main_draw_context;
+  SvrStats st{}, st_tr{};
+  SvrLightPass lp{};
+  mat4 viewproj;
+  std::memcpy(viewproj.data(), scene_data.viewproj, 64);
+  const mat4 inv = svrm::inverse(viewproj);
+  std::memcpy(lp.inv_viewproj, inv.data(), 64);
+  std::memcpy(lp.ambient_color, scene_data.ambient_color, 16);
+  std::memcpy(lp.sunlight_direction, scene_data.sunlight_direction, 16);
+  std::memcpy(lp.sunlight_color, scene_data.sunlight_color, 16);
+  int rc = api.svr_draw_geometry(ctx, &scene_data, dc.opaque_surfaces.data(), dc.opaque_surfaces.size(), nullptr, 0, &st);
+  if (!rc) rc = api.svr_light_pass(ctx, &lp);
+  if (!rc) rc = api.svr_set_depth_load_op(ctx, SVR_DEPTH_LOAD);
+  if (!rc) {
+    rc = api.svr_draw_geometry(ctx, &scene_data, nullptr, 0, dc.transparent_surfaces.data(), dc.transparent_surfaces.size(), &st_tr);
+    if (rc) error = api.svr_last_error();
+    if (api.svr_set_depth_load_op(ctx, SVR_DEPTH_CLEAR) && !rc) rc = SVR_ERR_DEVICE;
+  }
+  if (rc) {
+    if (error.empty()) error = api.svr_last_error();
+    return false;
+  }
+  stats.drawcall_count = st.drawcall_count + st_tr.drawcall_count;
+  stats.triangle_count = st.triangle_count + st_tr.triangle_count;
+  stats.mesh_draw_time = st.mesh_draw_time + st_tr.mesh_draw_time;
   main_draw_context.opaque_surfaces.clear();
   main_draw_context.transparent_surfaces.clear();
   drawn_sources.swap(main_draw_context.opaque_sources);

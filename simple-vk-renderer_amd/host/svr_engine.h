@@ -19,6 +19,8 @@
 #include "../../include/svr_draw_list.h"
 #include "../../include/svr_ids.h"
 #include "../../include/svr_depth.h"
+#include "../../include/svr_lighting.h"
+#include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
@@ -47,6 +49,8 @@ struct SvrApi {
   // include/svr_occlusion.h: optional (HIP library only), needed by SvrEngine::occlusion
   SVR_FN(svr_create_depth_pyramid) SVR_FN(svr_destroy_depth_pyramid) SVR_FN(svr_build_depth_pyramid)
   SVR_FN(svr_set_occlusion_pyramid)
+  // include/svr_attributes.h, svr_lighting.h and svr_load.h: optional (HIP library only), needed by SvrEngine::draw_deferred
+  SVR_FN(svr_enable_attributes) SVR_FN(svr_light_pass) SVR_FN(svr_set_depth_load_op)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -157,6 +161,12 @@ struct SvrEngine {
   // Depth-only frames (svr_demo --depth-only 1, include/svr_depth.h): the draw context's opaque surfaces (or the draw
   // list's, retained) into the depth target without shading; the colour target keeps the background just drawn.
   bool draw_depth();
+  // Deferred frames (svr_demo --deferred 1): the opaque surfaces with the NORMAL and ALBEDO planes (include/
+  // svr_attributes.h), svr_light_pass with the scene's sun and ambient, no point lights and no shadow map (include/
+  // svr_lighting.h), then the transparent surfaces under SVR_DEPTH_LOAD (include/svr_load.h): tested against the opaque
+  // depth, blended over the lit colour.  The frame is the forward one, bit for bit.
+  bool gbuffer = false;  // the planes are enabled
+  bool draw_deferred();
   // Occlusion culling (svr_demo --occlusion off|last|prepass, include/svr_occlusion.h).  Last: each frame's geometry
   // culls against the pyramid of the previous frame's depth (built behind every frame; before the first it is all 0.0
   // and culls nothing).  Prepass: each frame first draws the opaque objects whose material is in occluder_materials
