@@ -31,6 +31,7 @@
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "svr_launch.h"
 
@@ -1151,6 +1152,7 @@ __device__ __forceinline__ void sort_bin_by_key(const FrameParams& P, unsigned l
 //              128-register line and every change to the fragment stage paid in scratch traffic)
 //   [8K, 12K)  the tile's opaque depth bits for phase C's depth test (phase A of a quarter: its triangle list, to the end)
 //   [12K, 23K) phase C: sort scratch (11 KiB), then per wave its fragment queue | shaded colours (2 KiB each)
+// TileLds below hands out these views; nothing else casts the block.
 constexpr uint32_t LDS_Z_OFF = TILE * TILE * 8;
 constexpr uint32_t LDS_C_OFF = LDS_Z_OFF + TILE * TILE * 4;
 constexpr uint32_t WAVE_C_BYTES = QUEUE_CAP * 8 + 64 * 16;  // queue | shaded colours
@@ -1158,6 +1160,144 @@ constexpr uint32_t WAVE_C_BYTES = QUEUE_CAP * 8 + 64 * 16;  // queue | shaded co
 // The workgroup's LDS — this + the 8 KiB staging buffer + a few words — stays under 32 000 bytes (25 granules of 1280 B):
 // five workgroups per CU.
 constexpr uint32_t PHASE_C_BYTES = LDS_C_OFF + (SORT_CAP * 8 > 4 * WAVE_C_BYTES ? SORT_CAP * 8 : 4 * WAVE_C_BYTES);
+
+#ifndef SVR_TILE_WAVES
+#define SVR_TILE_WAVES 5  // waves per SIMD (= workgroups per CU) the tile kernel is compiled for (A/B builds: tools/build_variant.sh)
+#endif
+#ifndef SVR_DEPTH_WAVES
+#define SVR_DEPTH_WAVES 5  // waves per SIMD (= workgroups per CU) of the depth-only tile kernels (A/B builds: tools/build_variant.sh)
+// (phase A alone needs 90-96 VGPRs: at 6 and more the depth-only instances spill, and 6 measured no faster: DESIGN §5)
+#endif
+// LDS of a depth-only workgroup: s_cov, s_idx, the visibility tile and a list of this many entries fill the workgroup's share
+// of gfx950's 128 granules of 1280 bytes at SVR_DEPTH_WAVES workgroups per CU (8: 928 entries, 6: 2528, 5: 3808)
+constexpr uint32_t depth_list_cap(uint32_t wgs) {
+  return (((128u / wgs) * 1280u - BATCH * 8 * 16 - BATCH * 4 - 64u - LDS_Z_OFF) / 4u) & ~31u;
+}
+constexpr uint32_t DEPTH_LIST_CAP = depth_list_cap(SVR_DEPTH_WAVES) < QUARTER_LIST_CAP ? depth_list_cap(SVR_DEPTH_WAVES) : QUARTER_LIST_CAP;
+static_assert(DEPTH_LIST_CAP >= BATCH, "a depth-only list window holds a batch");
+
+// ------------------------------------------------------------------------------------------------
+// Pass kinds.  What a tile kernel instance does beyond the plain colour pass is named here, once: a kind is a struct of
+// flags, Variant<Kind> adds what follows from them and refuses the combinations that are not built.
+//   IDS   the pass writes an ID target (include/svr_ids.h, FrameParams::ids): {object, primitive} of every winner
+//         leaves with the depth
+//   MV    a multiview pass (include/svr_views.h): the tile's layer is its tile row / P.layer_rows; its pixel rows are
+//         layer-local and its targets start at the layer's base, so rows past the layer's last (a partial last tile row:
+//         the next layer's memory) are outside the scissor like any other
+//   DO    a depth-only pass (include/svr_depth.h): phase A and the depth / ID store, then the workgroup is done.  Its s_c
+//         holds the visibility tile and a quarter's (or a filter window's) list of LCAP entries, nothing of phases B to D.
+//   ATTR  an attribute pass (include/svr_attributes.h): phase B also stores what shade_pixel computed for the winners into
+//         the planes of P.attr that are bound; the ID target (IDS is set in this kind) is then a run-time matter, P.ids.
+//   LOAD  a pass under SVR_DEPTH_LOAD (include/svr_load.h): the visibility tile starts from the depth target's own words
+//         instead of 0 — a loaded pixel enters as (depth bits << 32 | key 0), below every fragment of its depth and above
+//         every farther one, so the maximum over (depth, key) IS GREATER_OR_EQUAL against the loaded depth — and a tile
+//         without an opaque bin stores no depth.  The loaded word is only ever compared and stored back: it never forms
+//         an address.
+struct PlainPass {  // tile_kernel: the kernel as it was before any of the flags
+  static constexpr bool IDS = false, MV = false, DO = false, ATTR = false, LOAD = false;
+};
+struct IdsPass : PlainPass {
+  static constexpr bool IDS = true;
+};
+struct MvPass : PlainPass {
+  static constexpr bool MV = true;
+};
+struct MvIdsPass : PlainPass {
+  static constexpr bool IDS = true, MV = true;
+};
+struct AttrPass : PlainPass {  // one instance whatever planes are bound, and with or without an ID target
+  static constexpr bool IDS = true, ATTR = true;
+};
+struct LoadPass : PlainPass {  // the plain colour instance over the depth the target holds
+  static constexpr bool LOAD = true;
+};
+template <bool IDS_, bool MV_>
+struct DepthPass : PlainPass {  // one instance for both colour formats: the colour target is not touched
+  static constexpr bool IDS = IDS_, MV = MV_, DO = true;
+};
+
+template <class Kind>
+struct Variant : Kind {
+  using Kind::ATTR;
+  using Kind::DO;
+  using Kind::IDS;
+  using Kind::LOAD;
+  using Kind::MV;
+  // entries of a quarter's (or a filter window's) list behind the visibility tile: a depth-only workgroup has no phase-C
+  // block and sizes the list by its own LDS budget
+  static constexpr uint32_t LCAP = DO ? DEPTH_LIST_CAP : QUARTER_LIST_CAP;
+  static constexpr uint32_t SC_BYTES = DO ? LDS_Z_OFF + LCAP * 4 : PHASE_C_BYTES;  // s_c: phase A's tile and list, phase C's blocks
+  static_assert(!LOAD || (!MV && !DO && !IDS && !ATTR),
+                "depth LOAD: single-view colour passes only, and enqueue_pass binds neither attribute planes nor an ID target to one");
+  static_assert(!ATTR || IDS, "an attribute pass compiles the ID store in and tests P.ids at run time: one instance with or without the target");
+  static_assert(!ATTR || (!MV && !DO), "enqueue_pass binds attribute planes to single-view shading passes only");
+  static_assert(LDS_Z_OFF + LCAP * 4 <= SC_BYTES, "depth tile + a quarter's triangle list");
+};
+
+// ------------------------------------------------------------------------------------------------
+// The workgroup's three LDS arrays (declared in tile_main) and every view the phases take of them.  Each accessor takes
+// the array it views: no object is passed around (a struct of the three pointers handed to tile_body by reference changes
+// every instance's code).  The views alias in time, not in use: each assert sits at the cast it licenses.
+constexpr uint32_t IDX_LIST_COUNT = 0;  // s_idx words during phase A: the filter's list length,
+constexpr uint32_t IDX_SCAN_BM = 16;    // [32] scan_columns' two sets of sixteen block minima,
+constexpr uint32_t IDX_FILTER_BM = 48;  // [16] the filter's block minima (phase C has all BATCH words: the staged records' indices)
+static_assert(IDX_LIST_COUNT + 1 <= IDX_SCAN_BM && IDX_SCAN_BM + 32 <= IDX_FILTER_BM && IDX_FILTER_BM + 16 <= BATCH,
+              "s_idx: count, scan minima and filter minima side by side in BATCH words");
+static_assert(IDX_SCAN_BM % 4 == 0 && IDX_FILTER_BM % 4 == 0, "the block minima are read as uint4 (s_idx is 16-byte aligned)");
+
+template <class V, int FMT>
+struct TileLds {
+  typedef typename Codec<FMT>::enc_t enc_t;
+  // s_cov: [BATCH * 8] the staged records; s_idx: [BATCH]; s_c: [V::SC_BYTES]
+
+  // phase A: the (depth bits << 32 | key) tile
+  static __device__ __forceinline__ unsigned long long* visibility(unsigned char* s_c) { return reinterpret_cast<unsigned long long*>(s_c); }
+  // from phase B on: the tile's colour, in the target's encoding, over the dead visibility tile
+  static __device__ __forceinline__ enc_t* color(unsigned char* s_c) {
+    static_assert(TILE * TILE * 8 >= TILE * TILE * sizeof(enc_t), "the colour tile aliases the visibility tile");
+    return reinterpret_cast<enc_t*>(s_c);
+  }
+  // the tile's opaque depth bits for phase C's depth test, taken on the way out by the depth store
+  static __device__ __forceinline__ uint32_t* s_z(unsigned char* s_c) { return reinterpret_cast<uint32_t*>(s_c + LDS_Z_OFF); }
+  // phase A of a quarter or a deep bin: the window's list, in s_z's place and on to the end of the block
+  // (its V::LCAP entries end inside s_c: Variant's assert)
+  static __device__ __forceinline__ uint32_t* list(unsigned char* s_c) { return reinterpret_cast<uint32_t*>(s_c + LDS_Z_OFF); }
+  static __device__ __forceinline__ uint32_t* list_count(uint32_t* s_idx) { return s_idx + IDX_LIST_COUNT; }
+  static __device__ __forceinline__ uint32_t* s_bm(uint32_t* s_idx) { return s_idx + IDX_SCAN_BM; }
+  static __device__ __forceinline__ uint32_t* f_bm(uint32_t* s_idx) { return s_idx + IDX_FILTER_BM; }
+  // phase C, before the scan: the sort's keys and record indices, where the waves' blocks will be
+  static __device__ __forceinline__ unsigned long long* sort_scratch(unsigned char* s_c) {
+    static_assert(V::DO || (SPLIT_SORT_MAX <= SORT_CAP && PHASE_C_BYTES - LDS_C_OFF >= SORT_CAP * 8 && PHASE_C_BYTES - LDS_C_OFF >= RANK_SORT_MAX * 8 &&
+                            PHASE_C_BYTES - LDS_C_OFF >= 4 * WAVE_C_BYTES),
+                  "sort scratch aliases the waves' phase-C blocks");
+    return reinterpret_cast<unsigned long long*>(s_c + LDS_C_OFF);
+  }
+  // the same block as bytes, for a quarter's sort of its own part of the bin (sort_quarter_bin: keys | record indices)
+  static __device__ __forceinline__ unsigned char* sort_bytes(unsigned char* s_c) { return reinterpret_cast<unsigned char*>(sort_scratch(s_c)); }
+  // the sort's [SORT_CAP] marks: the record staging buffer, idle during the sort
+  static __device__ __forceinline__ uint32_t* sort_marks(uint4* s_cov) {
+    static_assert(sizeof(uint4) * BATCH * 8 >= SORT_CAP * 4, "the sort's marks fit s_cov");
+    return reinterpret_cast<uint32_t*>(s_cov);
+  }
+  // phase C, the scan: wave wv's block — its fragment queue and, behind it, its group's shaded colours
+  static __device__ __forceinline__ unsigned char* wave_block(unsigned char* s_c, uint32_t wv) { return s_c + LDS_C_OFF + wv * WAVE_C_BYTES; }
+  static __device__ __forceinline__ uint2* wave_queue(unsigned char* block) { return reinterpret_cast<uint2*>(block); }
+  static __device__ __forceinline__ float4* wave_src(unsigned char* block) {
+    static_assert(QUEUE_CAP * 8 + 64 * sizeof(float4) <= WAVE_C_BYTES, "queue | shaded colours of a group of 64");
+    return reinterpret_cast<float4*>(block + QUEUE_CAP * 8);
+  }
+  // the ID tile on its way out as whole rows: s_cov, idle between phases A and C
+  static __device__ __forceinline__ uint2* id_tile(uint4* s_cov) {
+    static_assert(sizeof(uint4) * BATCH * 8 >= TILE * TILE * sizeof(uint2), "an ID tile fits s_cov");
+    return reinterpret_cast<uint2*>(s_cov);
+  }
+};
+
+// Pixel slots: slot k of a lane is the pixel (rx + slot_dx(k), ry + slot_dy(k)) of the tile, word li + slot_word(k) of its
+// LDS images (pixel ownership: tile_body).
+__host__ __device__ __forceinline__ constexpr int slot_dx(int k) { return (k & 1) * 8; }
+__host__ __device__ __forceinline__ constexpr int slot_dy(int k) { return (k >> 1) * 8; }
+__host__ __device__ __forceinline__ constexpr uint32_t slot_word(int k) { return (uint32_t)((k & 1) * 8 + (k >> 1) * 256); }
 
 // The lane's pixel (rx, ry) in the tile and its word li in the tile's LDS images, made afresh from the thread index
 // where a later phase needs them.  Kept in registers from the top of the kernel they are the two values the allocator
@@ -1234,23 +1374,15 @@ __device__ __forceinline__ void tile_epilogue(const FrameParams& P, const bool s
 // by blockIdx alone: sharing one body with run-time row ranges cost the whole-tile path 20-35 spilled
 // registers and 8-13 % of the frame, and choosing by a flag in tile_info put a dependent load in front of
 // every tile (+2 %).
-// MV: a multiview pass (include/svr_views.h): the tile's layer is its tile row / P.layer_rows; its pixel rows are
-// layer-local and its targets start at the layer's base, so rows past the layer's last (a partial last tile row: the next
-// layer's memory) are outside the scissor like any other
-// DO: a depth-only pass (include/svr_depth.h): phase A and the depth / ID store, then the workgroup is done.  Its s_c holds
-// the visibility tile and a quarter's (or a filter window's) list of LCAP entries, nothing of phases B to D.
-// ATTR: an attribute pass (include/svr_attributes.h): phase B also stores what shade_pixel computed for the winners into
-// the planes of P.attr that are bound; the ID target (IDS is set in these instances) is then a run-time matter, P.ids.
-// LOAD: a pass under SVR_DEPTH_LOAD (include/svr_load.h): the visibility tile starts from the depth target's own words
-// instead of 0 — a loaded pixel enters as (depth bits << 32 | key 0), below every fragment of its depth and above every
-// farther one, so the maximum over (depth, key) IS GREATER_OR_EQUAL against the loaded depth — and a tile without an opaque
-// bin stores no depth.  The loaded word is only ever compared and stored back: it never forms an address.
-template <int FMT, bool INSTR, bool QUARTER, bool SPLIT, bool IDS, bool MV, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false,
-          bool LOAD = false>
+// V: the pass kind (Variant<...> above).
+template <class V, int FMT, bool INSTR, bool QUARTER, bool SPLIT>
 __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, const uint4 i1, uint4* s_cov, uint32_t* s_idx, unsigned char* s_c,
                                           const uint32_t wv, const bool hiz_on, const uint32_t wg_start = 0) {
+  constexpr bool IDS = V::IDS, MV = V::MV, DO = V::DO, ATTR = V::ATTR, LOAD = V::LOAD;
+  constexpr uint32_t LCAP = V::LCAP;
   typedef Codec<FMT> CD;
   typedef typename CD::enc_t enc_t;
+  typedef TileLds<V, FMT> LDS;
   // Workgroups are dispatched in blockIdx order: walk the tiles heaviest class first (fill_kernel's
   // tile_order).  Tiles are dealt round-robin over the 8 XCDs; a contiguous span per XCD was tried
   // and loses: the heavy rows of the frame all land on one XCD and the other seven idle.
@@ -1288,19 +1420,18 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
   const int x_end = (int)(P.sx + P.sw), y_end = (int)(P.sy + P.sh);
   const int sub_y0 = ty0 + row0;
   // pixel ownership: wave w the 16x16 quadrant w, lane l one pixel in each of its four 8x8 blocks; slot k of a
-  // lane is the pixel (rx + (k & 1) * 8, ry + (k >> 1) * 8) of the tile, word li + (k & 1) * 8 + (k >> 1) * 256 of its LDS images
+  // lane is the pixel (rx + slot_dx(k), ry + slot_dy(k)) of the tile, word li + slot_word(k) of its LDS images
   const int rx = (int)((wave & 1u) * 16u + (lane & 7u)), ry = (int)((wave >> 1) * 16u + (lane >> 3));
   const uint32_t li = (uint32_t)ry * TILE + (uint32_t)rx;
   // the whole tile lies inside the scissor (every pixel of it is this workgroup's to write): wave-uniform
   const bool inside = !QUARTER && tx0 + TILE <= x_end && ty0 + TILE <= y_end;
   const bool aligned = ((P.W | P.sx) & 3u) == 0u;
-  static_assert(!LOAD || (!MV && !DO && !IDS && !ATTR), "depth LOAD: single-view colour passes, the plain instances");
 
   bool pix_ok[4];
   uint32_t recs[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    int px = tx0 + rx + (k & 1) * 8, py = ty0 + ry + (k >> 1) * 8;
+    int px = tx0 + rx + slot_dx(k), py = ty0 + ry + slot_dy(k);
     pix_ok[k] = px < x_end && py < y_end && (!QUARTER || (uint32_t)(py - sub_y0) < (uint32_t)nrows);
     recs[k] = NO_REC;
   }
@@ -1310,9 +1441,9 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
   const bool stamps = P.tile_cycles != nullptr;
   if (stamps) stamp[0] = clock64();
 
-  unsigned long long* s_depth = reinterpret_cast<unsigned long long*>(s_c);
-  enc_t* lc = reinterpret_cast<enc_t*>(s_c);
-  uint32_t* s_z = reinterpret_cast<uint32_t*>(s_c + LDS_Z_OFF);
+  unsigned long long* s_depth = LDS::visibility(s_c);
+  enc_t* lc = LDS::color(s_c);
+  uint32_t* s_z = LDS::s_z(s_c);
 
   // ---- phase A: opaque visibility
   if (n_op) {
@@ -1327,8 +1458,8 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #pragma unroll
         for (int k = 0; k < 4; k++) {  // pixels outside the scissor or the quarter's rows enter as 0: they are never written back
           uint32_t z = 0u;
-          if (pix_ok[k]) z = f2u(depth[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)]);
-          s_depth[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] = (unsigned long long)z << 32;
+          if (pix_ok[k]) z = f2u(depth[(size_t)(ty0 + ry + slot_dy(k)) * P.W + (size_t)(tx0 + rx + slot_dx(k))]);
+          s_depth[li + slot_word(k)] = (unsigned long long)z << 32;
         }
       }
     } else {
@@ -1349,15 +1480,15 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       // 8K x16 frame nine of ten are hidden).  Windows of 1024 entries then, the sixteen block depths taken off the
       // visibility tile between two of them.  Instrumented passes keep everything and tag what would go (bit 31).
       // (Visibility is a maximum: how the bin is cut into windows does not change what wins.)
-      uint32_t* s_list = reinterpret_cast<uint32_t*>(s_c + LDS_Z_OFF);
-      uint32_t* f_bm = s_idx + 48;  // [16] block depths of the filter (scan_columns has s_idx[16..47])
+      uint32_t* s_list = LDS::list(s_c);
+      uint32_t* f_bm = LDS::f_bm(s_idx);  // [16] block depths of the filter
       constexpr uint32_t FILTER_WIN = LCAP < 1024u ? LCAP : 1024u;
       const uint32_t WIN = hiz_filter ? FILTER_WIN : LCAP;
       for (uint32_t win = 0; win < n_op; win += WIN) {
         const uint32_t n_win = min(n_op - win, WIN);
         const bool ftest = hiz_filter && win != 0u;
         __syncthreads();  // the previous window's list is consumed, its count read by everybody
-        if (threadIdx.x == 0) s_idx[0] = 0u;
+        if (threadIdx.x == 0) *LDS::list_count(s_idx) = 0u;
         if (ftest && threadIdx.x < 16u) f_bm[threadIdx.x] = 0xffffffffu;
         __syncthreads();
         if (ftest) {
@@ -1411,30 +1542,31 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
             }
             unsigned long long m = __ballot(keep);
             uint32_t at = 0;
-            if (lane == 0 && m) at = atomicAdd(&s_idx[0], (uint32_t)__popcll(m));  // LDS
+            if (lane == 0 && m) at = atomicAdd(LDS::list_count(s_idx), (uint32_t)__popcll(m));  // LDS
             at = __shfl(at, 0);
             if (keep) s_list[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = ri[k] | tag;
           }
         }
         __syncthreads();
-        const uint32_t n_mine = s_idx[0];
-        if (hiz_on) scan_columns<INSTR, true, true>(P, s_cov, s_list, 0u, n_mine, s_depth, s_idx + 16, tx0, ty0, sub_y0, nrows, n_raster, n_hiz_bad, occl);
-        else scan_columns<INSTR, true, false>(P, s_cov, s_list, 0u, n_mine, s_depth, s_idx + 16, tx0, ty0, sub_y0, nrows, n_raster, n_hiz_bad, occl);
+        const uint32_t n_mine = *LDS::list_count(s_idx);
+        if (hiz_on) scan_columns<INSTR, true, true>(P, s_cov, s_list, 0u, n_mine, s_depth, LDS::s_bm(s_idx), tx0, ty0, sub_y0, nrows, n_raster, n_hiz_bad, occl);
+        else scan_columns<INSTR, true, false>(P, s_cov, s_list, 0u, n_mine, s_depth, LDS::s_bm(s_idx), tx0, ty0, sub_y0, nrows, n_raster, n_hiz_bad, occl);
       }
     } else {
-      if (hiz_on) scan_columns<INSTR, false, true>(P, s_cov, nullptr, off_op, n_op, s_depth, s_idx + 16, tx0, ty0, QUARTER ? sub_y0 : ty0, nrows, n_raster, n_hiz_bad, occl);
-      else scan_columns<INSTR, false, false>(P, s_cov, nullptr, off_op, n_op, s_depth, s_idx + 16, tx0, ty0, QUARTER ? sub_y0 : ty0, nrows, n_raster, n_hiz_bad, occl);
+      if (hiz_on) scan_columns<INSTR, false, true>(P, s_cov, nullptr, off_op, n_op, s_depth, LDS::s_bm(s_idx), tx0, ty0, QUARTER ? sub_y0 : ty0, nrows, n_raster, n_hiz_bad, occl);
+      else scan_columns<INSTR, false, false>(P, s_cov, nullptr, off_op, n_op, s_depth, LDS::s_bm(s_idx), tx0, ty0, QUARTER ? sub_y0 : ty0, nrows, n_raster, n_hiz_bad, occl);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 4; k++) {  // the winners' records move into the owning lanes' registers
-      unsigned long long v = s_depth[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)];
+      unsigned long long v = s_depth[li + slot_word(k)];
+      // (the row written out, not slot_dy: through the helper the instrumented depth-only instances' code changes)
       // (instrumented passes drop nothing: every pixel of the workgroup's rows must then have reached what the
       // occluders of scan_columns claimed for it — the claim everything dropped behind them rests on)
       if (INSTR && occl && (!QUARTER || (uint32_t)(ry + (k >> 1) * 8 - row0) < (uint32_t)nrows) && (uint32_t)(v >> 32) < occl) n_hiz_bad++;
       if ((uint32_t)v != 0u) {
         uint32_t main_slot = ((uint32_t)v >> 2) - 1u;
-        uint32_t rec = ((uint32_t)v & 1u) ? resolve_record(P, main_slot, tx0 + rx + (k & 1) * 8, ty0 + ry + (k >> 1) * 8) : main_slot;
+        uint32_t rec = ((uint32_t)v & 1u) ? resolve_record(P, main_slot, tx0 + rx + slot_dx(k), ty0 + ry + slot_dy(k)) : main_slot;
         recs[k] = rec | (((uint32_t)v & 2u) ? REC_COMMON : 0u);
       }
     }
@@ -1466,8 +1598,8 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
         lane_pixel(wv, rx, ry, li);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-          const uint32_t w = li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256);
-          float* const at = depth + (size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8);
+          const uint32_t w = li + slot_word(k);
+          float* const at = depth + (size_t)(ty0 + ry + slot_dy(k)) * P.W + (size_t)(tx0 + rx + slot_dx(k));
           uint32_t z = 0u;  // (pixels outside the scissor or the quarter's rows: no fragment reaches them)
           if (n_op) {
             z = (uint32_t)(s_depth[w] >> 32);
@@ -1496,9 +1628,9 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
     lane_pixel(wv, rx, ry, li);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      const uint32_t w = li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256);
+      const uint32_t w = li + slot_word(k);
       uint32_t z = n_op ? (uint32_t)(s_depth[w] >> 32) : 0u;
-      if (pix_ok[k]) depth[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = u2f(z);
+      if (pix_ok[k]) depth[(size_t)(ty0 + ry + slot_dy(k)) * P.W + (size_t)(tx0 + rx + slot_dx(k))] = u2f(z);
       if (!DO && n_tr) s_z[w] = z;
     }
   }
@@ -1514,10 +1646,9 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       id[k] = recs[k] == NO_REC ? make_uint2(0u, 0u)
                                 : *reinterpret_cast<const uint2*>(reinterpret_cast<const uint4*>(P.recs + (recs[k] & ~REC_COMMON)) + REC_ID_PIECE);
     if (inside && aligned) {
-      static_assert(sizeof(uint4) * BATCH * 8 >= TILE * TILE * sizeof(uint2), "an ID tile fits s_cov");
-      uint2* s_id = reinterpret_cast<uint2*>(s_cov);
+      uint2* s_id = LDS::id_tile(s_cov);
 #pragma unroll
-      for (int k = 0; k < 4; k++) s_id[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] = id[k];
+      for (int k = 0; k < 4; k++) s_id[li + slot_word(k)] = id[k];
       __syncthreads();
       const uint32_t tid = tid_of(wv), row = tid >> 3, c = (tid & 7u) * 4u;
       const uint4* src = reinterpret_cast<const uint4*>(s_id + row * TILE + c);
@@ -1527,7 +1658,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
     } else {
 #pragma unroll
       for (int k = 0; k < 4; k++)
-        if (pix_ok[k]) ids[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] = id[k];
+        if (pix_ok[k]) ids[(size_t)(ty0 + ry + slot_dy(k)) * P.W + (size_t)(tx0 + rx + slot_dx(k))] = id[k];
     }
   }
   if constexpr (DO) {  // no phase B, C or D: their cycles are 0, and the pass shades nothing
@@ -1546,7 +1677,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const uint32_t tid = tid_of(wv);
-    const int qx = (int)(((tid >> 6) & 1u) * 16u + (tid & 7u)) + (k & 1) * 8, qy = (int)((tid >> 7) * 16u + ((tid >> 3) & 7u)) + (k >> 1) * 8;
+    const int qx = (int)(((tid >> 6) & 1u) * 16u + (tid & 7u)) + slot_dx(k), qy = (int)((tid >> 7) * 16u + ((tid >> 3) & 7u)) + slot_dy(k);
     const int px = tx0 + qx, py = ty0 + qy;
     if (__all(!dirty[k] || (recs[k] & REC_COMMON))) {
       // every quad of this 8x8 block of one triangle (or empty): lane ^ 1 is the pixel to the left or right, lane ^ 8 above or below
@@ -1581,6 +1712,8 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
       int rx, ry;
       uint32_t li;
       lane_pixel(wv, rx, ry, li);
+      // (the slot's addressing written out, not slot_dx / slot_dy / slot_word: k is a run-time value here, and through the
+      // helpers the compiler shares the terms between px and the LDS word differently — the instances' code changes)
       int px = tx0 + rx + (k & 1) * 8, py = ty0 + ry + (k >> 1) * 8;
       FragAttr fa = {};  // (ATTR only)
       if (d) {
@@ -1607,7 +1740,7 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #pragma unroll
     for (int k = 0; k < 4; k++)
       if (!dirty[k] && pix_ok[k]) {
-        lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] = cv;
+        lc[li + slot_word(k)] = cv;
         dirty[k] = true;
       }
   }
@@ -1616,16 +1749,16 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
   if (n_tr) {
     uint32_t tbase = off_tr;
     const uint32_t* order = P.bins + tbase;
-    unsigned long long* scratch = reinterpret_cast<unsigned long long*>(s_c + LDS_C_OFF);
+    unsigned long long* scratch = LDS::sort_scratch(s_c);
     uint32_t n_list = n_tr;
     if (QUARTER) {  // n_tr <= SORT_CAP: the quarter's own part of the bin, sorted in LDS, written to its span of the arena
       uint32_t* own_list = reinterpret_cast<uint32_t*>(P.sort_arena + sort_base + (uint32_t)(row0 >> 3) * ((n_tr + 1u) >> 1));
-      n_list = sort_quarter_bin(P, reinterpret_cast<unsigned char*>(scratch), reinterpret_cast<uint32_t*>(s_cov), tbase, n_tr, tx0, sub_y0, nrows, own_list, wv);
+      n_list = sort_quarter_bin(P, LDS::sort_bytes(s_c), LDS::sort_marks(s_cov), tbase, n_tr, tx0, sub_y0, nrows, own_list, wv);
       order = own_list;
     } else if (n_tr <= SORT_CAP) {
-      sort_bin_by_key<SPLIT>(P, scratch, reinterpret_cast<uint32_t*>(s_cov), tbase, n_tr, P.bins + tbase, wv);
+      sort_bin_by_key<SPLIT>(P, scratch, LDS::sort_marks(s_cov), tbase, n_tr, P.bins + tbase, wv);
     } else {
-      sort_bin_by_key<SPLIT>(P, P.sort_arena + sort_base, reinterpret_cast<uint32_t*>(s_cov), tbase, n_tr, P.bins + tbase, wv);  // rare: a bin too large for LDS
+      sort_bin_by_key<SPLIT>(P, P.sort_arena + sort_base, LDS::sort_marks(s_cov), tbase, n_tr, P.bins + tbase, wv);  // rare: a bin too large for LDS
     }
     if (n_list) {  // (a quarter none of the bin's triangles reaches leaves its pixels as they are)
     int rx, ry;
@@ -1634,12 +1767,12 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #pragma unroll
     for (int k = 0; k < 4; k++)  // colour loadOp LOAD for what neither the opaque pass nor a clear has written
       if (!dirty[k] && pix_ok[k])
-        lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)] =
-            color[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)];
-    unsigned char* mine = s_c + LDS_C_OFF + wv * WAVE_C_BYTES;
+        lc[li + slot_word(k)] =
+            color[(size_t)(ty0 + ry + slot_dy(k)) * P.W + (size_t)(tx0 + rx + slot_dx(k))];
+    unsigned char* mine = LDS::wave_block(s_c, wv);
     enc_t* col = lc + (uint32_t)(row0 + ((int)wv << lrpw)) * TILE;  // this wave's rows of the colour tile
-    uint2* q = reinterpret_cast<uint2*>(mine);
-    float4* s_src = reinterpret_cast<float4*>(mine + QUEUE_CAP * 8);
+    uint2* q = LDS::wave_queue(mine);
+    float4* s_src = LDS::wave_src(mine);
     scan_columns_ordered<FMT, INSTR>(P, s_cov, s_idx, order, n_list, tx0, ty0, row0, lrpw, s_z, col, q, s_src, n_raster, n_shaded, wv);
 #pragma unroll
     for (int k = 0; k < 4; k++) dirty[k] = pix_ok[k];
@@ -1668,8 +1801,8 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 #pragma unroll
     for (int k = 0; k < 4; k++)
       if (pix_ok[k] && dirty[k])
-        color[(size_t)(ty0 + ry + (k >> 1) * 8) * P.W + (size_t)(tx0 + rx + (k & 1) * 8)] =
-            lc[li + (uint32_t)((k & 1) * 8 + (k >> 1) * 256)];
+        color[(size_t)(ty0 + ry + slot_dy(k)) * P.W + (size_t)(tx0 + rx + slot_dx(k))] =
+            lc[li + slot_word(k)];
   }
   if (stamps) stamp[4] = clock64();
   tile_epilogue<INSTR>(P, stamps, stamp, tile, row0, wv, wg_start, lane, n_raster, n_shaded, n_hiz_bad);
@@ -1678,39 +1811,15 @@ __device__ __forceinline__ void tile_body(const FrameParams& P, const uint4 i0, 
 // SPLIT: the launch is headed by SPLIT_EXTRA slots for the quarters of split tiles.  A kernel of its own: the
 // quarter path merely compiled in costs the whole-tile path 2-3 % (registers, code size), which a pass with
 // more than SPLIT_TILES_MAX tiles — where no tile is worth splitting — need not pay.
-#ifndef SVR_TILE_WAVES
-#define SVR_TILE_WAVES 5  // waves per SIMD (= workgroups per CU) the tile kernel is compiled for (A/B builds: tools/build_variant.sh)
-#endif
-#ifndef SVR_DEPTH_WAVES
-#define SVR_DEPTH_WAVES 5  // waves per SIMD (= workgroups per CU) of the depth-only tile kernels (A/B builds: tools/build_variant.sh)
-// (phase A alone needs 90-96 VGPRs: at 6 and more the depth-only instances spill, and 6 measured no faster: DESIGN §5)
-#endif
-// LDS of a depth-only workgroup: s_cov, s_idx, the visibility tile and a list of this many entries fill the workgroup's share
-// of gfx950's 128 granules of 1280 bytes at SVR_DEPTH_WAVES workgroups per CU (8: 928 entries, 6: 2528, 5: 3808)
-constexpr uint32_t depth_list_cap(uint32_t wgs) {
-  return (((128u / wgs) * 1280u - BATCH * 8 * 16 - BATCH * 4 - 64u - LDS_Z_OFF) / 4u) & ~31u;
-}
-constexpr uint32_t DEPTH_LIST_CAP = depth_list_cap(SVR_DEPTH_WAVES) < QUARTER_LIST_CAP ? depth_list_cap(SVR_DEPTH_WAVES) : QUARTER_LIST_CAP;
-static_assert(DEPTH_LIST_CAP >= BATCH, "a depth-only list window holds a batch");
-
-// IDS: the pass writes an ID target (FrameParams::ids): tile_ids_kernel below; tile_kernel is the kernel as it was
-// DO: a depth-only pass (tile_depth_kernel): s_c is the visibility tile and an LCAP-entry list only
-// ATTR: an attribute pass (tile_attr_kernel)
-// LOAD: a pass under SVR_DEPTH_LOAD (tile_load_kernel)
-template <int FMT, bool INSTR, bool SPLIT, bool IDS, bool MV = false, bool DO = false, uint32_t LCAP = QUARTER_LIST_CAP, bool ATTR = false, bool LOAD = false>
+template <class V, int FMT, bool INSTR, bool SPLIT>
 __device__ __forceinline__ void tile_main(const FrameParams& P) {
-  constexpr uint32_t SC_BYTES = DO ? LDS_Z_OFF + LCAP * 4 : PHASE_C_BYTES;
   __shared__ uint4 s_cov[BATCH * 8];
-  __shared__ __attribute__((aligned(16))) uint32_t s_idx[BATCH];  // s_idx + 16 and + 48 are read as uint4 (scan_columns, tile_body's filter)
-  __shared__ __attribute__((aligned(16))) unsigned char s_c[SC_BYTES];  // phase A depth tile, phase C blocks
-  static_assert(LDS_Z_OFF + LCAP * 4 <= SC_BYTES, "depth tile + a quarter's triangle list");
-  static_assert(DO || (SPLIT_SORT_MAX <= SORT_CAP && PHASE_C_BYTES - LDS_C_OFF >= SORT_CAP * 8 && PHASE_C_BYTES - LDS_C_OFF >= RANK_SORT_MAX * 8 &&
-                    PHASE_C_BYTES - LDS_C_OFF >= 4 * WAVE_C_BYTES), "sort scratch aliases the waves' phase-C blocks");
+  __shared__ __attribute__((aligned(16))) uint32_t s_idx[BATCH];  // the block minima in it are read as uint4 (IDX_SCAN_BM, IDX_FILTER_BM)
+  __shared__ __attribute__((aligned(16))) unsigned char s_c[V::SC_BYTES];  // phase A depth tile, phase C blocks
   // gfx950 hands out its 160 KiB of LDS in granules of 1280 bytes (320 dwords): five workgroups per CU need 25 granules
   // each, 32 000 bytes — NOT 32 768 (at 32 064 bytes the kernel stayed at four per CU: tools/frames.py --wgtimes)
-  static_assert(DO || sizeof(s_cov) + sizeof(s_idx) + PHASE_C_BYTES + 64 <= 25 * 1280, "five workgroups per CU: 25 LDS granules of 1280 B");
-  static_assert(!DO || sizeof(s_cov) + sizeof(s_idx) + SC_BYTES + 64 <= (128 / SVR_DEPTH_WAVES) * 1280, "SVR_DEPTH_WAVES depth-only workgroups per CU");
-  static_assert(TILE * TILE * 8 >= TILE * TILE * sizeof(uint2), "the colour tile aliases the visibility tile");
+  static_assert(V::DO || sizeof(s_cov) + sizeof(s_idx) + PHASE_C_BYTES + 64 <= 25 * 1280, "five workgroups per CU: 25 LDS granules of 1280 B");
+  static_assert(!V::DO || sizeof(s_cov) + sizeof(s_idx) + V::SC_BYTES + 64 <= (128 / SVR_DEPTH_WAVES) * 1280, "SVR_DEPTH_WAVES depth-only workgroups per CU");
 
   // Everything the workgroup needs before it can start comes in ONE round of scalar loads: the failure flags
   // and the launch slot's tile_info.  (Written as plain loads they compiled to a chain of four round trips
@@ -1764,12 +1873,12 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   } else if (SPLIT) {
     if (blockIdx.x < SPLIT_EXTRA) {  // the quarters of split tiles, as many as fill_kernel made
       if (blockIdx.x >= 4u * min(n_split, SPLIT_MAX)) return;
-      tile_body<FMT, INSTR, true, true, IDS, MV, DO, LCAP, ATTR, LOAD>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<V, FMT, INSTR, true, true>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     } else {
-      tile_body<FMT, INSTR, false, true, IDS, MV, DO, LCAP, ATTR, LOAD>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+      tile_body<V, FMT, INSTR, false, true>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
     }
   } else {
-    tile_body<FMT, INSTR, false, false, IDS, MV, DO, LCAP, ATTR, LOAD>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
+    tile_body<V, FMT, INSTR, false, false>(P, i0, i1, s_cov, s_idx, s_c, wv, hiz_on, wg_start);
   }
   // ... and every workgroup's end, one of 64 words each: plain stores, the last one into a word stays (an atomic maximum on
   // pinned host memory is not an operation the host link carries: it would become a compare-and-swap loop of round trips
@@ -1783,37 +1892,29 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
   if (P.host_clock && threadIdx.x == 0 && (P.n_tiles <= SPLIT_TILES_MAX || (blockIdx.x & 7u) == 0u))
     __hip_atomic_store(P.host_clock + (1u + ((blockIdx.x >> 3) & 63u)) * CLOCK_STRIDE, wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// The entry points: one per pass kind, each naming its variant.
 template <int FMT, bool INSTR, bool SPLIT>
-__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false>(P); }
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_kernel(FrameParams P) { tile_main<Variant<PlainPass>, FMT, INSTR, SPLIT>(P); }
 template <int FMT, bool INSTR, bool SPLIT>
-__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_ids_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, true>(P); }
-// multiview passes (include/svr_views.h)
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_ids_kernel(FrameParams P) { tile_main<Variant<IdsPass>, FMT, INSTR, SPLIT>(P); }
 template <int FMT, bool INSTR, bool SPLIT>
-__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, false, true>(P); }
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_kernel(FrameParams P) { tile_main<Variant<MvPass>, FMT, INSTR, SPLIT>(P); }
 template <int FMT, bool INSTR, bool SPLIT>
-__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_ids_kernel(FrameParams P) { tile_main<FMT, INSTR, SPLIT, true, true>(P); }
-// attribute passes (include/svr_attributes.h): one instance whatever planes are bound, and with or without an ID target
-// (both tested at run time).  SVR_ATTR_WAVES workgroups per CU (A/B builds: tools/build_variant.sh): five, like the
-// other instances — the uninstrumented ones fit 96 VGPRs without a spilled VGPR or a scratch frame.  At four per CU the
-// same stores measured 10-13 us per 4K frame slower (DESIGN.md "Attribute targets").
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_mv_ids_kernel(FrameParams P) { tile_main<Variant<MvIdsPass>, FMT, INSTR, SPLIT>(P); }
+// SVR_ATTR_WAVES workgroups per CU (A/B builds: tools/build_variant.sh): five, like the other instances — the
+// uninstrumented ones fit 96 VGPRs without a spilled VGPR or a scratch frame.  At four per CU the same stores measured
+// 10-13 us per 4K frame slower (DESIGN.md "Attribute targets").
 #ifndef SVR_ATTR_WAVES
 #define SVR_ATTR_WAVES 5
 #endif
 template <int FMT, bool INSTR, bool SPLIT>
-__global__ __launch_bounds__(256, SVR_ATTR_WAVES) void tile_attr_kernel(FrameParams P) {
-  tile_main<FMT, INSTR, SPLIT, true, false, false, QUARTER_LIST_CAP, true>(P);
-}
-// passes under SVR_DEPTH_LOAD (include/svr_load.h): the plain colour instance over the depth the target holds; they write
-// no ID target and no attribute plane, so there is one per colour format whatever is bound
+__global__ __launch_bounds__(256, SVR_ATTR_WAVES) void tile_attr_kernel(FrameParams P) { tile_main<Variant<AttrPass>, FMT, INSTR, SPLIT>(P); }
 template <int FMT, bool INSTR, bool SPLIT>
-__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_load_kernel(FrameParams P) {
-  tile_main<FMT, INSTR, SPLIT, false, false, false, QUARTER_LIST_CAP, false, true>(P);
-}
-// depth-only passes (include/svr_depth.h): one instance for both colour formats (the colour target is not touched), IDS and
-// MV as above
+__global__ __launch_bounds__(256, SVR_TILE_WAVES) void tile_load_kernel(FrameParams P) { tile_main<Variant<LoadPass>, FMT, INSTR, SPLIT>(P); }
 template <bool INSTR, bool SPLIT, bool IDS, bool MV>
 __global__ __launch_bounds__(256, SVR_DEPTH_WAVES) void tile_depth_kernel(FrameParams P) {
-  tile_main<SVR_COLOR_RGBA8, INSTR, SPLIT, IDS, MV, true, DEPTH_LIST_CAP>(P);
+  tile_main<Variant<DepthPass<IDS, MV>>, SVR_COLOR_RGBA8, INSTR, SPLIT>(P);
 }
 
 // Instrumented passes only: the counters go to the host (pinned, device-visible) by a one-wave kernel
@@ -1827,9 +1928,41 @@ __global__ __launch_bounds__(64) void report_kernel(FrameParams P) {
                        reinterpret_cast<const uint32_t*>(P.counters)[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// done: signalled when the pass's last kernel has finished.  It rides on that kernel's
-// own dispatch packet (hipExtLaunchKernel's stopEvent): a separate hipEventRecord is one more packet
-// for the command processor between two tile kernels.
+typedef void (*pass_kernel_t)(FrameParams);
+
+// A run-time bool as a compile-time one: f is called with std::true_type or std::false_type.
+template <class F>
+static auto lift(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// The tile kernel instance of a pass: the kind by precedence, then its format, instrumentation and launch shape.
+// (enqueue_pass binds attribute planes to single-view shading passes only, and neither planes nor an ID target to a
+// pass under SVR_DEPTH_LOAD: P.depth_load, include/svr_load.h)
+template <int FMT, bool INSTR, bool SPLIT>
+static pass_kernel_t tile_kernel_of(const FrameParams& P, bool depth_only) {
+  const bool mv = P.layer_rows != 0, ids = P.ids != nullptr;
+  if (depth_only) {
+    if (mv && ids) return tile_depth_kernel<INSTR, SPLIT, true, true>;
+    if (mv) return tile_depth_kernel<INSTR, SPLIT, false, true>;
+    if (ids) return tile_depth_kernel<INSTR, SPLIT, true, false>;
+    return tile_depth_kernel<INSTR, SPLIT, false, false>;
+  }
+  if (P.depth_load) return tile_load_kernel<FMT, INSTR, SPLIT>;
+  if (P.attr[0] || P.attr[1] || P.attr[2] || P.attr[3]) return tile_attr_kernel<FMT, INSTR, SPLIT>;
+  if (mv && ids) return tile_mv_ids_kernel<FMT, INSTR, SPLIT>;
+  if (mv) return tile_mv_kernel<FMT, INSTR, SPLIT>;
+  if (ids) return tile_ids_kernel<FMT, INSTR, SPLIT>;
+  return tile_kernel<FMT, INSTR, SPLIT>;
+}
+
+// stop: signalled when the kernel has finished.  It rides on the kernel's own dispatch packet (hipExtLaunchKernel's
+// stopEvent): a separate hipEventRecord is one more packet for the command processor between two tile kernels.
+static void launch_pass_kernel(pass_kernel_t kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t s, hipEvent_t stop, const FrameParams& P) {
+  hipExtLaunchKernelGGL(kernel, grid, block, lds, s, nullptr, stop, 0, P);
+}
+
+// done: signalled when the pass's last kernel has finished.
 void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, bool depth_only, hipStream_t s, hipEvent_t done) {
   const bool split = !(P.tuning & (TUNE_NO_SPLIT | TUNE_NO_TILE_ORDER));
   dim3 grid(split ? P.n_tiles + SPLIT_EXTRA : P.n_tiles), block(256);
@@ -1854,56 +1987,16 @@ void launch_tiles(const FrameParams& P, int color_format, bool count_fragments, 
 #else
   const uint32_t pad = P.n_tiles <= SPLIT_TILES_MAX ? 1280u : 0u;
 #endif
-  if (depth_only) {  // no pad: the small-pass reasoning above is the shading kernel's (depth-only passes)
-#define SVR_LAUNCH_DEPTH(INSTR, SPLIT)                                                                                                         \
-  do {                                                                                                                                         \
-    if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, true>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);  \
-    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, true>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);    \
-    else if (P.ids) hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, true, false>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);           \
-    else hipExtLaunchKernelGGL((tile_depth_kernel<INSTR, SPLIT, false, false>), grid, block, lds_pad, s, nullptr, tile_done, 0, P);                     \
-  } while (0)
-    if (count_fragments) {
-      if (split) SVR_LAUNCH_DEPTH(true, true);
-      else SVR_LAUNCH_DEPTH(true, false);
-    } else {
-      if (split) SVR_LAUNCH_DEPTH(false, true);
-      else SVR_LAUNCH_DEPTH(false, false);
-    }
-#undef SVR_LAUNCH_DEPTH
-    if (report) hipExtLaunchKernelGGL(report_kernel, dim3(1), dim3(64), 0, s, nullptr, done, 0, P);
-    return;
-  }
-  // (enqueue_pass binds attribute planes to single-view shading passes only, and neither planes nor an ID target to a
-  // pass under SVR_DEPTH_LOAD: P.depth_load, include/svr_load.h)
-  const bool attr = P.attr[0] || P.attr[1] || P.attr[2] || P.attr[3];
-#define SVR_LAUNCH_TILES(FMT, INSTR, SPLIT)                                                                                          \
-  do {                                                                                                                               \
-    if (P.depth_load) hipExtLaunchKernelGGL((tile_load_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);     \
-    else if (attr) hipExtLaunchKernelGGL((tile_attr_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);         \
-    else if (P.layer_rows && P.ids) hipExtLaunchKernelGGL((tile_mv_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P); \
-    else if (P.layer_rows) hipExtLaunchKernelGGL((tile_mv_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);  \
-    else if (P.ids) hipExtLaunchKernelGGL((tile_ids_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);      \
-    else hipExtLaunchKernelGGL((tile_kernel<FMT, INSTR, SPLIT>), grid, block, lds_pad + pad, s, nullptr, tile_done, 0, P);                \
-  } while (0)
-  if (color_format == SVR_COLOR_RGBA16F) {
-    if (count_fragments) {
-      if (split) SVR_LAUNCH_TILES(SVR_COLOR_RGBA16F, true, true);
-      else SVR_LAUNCH_TILES(SVR_COLOR_RGBA16F, true, false);
-    } else {
-      if (split) SVR_LAUNCH_TILES(SVR_COLOR_RGBA16F, false, true);
-      else SVR_LAUNCH_TILES(SVR_COLOR_RGBA16F, false, false);
-    }
-  } else {
-    if (count_fragments) {
-      if (split) SVR_LAUNCH_TILES(SVR_COLOR_RGBA8, true, true);
-      else SVR_LAUNCH_TILES(SVR_COLOR_RGBA8, true, false);
-    } else {
-      if (split) SVR_LAUNCH_TILES(SVR_COLOR_RGBA8, false, true);
-      else SVR_LAUNCH_TILES(SVR_COLOR_RGBA8, false, false);
-    }
-  }
-#undef SVR_LAUNCH_TILES
-  if (report) hipExtLaunchKernelGGL(report_kernel, dim3(1), dim3(64), 0, s, nullptr, done, 0, P);
+  const pass_kernel_t kernel = lift(color_format == SVR_COLOR_RGBA16F, [&](auto f16) {
+    return lift(count_fragments, [&](auto instr) {
+      return lift(split, [&](auto spl) {
+        return tile_kernel_of<decltype(f16)::value ? SVR_COLOR_RGBA16F : SVR_COLOR_RGBA8, decltype(instr)::value, decltype(spl)::value>(P, depth_only);
+      });
+    });
+  });
+  // depth-only: no pad, the small-pass reasoning above is the shading kernel's (depth-only passes)
+  launch_pass_kernel(kernel, grid, block, depth_only ? lds_pad : lds_pad + pad, s, tile_done, P);
+  if (report) launch_pass_kernel(report_kernel, dim3(1), dim3(64), 0, s, done, P);
 }
 
 }  // namespace svr

@@ -14,7 +14,7 @@ import pytest
 import __graft_entry__ as g
 import scenarios as SC
 import svr_testlib as T
-from test_ids_gpu import HIP_STATS, ISOLATED, TUNE_HIZ, TUNE_NO_HIZ, _objects, assert_frames_same, assert_ids_same
+from test_ids_gpu import HIP_STATS, ISOLATED, TUNE_HIZ, TUNE_NO_HIZ, TUNE_NO_SPLIT, _objects, assert_frames_same, assert_ids_same
 
 pkg = g.load_package()
 A, S = pkg.abi, pkg.scenes
@@ -205,7 +205,8 @@ def test_every_path_and_variant_gives_the_same_planes(hip, name, monkeypatch):
         got = run(hip, name, monkeypatch, path=path)
         assert_planes_same(got["attr"], first["attr"], f"{name} {path}")
     for opts in (((A.OPT_COUNT_FRAGMENTS, 0),), ((A.OPT_TUNING, TUNE_NO_HIZ),), ((A.OPT_TUNING, TUNE_HIZ),),
-                 ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_HIZ)), ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_NO_HIZ))):
+                 ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_HIZ)), ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_NO_HIZ)),
+                 ((A.OPT_TUNING, TUNE_NO_SPLIT),), ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_NO_SPLIT))):
         got = run(hip, name, monkeypatch, options=opts)
         assert_planes_same(got["attr"], first["attr"], f"{name} {opts}")
     for attr in ATTRS:  # a single plane against the same plane of all four

@@ -15,6 +15,7 @@ import pytest
 import __graft_entry__ as g
 import scenarios as SC
 import svr_testlib as T
+from test_ids_gpu import TUNE_NO_SPLIT
 
 _spec = importlib.util.spec_from_file_location("make_full_frames", os.path.join(T.GOLDEN_DIR, "make_full_frames.py"))
 MF = importlib.util.module_from_spec(_spec)
@@ -136,11 +137,19 @@ def test_scenarios_equal_the_opaque_pass(hip, name, monkeypatch):
     r, scene, opaque = box["r"], box["scene"], box["opaque"]
     for instr in (1, 0):
         r.set_option(A.OPT_COUNT_FRAGMENTS, instr)
-        for tuning in (0, TUNE_NO_HIZ, TUNE_HIZ):
+        for tuning in (0, TUNE_NO_HIZ, TUNE_HIZ, TUNE_NO_SPLIT):
             r.set_option(A.OPT_TUNING, tuning)
             for flatten in (2, 1):
                 r.set_option(A.OPT_DEVICE_FLATTEN, flatten)
-                _check_equivalent(r, scene, opaque, f"{name} instr={instr} tuning={tuning} flatten={flatten}")
+                got, _ = _check_equivalent(r, scene, opaque, f"{name} instr={instr} tuning={tuning} flatten={flatten}")
+                if tuning == 0 and flatten == 2:
+                    split = got
+                if tuning == TUNE_NO_SPLIT:  # the instances without the quarter path: also against the split pass itself
+                    T.assert_images_identical(got["depth"], split["depth"], f"{name} instr={instr} no split: depth")
+                    T.assert_images_identical(got["ids"], split["ids"], f"{name} instr={instr} no split: ids")
+        r.set_option(A.OPT_DEVICE_FLATTEN, 2)  # (tuning: still TUNE_NO_SPLIT)
+        got, _ = _check_equivalent(r, scene, opaque, f"{name} instr={instr} no split, without IDs", ids=False)
+        T.assert_images_identical(got["depth"], split["depth"], f"{name} instr={instr} no split, without IDs: depth")
     r.set_option(A.OPT_TUNING, 0)
     r.set_option(A.OPT_DEVICE_FLATTEN, 0)
     _check_equivalent(r, scene, opaque, f"{name} without IDs", ids=False)
@@ -242,7 +251,10 @@ def test_multiview_layers_equal_single_passes(hip, k, ids):
         for f in STATS:
             sums[f] += getattr(wst, f)
     lst = r.create_draw_list(opaque, transparent)
-    for form in ("array", "list"):
+    # (form, tuning, instrumented; the last two: the instances without the quarter path, tile_depth_kernel<.., SPLIT = false, .., MV>)
+    for form, tuning, instr in (("array", 0, 1), ("list", 0, 1), ("list", 0, 0), ("array", TUNE_NO_SPLIT, 1), ("array", TUNE_NO_SPLIT, 0)):
+        r.set_option(A.OPT_TUNING, tuning)
+        r.set_option(A.OPT_COUNT_FRAGMENTS, instr)
         _, depth, idt = _targets(r, k, ids)
         if form == "array":
             r.draw_depth_views(scenes, depth.data_ptr(), opaque, ids_ptr=idt.data_ptr() if ids else None)
@@ -252,10 +264,10 @@ def test_multiview_layers_equal_single_passes(hip, k, ids):
         torch.cuda.synchronize()
         dh, ih = _host(depth), (_host(idt).view(np.uint32) if ids else None)
         for i, want in enumerate(singles):
-            T.assert_images_identical(dh[i], want["depth"], f"{form} K={k} layer {i} depth")
+            T.assert_images_identical(dh[i], want["depth"], f"{form} tuning={tuning} instr={instr} K={k} layer {i} depth")
             if ids:
                 T.assert_images_identical(ih[i], want["ids"], f"{form} K={k} layer {i} ids")
-        for f in STATS:
+        for f in (STATS if instr else ()):  # (an uninstrumented pass counts no fragments)
             assert getattr(st, f) == sums[f], f"{form} K={k}: {f}"
         assert st.shaded_fragments == 0
     lst.close()

@@ -12,6 +12,7 @@ import __graft_entry__ as g
 import lighting_ref as LR
 import scenarios as SC
 import svr_testlib as T
+from test_ids_gpu import TUNE_NO_SPLIT
 
 pkg = g.load_package()
 A, S = pkg.abi, pkg.scenes
@@ -89,10 +90,12 @@ TWO_PASS = ["soup", "soup_rgba8", "soup_scissor", "soup_odd_size", "transparent_
 @pytest.mark.parametrize("instrumented", [True, False], ids=["instrumented", "timed"])
 @pytest.mark.parametrize("name", TWO_PASS)
 def test_two_passes_equal_one(hip, name, instrumented, monkeypatch):
-    options = ((A.OPT_COUNT_FRAGMENTS, 1 if instrumented else 0),)
-    want = run(hip, name, monkeypatch, one_pass, options)
-    got = run(hip, name, monkeypatch, two_passes, options)
-    assert_same(got, want, f"{name}: opaque under CLEAR then transparent under LOAD, against one pass")
+    for tuning in (0, TUNE_NO_SPLIT):  # with and without the quarter path: tile_load_kernel<.., SPLIT> both ways
+        options = ((A.OPT_COUNT_FRAGMENTS, 1 if instrumented else 0), (A.OPT_TUNING, tuning))
+        if tuning == 0:
+            want = run(hip, name, monkeypatch, one_pass, options)  # (the split one pass is the reference for both)
+        got = run(hip, name, monkeypatch, two_passes, options)
+        assert_same(got, want, f"{name} tuning={tuning}: opaque under CLEAR then transparent under LOAD, against one pass")
 
 
 @pytest.mark.parametrize("instrumented", [True, False], ids=["instrumented", "timed"])

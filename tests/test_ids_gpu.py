@@ -17,6 +17,7 @@ A, S = pkg.abi, pkg.scenes
 pytestmark = pytest.mark.gpu
 
 TUNE_NO_HIZ, TUNE_HIZ = 32, 64  # SVR_OPT_TUNING bits (csrc/svr_device.h)
+TUNE_NO_SPLIT = 8  # SVR_OPT_TUNING bit 3: no tile is split, launch_tiles picks the instances without the quarter path
 HIP_STATS = ("triangle_count", "drawcall_count", "culled_draws", "rasterized_fragments", "shaded_fragments",
              "binned_triangles", "bin_entries")
 # scenarios whose objects are few enough to isolate one by one on the oracle (and with no fragment at depth 0.0)
@@ -109,9 +110,12 @@ def test_ids_change_nothing_and_agree_on_every_path(hip, name, monkeypatch):
                 assert_ids_match_depth(first, got["depth"], name)
         assert_ids_same(got["ids"], first, f"{name} {path}")
     for opts in (((A.OPT_COUNT_FRAGMENTS, 0),), ((A.OPT_TUNING, TUNE_NO_HIZ),), ((A.OPT_TUNING, TUNE_HIZ),),
-                 ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_HIZ))):
+                 ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_HIZ)),
+                 ((A.OPT_TUNING, TUNE_NO_SPLIT),), ((A.OPT_COUNT_FRAGMENTS, 0), (A.OPT_TUNING, TUNE_NO_SPLIT))):
         got = run(hip, name, monkeypatch, options=opts)
         assert_ids_same(got["ids"], first, f"{name} {opts}")
+        if opts[-1] == (A.OPT_TUNING, TUNE_NO_SPLIT):  # the instances without the quarter path: the whole frame, not only the IDs
+            assert_frames_same(got, want, f"{name} {opts}", stats=())
 
 
 def _sponza_frame(hip, w, h, instanced, path="host", ids=True, options=()):

@@ -21,6 +21,7 @@ SETTINGS = {  # name: (instrumented, tuning)
     "hiz": (0, TUNE_HIZ),
     "hiz_no_split": (0, TUNE_HIZ | TUNE_NO_SPLIT),
     "hiz_instrumented": (1, TUNE_HIZ),
+    "no_split_instrumented": (1, TUNE_NO_SPLIT),
 }
 COUNTS = ("triangle_count", "drawcall_count", "culled_draws")
 INSTR_COUNTS = COUNTS + ("rasterized_fragments", "binned_triangles")

@@ -11,6 +11,7 @@ import pytest
 import __graft_entry__ as g
 import scenarios as SC
 import svr_testlib as T
+from test_ids_gpu import TUNE_NO_SPLIT
 
 pkg = g.load_package()
 A, S, GM = pkg.abi, pkg.scenes, pkg.glmath
@@ -171,13 +172,24 @@ def test_layers_match_single_passes(hip, name, k, monkeypatch):
     scenes = [clip_transformed(box["scene"], i) for i in range(k)]
     got, st = _views(r, scenes, box["opaque"], box["transparent"], init, ids=True)
     sums = {f: 0 for f in SUM_STATS}
+    wants = []
     for i, sc in enumerate(scenes):
         want, wst = _single(r, sc, box["opaque"], box["transparent"], init, ids=True)
+        wants.append(want)
         _assert_layer(got, i, want, f"{name} K={k}")
         for f in SUM_STATS:
             sums[f] += getattr(wst, f)
     for f in SUM_STATS:
         assert getattr(st, f) == sums[f], f"{name}: {f}"
+    if k == 2:  # the instances without the quarter path (tile_mv_kernel, tile_mv_ids_kernel <.., SPLIT = false>): the same layers
+        r.set_option(A.OPT_TUNING, TUNE_NO_SPLIT)
+        for ids in (True, False):
+            for instr in (1, 0):
+                r.set_option(A.OPT_COUNT_FRAGMENTS, instr)
+                got, _ = _views(r, scenes, box["opaque"], box["transparent"], init, ids=ids)
+                for i, want in enumerate(wants):
+                    _assert_layer(got, i, {key: v for key, v in want.items() if ids or key != "ids"},
+                                  f"{name} K={k} no split ids={ids} instr={instr}")
     r.close()
 
 
