@@ -109,6 +109,10 @@ MAX_LIGHTS = 4096
 # include/svr_load.h: the depth loadOp of geometry passes, HIP library only
 LOAD_SYMBOLS = ["svr_set_depth_load_op", "svr_get_depth_load_op"]
 DEPTH_CLEAR, DEPTH_LOAD = 0, 1
+# include/svr_post.h: the HDR post pass (exposure, bloom, tone mapping), HIP library only
+POST_SYMBOLS = ["svr_post_pass"]
+POST_MAX_LEVELS = 8
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -129,6 +133,11 @@ class SvrLightPass(C.Structure):  # include/svr_lighting.h
                 ("sunlight_color", C.c_float * 4), ("lights", C.c_void_p), ("n_lights", C.c_uint32),
                 ("shadow_depth", C.c_void_p), ("shadow_width", C.c_uint32), ("shadow_height", C.c_uint32),
                 ("shadow_viewproj", C.c_float * 16), ("shadow_bias", C.c_float)]
+
+
+class SvrPostPass(C.Structure):  # include/svr_post.h
+    _fields_ = [("exposure", C.c_float), ("bloom_threshold", C.c_float), ("bloom_intensity", C.c_float),
+                ("bloom_levels", C.c_uint32), ("tonemap", C.c_uint32)]
 
 
 POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("intensity", "<f4")])
@@ -242,6 +251,9 @@ class SvrLib:
         if self.has_lighting:
             L.svr_light_pass.argtypes = [P, C.POINTER(SvrLightPass)]
             L.svr_debug_read_light_tiles.argtypes = [P, P, C.c_size_t, C.POINTER(C.c_uint32)]
+        self.has_post = hasattr(L, "svr_post_pass")
+        if self.has_post:
+            L.svr_post_pass.argtypes = [P, C.POINTER(SvrPostPass)]
         self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
         if self.has_depth_load:
             L.svr_set_depth_load_op.argtypes = [P, C.c_int]
@@ -762,6 +774,15 @@ class Renderer:
         if n.value:
             self.lib.check(L.svr_debug_read_light_tiles(self.h, out.ctypes.data, out.size, C.byref(n)))
         return out
+
+    # ---- the HDR post pass (include/svr_post.h)
+    def post_pass(self, exposure=1.0, bloom_threshold=1.0, bloom_intensity=1.0, bloom_levels=4, tonemap=TONEMAP_ACES):
+        """svr_post_pass: expose, bloom and tone-map the scissor's pixels of the RGBA16F colour target in place.
+        bloom_levels: 0 .. POST_MAX_LEVELS (0: the tone map alone); tonemap: TONEMAP_*"""
+        if not getattr(self.lib, "has_post", False):
+            raise SvrError(-5, f"{self.lib.backend} has no post pass (include/svr_post.h)")
+        p = SvrPostPass(float(exposure), float(bloom_threshold), float(bloom_intensity), int(bloom_levels), int(tonemap))
+        self.lib.check(self.lib.lib.svr_post_pass(self.h, C.byref(p)))
 
     # ---- the depth loadOp (include/svr_load.h)
     def _need_depth_load(self):

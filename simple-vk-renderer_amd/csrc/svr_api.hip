@@ -29,6 +29,7 @@
 #include "../../include/svr_attributes.h"
 #include "../../include/svr_ids.h"
 #include "../../include/svr_lighting.h"
+#include "../../include/svr_post.h"
 #include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
@@ -257,7 +258,7 @@ struct SvrContext {
   PassSet sets[NSETS];
   int set_pos = 0;
   // operation log (see "the operation log" below): a pass, or a fill of the colour target (every other operation)
-  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass
+  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light, Post };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass; Post: svr_post_pass
   enum class PassInput { Draws, Objects, List };  // what a pass reads: the one place that says so (P.flatten follows it)
   struct LoggedOp {
     OpKind kind = OpKind::Pass;
@@ -288,6 +289,8 @@ struct SvrContext {
     LightLaunch light{};
     uint32_t light_tiles_y = 0;
     std::vector<SvrPointLight> lights;
+    // Post (include/svr_post.h): the kernels' parameters as recorded
+    PostLaunch post{};
     bool flattened() const { return input != PassInput::Draws; }
     // a fill: colour target, its format and extent, the rows it writes
     void* target = nullptr;
@@ -353,6 +356,9 @@ struct SvrContext {
   DevPtr<SvrPointLight> d_lights;
   DevPtr<uint32_t> d_light_tiles;
   uint32_t light_tiles_n = 0;
+  // svr_post_pass: the level images of the bloom (4 halves per texel), sized for the context's extent; allocated once, by
+  // the first post pass
+  DevPtr<uint2> d_post_levels;
   SvrStats stats{};
   // Declared last, so it goes first: its entries hold draw-list versions and pyramids, and name the memory above.
   std::deque<LoggedOp> log;
@@ -782,6 +788,8 @@ int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying 
       HIPCHK(hipMemcpyAsync(ctx->d_lights.get(), stage, bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     launch_light(op.light, op.target_fmt, op.light_tiles_y, ctx->stream);
+  } else if (op.kind == SvrContext::OpKind::Post) {  // (every kernel of it writes nothing while the poison flag is up)
+    launch_post(op.post, ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Background) {
     launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison.get(), ctx->stream);
   } else {
@@ -2591,6 +2599,45 @@ int svr_debug_read_light_tiles(SvrContext* ctx, uint32_t* counts, size_t capacit
   if (capacity < ctx->light_tiles_n) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: buffer too small");
   if (ctx->light_tiles_n) HIPCHK(hipMemcpy(counts, ctx->d_light_tiles.get(), (size_t)ctx->light_tiles_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return SVR_OK;
+}
+
+// ---------------------------------------------------------------- the HDR post pass (include/svr_post.h)
+int svr_post_pass(SvrContext* ctx, const SvrPostPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: null argument");
+  if (!(std::isfinite(pass->exposure) && pass->exposure > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the exposure must be finite and greater than 0");
+  if (!(std::isfinite(pass->bloom_threshold) && pass->bloom_threshold >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the bloom threshold must be finite and at least 0");
+  if (!(std::isfinite(pass->bloom_intensity) && pass->bloom_intensity >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the bloom intensity must be finite and at least 0");
+  if (pass->bloom_levels > SVR_POST_MAX_LEVELS) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: more than SVR_POST_MAX_LEVELS bloom levels");
+  if (pass->tonemap > SVR_TONEMAP_ACES) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: unknown tone-mapping operator");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_post_pass: the colour target must be RGBA16F (an RGBA8 target holds no HDR values)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_post_pass: not under svr_set_row_interleave with a stride above 1");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  uint32_t off[SVR_POST_MAX_LEVELS], lw[SVR_POST_MAX_LEVELS], lh[SVR_POST_MAX_LEVELS];
+  // (the extents grow with the image's, so the levels of any scissor fit in those of the whole target)
+  if (!ctx->d_post_levels) DEV_ALLOC(ctx->d_post_levels, post_level_layout(ctx->W, ctx->H, SVR_POST_MAX_LEVELS, off, lw, lh) * sizeof(uint2));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Post, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
+  PostLaunch& P = op->post;
+  P.color = (uint2*)ctx->color;
+  P.W = ctx->W;
+  P.sx = ctx->sx;
+  P.sy = ctx->sy;
+  P.sw = ctx->sw;
+  P.sh = ctx->sh;
+  P.levels = ctx->d_post_levels.get();
+  P.n_levels = pass->bloom_levels;
+  post_level_layout(ctx->sw, ctx->sh, pass->bloom_levels, P.off, P.lw, P.lh);
+  P.exposure = pass->exposure;
+  P.threshold = pass->bloom_threshold;
+  P.intensity = pass->bloom_intensity;
+  P.tonemap = pass->tonemap;
+  P.poison = ctx->d_poison.get();
+  return submit_fill(ctx, *op);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // svr_launch.h — host-callable launchers of the HIP kernels (one per kernel file).
 #pragma once
 #include "../../include/svr_lighting.h"
+#include "../../include/svr_post.h"
 #include "svr_device.h"
 
 namespace svr {
@@ -73,6 +74,22 @@ struct LightLaunch {
   const uint32_t* poison;
 };
 void launch_light(const LightLaunch& L, int color_format, uint32_t tiles_y, hipStream_t s);
+// k_post.hip: the HDR post pass (include/svr_post.h)
+struct PostLaunch {
+  uint2* color;                 // the RGBA16F colour target, W texels per row: the scissor's RGB halves are rewritten in place
+  uint32_t W;
+  uint32_t sx, sy, sw, sh;      // the scissor: the image of the pass
+  uint2* levels;                // the context's level images (B_i, then U_i in place): 4 halves per texel
+  uint32_t n_levels;            // 0 .. SVR_POST_MAX_LEVELS
+  uint32_t off[SVR_POST_MAX_LEVELS], lw[SVR_POST_MAX_LEVELS], lh[SVR_POST_MAX_LEVELS];  // C22: texel offset (even) and extent of each level
+  float exposure, threshold, intensity;
+  uint32_t tonemap;             // SVR_TONEMAP_*
+  const uint32_t* poison;
+};
+// C22: the level extents of a sw x sh image and their packed offsets (each level starts on 16 bytes); returns the texels
+size_t post_level_layout(uint32_t sw, uint32_t sh, uint32_t n_levels, uint32_t* off, uint32_t* lw, uint32_t* lh);
+// n_levels bloom_level_kernel launches, n_levels - 1 bloom_up_kernel launches and one post_composite_kernel, all on s
+void launch_post(const PostLaunch& P, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

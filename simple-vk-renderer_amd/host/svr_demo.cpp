@@ -12,6 +12,9 @@
 //       --deferred 1: every frame is the opaque objects with normal and albedo planes, a lighting pass, then the transparent
 //           objects under SVR_DEPTH_LOAD (include/svr_attributes.h, svr_lighting.h, svr_load.h; HIP library only): the
 //           dumps are a normal run's
+//       --post clamp|reinhard|aces:<levels> [--exposure E] [--bloom-threshold T] [--bloom-intensity I]: the HDR post pass
+//           (include/svr_post.h, HIP library only) behind every frame's last pass and before the swapchain copy: the
+//           .color and .swapchain dumps are taken after it
 //       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
 //           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
 //           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
@@ -81,7 +84,8 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false;
-  std::string occlusion = "off";
+  std::string occlusion = "off", post_arg;
+  SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
   bool select = false;
@@ -105,6 +109,10 @@ int main(int argc, char** argv) {
     else if (a == "--retained") retained = atoi(argv[i + 1]);  // 1: draw through a draw list (include/svr_draw_list.h)
     else if (a == "--depth-only") depth_only = atoi(argv[i + 1]) != 0;  // depth-only passes (include/svr_depth.h)
     else if (a == "--deferred") deferred = atoi(argv[i + 1]) != 0;  // G-buffer pass, lighting pass, transparent objects under LOAD
+    else if (a == "--post") post_arg = argv[i + 1];  // <operator>:<levels> (include/svr_post.h)
+    else if (a == "--exposure") post.exposure = (float)atof(argv[i + 1]);
+    else if (a == "--bloom-threshold") post.bloom_threshold = (float)atof(argv[i + 1]);
+    else if (a == "--bloom-intensity") post.bloom_intensity = (float)atof(argv[i + 1]);
     else if (a == "--occlusion") occlusion = argv[i + 1];  // off | last | prepass (include/svr_occlusion.h)
     else if (a == "--views") views = (uint32_t)atoi(argv[i + 1]);  // N cameras in one multiview pass (include/svr_views.h)
     else if (a == "--yaw") { yaw = (float)atof(argv[i + 1]); set_yaw = true; }  // the camera's yaw (radians), after the scene's own
@@ -137,8 +145,30 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: svr_demo --lib <shared library exporting svr.h> [--width W --height H --frames N --dump prefix]\n"
                     "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n"
                     "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1] [--deferred 1]\n"
-                    "                [--occlusion off|last|prepass]\n");
+                    "                [--occlusion off|last|prepass]\n"
+                    "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n");
     return 2;
+  }
+  if (!post_arg.empty()) {
+    const size_t colon = post_arg.find(':');
+    const std::string op = post_arg.substr(0, colon);
+    char* end = nullptr;
+    const long levels = colon == std::string::npos ? -1 : strtol(post_arg.c_str() + colon + 1, &end, 10);
+    const bool known = op == "clamp" || op == "reinhard" || op == "aces";
+    post.tonemap = op == "aces" ? SVR_TONEMAP_ACES : (op == "reinhard" ? SVR_TONEMAP_REINHARD : SVR_TONEMAP_CLAMP);
+    if (!known || levels < 0 || levels > SVR_POST_MAX_LEVELS || !end || *end || end == post_arg.c_str() + colon + 1) {
+      fprintf(stderr, "--post: expected clamp|reinhard|aces:<levels 0..%d>, got '%s'\n", SVR_POST_MAX_LEVELS, post_arg.c_str());
+      return 2;
+    }
+    post.bloom_levels = (uint32_t)levels;
+    if (views) {
+      fprintf(stderr, "--post: not with --views (the pass works on the context's own colour target)\n");
+      return 1;
+    }
+    if (ranks > 1) {
+      fprintf(stderr, "--post: not with --ranks (a band rank would bloom its own rows only)\n");
+      return 1;
+    }
   }
   // the sharded frame: one process per rank, forked before anything touches the GPU; rank 0 makes the id
   int rank = 0;
@@ -432,6 +462,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--deferred: not with --views, --depth-only, --retained or --occlusion\n");
     return 1;
   }
+  if (!post_arg.empty() && !eng.api.svr_post_pass) {
+    fprintf(stderr, "--post: the library has no post pass (include/svr_post.h)\n");
+    return 1;
+  }
   if (select && !eng.enable_ids()) {
     fprintf(stderr, "--select: %s\n", eng.error.c_str());
     return 1;
@@ -445,6 +479,10 @@ int main(int argc, char** argv) {
     }
     if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : (depth_only ? eng.draw_depth() : (deferred ? eng.draw_deferred() : eng.draw_geometry())))) {
       fprintf(stderr, "draw failed: %s\n", eng.error.c_str());
+      return 1;
+    }
+    if (!post_arg.empty() && !eng.post_pass(post)) {  // behind the frame's last pass, before the swapchain copy
+      fprintf(stderr, "%s\n", eng.error.rfind("--post", 0) == 0 ? eng.error.c_str() : ("--post: " + eng.error).c_str());
       return 1;
     }
   }

@@ -47,6 +47,7 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_enable_attributes = reinterpret_cast<decltype(svr_enable_attributes)>(dlsym(handle, "svr_enable_attributes"));
   svr_light_pass = reinterpret_cast<decltype(svr_light_pass)>(dlsym(handle, "svr_light_pass"));
   svr_set_depth_load_op = reinterpret_cast<decltype(svr_set_depth_load_op)>(dlsym(handle, "svr_set_depth_load_op"));
+  svr_post_pass = reinterpret_cast<decltype(svr_post_pass)>(dlsym(handle, "svr_post_pass"));
   return ok;
 }
 void SvrApi::unload() {
@@ -390,6 +391,18 @@ bool SvrEngine::draw_depth() {  // draw_geometry without shading: a shadow or de
   main_draw_context.transparent_surfaces.clear();
   drawn_sources.swap(main_draw_context.opaque_sources);
   main_draw_context.opaque_sources.clear();
+  return true;
+}
+
+bool SvrEngine::post_pass(const SvrPostPass& pass) {
+  if (!api.svr_post_pass) {
+    error = "--post: the library has no post pass (include/svr_post.h)";
+    return false;
+  }
+  if (api.svr_post_pass(ctx, &pass)) {
+    error = api.svr_last_error();
+    return false;
+  }
   return true;
 }
 

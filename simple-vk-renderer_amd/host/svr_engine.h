@@ -22,6 +22,7 @@
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
+#include "../../include/svr_post.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -51,6 +52,8 @@ struct SvrApi {
   SVR_FN(svr_set_occlusion_pyramid)
   // include/svr_attributes.h, svr_lighting.h and svr_load.h: optional (HIP library only), needed by SvrEngine::draw_deferred
   SVR_FN(svr_enable_attributes) SVR_FN(svr_light_pass) SVR_FN(svr_set_depth_load_op)
+  // include/svr_post.h: optional (HIP library only), needed by SvrEngine::post_pass
+  SVR_FN(svr_post_pass)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -167,6 +170,9 @@ struct SvrEngine {
   // depth, blended over the lit colour.  The frame is the forward one, bit for bit.
   bool gbuffer = false;  // the planes are enabled
   bool draw_deferred();
+  // The HDR post pass (svr_demo --post <operator>:<levels>, include/svr_post.h): exposure, bloom and the operator over the
+  // colour target, after the frame's last pass and before the swapchain copy.
+  bool post_pass(const SvrPostPass& pass);
   // Occlusion culling (svr_demo --occlusion off|last|prepass, include/svr_occlusion.h).  Last: each frame's geometry
   // culls against the pyramid of the previous frame's depth (built behind every frame; before the first it is all 0.0
   // and culls nothing).  Prepass: each frame first draws the opaque objects whose material is in occluder_materials
