@@ -113,6 +113,9 @@ DEPTH_CLEAR, DEPTH_LOAD = 0, 1
 POST_SYMBOLS = ["svr_post_pass"]
 POST_MAX_LEVELS = 8
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+# include/svr_temporal.h: temporal antialiasing (history reprojection, neighbourhood clamp, blend), HIP library only
+TEMPORAL_SYMBOLS = ["svr_temporal_resolve", "svr_debug_read_temporal_history"]
+TEMPORAL_RESET, TEMPORAL_NO_CLAMP = 1, 2
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -138,6 +141,10 @@ class SvrLightPass(C.Structure):  # include/svr_lighting.h
 class SvrPostPass(C.Structure):  # include/svr_post.h
     _fields_ = [("exposure", C.c_float), ("bloom_threshold", C.c_float), ("bloom_intensity", C.c_float),
                 ("bloom_levels", C.c_uint32), ("tonemap", C.c_uint32)]
+
+
+class SvrTemporalPass(C.Structure):  # include/svr_temporal.h
+    _fields_ = [("reproject", C.c_float * 16), ("blend", C.c_float), ("flags", C.c_uint32)]
 
 
 POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("intensity", "<f4")])
@@ -254,6 +261,10 @@ class SvrLib:
         self.has_post = hasattr(L, "svr_post_pass")
         if self.has_post:
             L.svr_post_pass.argtypes = [P, C.POINTER(SvrPostPass)]
+        self.has_temporal = hasattr(L, "svr_temporal_resolve")
+        if self.has_temporal:
+            L.svr_temporal_resolve.argtypes = [P, C.POINTER(SvrTemporalPass)]
+            L.svr_debug_read_temporal_history.argtypes = [P, P, C.c_size_t, C.POINTER(C.c_uint32)]
         self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
         if self.has_depth_load:
             L.svr_set_depth_load_op.argtypes = [P, C.c_int]
@@ -783,6 +794,29 @@ class Renderer:
             raise SvrError(-5, f"{self.lib.backend} has no post pass (include/svr_post.h)")
         p = SvrPostPass(float(exposure), float(bloom_threshold), float(bloom_intensity), int(bloom_levels), int(tonemap))
         self.lib.check(self.lib.lib.svr_post_pass(self.h, C.byref(p)))
+
+    # ---- temporal antialiasing (include/svr_temporal.h)
+    def _need_temporal(self):
+        if not getattr(self.lib, "has_temporal", False):
+            raise SvrError(-5, f"{self.lib.backend} has no temporal pass (include/svr_temporal.h)")
+
+    def temporal_resolve(self, reproject, blend, flags=0):
+        """svr_temporal_resolve: blend the scissor's pixels of the RGBA16F colour target with the reprojected, clamped
+        history, in place.  reproject: 4 x 4 indexed [col][row] like glmath's matrices
+        (glmath.temporal_reproject); blend: the current frame's weight in (0, 1]; flags: TEMPORAL_*"""
+        self._need_temporal()
+        p = SvrTemporalPass()
+        p.reproject = _f16m(reproject)
+        p.blend, p.flags = float(blend), int(flags)
+        self.lib.check(self.lib.lib.svr_temporal_resolve(self.h, C.byref(p)))
+
+    def read_temporal_history(self):
+        """svr_debug_read_temporal_history -> (uint16 [H, W, 4] fp16 bit patterns the next resolve will read, valid)"""
+        self._need_temporal()
+        out = np.zeros((self.height, self.width, 4), np.uint16)
+        valid = C.c_uint32(0)
+        self.lib.check(self.lib.lib.svr_debug_read_temporal_history(self.h, out.ctypes.data, out.nbytes, C.byref(valid)))
+        return out, bool(valid.value)
 
     # ---- the depth loadOp (include/svr_load.h)
     def _need_depth_load(self):

@@ -30,6 +30,7 @@
 #include "../../include/svr_ids.h"
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_post.h"
+#include "../../include/svr_temporal.h"
 #include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
@@ -258,7 +259,7 @@ struct SvrContext {
   PassSet sets[NSETS];
   int set_pos = 0;
   // operation log (see "the operation log" below): a pass, or a fill of the colour target (every other operation)
-  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light, Post };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass; Post: svr_post_pass
+  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light, Post, Temporal };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass; Post: svr_post_pass; Temporal: svr_temporal_resolve
   enum class PassInput { Draws, Objects, List };  // what a pass reads: the one place that says so (P.flatten follows it)
   struct LoggedOp {
     OpKind kind = OpKind::Pass;
@@ -291,6 +292,8 @@ struct SvrContext {
     std::vector<SvrPointLight> lights;
     // Post (include/svr_post.h): the kernels' parameters as recorded
     PostLaunch post{};
+    // Temporal (include/svr_temporal.h): the kernels' parameters as recorded, the history roles and validity among them
+    TemporalLaunch temporal{};
     bool flattened() const { return input != PassInput::Draws; }
     // a fill: colour target, its format and extent, the rows it writes
     void* target = nullptr;
@@ -359,6 +362,13 @@ struct SvrContext {
   // svr_post_pass: the level images of the bloom (4 halves per texel), sized for the context's extent; allocated once, by
   // the first post pass
   DevPtr<uint2> d_post_levels;
+  // svr_temporal_resolve: the two history images (4 halves per texel, the context's extent), allocated and zeroed by the
+  // first resolve.  temporal_read names the one the next resolve reads; temporal_has: a resolve was accepted, with the
+  // scissor temporal_scissor.  All three change at an accepted call only, in call order.
+  DevPtr<uint2> d_temporal[2];
+  int temporal_read = 0;
+  bool temporal_has = false;
+  uint32_t temporal_scissor[4] = {0, 0, 0, 0};
   SvrStats stats{};
   // Declared last, so it goes first: its entries hold draw-list versions and pyramids, and name the memory above.
   std::deque<LoggedOp> log;
@@ -790,6 +800,8 @@ int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying 
     launch_light(op.light, op.target_fmt, op.light_tiles_y, ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Post) {  // (every kernel of it writes nothing while the poison flag is up)
     launch_post(op.post, ctx->stream);
+  } else if (op.kind == SvrContext::OpKind::Temporal) {  // (both kernels write nothing while the poison flag is up)
+    launch_temporal(op.temporal, ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Background) {
     launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison.get(), ctx->stream);
   } else {
@@ -2638,6 +2650,76 @@ int svr_post_pass(SvrContext* ctx, const SvrPostPass* pass) {
   P.tonemap = pass->tonemap;
   P.poison = ctx->d_poison.get();
   return submit_fill(ctx, *op);
+}
+
+// ---------------------------------------------------------------- temporal antialiasing (include/svr_temporal.h)
+static bool temporal_history_usable(const SvrContext* ctx) {
+  return ctx->temporal_has && ctx->temporal_scissor[0] == ctx->sx && ctx->temporal_scissor[1] == ctx->sy &&
+         ctx->temporal_scissor[2] == ctx->sw && ctx->temporal_scissor[3] == ctx->sh;
+}
+
+int svr_temporal_resolve(SvrContext* ctx, const SvrTemporalPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: null argument");
+  if (!(std::isfinite(pass->blend) && pass->blend > 0.0f && pass->blend <= 1.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: the blend must be finite, greater than 0 and at most 1");
+  if (pass->flags & ~(uint32_t)(SVR_TEMPORAL_RESET | SVR_TEMPORAL_NO_CLAMP)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: unknown flag bits");
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(pass->reproject[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: reproject[" + std::to_string(i) + "] is not finite");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: the colour target must be RGBA16F");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: not under svr_set_row_interleave with a stride above 1");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  const size_t hist_bytes = (size_t)ctx->W * ctx->H * sizeof(uint2);
+  for (int i = 0; i < 2; i++)
+    if (!ctx->d_temporal[i]) {  // zeroed once: the read-back hook shows the whole extent, the kernels read the scissor only
+      DEV_ALLOC(ctx->d_temporal[i], hist_bytes);
+      HIPCHK(hipMemsetAsync(ctx->d_temporal[i].get(), 0, hist_bytes, ctx->stream));
+    }
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Temporal, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
+  TemporalLaunch& T = op->temporal;
+  T.color = (uint2*)ctx->color;
+  T.depth = ctx->depth;
+  T.W = ctx->W;
+  T.H = ctx->H;
+  T.sx = ctx->sx;
+  T.sy = ctx->sy;
+  T.sw = ctx->sw;
+  T.sh = ctx->sh;
+  // the roles and the validity are decided here, in call order, and travel with the operation: a replay finds them as they were
+  T.hist_in = ctx->d_temporal[ctx->temporal_read].get();
+  T.hist_out = ctx->d_temporal[ctx->temporal_read ^ 1].get();
+  T.history_valid = temporal_history_usable(ctx) && !(pass->flags & SVR_TEMPORAL_RESET) ? 1u : 0u;
+  T.clamp = (pass->flags & SVR_TEMPORAL_NO_CLAMP) ? 0u : 1u;
+  std::memcpy(T.reproject, pass->reproject, sizeof(T.reproject));
+  T.blend = pass->blend;
+  T.two_over_w = 2.0f / (float)ctx->W;
+  T.two_over_h = 2.0f / (float)ctx->H;
+  T.half_w = (float)ctx->W * 0.5f;
+  T.half_h = (float)ctx->H * 0.5f;
+  T.poison = ctx->d_poison.get();
+  ctx->temporal_read ^= 1;
+  ctx->temporal_has = true;
+  ctx->temporal_scissor[0] = ctx->sx;
+  ctx->temporal_scissor[1] = ctx->sy;
+  ctx->temporal_scissor[2] = ctx->sw;
+  ctx->temporal_scissor[3] = ctx->sh;
+  return submit_fill(ctx, *op);
+}
+
+int svr_debug_read_temporal_history(SvrContext* ctx, void* dst, size_t bytes, uint32_t* valid) {
+  if (!ctx || !valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_temporal_history: null argument");
+  const size_t need = (size_t)ctx->W * ctx->H * sizeof(uint2);
+  if (dst && bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_temporal_history: buffer too small");
+  if (int e = svr_sync(ctx)) return e;
+  *valid = temporal_history_usable(ctx) ? 1u : 0u;
+  if (!dst) return SVR_OK;
+  if (ctx->d_temporal[ctx->temporal_read])
+    HIPCHK(hipMemcpy(dst, ctx->d_temporal[ctx->temporal_read].get(), need, hipMemcpyDeviceToHost));
+  else
+    std::memset(dst, 0, need);
+  return SVR_OK;
 }
 
 }  // extern "C"

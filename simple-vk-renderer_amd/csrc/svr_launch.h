@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_post.h"
+#include "../../include/svr_temporal.h"
 #include "svr_device.h"
 
 namespace svr {
@@ -90,6 +91,24 @@ struct PostLaunch {
 size_t post_level_layout(uint32_t sw, uint32_t sh, uint32_t n_levels, uint32_t* off, uint32_t* lw, uint32_t* lh);
 // n_levels bloom_level_kernel launches, n_levels - 1 bloom_up_kernel launches and one post_composite_kernel, all on s
 void launch_post(const PostLaunch& P, hipStream_t s);
+// k_temporal.hip: temporal antialiasing (include/svr_temporal.h)
+struct TemporalLaunch {
+  uint2* color;                 // the RGBA16F colour target, W texels per row: the scissor's RGB halves are rewritten in place
+  const float* depth;           // the depth target, read as it stands in stream order
+  uint32_t W, H;
+  uint32_t sx, sy, sw, sh;      // the scissor: the image of the pass
+  const uint2* hist_in;         // the history this resolve reads (W x H texels of 4 halves); read only where history_valid
+  uint2* hist_out;              // ... and the one it writes: the roles are fixed at the call
+  uint32_t history_valid;       // decided at the call (include/svr_temporal.h "History")
+  uint32_t clamp;               // 0 under SVR_TEMPORAL_NO_CLAMP
+  float reproject[16];
+  float blend;
+  float two_over_w, two_over_h; // C17: divided once, on the host
+  float half_w, half_h;         // C29: W / 2, H / 2
+  const uint32_t* poison;
+};
+// one temporal_resolve_kernel and one temporal_copy_kernel, on s
+void launch_temporal(const TemporalLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

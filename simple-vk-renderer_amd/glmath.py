@@ -195,3 +195,72 @@ def trs(translation, rotation_xyzw, scale_v):
     rm = quat_to_mat4((w, x, y, z))
     sm = scale(identity(), scale_v)
     return matmul(matmul(tm, rm), sm)
+
+
+# ---- temporal antialiasing (include/svr_temporal.h): the caller's side, bit for bit host/svr_math.h's
+def halton(i, base):
+    """the i-th element (i >= 1) of the Halton sequence of a base: accumulated in double, rounded once"""
+    i, base = int(i), int(base)
+    f, r = 1.0, 0.0
+    while i > 0:
+        f = f / float(base)
+        r = r + f * float(i % base)
+        i //= base
+    return f32(r)
+
+
+def jitter_projection(proj, jx, jy, w, h):
+    """proj shifted by (jx, jy) pixels in a w x h target: a point at pixel (px, py) lands at (px + jx, py + jy)"""
+    proj = np.asarray(proj, dtype=f32)
+    ax, ay = (f32(2) * f32(jx)) / f32(w), (f32(2) * f32(jy)) / f32(h)
+    r = proj.copy()
+    for c in range(4):
+        r[c][0] = proj[c][0] + ax * proj[c][3]
+        r[c][1] = proj[c][1] + ay * proj[c][3]
+    return r
+
+
+def temporal_reproject(prev_viewproj, viewproj):
+    """SvrTemporalPass.reproject = prev_viewproj * inverse(viewproj), both without jitter: the inverse (inverse()'s cofactor
+    expansion) and the product are taken in double and rounded to fp32 once"""
+    m = [[float(x) for x in col] for col in np.asarray(viewproj, dtype=f32)]
+    p = [[float(x) for x in col] for col in np.asarray(prev_viewproj, dtype=f32)]
+    c00 = m[2][2] * m[3][3] - m[3][2] * m[2][3]
+    c02 = m[1][2] * m[3][3] - m[3][2] * m[1][3]
+    c03 = m[1][2] * m[2][3] - m[2][2] * m[1][3]
+    c04 = m[2][1] * m[3][3] - m[3][1] * m[2][3]
+    c06 = m[1][1] * m[3][3] - m[3][1] * m[1][3]
+    c07 = m[1][1] * m[2][3] - m[2][1] * m[1][3]
+    c08 = m[2][1] * m[3][2] - m[3][1] * m[2][2]
+    c10 = m[1][1] * m[3][2] - m[3][1] * m[1][2]
+    c11 = m[1][1] * m[2][2] - m[2][1] * m[1][2]
+    c12 = m[2][0] * m[3][3] - m[3][0] * m[2][3]
+    c14 = m[1][0] * m[3][3] - m[3][0] * m[1][3]
+    c15 = m[1][0] * m[2][3] - m[2][0] * m[1][3]
+    c16 = m[2][0] * m[3][2] - m[3][0] * m[2][2]
+    c18 = m[1][0] * m[3][2] - m[3][0] * m[1][2]
+    c19 = m[1][0] * m[2][2] - m[2][0] * m[1][2]
+    c20 = m[2][0] * m[3][1] - m[3][0] * m[2][1]
+    c22 = m[1][0] * m[3][1] - m[3][0] * m[1][1]
+    c23 = m[1][0] * m[2][1] - m[2][0] * m[1][1]
+    f0, f1, f2 = (c00, c00, c02, c03), (c04, c04, c06, c07), (c08, c08, c10, c11)
+    f3, f4, f5 = (c12, c12, c14, c15), (c16, c16, c18, c19), (c20, c20, c22, c23)
+    v0 = (m[1][0], m[0][0], m[0][0], m[0][0])
+    v1 = (m[1][1], m[0][1], m[0][1], m[0][1])
+    v2 = (m[1][2], m[0][2], m[0][2], m[0][2])
+    v3 = (m[1][3], m[0][3], m[0][3], m[0][3])
+    sa, sb = (1.0, -1.0, 1.0, -1.0), (-1.0, 1.0, -1.0, 1.0)
+    inv = [[0.0] * 4 for _ in range(4)]
+    for k in range(4):
+        inv[0][k] = (v1[k] * f0[k] - v2[k] * f1[k] + v3[k] * f2[k]) * sa[k]
+        inv[1][k] = (v0[k] * f0[k] - v2[k] * f3[k] + v3[k] * f4[k]) * sb[k]
+        inv[2][k] = (v0[k] * f1[k] - v1[k] * f3[k] + v3[k] * f5[k]) * sa[k]
+        inv[3][k] = (v0[k] * f2[k] - v1[k] * f4[k] + v2[k] * f5[k]) * sb[k]
+    d0, d1, d2, d3 = m[0][0] * inv[0][0], m[0][1] * inv[1][0], m[0][2] * inv[2][0], m[0][3] * inv[3][0]
+    one_over_det = 1.0 / ((d0 + d1) + (d2 + d3))
+    r = np.empty((4, 4), dtype=f32)
+    for j in range(4):
+        col = [inv[j][k] * one_over_det for k in range(4)]
+        for k in range(4):
+            r[j][k] = f32(((p[0][k] * col[0] + p[1][k] * col[1]) + p[2][k] * col[2]) + p[3][k] * col[3])
+    return r

@@ -15,6 +15,10 @@
 //       --post clamp|reinhard|aces:<levels> [--exposure E] [--bloom-threshold T] [--bloom-intensity I]: the HDR post pass
 //           (include/svr_post.h, HIP library only) behind every frame's last pass and before the swapchain copy: the
 //           .color and .swapchain dumps are taken after it
+//       --taa <blend>: temporal antialiasing (include/svr_temporal.h, HIP library only): every frame is drawn with a sub-pixel
+//           jitter (Halton(2, 3) - 0.5 pixels, a period of 16 frames) and resolved against the reprojected, clamped history
+//           with the given weight of the current frame, behind the frame's last geometry or lighting pass and in front of
+//           --post; not with --views or --ranks
 //       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
 //           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
 //           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
@@ -84,7 +88,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false;
-  std::string occlusion = "off", post_arg;
+  std::string occlusion = "off", post_arg, taa_arg;
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -110,6 +114,7 @@ int main(int argc, char** argv) {
     else if (a == "--depth-only") depth_only = atoi(argv[i + 1]) != 0;  // depth-only passes (include/svr_depth.h)
     else if (a == "--deferred") deferred = atoi(argv[i + 1]) != 0;  // G-buffer pass, lighting pass, transparent objects under LOAD
     else if (a == "--post") post_arg = argv[i + 1];  // <operator>:<levels> (include/svr_post.h)
+    else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
     else if (a == "--exposure") post.exposure = (float)atof(argv[i + 1]);
     else if (a == "--bloom-threshold") post.bloom_threshold = (float)atof(argv[i + 1]);
     else if (a == "--bloom-intensity") post.bloom_intensity = (float)atof(argv[i + 1]);
@@ -146,8 +151,26 @@ int main(int argc, char** argv) {
                     "                [--gltf file.glb|file.gltf --camera x,y,z,pitch,yaw] [--background 0|1] [--swapchain WxH]\n"
                     "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1] [--deferred 1]\n"
                     "                [--occlusion off|last|prepass]\n"
-                    "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n");
+                    "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
+                    "                [--taa blend]\n");
     return 2;
+  }
+  float taa_blend = 0.f;
+  if (!taa_arg.empty()) {
+    char* end = nullptr;
+    taa_blend = strtof(taa_arg.c_str(), &end);
+    if (!end || *end || end == taa_arg.c_str() || !(taa_blend > 0.f && taa_blend <= 1.f)) {
+      fprintf(stderr, "--taa: expected a blend in (0, 1], got '%s'\n", taa_arg.c_str());
+      return 2;
+    }
+    if (views) {
+      fprintf(stderr, "--taa: not with --views (the pass works on the context's own colour target)\n");
+      return 1;
+    }
+    if (ranks > 1) {
+      fprintf(stderr, "--taa: not with --ranks (a band rank would clamp taps at its band's edge and keep its own history)\n");
+      return 1;
+    }
   }
   if (!post_arg.empty()) {
     const size_t colon = post_arg.find(':');
@@ -466,6 +489,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--post: the library has no post pass (include/svr_post.h)\n");
     return 1;
   }
+  if (!taa_arg.empty() && !eng.api.svr_temporal_resolve) {
+    fprintf(stderr, "--taa: the library has no temporal pass (include/svr_temporal.h)\n");
+    return 1;
+  }
+  eng.taa_blend = taa_blend;
   if (select && !eng.enable_ids()) {
     fprintf(stderr, "--select: %s\n", eng.error.c_str());
     return 1;
@@ -479,6 +507,10 @@ int main(int argc, char** argv) {
     }
     if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : (depth_only ? eng.draw_depth() : (deferred ? eng.draw_deferred() : eng.draw_geometry())))) {
       fprintf(stderr, "draw failed: %s\n", eng.error.c_str());
+      return 1;
+    }
+    if (taa_blend > 0.f && !eng.temporal_resolve()) {  // behind the frame's last pass, in front of the post pass
+      fprintf(stderr, "%s\n", eng.error.rfind("--taa", 0) == 0 ? eng.error.c_str() : ("--taa: " + eng.error).c_str());
       return 1;
     }
     if (!post_arg.empty() && !eng.post_pass(post)) {  // behind the frame's last pass, before the swapchain copy

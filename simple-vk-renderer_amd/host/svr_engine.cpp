@@ -48,6 +48,7 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_light_pass = reinterpret_cast<decltype(svr_light_pass)>(dlsym(handle, "svr_light_pass"));
   svr_set_depth_load_op = reinterpret_cast<decltype(svr_set_depth_load_op)>(dlsym(handle, "svr_set_depth_load_op"));
   svr_post_pass = reinterpret_cast<decltype(svr_post_pass)>(dlsym(handle, "svr_post_pass"));
+  svr_temporal_resolve = reinterpret_cast<decltype(svr_temporal_resolve)>(dlsym(handle, "svr_temporal_resolve"));
   return ok;
 }
 void SvrApi::unload() {
@@ -215,6 +216,12 @@ void SvrEngine::update_scene() {  // src/vk_engine.cpp:1479-1512
   mat4 proj = svrm::perspective(svrm::radians(70.f), (float)width / (float)height, 10000.f, 0.1f);
   proj.m[1][1] *= -1;
   mat4 viewproj = svrm::mul(proj, view);
+  if (taa_blend > 0.f) {  // --taa: the frame is drawn with a sub-pixel shift, the reprojection uses the unshifted matrices
+    taa_viewproj = viewproj;
+    const unsigned i = taa_frame % 16u + 1u;
+    proj = svrm::jitter_projection(proj, svrm::halton(i, 2) - 0.5f, svrm::halton(i, 3) - 0.5f, (float)width, (float)height);
+    viewproj = svrm::mul(proj, view);
+  }
   std::memcpy(scene_data.view, view.data(), 64);
   std::memcpy(scene_data.proj, proj.data(), 64);
   std::memcpy(scene_data.viewproj, viewproj.data(), 64);
@@ -403,6 +410,25 @@ bool SvrEngine::post_pass(const SvrPostPass& pass) {
     error = api.svr_last_error();
     return false;
   }
+  return true;
+}
+
+bool SvrEngine::temporal_resolve() {
+  if (!api.svr_temporal_resolve) {
+    error = "--taa: the library has no temporal pass (include/svr_temporal.h)";
+    return false;
+  }
+  SvrTemporalPass tp{};
+  const mat4 m = taa_has_prev ? svrm::temporal_reproject(taa_prev_viewproj, taa_viewproj) : svrm::identity();
+  std::memcpy(tp.reproject, m.data(), 64);
+  tp.blend = taa_blend;
+  if (api.svr_temporal_resolve(ctx, &tp)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  taa_prev_viewproj = taa_viewproj;
+  taa_has_prev = true;
+  taa_frame++;
   return true;
 }
 

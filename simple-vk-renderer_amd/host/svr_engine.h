@@ -23,6 +23,7 @@
 #include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_post.h"
+#include "../../include/svr_temporal.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -54,6 +55,8 @@ struct SvrApi {
   SVR_FN(svr_enable_attributes) SVR_FN(svr_light_pass) SVR_FN(svr_set_depth_load_op)
   // include/svr_post.h: optional (HIP library only), needed by SvrEngine::post_pass
   SVR_FN(svr_post_pass)
+  // include/svr_temporal.h: optional (HIP library only), needed by SvrEngine::temporal_resolve
+  SVR_FN(svr_temporal_resolve)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -173,6 +176,15 @@ struct SvrEngine {
   // The HDR post pass (svr_demo --post <operator>:<levels>, include/svr_post.h): exposure, bloom and the operator over the
   // colour target, after the frame's last pass and before the swapchain copy.
   bool post_pass(const SvrPostPass& pass);
+  // Temporal antialiasing (svr_demo --taa <blend>, include/svr_temporal.h).  With taa_blend > 0 update_scene shifts the
+  // projection by Halton(2, 3) - 0.5 pixels, a period of 16 frames, and keeps the unjittered viewproj; temporal_resolve,
+  // called behind the frame's last geometry or lighting pass and in front of the post pass, reprojects with
+  // last frame's unjittered viewproj times the inverse of this frame's (the identity on the first frame).
+  float taa_blend = 0.f;
+  uint32_t taa_frame = 0;
+  bool taa_has_prev = false;
+  mat4 taa_viewproj{}, taa_prev_viewproj{};
+  bool temporal_resolve();
   // Occlusion culling (svr_demo --occlusion off|last|prepass, include/svr_occlusion.h).  Last: each frame's geometry
   // culls against the pyramid of the previous frame's depth (built behind every frame; before the first it is all 0.0
   // and culls nothing).  Prepass: each frame first draws the opaque objects whose material is in occluder_materials

@@ -134,4 +134,67 @@ inline mat4 inverse(const mat4& mm) {
   return inv;
 }
 
+// ---- temporal antialiasing (include/svr_temporal.h): the caller's side.  glmath.py restates these three; the two agree
+// bit for bit (tests/test_jitter.py).
+// The i-th element (i >= 1) of the Halton sequence of a base: the radical inverse, accumulated in double, rounded once.
+inline float halton(unsigned i, unsigned base) {
+  double f = 1.0, r = 0.0;
+  while (i > 0u) {
+    f = f / (double)base;
+    r = r + f * (double)(i % base);
+    i /= base;
+  }
+  return (float)r;
+}
+// proj with a sub-pixel shift of (jx, jy) pixels in a w x h target: 2 jx / w and 2 jy / h times the w row are added to the
+// x and y rows, so a point that landed at pixel (px, py) lands at (px + jx, py + jy).
+inline mat4 jitter_projection(const mat4& proj, float jx, float jy, float w, float h) {
+  const float ax = (2.0f * jx) / w, ay = (2.0f * jy) / h;
+  mat4 r = proj;
+  for (int c = 0; c < 4; c++) {
+    r.m[c][0] = proj.m[c][0] + ax * proj.m[c][3];
+    r.m[c][1] = proj.m[c][1] + ay * proj.m[c][3];
+  }
+  return r;
+}
+// SvrTemporalPass.reproject = prev_viewproj * inverse(viewproj), both without jitter: the inverse (the cofactor expansion
+// above) and the product are taken in double and rounded to fp32 once.
+inline mat4 temporal_reproject(const mat4& prev_viewproj, const mat4& viewproj) {
+  double m[4][4], p[4][4], inv[4][4];
+  for (int c = 0; c < 4; c++)
+    for (int k = 0; k < 4; k++) {
+      m[c][k] = (double)viewproj.m[c][k];
+      p[c][k] = (double)prev_viewproj.m[c][k];
+    }
+  double c00 = m[2][2] * m[3][3] - m[3][2] * m[2][3], c02 = m[1][2] * m[3][3] - m[3][2] * m[1][3];
+  double c03 = m[1][2] * m[2][3] - m[2][2] * m[1][3], c04 = m[2][1] * m[3][3] - m[3][1] * m[2][3];
+  double c06 = m[1][1] * m[3][3] - m[3][1] * m[1][3], c07 = m[1][1] * m[2][3] - m[2][1] * m[1][3];
+  double c08 = m[2][1] * m[3][2] - m[3][1] * m[2][2], c10 = m[1][1] * m[3][2] - m[3][1] * m[1][2];
+  double c11 = m[1][1] * m[2][2] - m[2][1] * m[1][2], c12 = m[2][0] * m[3][3] - m[3][0] * m[2][3];
+  double c14 = m[1][0] * m[3][3] - m[3][0] * m[1][3], c15 = m[1][0] * m[2][3] - m[2][0] * m[1][3];
+  double c16 = m[2][0] * m[3][2] - m[3][0] * m[2][2], c18 = m[1][0] * m[3][2] - m[3][0] * m[1][2];
+  double c19 = m[1][0] * m[2][2] - m[2][0] * m[1][2], c20 = m[2][0] * m[3][1] - m[3][0] * m[2][1];
+  double c22 = m[1][0] * m[3][1] - m[3][0] * m[1][1], c23 = m[1][0] * m[2][1] - m[2][0] * m[1][1];
+  double f0[4] = {c00, c00, c02, c03}, f1[4] = {c04, c04, c06, c07}, f2[4] = {c08, c08, c10, c11};
+  double f3[4] = {c12, c12, c14, c15}, f4[4] = {c16, c16, c18, c19}, f5[4] = {c20, c20, c22, c23};
+  double v0[4] = {m[1][0], m[0][0], m[0][0], m[0][0]}, v1[4] = {m[1][1], m[0][1], m[0][1], m[0][1]};
+  double v2[4] = {m[1][2], m[0][2], m[0][2], m[0][2]}, v3[4] = {m[1][3], m[0][3], m[0][3], m[0][3]};
+  const double sa[4] = {1, -1, 1, -1}, sb[4] = {-1, 1, -1, 1};
+  for (int k = 0; k < 4; k++) {
+    inv[0][k] = (v1[k] * f0[k] - v2[k] * f1[k] + v3[k] * f2[k]) * sa[k];
+    inv[1][k] = (v0[k] * f0[k] - v2[k] * f3[k] + v3[k] * f4[k]) * sb[k];
+    inv[2][k] = (v0[k] * f1[k] - v1[k] * f3[k] + v3[k] * f5[k]) * sa[k];
+    inv[3][k] = (v0[k] * f2[k] - v1[k] * f4[k] + v2[k] * f5[k]) * sb[k];
+  }
+  const double d0 = m[0][0] * inv[0][0], d1 = m[0][1] * inv[1][0], d2 = m[0][2] * inv[2][0], d3 = m[0][3] * inv[3][0];
+  const double one_over_det = 1.0 / ((d0 + d1) + (d2 + d3));
+  mat4 r;
+  for (int j = 0; j < 4; j++) {
+    double col[4];
+    for (int k = 0; k < 4; k++) col[k] = inv[j][k] * one_over_det;
+    for (int k = 0; k < 4; k++) r.m[j][k] = (float)(((p[0][k] * col[0] + p[1][k] * col[1]) + p[2][k] * col[2]) + p[3][k] * col[3]);
+  }
+  return r;
+}
+
 }  // namespace svrm
