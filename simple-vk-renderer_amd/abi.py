@@ -116,6 +116,11 @@ TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 # include/svr_temporal.h: temporal antialiasing (history reprojection, neighbourhood clamp, blend), HIP library only
 TEMPORAL_SYMBOLS = ["svr_temporal_resolve", "svr_debug_read_temporal_history"]
 TEMPORAL_RESET, TEMPORAL_NO_CLAMP = 1, 2
+# include/svr_ambient.h: screen-space ambient occlusion over the G-buffer, HIP library only
+AMBIENT_SYMBOLS = ["svr_ambient_pass", "svr_bind_ambient_target", "svr_get_ambient_target", "svr_read_ambient",
+                   "svr_set_light_ambient_occlusion", "svr_debug_read_ambient_raw"]
+AMBIENT_NO_BLUR = 1
+AMBIENT_MAX_REACH, AMBIENT_TAPS = 16, 8
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -145,6 +150,11 @@ class SvrPostPass(C.Structure):  # include/svr_post.h
 
 class SvrTemporalPass(C.Structure):  # include/svr_temporal.h
     _fields_ = [("reproject", C.c_float * 16), ("blend", C.c_float), ("flags", C.c_uint32)]
+
+
+class SvrAmbientPass(C.Structure):  # include/svr_ambient.h
+    _fields_ = [("inv_viewproj", C.c_float * 16), ("radius", C.c_float), ("pixels_per_unit", C.c_float), ("bias", C.c_float),
+                ("intensity", C.c_float), ("sharpness", C.c_float), ("flags", C.c_uint32)]
 
 
 POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("intensity", "<f4")])
@@ -265,6 +275,14 @@ class SvrLib:
         if self.has_temporal:
             L.svr_temporal_resolve.argtypes = [P, C.POINTER(SvrTemporalPass)]
             L.svr_debug_read_temporal_history.argtypes = [P, P, C.c_size_t, C.POINTER(C.c_uint32)]
+        self.has_ambient = hasattr(L, "svr_ambient_pass")
+        if self.has_ambient:
+            L.svr_ambient_pass.argtypes = [P, C.POINTER(SvrAmbientPass)]
+            L.svr_bind_ambient_target.argtypes = [P, P]
+            L.svr_get_ambient_target.argtypes = [P, C.POINTER(P)]
+            L.svr_read_ambient.argtypes = [P, P, C.c_size_t]
+            L.svr_set_light_ambient_occlusion.argtypes = [P, C.c_int]
+            L.svr_debug_read_ambient_raw.argtypes = [P, P, C.c_size_t]
         self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
         if self.has_depth_load:
             L.svr_set_depth_load_op.argtypes = [P, C.c_int]
@@ -817,6 +835,52 @@ class Renderer:
         valid = C.c_uint32(0)
         self.lib.check(self.lib.lib.svr_debug_read_temporal_history(self.h, out.ctypes.data, out.nbytes, C.byref(valid)))
         return out, bool(valid.value)
+
+    # ---- ambient occlusion (include/svr_ambient.h)
+    def _need_ambient(self):
+        if not getattr(self.lib, "has_ambient", False):
+            raise SvrError(-5, f"{self.lib.backend} has no ambient pass (include/svr_ambient.h)")
+
+    def ambient_pass(self, inv_viewproj, radius, pixels_per_unit, bias=0.0, intensity=1.0, sharpness=0.05, flags=0):
+        """svr_ambient_pass: the ambient factor of the scissor's pixels, from the depth target and the NORMAL plane, into
+        the ambient target.  inv_viewproj: 4 x 4 indexed [col][row] like glmath's matrices; radius, bias: world units;
+        pixels_per_unit: glmath.pixels_per_unit(proj, height); flags: AMBIENT_*"""
+        self._need_ambient()
+        p = SvrAmbientPass()
+        p.inv_viewproj = _f16m(inv_viewproj)
+        p.radius, p.pixels_per_unit, p.bias = float(radius), float(pixels_per_unit), float(bias)
+        p.intensity, p.sharpness, p.flags = float(intensity), float(sharpness), int(flags)
+        self.lib.check(self.lib.lib.svr_ambient_pass(self.h, C.byref(p)))
+
+    def bind_ambient_target(self, ptr):
+        """caller-owned device memory (width * height floats, 16-byte aligned) as the ambient target; None/0 = the context's"""
+        self._need_ambient()
+        self.lib.check(self.lib.lib.svr_bind_ambient_target(self.h, C.c_void_p(ptr or None)))
+
+    def get_ambient_target(self):
+        self._need_ambient()
+        p = C.c_void_p()
+        self.lib.check(self.lib.lib.svr_get_ambient_target(self.h, C.byref(p)))
+        return p.value
+
+    def read_ambient(self):
+        """(H, W) float32: the current ambient target (fences)"""
+        self._need_ambient()
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self.lib.check(self.lib.lib.svr_read_ambient(self.h, out.ctypes.data, out.nbytes))
+        return out
+
+    def read_ambient_raw(self):
+        """svr_debug_read_ambient_raw -> (H, W, 2) float32: the (a, 1/w) scratch plane of the last passes (fences)"""
+        self._need_ambient()
+        out = np.empty((self.height, self.width, 2), dtype=np.float32)
+        self.lib.check(self.lib.lib.svr_debug_read_ambient_raw(self.h, out.ctypes.data, out.nbytes))
+        return out
+
+    def set_light_ambient_occlusion(self, on=True):
+        """later light_pass calls scale their ambient term by the ambient target current at their enqueue"""
+        self._need_ambient()
+        self.lib.check(self.lib.lib.svr_set_light_ambient_occlusion(self.h, 1 if on else 0))
 
     # ---- the depth loadOp (include/svr_load.h)
     def _need_depth_load(self):

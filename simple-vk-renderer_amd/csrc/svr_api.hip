@@ -31,6 +31,7 @@
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
+#include "../../include/svr_ambient.h"
 #include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
@@ -259,7 +260,7 @@ struct SvrContext {
   PassSet sets[NSETS];
   int set_pos = 0;
   // operation log (see "the operation log" below): a pass, or a fill of the colour target (every other operation)
-  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light, Post, Temporal };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass; Post: svr_post_pass; Temporal: svr_temporal_resolve
+  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light, Post, Temporal, Ambient };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass; Post: svr_post_pass; Temporal: svr_temporal_resolve; Ambient: svr_ambient_pass
   enum class PassInput { Draws, Objects, List };  // what a pass reads: the one place that says so (P.flatten follows it)
   struct LoggedOp {
     OpKind kind = OpKind::Pass;
@@ -294,6 +295,8 @@ struct SvrContext {
     PostLaunch post{};
     // Temporal (include/svr_temporal.h): the kernels' parameters as recorded, the history roles and validity among them
     TemporalLaunch temporal{};
+    // Ambient (include/svr_ambient.h): the kernels' parameters as recorded, the planes it reads and writes among them
+    AmbientLaunch ambient{};
     bool flattened() const { return input != PassInput::Draws; }
     // a fill: colour target, its format and extent, the rows it writes
     void* target = nullptr;
@@ -369,6 +372,13 @@ struct SvrContext {
   int temporal_read = 0;
   bool temporal_has = false;
   uint32_t temporal_scissor[4] = {0, 0, 0, 0};
+  // svr_ambient_pass: the (a, 1/w) scratch plane and the context's own ambient target, both of the context's extent,
+  // allocated and zeroed by the first pass that needs them.  ambient_bound: the caller's plane, or null.  light_ao:
+  // svr_set_light_ambient_occlusion.
+  DevPtr<float2> d_ambient_raw;
+  DevPtr<float> d_ambient_own;
+  float* ambient_bound = nullptr;
+  bool light_ao = false;
   SvrStats stats{};
   // Declared last, so it goes first: its entries hold draw-list versions and pyramids, and name the memory above.
   std::deque<LoggedOp> log;
@@ -802,6 +812,8 @@ int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying 
     launch_post(op.post, ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Temporal) {  // (both kernels write nothing while the poison flag is up)
     launch_temporal(op.temporal, ctx->stream);
+  } else if (op.kind == SvrContext::OpKind::Ambient) {  // (both kernels write nothing while the poison flag is up)
+    launch_ambient(op.ambient, ctx->stream);
   } else if (op.kind == SvrContext::OpKind::Background) {
     launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison.get(), ctx->stream);
   } else {
@@ -2556,6 +2568,11 @@ int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: the shadow map's extent must be 1 .. 2^24 each way");
   if (!ctx->attr[2] || !ctx->attr[3])
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: needs the SVR_ATTR_NORMAL and SVR_ATTR_ALBEDO planes (svr_enable_attributes / svr_bind_attribute_target)");
+  const float* ao = nullptr;  // include/svr_ambient.h: the ambient target current at this call
+  if (ctx->light_ao) {
+    ao = ctx->ambient_bound ? ctx->ambient_bound : ctx->d_ambient_own.get();
+    if (!ao) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: svr_set_light_ambient_occlusion is on and there is no ambient target (svr_ambient_pass / svr_bind_ambient_target)");
+  }
   if (int e = use_device(ctx)) return e;
   if (int e = poll_pending(ctx)) return e;
   if (!ctx->d_lights) DEV_ALLOC(ctx->d_lights, SVR_MAX_LIGHTS * sizeof(SvrPointLight));
@@ -2598,6 +2615,7 @@ int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
   }
   L.tile_counts = ctx->d_light_tiles.get();
   L.poison = ctx->d_poison.get();
+  L.ao = ao;
   ctx->light_tiles_n = L.tiles_x * op->light_tiles_y;
   return submit_fill(ctx, *op);
 }
@@ -2719,6 +2737,104 @@ int svr_debug_read_temporal_history(SvrContext* ctx, void* dst, size_t bytes, ui
     HIPCHK(hipMemcpy(dst, ctx->d_temporal[ctx->temporal_read].get(), need, hipMemcpyDeviceToHost));
   else
     std::memset(dst, 0, need);
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- ambient occlusion (include/svr_ambient.h)
+static float* ambient_target(const SvrContext* ctx) { return ctx->ambient_bound ? ctx->ambient_bound : ctx->d_ambient_own.get(); }
+
+int svr_ambient_pass(SvrContext* ctx, const SvrAmbientPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: null argument");
+  if (!(std::isfinite(pass->radius) && pass->radius > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the radius must be finite and greater than 0");
+  if (!(std::isfinite(pass->pixels_per_unit) && pass->pixels_per_unit > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: pixels_per_unit must be finite and greater than 0");
+  if (!(std::isfinite(pass->bias) && pass->bias >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the bias must be finite and at least 0");
+  if (!(std::isfinite(pass->intensity) && pass->intensity >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the intensity must be finite and at least 0");
+  if (!(std::isfinite(pass->sharpness) && pass->sharpness >= 0.0f && pass->sharpness < 1.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the sharpness must be finite, at least 0 and less than 1");
+  if (pass->flags & ~(uint32_t)SVR_AMBIENT_NO_BLUR) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: unknown flag bits");
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(pass->inv_viewproj[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: inv_viewproj[" + std::to_string(i) + "] is not finite");
+  if (!ctx->attr[2]) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: needs the SVR_ATTR_NORMAL plane (svr_enable_attributes / svr_bind_attribute_target)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_ambient_pass: not under svr_set_row_interleave with a stride above 1");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  const size_t n = (size_t)ctx->W * ctx->H;
+  // zeroed once: the read-backs show the whole extent, the kernels touch the scissor only
+  if (!ctx->d_ambient_raw) {
+    DEV_ALLOC(ctx->d_ambient_raw, n * sizeof(float2));
+    HIPCHK(hipMemsetAsync(ctx->d_ambient_raw.get(), 0, n * sizeof(float2), ctx->stream));
+  }
+  if (!ctx->ambient_bound && !ctx->d_ambient_own) {
+    DEV_ALLOC(ctx->d_ambient_own, n * sizeof(float));
+    HIPCHK(hipMemsetAsync(ctx->d_ambient_own.get(), 0, n * sizeof(float), ctx->stream));
+  }
+  // (no flush_clear: the pass neither reads nor writes colour)
+  SvrContext::LoggedOp* op = nullptr;
+  if (int e = log_fill(ctx, SvrContext::OpKind::Ambient, nullptr, 0, ctx->sy, ctx->sh, &op)) return e;
+  AmbientLaunch& T = op->ambient;
+  T.depth = ctx->depth;
+  T.normal = (const float4*)ctx->attr[2];
+  T.raw = ctx->d_ambient_raw.get();
+  T.out = ambient_target(ctx);
+  T.W = ctx->W;
+  T.H = ctx->H;
+  T.sx = ctx->sx;
+  T.sy = ctx->sy;
+  T.sw = ctx->sw;
+  T.sh = ctx->sh;
+  std::memcpy(T.inv_viewproj, pass->inv_viewproj, sizeof(T.inv_viewproj));
+  T.two_over_w = 2.0f / (float)ctx->W;
+  T.two_over_h = 2.0f / (float)ctx->H;
+  T.radius_px = pass->radius * pass->pixels_per_unit;
+  T.radius2 = pass->radius * pass->radius;
+  T.bias = pass->bias;
+  T.coef = (pass->intensity * pass->radius) * 0.125f;
+  T.sharpness = pass->sharpness;
+  T.blur = (pass->flags & SVR_AMBIENT_NO_BLUR) ? 0u : 1u;
+  T.poison = ctx->d_poison.get();
+  return submit_fill(ctx, *op);
+}
+
+int svr_bind_ambient_target(SvrContext* ctx, float* dev) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  if (((uintptr_t)dev & 15u) != 0u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_bind_ambient_target: the target must be 16-byte aligned");
+  if (int e = use_device(ctx)) return e;
+  // no fence: passes already enqueued carry their own planes (also for a replay), as with svr_bind_attribute_target
+  if (int e = poll_pending(ctx)) return e;
+  ctx->ambient_bound = dev;
+  return SVR_OK;
+}
+
+int svr_get_ambient_target(SvrContext* ctx, float** dev) {
+  if (!ctx || !dev) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_ambient_target: null argument");
+  *dev = ambient_target(ctx);
+  return SVR_OK;
+}
+
+int svr_read_ambient(SvrContext* ctx, void* dst_host, size_t bytes) {
+  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: null argument");
+  if (!ambient_target(ctx)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: no ambient target (svr_ambient_pass / svr_bind_ambient_target)");
+  if (bytes != (size_t)ctx->W * ctx->H * sizeof(float)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: the size is not the plane's");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst_host, ambient_target(ctx), bytes, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+int svr_set_light_ambient_occlusion(SvrContext* ctx, int on) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  ctx->light_ao = on != 0;
+  return SVR_OK;
+}
+
+int svr_debug_read_ambient_raw(SvrContext* ctx, void* dst_host, size_t bytes) {
+  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: null argument");
+  if (!ctx->d_ambient_raw) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: no ambient pass yet");
+  if (bytes != (size_t)ctx->W * ctx->H * sizeof(float2)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: the size is not the plane's");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst_host, ctx->d_ambient_raw.get(), bytes, hipMemcpyDeviceToHost));
   return SVR_OK;
 }
 

@@ -1,5 +1,6 @@
 // svr_launch.h — host-callable launchers of the HIP kernels (one per kernel file).
 #pragma once
+#include "../../include/svr_ambient.h"
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
@@ -73,6 +74,7 @@ struct LightLaunch {
   float shadow_bias;
   uint32_t* tile_counts;        // [tiles_x * tiles_y]: the lights each tile kept (svr_debug_read_light_tiles)
   const uint32_t* poison;
+  const float* ao;              // the ambient target (include/svr_ambient.h), or null: light_ao_kernel / light_kernel
 };
 void launch_light(const LightLaunch& L, int color_format, uint32_t tiles_y, hipStream_t s);
 // k_post.hip: the HDR post pass (include/svr_post.h)
@@ -109,6 +111,26 @@ struct TemporalLaunch {
 };
 // one temporal_resolve_kernel and one temporal_copy_kernel, on s
 void launch_temporal(const TemporalLaunch& A, hipStream_t s);
+// k_ambient.hip: screen-space ambient occlusion (include/svr_ambient.h)
+struct AmbientLaunch {
+  const float* depth;           // the depth target, read as it stands in stream order
+  const float4* normal;         // the SVR_ATTR_NORMAL plane
+  float2* raw;                  // the context's (a, 1/w) scratch plane (C36), W texels per row
+  float* out;                   // the ambient target, W floats per row
+  uint32_t W, H;
+  uint32_t sx, sy, sw, sh;      // the scissor: the image of the pass
+  float inv_viewproj[16];
+  float two_over_w, two_over_h; // C17: divided once, on the host
+  float radius_px;              // C33: radius * pixels_per_unit
+  float radius2;                // C35: radius * radius
+  float bias;
+  float coef;                   // C36: (intensity * radius) * 0.125f
+  float sharpness;
+  uint32_t blur;                // 0 under SVR_AMBIENT_NO_BLUR
+  const uint32_t* poison;
+};
+// one ambient_raw_kernel and one ambient_blur_kernel, on s
+void launch_ambient(const AmbientLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

@@ -264,3 +264,9 @@ def temporal_reproject(prev_viewproj, viewproj):
         for k in range(4):
             r[j][k] = f32(((p[0][k] * col[0] + p[1][k] * col[1]) + p[2][k] * col[2]) + p[3][k] * col[3])
     return r
+
+
+# ---- ambient occlusion (include/svr_ambient.h): the caller's side, bit for bit host/svr_math.h's
+def pixels_per_unit(proj, height):
+    """SvrAmbientPass.pixels_per_unit: the pixels one world unit spans at clip w = 1 in a target of the given height"""
+    return (f32(0.5) * f32(height)) * abs(f32(np.asarray(proj, dtype=f32)[1][1]))

@@ -19,6 +19,9 @@
 //           jitter (Halton(2, 3) - 0.5 pixels, a period of 16 frames) and resolved against the reprojected, clamped history
 //           with the given weight of the current frame, behind the frame's last geometry or lighting pass and in front of
 //           --post; not with --views or --ranks
+//       --ao <radius>:<intensity>: screen-space ambient occlusion (include/svr_ambient.h, HIP library only) with --deferred 1:
+//           svr_ambient_pass between the G-buffer pass and the lighting pass, which scales its ambient term by the result
+//           (bias 0.02 radius, sharpness 0.05); an intensity of 0 gives the frame without the flag; not with --views or --ranks
 //       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
 //           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
 //           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
@@ -88,7 +91,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false;
-  std::string occlusion = "off", post_arg, taa_arg;
+  std::string occlusion = "off", post_arg, taa_arg, ao_arg;
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -115,6 +118,7 @@ int main(int argc, char** argv) {
     else if (a == "--deferred") deferred = atoi(argv[i + 1]) != 0;  // G-buffer pass, lighting pass, transparent objects under LOAD
     else if (a == "--post") post_arg = argv[i + 1];  // <operator>:<levels> (include/svr_post.h)
     else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
+    else if (a == "--ao") ao_arg = argv[i + 1];  // <radius>:<intensity> (include/svr_ambient.h)
     else if (a == "--exposure") post.exposure = (float)atof(argv[i + 1]);
     else if (a == "--bloom-threshold") post.bloom_threshold = (float)atof(argv[i + 1]);
     else if (a == "--bloom-intensity") post.bloom_intensity = (float)atof(argv[i + 1]);
@@ -152,7 +156,7 @@ int main(int argc, char** argv) {
                     "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1] [--deferred 1]\n"
                     "                [--occlusion off|last|prepass]\n"
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
-                    "                [--taa blend]\n");
+                    "                [--taa blend] [--ao radius:intensity]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -169,6 +173,30 @@ int main(int argc, char** argv) {
     }
     if (ranks > 1) {
       fprintf(stderr, "--taa: not with --ranks (a band rank would clamp taps at its band's edge and keep its own history)\n");
+      return 1;
+    }
+  }
+  float ao_radius = 0.f, ao_intensity = 0.f;
+  if (!ao_arg.empty()) {
+    const size_t colon = ao_arg.find(':');
+    char *end_r = nullptr, *end_i = nullptr;
+    ao_radius = strtof(ao_arg.c_str(), &end_r);
+    if (colon != std::string::npos) ao_intensity = strtof(ao_arg.c_str() + colon + 1, &end_i);
+    if (colon == std::string::npos || colon == 0 || end_r != ao_arg.c_str() + colon || !end_i || *end_i || end_i == ao_arg.c_str() + colon + 1 ||
+        !(ao_radius > 0.f && ao_radius < INFINITY) || !(ao_intensity >= 0.f && ao_intensity < INFINITY)) {
+      fprintf(stderr, "--ao: expected <radius > 0>:<intensity >= 0>, got '%s'\n", ao_arg.c_str());
+      return 2;
+    }
+    if (!deferred) {
+      fprintf(stderr, "--ao: needs --deferred 1 (the pass reads the G-buffer and the lighting pass applies it)\n");
+      return 1;
+    }
+    if (views) {
+      fprintf(stderr, "--ao: not with --views (the pass works on the context's own targets)\n");
+      return 1;
+    }
+    if (ranks > 1) {
+      fprintf(stderr, "--ao: not with --ranks (a band rank would cut taps at its band's edge)\n");
       return 1;
     }
   }
@@ -493,7 +521,13 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--taa: the library has no temporal pass (include/svr_temporal.h)\n");
     return 1;
   }
+  if (!ao_arg.empty() && !eng.api.svr_ambient_pass) {
+    fprintf(stderr, "--ao: the library has no ambient pass (include/svr_ambient.h)\n");
+    return 1;
+  }
   eng.taa_blend = taa_blend;
+  eng.ao_radius = ao_radius;
+  eng.ao_intensity = ao_intensity;
   if (select && !eng.enable_ids()) {
     fprintf(stderr, "--select: %s\n", eng.error.c_str());
     return 1;

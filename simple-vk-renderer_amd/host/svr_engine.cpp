@@ -49,6 +49,8 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_set_depth_load_op = reinterpret_cast<decltype(svr_set_depth_load_op)>(dlsym(handle, "svr_set_depth_load_op"));
   svr_post_pass = reinterpret_cast<decltype(svr_post_pass)>(dlsym(handle, "svr_post_pass"));
   svr_temporal_resolve = reinterpret_cast<decltype(svr_temporal_resolve)>(dlsym(handle, "svr_temporal_resolve"));
+  svr_ambient_pass = reinterpret_cast<decltype(svr_ambient_pass)>(dlsym(handle, "svr_ambient_pass"));
+  svr_set_light_ambient_occlusion = reinterpret_cast<decltype(svr_set_light_ambient_occlusion)>(dlsym(handle, "svr_set_light_ambient_occlusion"));
   return ok;
 }
 void SvrApi::unload() {
@@ -453,6 +455,23 @@ bool SvrEngine::draw_deferred() {  // draw_geometry in three steps: G-buffer pas
   std::memcpy(lp.sunlight_direction, scene_data.sunlight_direction, 16);
   std::memcpy(lp.sunlight_color, scene_data.sunlight_color, 16);
   int rc = api.svr_draw_geometry(ctx, &scene_data, dc.opaque_surfaces.data(), dc.opaque_surfaces.size(), nullptr, 0, &st);
+  if (!rc && ao_radius > 0.f) {  // --ao: the ambient factor of this frame's G-buffer, used by the lighting pass below
+    if (!api.svr_ambient_pass || !api.svr_set_light_ambient_occlusion) {
+      error = "--ao: the library has no ambient pass (include/svr_ambient.h)";
+      return false;
+    }
+    SvrAmbientPass ap{};
+    std::memcpy(ap.inv_viewproj, inv.data(), 64);
+    mat4 proj;
+    std::memcpy(proj.data(), scene_data.proj, 64);
+    ap.radius = ao_radius;
+    ap.pixels_per_unit = svrm::pixels_per_unit(proj, (float)height);
+    ap.bias = 0.02f * ao_radius;
+    ap.intensity = ao_intensity;
+    ap.sharpness = 0.05f;
+    rc = api.svr_ambient_pass(ctx, &ap);
+    if (!rc) rc = api.svr_set_light_ambient_occlusion(ctx, 1);
+  }
   if (!rc) rc = api.svr_light_pass(ctx, &lp);
   if (!rc) rc = api.svr_set_depth_load_op(ctx, SVR_DEPTH_LOAD);
   if (!rc) {

@@ -24,6 +24,7 @@
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
+#include "../../include/svr_ambient.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -57,6 +58,8 @@ struct SvrApi {
   SVR_FN(svr_post_pass)
   // include/svr_temporal.h: optional (HIP library only), needed by SvrEngine::temporal_resolve
   SVR_FN(svr_temporal_resolve)
+  // include/svr_ambient.h: optional (HIP library only), needed by SvrEngine::draw_deferred with ao_radius > 0
+  SVR_FN(svr_ambient_pass) SVR_FN(svr_set_light_ambient_occlusion)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -171,7 +174,10 @@ struct SvrEngine {
   // svr_attributes.h), svr_light_pass with the scene's sun and ambient, no point lights and no shadow map (include/
   // svr_lighting.h), then the transparent surfaces under SVR_DEPTH_LOAD (include/svr_load.h): tested against the opaque
   // depth, blended over the lit colour.  The frame is the forward one, bit for bit.
+  // With ao_radius > 0 (svr_demo --ao <radius>:<intensity>, include/svr_ambient.h) svr_ambient_pass runs between the
+  // G-buffer pass and the lighting pass, and the lighting pass scales its ambient term by the plane it wrote.
   bool gbuffer = false;  // the planes are enabled
+  float ao_radius = 0.f, ao_intensity = 0.f;
   bool draw_deferred();
   // The HDR post pass (svr_demo --post <operator>:<levels>, include/svr_post.h): exposure, bloom and the operator over the
   // colour target, after the frame's last pass and before the swapchain copy.

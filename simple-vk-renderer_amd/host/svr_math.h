@@ -197,4 +197,9 @@ inline mat4 temporal_reproject(const mat4& prev_viewproj, const mat4& viewproj) 
   return r;
 }
 
+// ---- ambient occlusion (include/svr_ambient.h): the caller's side; glmath.py's pixels_per_unit is the same bit for bit
+// (tests/test_ambient_math.py).
+// SvrAmbientPass.pixels_per_unit: the pixels one world unit spans at clip w = 1 in a target of the given height.
+inline float pixels_per_unit(const mat4& proj, float height) { return (0.5f * height) * std::fabs(proj.m[1][1]); }
+
 }  // namespace svrm
