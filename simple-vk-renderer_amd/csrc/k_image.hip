@@ -2,7 +2,8 @@
 //   fill_color      result of draw_background (src/vk_engine.cpp:1341-1355, gradient_color.comp with
 //                   data1 == data2): one constant RGBA over the whole colour target
 //   downsample      one level of vkutil::generate_mipmaps (src/vk_images.cpp:95-128): 2:1 LINEAR blit
-//                   in exact integer arithmetic (contract C13)
+//                   in exact integer arithmetic (contract C13), tiled level to tiled level
+//   retile          linear rows <-> a tiled level of the texel arena (svr_device.h texel_offset): upload and read-back
 //   rgba16f_to_rgba8  identity-extent vkutil::copy_image (src/vk_images.cpp:33-64): clamp, *255, RNE
 //   background      draw_background's two compute effects (gradient_color.comp, sky.comp)
 //   blit            vkutil::copy_image in general: LINEAR-filter scaling blit to the swapchain format
@@ -47,9 +48,10 @@ void launch_fill_color(void* color, uint32_t n_pixels, int color_format, uint64_
   }
 }
 
-// one destination texel per lane; weights are exact rationals (see oracle downsample_level)
-__global__ __launch_bounds__(256) void downsample_kernel(const uint32_t* src, uint32_t sw, uint32_t sh, uint32_t* dst,
-                                                         uint32_t dw, uint32_t dh) {
+// one destination texel per lane; weights are exact rationals (see oracle downsample_level).
+// Both levels are tiled: splw, dplw = log2 of their padded widths (level_lw).
+__global__ __launch_bounds__(256) void downsample_kernel(const uint32_t* src, uint32_t sw, uint32_t sh, uint32_t splw, uint32_t* dst,
+                                                         uint32_t dw, uint32_t dh, uint32_t dplw) {
   uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= dw * dh) return;
   uint32_t i = idx % dw, j = idx / dw;
@@ -64,7 +66,8 @@ __global__ __launch_bounds__(256) void downsample_kernel(const uint32_t* src, ui
   i1 = min(max(i1, 0ll), (long long)sw - 1);
   j0 = min(max(j0, 0ll), (long long)sh - 1);
   j1 = min(max(j1, 0ll), (long long)sh - 1);
-  uint32_t t00 = src[j0 * sw + i0], t10 = src[j0 * sw + i1], t01 = src[j1 * sw + i0], t11 = src[j1 * sw + i1];
+  auto at = [&](long long x, long long y) { return src[texel_offset(splw, (uint32_t)x, (uint32_t)y) >> 2]; };
+  uint32_t t00 = at(i0, j0), t10 = at(i1, j0), t01 = at(i0, j1), t11 = at(i1, j1);
   long long den = dx * dy;
   uint32_t out = 0;
 #pragma unroll
@@ -76,14 +79,31 @@ __global__ __launch_bounds__(256) void downsample_kernel(const uint32_t* src, ui
     if (2 * r > den || (2 * r == den && (q & 1))) q++;
     out |= (uint32_t)q << (8 * c);
   }
-  dst[idx] = out;
+  dst[texel_offset(dplw, i, j) >> 2] = out;
 }
 
-void launch_downsample(const uint8_t* src, uint32_t sw, uint32_t sh, uint8_t* dst, uint32_t dw, uint32_t dh,
-                       hipStream_t s) {
+void launch_downsample(const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t splw, uint8_t* dst, uint32_t dw, uint32_t dh,
+                       uint32_t dplw, hipStream_t s) {
   uint32_t n = dw * dh;
-  hipLaunchKernelGGL(downsample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)src, sw, sh,
-                     (uint32_t*)dst, dw, dh);
+  hipLaunchKernelGGL(downsample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t*)src, sw, sh, splw,
+                     (uint32_t*)dst, dw, dh, dplw);
+}
+
+// one texel per lane: w x h linear rows to (TO_TILED) or from a tiled level of padded width 2^plw.  Padding texels of
+// the level are never written and never read.
+template <bool TO_TILED>
+__global__ __launch_bounds__(256) void retile_kernel(uint32_t* linear, uint32_t* tiled, uint32_t w, uint32_t h, uint32_t plw) {
+  const uint32_t n = w * h;
+  for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
+    const uint32_t t = texel_offset(plw, idx % w, idx / w) >> 2;
+    if (TO_TILED) tiled[t] = linear[idx];
+    else linear[idx] = tiled[t];
+  }
+}
+void launch_retile(bool to_tiled, void* linear, uint8_t* tiled, uint32_t w, uint32_t h, uint32_t plw, hipStream_t s) {
+  const dim3 grid(stream_grid(w * h)), block(256);
+  if (to_tiled) hipLaunchKernelGGL(retile_kernel<true>, grid, block, 0, s, (uint32_t*)linear, (uint32_t*)tiled, w, h, plw);
+  else hipLaunchKernelGGL(retile_kernel<false>, grid, block, 0, s, (uint32_t*)linear, (uint32_t*)tiled, w, h, plw);
 }
 
 __device__ __forceinline__ uint32_t h2un8(uint32_t hbits) {

@@ -81,10 +81,10 @@ struct Taps {
   uint32_t o00, o10, o01, o11;
   float alpha, beta;
 };
-// wl, hl: the level's extent; base: its byte offset in the arena.
+// wl, hl: the level's extent; plw: log2 of its padded width (level_lw); base: its byte offset in the arena.
 // POW2: the image's extents are powers of two (part of the COMMON case): REPEAT is a mask
 template <bool POW2 = false>
-__device__ __forceinline__ Taps level_taps(int wl, int hl, uint32_t base, bool linear, float u, float v) {
+__device__ __forceinline__ Taps level_taps(int wl, int hl, uint32_t plw, uint32_t base, bool linear, float u, float v) {
   float U = (u - floorf(u)) * (float)wl;
   float V = (v - floorf(v)) * (float)hl;
   float Uh = U - 0.5f, Vh = V - 0.5f;
@@ -107,12 +107,13 @@ __device__ __forceinline__ Taps level_taps(int wl, int hl, uint32_t base, bool l
     if (j0 >= hl) j0 -= hl;
     if (j1 >= hl) j1 -= hl;
   }
-  // rows and extents are below 2^14: the 24-bit multiply is full rate where v_mul_lo_u32 is quarter rate
-  const uint32_t r0 = __umul24((uint32_t)j0, (uint32_t)wl), r1 = __umul24((uint32_t)j1, (uint32_t)wl);
-  tp.o00 = base + (r0 + (uint32_t)i0) * 4u;
-  tp.o10 = base + (r0 + (uint32_t)i1) * 4u;
-  tp.o01 = base + (r1 + (uint32_t)i0) * 4u;
-  tp.o11 = base + (r1 + (uint32_t)i1) * 4u;
+  // tiled texels (svr_device.h texel_offset): shifts and masks once per axis, one three-operand add per tap
+  const uint32_t x0 = texel_offset_x((uint32_t)i0), x1 = texel_offset_x((uint32_t)i1);
+  const uint32_t y0 = base + texel_offset_y(plw, (uint32_t)j0), y1 = base + texel_offset_y(plw, (uint32_t)j1);
+  tp.o00 = y0 + x0;
+  tp.o10 = y0 + x1;
+  tp.o01 = y1 + x0;
+  tp.o11 = y1 + x1;
   return tp;
 }
 // a texel: the arena's base is wave-uniform (a kernel argument), the offset 32 bits per lane — a global load
@@ -238,11 +239,11 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   float delta = mip_linear ? lc - fl : 0.0f;
   int dlo = mip_linear ? min(dhi + 1, q) : dn;
   float us = (fabsf(u) < 8388608.0f) ? u : 0.0f, vs = (fabsf(v) < 8388608.0f) ? v : 0.0f;
-  // level extents and arena offsets.  The layout pads every level to powers of two (svr_device.h mip_offset), so
-  // the next level starts one padded level further on: no second evaluation of the closed form.
+  // level extents and arena offsets.  The layout pads every level to powers of two and whole tiles (svr_device.h
+  // mip_offset), so the next level starts one padded level further on: no second evaluation of the closed form.
   const int whi = (int)max(t.w >> dhi, 1u), hhi = (int)max(t.h >> dhi, 1u);
   const uint32_t bhi = t.base_off + mip_offset(t.lw, t.lh, (uint32_t)dhi);
-  Taps th = level_taps<COMMON>(whi, hhi, bhi, linear, us, vs);
+  Taps th = level_taps<COMMON>(whi, hhi, level_lw(t.lw, (uint32_t)dhi), bhi, linear, us, vs);
   const uint8_t* tb = P.tex_arena;
   uint32_t h00 = texel(tb, th.o00), h10 = texel(tb, th.o10), h01 = texel(tb, th.o01), h11 = texel(tb, th.o11);
   // The second level only matters where delta != 0 (lerp(H, L, 0) == H exactly): magnified and
@@ -253,9 +254,9 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   uint32_t l00 = 0, l10 = 0, l01 = 0, l11 = 0;
   if (two_levels) {
     const int wlo = (int)max(t.w >> dlo, 1u), hlo = (int)max(t.h >> dlo, 1u);
-    const uint32_t step = 4u << ((uint32_t)max((int)t.lw - dhi, 0) + (uint32_t)max((int)t.lh - dhi, 0));  // padded bytes of level dhi
+    const uint32_t step = level_bytes(t.lw, t.lh, (uint32_t)dhi);  // padded bytes of level dhi
     const uint32_t blo = dlo != dhi ? bhi + step : bhi;
-    tl = level_taps<COMMON>(wlo, hlo, blo, linear, us, vs);
+    tl = level_taps<COMMON>(wlo, hlo, level_lw(t.lw, (uint32_t)dlo), blo, linear, us, vs);
     l00 = texel(tb, tl.o00);
     l10 = texel(tb, tl.o10);
     l01 = texel(tb, tl.o01);

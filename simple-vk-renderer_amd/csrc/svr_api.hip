@@ -1400,29 +1400,33 @@ int svr_create_image(SvrContext* ctx, const void* rgba8, uint32_t width, uint32_
       im.levels++;
     }
   }
-  // Mip levels are laid out as if the image were padded to 2^lw x 2^lh, so a shader derives a
-  // level's offset from (lw, lh, level) alone (svr::mip_offset) and needs no per-image table.
+  // Mip levels are laid out as if the image were padded to 2^lw x 2^lh and every level to whole tiles, so a shader
+  // derives a level's offset from (lw, lh, level) alone (svr::mip_offset) and needs no per-image table.
   while ((1u << im.lw) < width) im.lw++;
   while ((1u << im.lh) < height) im.lh++;
   for (uint32_t l = 0; l < im.levels; l++) im.off[l] = mip_offset(im.lw, im.lh, l);
   uint32_t lw = width, lh = height;
-  size_t total = (size_t)mip_offset(im.lw, im.lh, im.levels - 1) +
-                 (size_t)std::max(1u, width >> (im.levels - 1)) * std::max(1u, height >> (im.levels - 1)) * 4;
   if (im.lw + im.lh > 28) return fail(SVR_ERR_UNSUPPORTED, "svr_create_image: image larger than 1 GiB");
+  const size_t total = (size_t)mip_offset(im.lw, im.lh, im.levels - 1) + level_bytes(im.lw, im.lh, im.levels - 1);
   im.bytes = std::max<size_t>(total, 256);
+  // the linear host image goes through a staging buffer; one kernel scatters it into level 0's tiles
+  const size_t linear = (size_t)width * height * 4;
+  DevPtr<uint8_t> staging;
+  if (dev_alloc(staging, linear) != hipSuccess) return fail(SVR_ERR_OUT_OF_MEMORY, "svr_create_image: staging buffer");
   if (int e = arena_alloc(ctx, im.bytes, &im.arena_off)) return e;
   uint8_t* base = ctx->tex_arena.get() + im.arena_off;
-  hipError_t r = hipMemcpy(base, rgba8, (size_t)width * height * 4, hipMemcpyHostToDevice);
+  hipError_t r = hipMemcpy(staging.get(), rgba8, linear, hipMemcpyHostToDevice);
   if (r != hipSuccess) {
     arena_free(ctx, im.arena_off, im.bytes);
     return fail(SVR_ERR_DEVICE, std::string("hipMemcpy(image): ") + hipGetErrorString(r));
   }
+  launch_retile(true, staging.get(), base, width, height, level_lw(im.lw, 0), ctx->stream);
   // generate_mipmaps: level n -> n+1, each a 2:1 linear blit (src/vk_images.cpp:66-133)
   lw = width;
   lh = height;
   for (uint32_t l = 1; l < im.levels; l++) {
     uint32_t dw = std::max(1u, lw >> 1), dh = std::max(1u, lh >> 1);
-    launch_downsample(base + im.off[l - 1], lw, lh, base + im.off[l], dw, dh, ctx->stream);
+    launch_downsample(base + im.off[l - 1], lw, lh, level_lw(im.lw, l - 1), base + im.off[l], dw, dh, level_lw(im.lw, l), ctx->stream);
     lw = dw;
     lh = dh;
   }
@@ -1456,7 +1460,12 @@ int svr_read_image_level(SvrContext* ctx, SvrImage image, uint32_t level, void* 
     size_t need = (size_t)lw * lh * 4;
     if (bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_image_level: buffer too small");
     if (int e = use_device(ctx)) return e;
-    HIPCHK(hipMemcpy(dst, ctx->tex_arena.get() + im->arena_off + im->off[level], need, hipMemcpyDeviceToHost));
+    DevPtr<uint8_t> staging;  // the level's tiles gathered back into linear rows
+    if (dev_alloc(staging, need) != hipSuccess) return fail(SVR_ERR_OUT_OF_MEMORY, "svr_read_image_level: staging buffer");
+    launch_retile(false, staging.get(), ctx->tex_arena.get() + im->arena_off + im->off[level], lw, lh, level_lw(im->lw, level), ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(dst, staging.get(), need, hipMemcpyDeviceToHost));
   }
   return SVR_OK;
 }

@@ -101,9 +101,10 @@ struct WaveChunk {
 
 // Texture + sampler as the fragment stage sees them (combined image sampler).  24 meaningful bytes
 // so the setup kernel can copy it into every TriRec: shading then needs no descriptor fetch.
-// Mip level l of an image lives at byte offset mip_offset(lw, lh, l) from base (levels are laid
-// out as if the image were padded to 2^lw x 2^lh, so the offset is a closed form), row pitch =
-// the level's true width max(w >> l, 1).
+// Mip level l of an image lives at byte offset mip_offset(lw, lh, l) from base.  A level is stored as TILES of
+// 2^TEX_TILE_LW x 2^TEX_TILE_LH texels, rows of a tile back to back (texel_offset below): an 8x8 pixel block's taps fall
+// on a square of texels, and a square of texels is few tiles where it is many rows.  Levels are laid out as if the image
+// were padded to 2^lw x 2^lh and every level to whole tiles, so offset and pitch are closed forms of (lw, lh, l).
 struct TexBinding {
   uint32_t base_off;        // RGBA8 texels of level 0: byte offset in the context's texel arena (FrameParams::tex_arena)
   uint32_t pad0;
@@ -114,18 +115,36 @@ struct TexBinding {
 };
 static_assert(sizeof(TexBinding) == 32, "TexBinding layout");
 
-// = sum over k < level of 4 * 2^max(lw-k,0) * 2^max(lh-k,0), for level <= max(lw, lh), without a loop
-// (the fragment stage evaluates it twice per pixel).  While both extents halve the sum is
-// 2^(lw+lh+4-2l) * (4^l - 1)/3, and (4^l - 1)/3 is the bit pattern 0101..01 with l ones; past the smaller
-// extent only the larger one halves: a geometric tail of 4 * 2^(b-k).
+constexpr uint32_t TEX_TILE_LW = 3, TEX_TILE_LH = 2;  // log2 of a tile's extent: 8x4 texels = 128 bytes, one cache line (4x4 was measured: DESIGN.md §5)
+constexpr uint32_t TEX_TILE_BYTES = 4u << (TEX_TILE_LW + TEX_TILE_LH);
+// log2 of level l's padded extents: the power-of-two extent halves down to one tile's
+__host__ __device__ inline uint32_t level_lw(uint32_t lw, uint32_t level) { return lw > level + TEX_TILE_LW ? lw - level : TEX_TILE_LW; }
+__host__ __device__ inline uint32_t level_lh(uint32_t lh, uint32_t level) { return lh > level + TEX_TILE_LH ? lh - level : TEX_TILE_LH; }
+__host__ __device__ inline uint32_t level_bytes(uint32_t lw, uint32_t lh, uint32_t level) { return 4u << (level_lw(lw, level) + level_lh(lh, level)); }
+
+// = sum over k < level of level_bytes(lw, lh, k), without a loop (the fragment stage evaluates it once per pixel).
+// nw, nh: how many times each padded extent halves before it is one tile.  While both halve the sum is
+// 2^(cw+ch+4-2l) * (4^l - 1)/3, and (4^l - 1)/3 is the bit pattern 0101..01 with l ones; past the first extent to
+// reach its tile only the other halves: a geometric tail from 4 * 2^(cw+ch-2a); past both every level is one tile.
 __host__ __device__ inline uint32_t mip_offset(uint32_t lw, uint32_t lh, uint32_t level) {
-  const uint32_t a = lw < lh ? lw : lh, b = lw < lh ? lh : lw;
-  const uint32_t l1 = level < a ? level : a;
+  const uint32_t cw = level_lw(lw, 0), ch = level_lh(lh, 0), nw = cw - TEX_TILE_LW, nh = ch - TEX_TILE_LH;
+  const uint32_t a = nw < nh ? nw : nh, b = nw < nh ? nh : nw;
+  const uint32_t l1 = level < a ? level : a, l2 = level < b ? level : b;
   const uint32_t ones = l1 ? (0x55555555u >> (32u - 2u * l1)) : 0u;
-  uint32_t off = ones << ((lw + lh + 4u - 2u * l1) & 31u);
-  if (level > a) off += 4u * ((1u << (b - a + 1u)) - (1u << (b - level + 1u)));
+  uint32_t off = ones << ((cw + ch + 4u - 2u * l1) & 31u);
+  if (level > a) off += (8u << (cw + ch - 2u * a)) - (8u << (cw + ch - a - l2));
+  if (level > b) off += (level - b) * TEX_TILE_BYTES;
   return off;
 }
+// Byte offset of texel (x, y) within a level whose padded width is 2^plw (level_lw): tiles row-major across the level.
+// The x and y parts share no bit (x < 2^plw), so a sampler forms each once per axis and adds them per tap.
+__host__ __device__ inline uint32_t texel_offset_x(uint32_t x) {
+  return ((x >> TEX_TILE_LW) << (TEX_TILE_LW + TEX_TILE_LH + 2u)) | ((x & ((1u << TEX_TILE_LW) - 1u)) << 2u);
+}
+__host__ __device__ inline uint32_t texel_offset_y(uint32_t plw, uint32_t y) {
+  return ((y >> TEX_TILE_LH) << (plw + TEX_TILE_LH + 2u)) | ((y & ((1u << TEX_TILE_LH) - 1u)) << (TEX_TILE_LW + 2u));
+}
+__host__ __device__ inline uint32_t texel_offset(uint32_t plw, uint32_t x, uint32_t y) { return texel_offset_x(x) + texel_offset_y(plw, y); }
 
 // A set-up triangle, 256 bytes: first half is all the coverage/depth loop reads, second half only
 // the winners' shading reads.  Edge functions are evaluated at integer pixel indices (px,py):

@@ -45,8 +45,10 @@ void launch_background(void* color, int color_format, uint32_t W, uint32_t H, ui
 void launch_blit(const void* color, int color_format, uint32_t W, uint32_t H, void* dst, uint32_t dw, uint32_t dh, uint32_t row_first,
                  uint32_t n_rows, int dst_format, const uint32_t* poison, uint32_t rstride, uint32_t roff, uint32_t row_end, uint32_t* status,
                  uint32_t status_ok, hipStream_t s);
-void launch_downsample(const uint8_t* src, uint32_t sw, uint32_t sh, uint8_t* dst, uint32_t dw, uint32_t dh,
-                       hipStream_t s);
+// texel arena levels are tiled (svr_device.h texel_offset): splw, dplw, plw = log2 of a level's padded width (level_lw)
+void launch_downsample(const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t splw, uint8_t* dst, uint32_t dw, uint32_t dh,
+                       uint32_t dplw, hipStream_t s);
+void launch_retile(bool to_tiled, void* linear, uint8_t* tiled, uint32_t w, uint32_t h, uint32_t plw, hipStream_t s);
 void launch_rgba16f_to_rgba8(const void* src, void* dst, uint32_t n_pixels, hipStream_t s);
 // k_pyramid.hip: the depth pyramid of occlusion culling (include/svr_occlusion.h)
 uint32_t pyramid_levels(uint32_t W, uint32_t H);
