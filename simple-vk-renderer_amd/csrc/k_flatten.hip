@@ -28,7 +28,7 @@ __device__ __forceinline__ void glm_matmul(const float* a, const float* b, float
     }
 }
 
-// is_visible, operation for operation as svr_api.hip's host version (and the oracle's)
+// is_visible, operation for operation as svr_cull.h's host version (and the oracle's)
 __device__ bool is_visible_dev(const SvrRenderObject& obj, const float* viewproj) {
   float m[16];
   glm_matmul(viewproj, obj.transform, m);

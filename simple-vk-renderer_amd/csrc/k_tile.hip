@@ -1858,7 +1858,7 @@ __device__ __forceinline__ void tile_main(const FrameParams& P) {
     if (P.host_clock && threadIdx.x == 0) __hip_atomic_store(P.host_clock, wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // A pass that overflowed a queue is void, and so is everything after it until the host has replayed
-  // it (svr_api.hip "the operation log"): the targets stay as they were before the failed pass.
+  // it (svr_log.hip "the operation log"): the targets stay as they were before the failed pass.
   if (overflow | poison) {
     if (blockIdx.x == 0 && poison == 0u) {  // the first failure: flag + tell the host which pass, and by how much
       // its counters go along (they keep counting past the capacities), so the replay can size the queues

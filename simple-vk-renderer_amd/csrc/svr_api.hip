@@ -1,184 +1,33 @@
-// svr_api.hip — the C ABI of include/svr.h over the HIP kernels (host code; no kernels here).
+// svr_api.hip — the C ABI of include/svr.h over the HIP kernels (host code; no kernels here): the context's life cycle,
+// its resources and targets, options and read-backs, and every geometry entry point.
 //
 // Host half of VulkanEngine::draw_geometry (src/vk_engine.cpp:1357-1477): is_visible cull, sort,
 // per-draw records (the push constants + bound buffers of the record lambda, :1412-1457) — or, for
-// large object counts, handing the objects to k_flatten.hip — then one pass of seven kernels:
-//   prologue -> setup -> clip -> count -> offsets -> fill   (internal stream: overlaps the previous tiles)
-//   tiles                                                    (caller's stream, after an event)
-// The pass is asynchronous like a recorded command buffer; svr_sync / read-backs are the fence.
-// Per-pass device buffers only grow.  A pass whose internal queues overflowed writes nothing to the
-// targets, and neither does anything after it, until the host has replayed it with larger queues
-// ("the operation log" below), so results never depend on the initial capacities.
-#include <hip/hip_runtime.h>
-
+// large object counts, handing the objects to k_flatten.hip — then one pass (svr_log.hip: its kernels, the
+// operation log that keeps it until it has fitted its queues).  The operations over finished targets are svr_screen.hip's.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <cstring>
-#include <deque>
-#include <memory>
 #include <numeric>
-#include <string>
-#include <type_traits>
-#include <utility>
-#include <vector>
 
-#include "../../include/svr_depth.h"
-#include "../../include/svr_draw_list.h"
-#include "../../include/svr_attributes.h"
-#include "../../include/svr_ids.h"
-#include "../../include/svr_lighting.h"
-#include "../../include/svr_post.h"
-#include "../../include/svr_temporal.h"
-#include "../../include/svr_ambient.h"
-#include "../../include/svr_load.h"
-#include "../../include/svr_occlusion.h"
-#include "../../include/svr_views.h"
+#include "svr_context.h"
 #include "svr_cull.h"
-#include "svr_launch.h"
 
 using namespace svr;
 
 namespace {
-
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) {
+thread_local std::string g_err;  // svr_last_error
+}
+int svr::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-// a failed runtime call: "<what>: <the runtime's text>"
-int hip_fail(hipError_t e, const char* what) {
+int svr::hip_fail(hipError_t e, const char* what) {
   return fail(e == hipErrorOutOfMemory ? SVR_ERR_OUT_OF_MEMORY : SVR_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
-// HIPCHK names the failed call by its own text.  HIPCHK_AS: by the text given — where the call goes through one of the
-// owners' helpers below, the runtime call it makes, as a caller has always read it in svr_last_error
-#define HIPCHK_AS(expr, text)                        \
-  do {                                               \
-    hipError_t e_ = (expr);                          \
-    if (e_ != hipSuccess) return hip_fail(e_, text); \
-  } while (0)
-#define HIPCHK(expr) HIPCHK_AS(expr, #expr)
-// hipMalloc of `bytes` into the DevPtr `owner`
-#define DEV_ALLOC(owner, bytes) HIPCHK_AS(dev_alloc(owner, bytes), "hipMalloc((void**)&" #owner ", " #bytes ")")
 
-// Everything the runtime hands out is held by a move-only owner that gives it back: a device allocation, a pinned host
-// block, an event, a stream.  Nothing below frees by hand; an early return frees what the call had got so far.
-struct DevFree {
-  void operator()(void* p) const { (void)hipFree(p); }
-};
-struct PinnedFree {
-  void operator()(void* p) const { (void)hipHostFree(p); }
-};
-struct EventDestroy {
-  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
-};
-struct StreamDestroy {
-  void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
-};
-template <class T> using DevPtr = std::unique_ptr<T, DevFree>;
-template <class T> using PinnedPtr = std::unique_ptr<T, PinnedFree>;
-using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
-using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
-
-template <class T> hipError_t dev_alloc(DevPtr<T>& out, size_t bytes) {
-  void* p = nullptr;
-  const hipError_t e = hipMalloc(&p, bytes);
-  if (e == hipSuccess) out.reset(static_cast<T*>(p));
-  return e;
-}
-template <class T> hipError_t pinned_alloc(PinnedPtr<T>& out, size_t bytes) {
-  void* p = nullptr;
-  const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-  if (e == hipSuccess) out.reset(static_cast<typename PinnedPtr<T>::pointer>(p));
-  return e;
-}
-hipError_t make_event(Event& out, unsigned flags) {
-  hipEvent_t ev = nullptr;
-  const hipError_t e = hipEventCreateWithFlags(&ev, flags);
-  if (e == hipSuccess) out.reset(ev);
-  return e;
-}
-
-// a device buffer that only grows
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    std::swap(p, o.p);
-    std::swap(cap, o.cap);
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  int ensure(size_t bytes) {  // contents are NOT preserved
-    if (bytes <= cap) return SVR_OK;
-    release();
-    size_t want = bytes + bytes / 4;
-    HIPCHK(hipMalloc(&p, want));
-    cap = want;
-    return SVR_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-struct MeshRes {
-  DevPtr<SvrVertex> vtx;
-  DevPtr<uint32_t> idx;
-  DevPtr<float> groups;  // float[6] per 192 indices: box of the vertices they name (setup kernel's chunk culling)
-  size_t n_vtx = 0, n_idx = 0;
-  bool alive = false;
-};
-struct ImageRes {
-  uint32_t arena_off = 0;   // byte offset of level 0 in the context's texel arena
-  size_t bytes = 0;         // all levels
-  uint32_t w = 0, h = 0, levels = 0;
-  uint32_t lw = 0, lh = 0;  // log2 of the power-of-two padded extent the mip layout is computed from
-  uint32_t off[16] = {0};   // = mip_offset(lw, lh, level)
-  bool alive = false;
-};
-struct MaterialRes {
-  int pass;
-  float cf[4], mr[4];
-  uint32_t image, sampler;  // 0-based
-};
-
-// One version of a draw list's device copy (include/svr_draw_list.h).  Copy-on-write: svr_update_draw_list makes a
-// new one, and the list and every logged pass that was enqueued with this one share it; the last to let go frees it
-// (a pass lets go when it is validated, after its completion event — or after its replay).
-struct ListVersion {
-  DevPtr<SvrRenderObject> dev;  // DRAW ORDER: opaque objects sorted by (material, mesh, submission index), then the transparent ones
-  uint32_t n_opaque = 0, n_transparent = 0;
-  uint64_t tris_max = 0;  // upper bounds that size the pass's buffers and grids (every object visible)
-  size_t chunks_max = 0;
-  uint64_t tris_max_opaque = 0;  // ... of the opaque objects alone (depth-only passes: include/svr_depth.h)
-  size_t chunks_max_opaque = 0;
-  DevPtr<uint32_t> obj_ids;  // [n_opaque] draw order -> position in the opaque array as submitted, + 1 (ID passes: svr_ids.h)
-};
-struct DrawListRes {
-  std::vector<SvrRenderObject> objs;  // submission order: opaque list, then transparent list
-  uint32_t n_opaque = 0;
-  std::shared_ptr<const ListVersion> cur;
-  uint64_t mesh_epoch = 0;  // SvrContext::mesh_epoch when the objects were last validated
-  bool valid = false;       // ... and whether they were valid then
-  std::string why;          // if not: validate_object's text
-  bool alive = false;
-};
-
-// A depth pyramid (include/svr_occlusion.h).  The handle, every logged build of it and every logged pass that culls
-// against it share its memory; the last to let go frees it (stream-ordered destruction, like a draw list's version).
-struct PyramidMem {
-  DevPtr<uint32_t> p;  // levels 1 .. levels back to back, level l at word off[l]
-  uint32_t levels = 0;
-  uint32_t off[PYR_MAX_LEVELS + 1] = {};
-  size_t words = 0;
-  Event ev_built;  // recorded behind the last build enqueued (the context's stream): stage 1 of a culling pass waits for it
-};
+namespace {
 
 // software fp32 -> fp16 (RTE) for the one clear colour the host encodes
 uint16_t host_f32_to_f16(float f) {
@@ -198,205 +47,6 @@ uint16_t host_f32_to_f16(float f) {
   uint32_t h = mant >> shift, rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
   if (rem > half || (rem == half && (h & 1u))) h++;
   return (uint16_t)(sign | h);
-}
-
-}  // namespace
-
-struct SvrContext {
-  int device = 0;
-  uint32_t W = 0, H = 0;
-  int fmt = SVR_COLOR_RGBA16F;
-  hipStream_t stream = nullptr;
-  DevPtr<void> color_own;
-  DevPtr<float> depth_own;
-  void* color = nullptr;
-  float* depth = nullptr;
-  DevPtr<uint2> ids_own;     // svr_enable_ids
-  uint2* ids = nullptr;      // the ID target (include/svr_ids.h): a caller's (svr_bind_id_target), ids_own or none
-  bool ids_bound = false;    // ... it is the caller's
-  DevPtr<void> attr_own[4];  // svr_enable_attributes: the context's planes, by bit number (include/svr_attributes.h)
-  void* attr[4] = {};        // the attribute targets: a caller's (svr_bind_attribute_target), attr_own or none
-  bool attr_bound[4] = {};   // ... it is the caller's
-  uint32_t sx = 0, sy = 0, sw = 0, sh = 0;
-  uint32_t rstride = 1, roff = 0;      // svr_set_row_interleave
-  int depth_load_op = SVR_DEPTH_CLEAR;  // svr_set_depth_load_op (include/svr_load.h)
-  uint32_t* present_status = nullptr;  // svr_set_present_status
-
-  std::vector<MeshRes> meshes;
-  std::vector<ImageRes> images;
-  std::vector<SvrSamplerDesc> samplers;
-  std::vector<MaterialRes> materials;
-  std::vector<DrawListRes> lists;  // svr_create_draw_list
-  std::vector<std::shared_ptr<PyramidMem>> pyramids;  // svr_create_depth_pyramid (handle - 1; null once destroyed)
-  uint32_t occl_bound = 0;                            // svr_set_occlusion_pyramid: the handle passes cull against, 0 = none
-  SvrOcclusionStats occl_stats{};                     // of the last instrumented pass
-  uint64_t mesh_epoch = 0;         // counts svr_destroy_mesh calls: a draw list re-validates when it has moved
-  // Texel arena: every image of the context lives in ONE allocation, so a texel's address is a 32-bit byte
-  // offset from one wave-uniform base (FrameParams::tex_arena): the fragment stage's eight gathers per pixel
-  // are global loads with an SGPR base and a 32-bit VGPR offset instead of 64-bit pointer arithmetic per tap,
-  // and records carry 4 bytes per texture, not a pointer.  Grows by reallocation (device copy, after a
-  // fence); offsets never change.  Bound: 4 GiB of texels per context.
-  DevPtr<uint8_t> tex_arena;
-  size_t tex_arena_cap = 0, tex_arena_top = 0;
-  std::vector<std::pair<size_t, size_t>> tex_holes;  // (offset, bytes) of destroyed images, sorted by offset
-  DevBuf tex_table;  // TexBinding[materials + 1]; last slot = scratch binding of svr_draw_tex_image
-  size_t tex_slots = 0;
-  // resource tables of the device flatten pass (k_flatten.hip), rebuilt when a mesh / material was added
-  DevBuf mesh_table, mat_table;
-  size_t mesh_table_n = 0, mat_table_n = 0;
-  int device_flatten = 0;  // SVR_OPT_DEVICE_FLATTEN: 0 auto (>= 2048 objects), 1 always, 2 never
-
-  // Per-pass device buffers, double-buffered: the geometry+binning stage of pass N+1 runs on the
-  // internal stream `gstream` while the tile stage of pass N still reads set N on the caller's
-  // stream.  ev_bin: set filled (recorded on gstream); ev_tile: set consumed (the pass's op_done event).
-  struct PassSet {
-    DevBuf inputs, recs, clipq, bigq, tiles, bins, pairs, flat, sorta, occl;  // occl: a culling pass's flag per chunk  // flat: keys / triangle counts / chunk bases of k_flatten  // inputs = DrawDesc[] then WaveChunk[] (one H2D copy)
-    Event ev_bin;
-    hipEvent_t ev_tile = nullptr;  // not owned: op_done of the pass that used the set last
-    bool used = false;
-  };
-  static const int MAX_OPS = 8;  // operations in flight (log slots)
-  static const int NSETS = 4;  // stage 1 of a small pass may run three passes ahead of the tile stage; a large one keeps to one (submit_pass)
-  PassSet sets[NSETS];
-  int set_pos = 0;
-  // operation log (see "the operation log" below): a pass, or a fill of the colour target (every other operation)
-  enum class OpKind { Pass, Clear, Background, Blit, Pyramid, Light, Post, Temporal, Ambient };  // Pyramid: svr_build_depth_pyramid (logged like a clear); Light: svr_light_pass; Post: svr_post_pass; Temporal: svr_temporal_resolve; Ambient: svr_ambient_pass
-  enum class PassInput { Draws, Objects, List };  // what a pass reads: the one place that says so (P.flatten follows it)
-  struct LoggedOp {
-    OpKind kind = OpKind::Pass;
-    int slot = 0;  // index into h_counters / op_done
-    // a pass
-    uint32_t seq = 0;  // running number, reported by the device if the pass overflows
-    bool timed = false;  // the tile kernel stamps its start and end into the slot's h_clock words: fold into the running mean at retirement
-    FrameParams P{};  // parameters as recorded
-    PassInput input = PassInput::Draws;
-    // what the pass is, as enqueue_pass took it from its PassRequest: the one place submit_pass, retire_pass and the
-    // replay read it from.  depth_only: include/svr_depth.h (the setup and tile kernels' depth instances);
-    // multiview: include/svr_views.h (P.layer_rows is the kernels' copy of it); depth_load: include/svr_load.h (P.depth_load
-    // is the tile launch's copy of it)
-    struct PassShape {
-      bool depth_only = false, multiview = false, depth_load = false;
-    } shape;
-    std::vector<DrawDesc> draws;  // Draws: records built on the host
-    std::vector<SvrRenderObject> objects;  // Objects: the caller's (opaque, then transparent), flattened on the device
-    uint32_t n_opaque_obj = 0, n_transparent_obj = 0;  // Objects and List
-    // List: the version of a resident draw list it was enqueued with (svr_draw_list): the objects stay on the device
-    std::shared_ptr<const ListVersion> list;
-    // List, multiview (svr_draw_list_views): the views' viewproj matrices, 16 floats each; empty = one view
-    std::vector<float> viewprojs;
-    // a pass: the pyramid it culls against (include/svr_occlusion.h), or none; Pyramid: the one it builds, from pyr_src
-    std::shared_ptr<PyramidMem> pyr;
-    const float* pyr_src = nullptr;
-    // Light (include/svr_lighting.h): the kernel's parameters as recorded, its owned tile rows and the caller's lights
-    LightLaunch light{};
-    uint32_t light_tiles_y = 0;
-    std::vector<SvrPointLight> lights;
-    // Post (include/svr_post.h): the kernels' parameters as recorded
-    PostLaunch post{};
-    // Temporal (include/svr_temporal.h): the kernels' parameters as recorded, the history roles and validity among them
-    TemporalLaunch temporal{};
-    // Ambient (include/svr_ambient.h): the kernels' parameters as recorded, the planes it reads and writes among them
-    AmbientLaunch ambient{};
-    bool flattened() const { return input != PassInput::Draws; }
-    // a fill: colour target, its format and extent, the rows it writes
-    void* target = nullptr;
-    int target_fmt = 0;
-    uint32_t tw = 0, th = 0, y_first = 0, n_rows = 0;
-    uint64_t clear_packed = 0;  // Clear: the encoded texel
-    int bg_effect = 0;  // Background
-    float bg_data[16] = {};
-    void* blit_dst = nullptr;  // Blit: the swapchain image
-    uint32_t blit_w = 0, blit_h = 0;
-    int blit_fmt = 0;
-    uint32_t blit_rstride = 1, blit_roff = 0, blit_row_end = 0;  // identity blits of an interleaved pass: its tile rows only
-    uint32_t* blit_status = nullptr;
-  };
-  Event op_done[MAX_OPS];
-  int op_pos = 0;
-  uint32_t replayed = 0;         // passes re-run by recover_from_overflow
-  // svr_clear_color deferred into the next pass (the attachment's loadOp CLEAR): see flush_clear
-  struct PendingClear {
-    bool valid = false;
-    void* target = nullptr;
-    uint32_t y0 = 0, rows = 0;
-    int fmt = 0;
-    uint64_t packed = 0;
-  } pending_clear;
-  uint32_t next_seq = 1;
-  PinnedPtr<uint32_t> h_failed_seq;  // written by the tile kernel of the first failing pass
-  DevPtr<uint32_t> d_poison;  // sticky device flag: a pass overflowed, later target writes are void
-  Stream gstream;
-  Stream gstream_hi;                  // the same at the highest priority: stage 1 of small passes (submit_pass)
-  hipStream_t last_g = nullptr;       // the one the previous pass used (not owned)
-  Event ev_gswitch;
-  DevBuf d_cvt;
-  uint32_t clip_cap = 0, extra_cap = 0, bin_cap = 0;
-  uint32_t debug_caps = 0;  // SVR_OPT_QUEUE_CAPS
-  // pinned host staging + read-back, one of each per operation-log slot
-  PinnedPtr<void> h_stage[MAX_OPS];  // per log slot
-  size_t h_stage_cap[MAX_OPS] = {};
-  PinnedPtr<Counters[]> h_counters;  // [MAX_OPS]
-  PinnedPtr<uint32_t> h_row_cost;  // [MAX_OPS][ROW_COST_MAX]: tile-row costs posted by every pass's tile kernel
-  PinnedPtr<unsigned long long> h_clock;  // [MAX_OPS][CLOCK_WORDS]: SVR_OPT_KERNEL_TIMING level 1 (FrameParams::host_clock)
-  std::vector<uint32_t> row_cost;  // ... of the pass validated last (svr_get_row_costs), with its scissor rows
-  uint32_t row_cost_y0 = 0, row_cost_rows = 0;
-
-  // SVR_OPT_KERNEL_TIMING: ring of event quadruples (before setup, after clip, after fill, after tiles)
-  static const int TRING = 16;
-  Event tev[TRING][5];  // geometry start, after clip, after fill (gstream) | tile start, tile end (stream)
-  bool tev_used[TRING] = {};
-  bool tev_all[TRING] = {};  // the slot holds all five events (level 2), not just the tile pair
-  int tev_pos = 0;
-  int kernel_timing = 0;  // 0 off, 1 tile kernel only (it stamps the clock itself: no events), 2 all three stages
-  double acc_ms[3] = {0, 0, 0};
-  uint32_t acc_n = 0;
-  FrameParams last{};        // parameters of the pass enqueued last (debug read-backs)
-  uint32_t last_n_draws = 0;  // ... and its draw count, if the host staged its records (svr_debug_read_records)
-  bool instrument = false;
-  bool tile_cycles = false;
-  uint32_t tuning = 0;
-  int trace_x = -1, trace_y = -1;
-  DevBuf d_trace, d_tile_cycles;
-  // svr_light_pass: the device copy of a pass's lights (SVR_MAX_LIGHTS records, refilled in stream order in front of
-  // every lighting pass) and the kept-light count per tile of the last one; both allocated once, by the first pass
-  DevPtr<SvrPointLight> d_lights;
-  DevPtr<uint32_t> d_light_tiles;
-  uint32_t light_tiles_n = 0;
-  // svr_post_pass: the level images of the bloom (4 halves per texel), sized for the context's extent; allocated once, by
-  // the first post pass
-  DevPtr<uint2> d_post_levels;
-  // svr_temporal_resolve: the two history images (4 halves per texel, the context's extent), allocated and zeroed by the
-  // first resolve.  temporal_read names the one the next resolve reads; temporal_has: a resolve was accepted, with the
-  // scissor temporal_scissor.  All three change at an accepted call only, in call order.
-  DevPtr<uint2> d_temporal[2];
-  int temporal_read = 0;
-  bool temporal_has = false;
-  uint32_t temporal_scissor[4] = {0, 0, 0, 0};
-  // svr_ambient_pass: the (a, 1/w) scratch plane and the context's own ambient target, both of the context's extent,
-  // allocated and zeroed by the first pass that needs them.  ambient_bound: the caller's plane, or null.  light_ao:
-  // svr_set_light_ambient_occlusion.
-  DevPtr<float2> d_ambient_raw;
-  DevPtr<float> d_ambient_own;
-  float* ambient_bound = nullptr;
-  bool light_ao = false;
-  SvrStats stats{};
-  // Declared last, so it goes first: its entries hold draw-list versions and pyramids, and name the memory above.
-  std::deque<LoggedOp> log;
-
-  // Every member gives back what it holds, after this: nothing is freed before the device has finished with it.
-  ~SvrContext() {
-    (void)hipSetDevice(device);
-    (void)hipStreamSynchronize(stream);
-    if (gstream) (void)hipStreamSynchronize(gstream.get());
-    if (gstream_hi) (void)hipStreamSynchronize(gstream_hi.get());
-  }
-};
-
-namespace {
-
-int use_device(SvrContext* ctx) {
-  HIPCHK(hipSetDevice(ctx->device));
-  return SVR_OK;
 }
 
 MeshRes* get_mesh(SvrContext* ctx, SvrMesh h) {
@@ -421,8 +71,6 @@ TexBinding make_binding(const ImageRes& im, const SvrSamplerDesc& s) {
 }
 
 // ---------------------------------------------------------------- texel arena
-int finish_pending(SvrContext* ctx);
-
 constexpr size_t ARENA_MAX = (size_t)0xffffff00u;  // offsets are 32-bit
 constexpr size_t ARENA_ALIGN = 256;
 
@@ -505,490 +153,7 @@ int upload_tex_table(SvrContext* ctx, const TexBinding* scratch) {
   return SVR_OK;
 }
 
-// ---------------------------------------------------------------- pass machinery
-// pinned staging buffer of a log slot (free: the slot's previous operation has been retired)
-int stage_buffer(SvrContext* ctx, int slot, size_t bytes, void** out) {
-  if (ctx->h_stage_cap[slot] < bytes) {
-    ctx->h_stage[slot].reset();
-    ctx->h_stage_cap[slot] = 0;
-    size_t want = bytes + bytes / 2 + 4096;
-    HIPCHK_AS(pinned_alloc(ctx->h_stage[slot], want), "hipHostMalloc(&ctx->h_stage[slot], want, hipHostMallocDefault)");
-    ctx->h_stage_cap[slot] = want;
-  }
-  *out = ctx->h_stage[slot].get();
-  return SVR_OK;
-}
-
-// fold one finished slot of the timing ring into the running means
-int harvest_timing(SvrContext* ctx, int slot) {
-  if (!ctx->tev_used[slot]) return SVR_OK;
-  HIPCHK(hipEventSynchronize(ctx->tev[slot][4].get()));
-  const int from[3] = {0, 1, 3}, to[3] = {1, 2, 4};
-  for (int k = ctx->tev_all[slot] ? 0 : 2; k < 3; k++) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->tev[slot][from[k]].get(), ctx->tev[slot][to[k]].get()));
-    ctx->acc_ms[k] += ms;
-  }
-  ctx->acc_n++;
-  ctx->tev_used[slot] = false;
-  return SVR_OK;
-}
-
-// head of a set's tile buffer: Counters (96 B) + 80 class counters (FrameParams::cls_count) + ROW_COST_MAX row costs, then tile_count
-constexpr size_t TILE_HEAD_BYTES = sizeof(Counters) + (80 + ROW_COST_MAX) * sizeof(uint32_t);
-static_assert(TILE_HEAD_BYTES % 16 == 0, "tile buffer head layout");
-
-// size the per-pass buffers for P.n_tris and the current capacities, fill the pointers
-int bind_pass_buffers(SvrContext* ctx, FrameParams& P, int set_index) {
-  SvrContext::PassSet& set = ctx->sets[set_index];
-  if (int e = set.recs.ensure(((size_t)P.n_tris + ctx->extra_cap) * sizeof(TriRec))) return e;
-  if (int e = set.clipq.ensure((size_t)ctx->clip_cap * sizeof(ClipItem))) return e;
-  if (int e = set.bigq.ensure(((size_t)P.n_tris + 64) * sizeof(uint32_t))) return e;
-  if (int e = set.tiles.ensure(TILE_HEAD_BYTES + ((size_t)P.n_tiles * 13 + 8 + (size_t)SPLIT_EXTRA * 8) * sizeof(uint32_t))) return e;
-  if (int e = set.bins.ensure((size_t)ctx->bin_cap * sizeof(uint32_t))) return e;
-  if (int e = set.pairs.ensure((size_t)ctx->bin_cap * 12)) return e;
-  if (int e = set.sorta.ensure((size_t)ctx->bin_cap * 2 * sizeof(unsigned long long))) return e;
-  P.recs = (TriRec*)set.recs.p;
-  P.extra_cap = ctx->extra_cap;
-  P.clip_queue = (ClipItem*)set.clipq.p;
-  P.clip_cap = ctx->clip_cap;
-  P.big_queue = (uint32_t*)set.bigq.p;
-  P.counters = (Counters*)set.tiles.p;
-  P.cls_count = (uint32_t*)((char*)set.tiles.p + sizeof(Counters));
-  P.row_cost = P.cls_count + 80;
-  P.tile_count = (uint32_t*)((char*)set.tiles.p + TILE_HEAD_BYTES);
-  P.tile_offset = P.tile_count + (((size_t)P.n_tiles * 2 + 3) & ~(size_t)3);  // 16-byte aligned
-  P.tile_info = (uint4*)(P.tile_offset + (((size_t)P.n_tiles * 2 + 3) & ~(size_t)3));  // 8 words per tile
-  P.tile_order = (uint32_t*)P.tile_info + ((size_t)P.n_tiles + SPLIT_EXTRA) * 8;  // the quarters of split tiles head tile_info
-  P.pairs = (uint2*)set.pairs.p;
-  P.pair_slot = (uint32_t*)((char*)set.pairs.p + (size_t)ctx->bin_cap * 8);
-  P.bins = (uint32_t*)set.bins.p;
-  P.bin_cap = ctx->bin_cap;
-  P.sort_arena = (unsigned long long*)set.sorta.p;
-  P.sort_cap = ctx->bin_cap * 2u;  // a sorted bin needs at most twice its entries (power-of-two padding)
-  P.poison = ctx->d_poison.get();
-  P.host_failed_seq = ctx->h_failed_seq.get();
-  return SVR_OK;
-}
-
-// Enqueue one pass.  Stage 1 (gstream): prologue (inputs + zeroing), setup, clip, bin count, offsets, bin fill
-// -> ev_bin.  Stage 2 (caller's stream): wait ev_bin, tile kernel, counters to the host
-// (report_kernel) -> op_done.  The caller sees stream order (everything it enqueued before the call precedes the tile
-// stage, the only one that touches the targets); stage 1 depends on host inputs alone, so it overlaps
-// the tile stages of the passes before it.  The op holds the pass: its parameters, number, log slot and input.
-int submit_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, bool pipe) {
-  FrameParams P = op.P;
-  const int op_slot = op.slot;
-  const std::vector<DrawDesc>& draws = op.draws;
-  const bool flatten = op.flattened(), resident = op.input == SvrContext::PassInput::List;
-  // queue capacities: generous first guesses; overflow -> replay (recover_from_overflow)
-  if (ctx->debug_caps) {  // SVR_OPT_QUEUE_CAPS: start tiny so that tests reach the replay path
-    ctx->clip_cap = std::max<uint32_t>(ctx->clip_cap, ctx->debug_caps);
-    ctx->extra_cap = std::max<uint32_t>(ctx->extra_cap, ctx->debug_caps);
-    ctx->bin_cap = std::max<uint32_t>(ctx->bin_cap, ctx->debug_caps);
-  } else {
-    ctx->clip_cap = std::max<uint32_t>(ctx->clip_cap, std::max<uint32_t>(65536u, P.n_tris / 4u));
-    ctx->extra_cap = std::max<uint32_t>(ctx->extra_cap, std::max<uint32_t>(65536u, P.n_tris / 2u));
-    ctx->bin_cap = std::max<uint32_t>(ctx->bin_cap, std::max<uint32_t>(1u << 22, P.n_tris * 8u));
-  }
-  const int set_index = ctx->set_pos;
-  ctx->set_pos = (ctx->set_pos + 1) % SvrContext::NSETS;
-  SvrContext::PassSet& set = ctx->sets[set_index];
-  // Stage 1 of a pass of few tiles (a 1920x1080 frame, a band of a sharded one) runs at the highest stream priority:
-  // such a pass is bounded by stage 1 — its setup kernel finds the CUs taken by the tile kernel's first, longest
-  // workgroups (21 us alone, 53 us beside it) — and with priority its workgroups get the slots that come free
-  // (1080p: -5 % per frame).  A 4K frame is bounded by its tile kernel and loses 0.8 % to the same favour.
-  // Either stream is made when a pass first needs it: the runtime maps a process's streams onto a handful of hardware
-  // queues (four by default), and streams that share one serialise — a context that only ever renders one size of pass
-  // must not take a queue it never uses (two contexts with both streams in one process: stage 1 and the tile kernel of
-  // the second ended up in ONE queue, 0.093 -> 0.27 ms per 1080p frame).
-  hipStream_t s = ctx->stream, g = ctx->stream;
-  if (pipe) {
-#ifdef SVR_AB_STAGE1_HI  // A/B builds only: stage 1 of every pass on the high-priority stream
-    const bool hi = true;
-#else
-    const bool hi = P.n_tiles <= SPLIT_TILES_MAX;
-#endif
-    Stream& slot = hi ? ctx->gstream_hi : ctx->gstream;
-    if (!slot) {
-      hipStream_t made = nullptr;
-      int least = 0, greatest = 0;
-      if (hi) (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-      if (!hi || hipStreamCreateWithPriority(&made, hipStreamNonBlocking, greatest) != hipSuccess) {
-        if (hi) (void)hipGetLastError();  // no priorities here: an ordinary stream does the job, a little later
-        made = nullptr;
-        HIPCHK(hipStreamCreateWithFlags(&made, hipStreamNonBlocking));
-      }
-      slot.reset(made);
-    }
-    g = slot.get();
-  }
-  if (pipe) {
-    if (ctx->last_g && ctx->last_g != g) {  // keep stage 1 of consecutive passes in order across the two streams
-      HIPCHK(hipEventRecord(ctx->ev_gswitch.get(), ctx->last_g));
-      HIPCHK(hipStreamWaitEvent(g, ctx->ev_gswitch.get(), 0));
-    }
-    ctx->last_g = g;
-  }
-  // per-pass inputs: draws + chunks through pinned staging, one copy
-  // (resident: the objects are a draw list's device copy, nothing to stage)
-  const size_t n_objects = flatten ? (size_t)op.n_opaque_obj + op.n_transparent_obj : 0;
-  const size_t n_views = op.viewprojs.size() / 16u;  // a multiview list pass: one draw per object and view at most
-  size_t draw_bytes = (flatten ? n_objects * std::max<size_t>(n_views, 1) : draws.size()) * sizeof(DrawDesc), chunk_bytes = (size_t)P.n_chunks * sizeof(WaveChunk);
-  if (int e = set.inputs.ensure(std::max<size_t>(draw_bytes + chunk_bytes + 16, 256))) return e;
-  if (flatten)
-    if (int e = set.flat.ensure(std::max(n_objects * (16 + sizeof(SvrRenderObject)), n_views * 64) + 128)) return e;
-  if (int e = bind_pass_buffers(ctx, P, set_index)) return e;
-  if (op.pyr) {  // occlusion culling (include/svr_occlusion.h)
-    if (int e = set.occl.ensure(std::max<size_t>(P.n_chunks, 16))) return e;
-    P.pyr = op.pyr->p.get();
-    P.pyr_levels = op.pyr->levels;
-    std::memcpy(P.pyr_off, op.pyr->off, sizeof(P.pyr_off));
-    P.occl_flags = (uint8_t*)set.occl.p;
-    // Stage 1 reads the pyramid: it waits for the last build enqueued before this pass (on the caller's stream; without
-    // the pipeline, stream order does it).  The other way round needs nothing: a later build of this pyramid runs on the
-    // caller's stream behind this pass's tile kernel, which waits for this pass's stage 1 (ev_bin).
-    if (pipe) HIPCHK(hipStreamWaitEvent(g, op.pyr->ev_built.get(), 0));
-  }
-  // How far stage 1 runs ahead.  A pass of few tiles (a band of a sharded frame: stage 1 56 us, tiles 50 us) is bounded
-  // by stage 1, which then wants to run back to back: it only waits for its set, last read by the tile stage of
-  // NSETS passes ago (a band of an eight-way split: -16 % per frame against two sets, with the priority above).  A 4K
-  // frame is bounded by its tile kernel, and stage-1 kernels that arrive earlier only take CU time from it (+0.6 %):
-  // it waits for the tile stage of two passes back (which is behind that of NSETS passes ago in the stream).
-  if (pipe) {
-    SvrContext::PassSet& gate = P.n_tiles > SPLIT_TILES_MAX ? ctx->sets[(set_index + SvrContext::NSETS - 2) % SvrContext::NSETS] : set;
-    if (gate.used) HIPCHK(hipStreamWaitEvent(g, gate.ev_tile, 0));
-    else if (set.used) HIPCHK(hipStreamWaitEvent(g, set.ev_tile, 0));
-  }
-  void* stage = nullptr;
-  if (int e = stage_buffer(ctx, op_slot, (flatten ? (resident ? n_views * 64 : n_objects * sizeof(SvrRenderObject)) : draw_bytes + chunk_bytes) + 64, &stage)) return e;
-  P.host_counters = &ctx->h_counters[op_slot];
-  P.host_row_cost = ctx->h_row_cost.get() + (size_t)op_slot * ROW_COST_MAX;
-  P.host_clock = nullptr;
-  if (op.timed) {  // (the slot is free: its previous pass has been retired)
-    P.host_clock = ctx->h_clock.get() + (size_t)op_slot * CLOCK_WORDS;
-    std::memset(P.host_clock, 0, sizeof(unsigned long long) * CLOCK_WORDS);
-  }
-  P.op_seq = op.seq;
-  if (flatten) {  // the objects themselves are the input; cull, sort, draw records and chunks happen on the device
-    if (!resident) std::memcpy(stage, op.objects.data(), n_objects * sizeof(SvrRenderObject));
-    if (n_views) std::memcpy(stage, op.viewprojs.data(), n_views * 64);  // the prologue puts them at the head of set.flat
-  } else {
-    std::memcpy(stage, draws.data(), draw_bytes);
-    WaveChunk* ch = reinterpret_cast<WaveChunk*>((char*)stage + draw_bytes);
-    size_t ci = 0;
-    for (size_t di = 0; di < draws.size(); di++)
-      for (uint32_t k = 0, nk = chunk_count(draws[di].first_index, draws[di].tri_count); k < nk; k++) {
-        ch[ci].draw = (uint32_t)di;
-        ch[ci].first_tri = chunk_first(draws[di].first_index, k);
-        ci++;
-      }
-  }
-  P.draws = (const DrawDesc*)set.inputs.p;
-  P.chunks = (const WaveChunk*)((const char*)set.inputs.p + draw_bytes);  // DrawDesc is 192 B: stays 16-byte aligned
-
-  int ts = -1;
-  if (ctx->kernel_timing >= 2) {
-    ts = ctx->tev_pos;
-    ctx->tev_pos = (ctx->tev_pos + 1) % SvrContext::TRING;
-    if (int e = harvest_timing(ctx, ts)) return e;
-    for (int k = 0; k < 5; k++)
-      if (!ctx->tev[ts][k]) HIPCHK_AS(make_event(ctx->tev[ts][k], hipEventDefault), "hipEventCreate(&ctx->tev[ts][k])");
-  }
-  // inputs out of the staging buffer + zero the counters, class counters and tile_count (adjacent)
-  launch_prologue(stage, n_views ? set.flat.p : set.inputs.p, n_views ? n_views * 64 : (flatten ? 0 : draw_bytes + chunk_bytes), P.counters,
-                  TILE_HEAD_BYTES + (size_t)P.n_tiles * 2 * sizeof(uint32_t), (flatten || op.shape.multiview) ? 0u : (uint32_t)draws.size(), P.scene, g);
-  if (flatten) {
-    FlattenParams F;
-    std::memset(&F, 0, sizeof(F));
-    F.objects = resident ? op.list->dev.get() : (const SvrRenderObject*)stage;
-    F.n_opaque = op.n_opaque_obj;
-    F.n_transparent = op.n_transparent_obj;
-    std::memcpy(F.viewproj, P.scene.viewproj, 64);
-    F.meshes = (const MeshEntry*)ctx->mesh_table.p;
-    F.materials = (const MatEntry*)ctx->mat_table.p;
-    F.keys = (unsigned long long*)set.flat.p;
-    F.draw_tris = (uint32_t*)((char*)set.flat.p + n_objects * 8);
-    F.chunk_base = F.draw_tris + n_objects;
-    F.objects_dev = (SvrRenderObject*)((char*)set.flat.p + ((n_objects * 16 + 63) & ~(size_t)63));
-    F.draws = (DrawDesc*)set.inputs.p;
-    F.chunks = (WaveChunk*)((char*)set.inputs.p + draw_bytes);
-    F.counters = P.counters;
-    F.ids = P.ids ? 1u : 0u;
-    F.obj_ids = (P.ids && resident) ? op.list->obj_ids.get() : nullptr;
-    F.n_views = (uint32_t)n_views;
-    F.viewprojs = n_views ? (const float*)set.flat.p : nullptr;
-    if (resident)
-      launch_list_flatten(F, g);
-    else
-      launch_flatten(F, g);
-  }
-  const bool all_stages = ctx->kernel_timing >= 2;
-  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][0].get(), g));
-  launch_setup(P, op.shape.depth_only, g);
-  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][1].get(), g));
-  launch_bin_count(P, g);
-  launch_bin_scan(P, g);
-  launch_bin_fill(P, g, pipe ? set.ev_bin.get() : nullptr);  // ev_bin rides on the fill kernel's dispatch
-  if (ts >= 0 && all_stages) HIPCHK(hipEventRecord(ctx->tev[ts][2].get(), g));
-  if (pipe) HIPCHK(hipStreamWaitEvent(s, set.ev_bin.get(), 0));
-  if (ts >= 0) HIPCHK(hipEventRecord(ctx->tev[ts][3].get(), s));
-  // op_done rides on the pass's last kernel (a start event would be a packet of its own in front of the tile kernel:
-  // with kernel timing level 1 the kernel stamps the clock itself, P.host_clock)
-  launch_tiles(P, ctx->fmt, P.instrument != 0, op.shape.depth_only, s, ctx->op_done[op_slot].get());
-  if (ts >= 0) {
-    HIPCHK(hipEventRecord(ctx->tev[ts][4].get(), s));
-    ctx->tev_used[ts] = true;
-    ctx->tev_all[ts] = all_stages;
-  }
-  HIPCHK(hipGetLastError());
-  // the one event of the pass: its counters are on the host, its set and staging buffer are free
-  set.ev_tile = ctx->op_done[op_slot].get();
-  set.used = true;
-  ctx->last = P;
-  ctx->last_n_draws = flatten ? 0u : (uint32_t)draws.size();
-  return SVR_OK;
-}
-
-// what the host learns from a pass that finished without overflowing, with its counters c
-int retire_pass(SvrContext* ctx, const SvrContext::LoggedOp& op, const Counters& c) {
-  if (op.P.instrument) {
-    ctx->stats.bin_entries = c.total_entries;
-    ctx->stats.rasterized_fragments = c.rasterized;
-    ctx->stats.shaded_fragments = c.shaded;
-    ctx->stats.binned_triangles = c.binned;
-    ctx->occl_stats.chunks_tested = c.occl_tested;
-    ctx->occl_stats.chunks_culled = c.occl_culled;
-    ctx->occl_stats.triangles_culled = c.occl_tris;
-    if (c.hiz_bad) return fail(SVR_ERR_DEVICE, "internal check failed: the hierarchical depth test dropped a fragment that wins (" + std::to_string(c.hiz_bad) + ")");
-  }
-  if (op.flattened()) {  // device-flattened passes learn these late
-    ctx->stats.drawcall_count = (int32_t)c.flat_draws;
-    ctx->stats.triangle_count = (int32_t)c.flat_tris;
-    ctx->stats.culled_draws = c.flat_culled;
-  }
-  // the tile rows' costs (posted by its tile kernel before anything else): svr_get_row_costs, of single-view colour passes
-  if (op.shape.multiview || op.shape.depth_only) return SVR_OK;
-  const uint32_t* src = ctx->h_row_cost.get() + (size_t)op.slot * ROW_COST_MAX;
-  ctx->row_cost.assign(src, src + std::min<uint32_t>(op.P.tiles_y, ROW_COST_MAX));
-  ctx->row_cost_y0 = op.P.sy;
-  ctx->row_cost_rows = op.P.sh;
-  return SVR_OK;
-}
-
-// ---------------------------------------------------------------- the operation log
-// Passes run asynchronously and several deep, so the host learns of a queue overflow late.  The
-// guarantee "results never depend on queue capacities" is kept like this: the tile kernel of a pass
-// that overflowed writes nothing and raises a sticky device flag (poison); every later target-writing
-// kernel of this context (tile kernels, clears) sees the flag and writes nothing either, so the
-// targets freeze in the state before the failed pass.  The host keeps every target-writing operation
-// in a log until its completion event has fired and its counters were checked; on an overflow it
-// drains the device, lowers the flag, grows the queues and replays the log from the failed operation
-// on, in order.  (Work the caller itself enqueues between passes is not in the log; SvrStats.
-// replayed_passes tells such a caller that a replay happened — see dist.py.)
-int log_slot(SvrContext* ctx, int* slot);
-int retire_ops(SvrContext* ctx, bool blocking);
-int flush_clear(SvrContext* ctx);
-
-// replaying: the operation is run again by recover_from_overflow (a present then reports 2 instead of 0)
-int submit_fill(SvrContext* ctx, const SvrContext::LoggedOp& op, bool replaying = false) {
-  if (op.kind == SvrContext::OpKind::Clear) {
-    const size_t px_bytes = op.target_fmt == SVR_COLOR_RGBA16F ? 8 : 4;
-    launch_fill_color((char*)op.target + (size_t)op.y_first * op.tw * px_bytes, op.tw * op.n_rows, op.target_fmt, op.clear_packed,
-                      ctx->d_poison.get(), ctx->stream);
-  } else if (op.kind == SvrContext::OpKind::Pyramid) {  // (writes nothing while the poison flag is up)
-    launch_pyramid(op.pyr_src, op.tw, op.th, op.pyr->p.get(), op.pyr->off, op.pyr->levels, ctx->d_poison.get(), ctx->stream);
-    HIPCHK(hipEventRecord(op.pyr->ev_built.get(), ctx->stream));
-  } else if (op.kind == SvrContext::OpKind::Light) {  // (writes nothing while the poison flag is up)
-    if (!op.lights.empty()) {
-      const size_t bytes = op.lights.size() * sizeof(SvrPointLight);
-      void* stage = nullptr;
-      if (int e = stage_buffer(ctx, op.slot, bytes, &stage)) return e;
-      std::memcpy(stage, op.lights.data(), bytes);
-      HIPCHK(hipMemcpyAsync(ctx->d_lights.get(), stage, bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    launch_light(op.light, op.target_fmt, op.light_tiles_y, ctx->stream);
-  } else if (op.kind == SvrContext::OpKind::Post) {  // (every kernel of it writes nothing while the poison flag is up)
-    launch_post(op.post, ctx->stream);
-  } else if (op.kind == SvrContext::OpKind::Temporal) {  // (both kernels write nothing while the poison flag is up)
-    launch_temporal(op.temporal, ctx->stream);
-  } else if (op.kind == SvrContext::OpKind::Ambient) {  // (both kernels write nothing while the poison flag is up)
-    launch_ambient(op.ambient, ctx->stream);
-  } else if (op.kind == SvrContext::OpKind::Background) {
-    launch_background(op.target, op.target_fmt, op.tw, op.th, op.y_first, op.n_rows, op.bg_effect, op.bg_data, ctx->d_poison.get(), ctx->stream);
-  } else {
-    launch_blit(op.target, op.target_fmt, op.tw, op.th, op.blit_dst, op.blit_w, op.blit_h, op.y_first, op.n_rows, op.blit_fmt, ctx->d_poison.get(),
-                op.blit_rstride, op.blit_roff, op.blit_row_end, op.blit_status, replaying ? 2u : 0u, ctx->stream);
-  }
-  HIPCHK(hipGetLastError());
-  return SVR_OK;
-}
-
-int recover_from_overflow(SvrContext* ctx) {
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->gstream) HIPCHK(hipStreamSynchronize(ctx->gstream.get()));
-  if (ctx->gstream_hi) HIPCHK(hipStreamSynchronize(ctx->gstream_hi.get()));
-  const uint32_t failed_seq = *(volatile uint32_t*)ctx->h_failed_seq.get();
-  *ctx->h_failed_seq = 0;
-  for (SvrContext::LoggedOp& op : ctx->log) {
-    if (op.kind != SvrContext::OpKind::Pass) {
-      HIPCHK(hipMemsetAsync(ctx->d_poison.get(), 0, sizeof(uint32_t), ctx->stream));
-      if (int e = submit_fill(ctx, op, true)) return e;
-      continue;
-    }
-    bool done = false;
-    Counters c;
-    std::memset(&c, 0, sizeof(c));
-    // the pass that failed reported its counters with its number (tile_kernel): grow before the first replay.
-    // The passes behind it were only void, not known to overflow: they start from the capacities as they are.
-    if (op.seq == failed_seq && ctx->h_counters[op.slot].overflow) c = ctx->h_counters[op.slot];
-    for (int attempt = 0; attempt < 13 && !done; attempt++) {
-      if (c.overflow & 1u) ctx->clip_cap = std::max<uint32_t>(ctx->clip_cap * 2u, c.n_clip + 1024u);
-      if (c.overflow & 2u) ctx->extra_cap = std::max<uint32_t>(ctx->extra_cap * 2u, c.n_extra + 1024u);
-      if (c.overflow & 4u) {
-        uint32_t need = std::max(c.total_entries, c.n_pairs + c.n_pairs_rest);
-        ctx->bin_cap = std::max<uint32_t>(ctx->bin_cap * 2u, need + need / 4u);
-      }
-      HIPCHK(hipMemsetAsync(ctx->d_poison.get(), 0, sizeof(uint32_t), ctx->stream));
-      if (int e = submit_pass(ctx, op, false)) return e;
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      HIPCHK(hipMemcpy(&c, ctx->last.counters, sizeof(Counters), hipMemcpyDeviceToHost));
-      *ctx->h_failed_seq = 0;
-      done = c.overflow == 0;
-    }
-    if (!done) {
-      ctx->log.clear();
-      return fail(SVR_ERR_OVERFLOW, "a pass kept overflowing its internal queues after 12 replays");
-    }
-    if (int e = retire_pass(ctx, op, c)) return e;
-    ctx->replayed++;
-  }
-  HIPCHK(hipMemsetAsync(ctx->d_poison.get(), 0, sizeof(uint32_t), ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->log.clear();
-  return SVR_OK;
-}
-
-// validate finished operations front to back; blocking = wait for all of them (a fence).
-// Clears record no event of their own (an event between two kernels is a bubble in the stream): a
-// clear is done when a pass behind it is, or when the stream has drained.
-int retire_ops(SvrContext* ctx, bool blocking) {
-  while (!ctx->log.empty()) {
-    size_t k = 0;  // first pass at or behind the front
-    while (k < ctx->log.size() && ctx->log[k].kind != SvrContext::OpKind::Pass) k++;
-    if (k == ctx->log.size()) {  // only clears left
-      if (!blocking) return SVR_OK;
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      ctx->log.clear();
-      return SVR_OK;
-    }
-    const int slot = ctx->log[k].slot;
-    if (blocking) {
-      HIPCHK(hipEventSynchronize(ctx->op_done[slot].get()));
-    } else {
-      hipError_t q = hipEventQuery(ctx->op_done[slot].get());
-      if (q == hipErrorNotReady) return SVR_OK;
-      HIPCHK(q);
-    }
-    // the device names the first pass that overflowed (tile_kernel); everything from it on is void
-    const uint32_t failed = *(volatile uint32_t*)ctx->h_failed_seq.get();
-    if (failed != 0 && failed == ctx->log[k].seq) {
-      // the clears in front of the failed pass did land: only it and what follows is replayed
-      ctx->log.erase(ctx->log.begin(), ctx->log.begin() + (long)k);
-      return recover_from_overflow(ctx);
-    }
-    if (ctx->log[k].timed) {  // the kernel's own stamps of the 100 MHz wall clock: first workgroup's start, last workgroup's end
-      const volatile unsigned long long* w = ctx->h_clock.get() + (size_t)slot * CLOCK_WORDS;
-      unsigned long long t_end = 0;
-      const unsigned long long t_start = w[0];
-      for (uint32_t i = 1; i <= 64; i++) {
-        const unsigned long long t = w[i * CLOCK_STRIDE];
-        if (t > t_end) t_end = t;
-      }
-      if (t_start != 0 && t_end >= t_start) {  // (a void pass stamps too; a pass whose kernel never ran does not count)
-        ctx->acc_ms[2] += (double)(t_end - t_start) * 1e-5;
-        ctx->acc_n++;
-      }
-    }
-    const int e = retire_pass(ctx, ctx->log[k], ctx->h_counters[slot]);
-    ctx->log.erase(ctx->log.begin(), ctx->log.begin() + (long)k + 1);
-    if (e) return e;
-  }
-  return SVR_OK;
-}
-
-// a free slot of the counters/event/staging ring for the next logged operation (waits if full)
-int log_slot(SvrContext* ctx, int* slot) {
-  if ((int)ctx->log.size() >= SvrContext::MAX_OPS) {
-    if (int e = retire_ops(ctx, false)) return e;
-    if ((int)ctx->log.size() >= SvrContext::MAX_OPS) {
-      bool any_pass = false;
-      for (const SvrContext::LoggedOp& op : ctx->log) any_pass |= op.kind == SvrContext::OpKind::Pass;
-      if (any_pass) {
-        for (const SvrContext::LoggedOp& op : ctx->log)
-          if (op.kind == SvrContext::OpKind::Pass) {
-            HIPCHK(hipEventSynchronize(ctx->op_done[op.slot].get()));
-            break;
-          }
-        if (int e = retire_ops(ctx, false)) return e;
-      } else if (int e = retire_ops(ctx, true)) {
-        return e;
-      }
-    }
-  }
-  *slot = ctx->op_pos;
-  ctx->op_pos = (ctx->op_pos + 1) % SvrContext::MAX_OPS;
-  return SVR_OK;
-}
-
-// log a fill of the rows [y_first, y_first + n_rows) of a colour target of the context's extent, in a free slot;
-// the caller sets the fields of its kind and submits it (submit_fill)
-int log_fill(SvrContext* ctx, SvrContext::OpKind kind, void* target, int fmt, uint32_t y_first, uint32_t n_rows,
-             SvrContext::LoggedOp** out) {
-  int slot = 0;
-  if (int e = log_slot(ctx, &slot)) return e;
-  ctx->log.emplace_back();
-  SvrContext::LoggedOp& op = ctx->log.back();
-  op.kind = kind;
-  op.slot = slot;
-  op.target = target;
-  op.target_fmt = fmt;
-  op.tw = ctx->W;
-  op.th = ctx->H;
-  op.y_first = y_first;
-  op.n_rows = n_rows;
-  *out = &op;
-  return SVR_OK;
-}
-
-// A clear of whole scissor rows is not run when it is asked for: the pass that follows writes every
-// pixel of those rows anyway (its tile grid covers the scissor), so it takes the clear value for the
-// pixels it does not cover and the separate 8-bytes-per-pixel fill disappears — what a Vulkan renderer
-// gets from loadOp = CLEAR instead of a clear command.  Anything else that touches or exposes the
-// target first (another operation, a read-back, a fence, a change of targets) runs the clear as its
-// own kernel here.  SVR_OPT_TUNING bit 2 turns the deferral off.
-int flush_clear(SvrContext* ctx) {
-  if (!ctx->pending_clear.valid) return SVR_OK;
-  const SvrContext::PendingClear pc = ctx->pending_clear;
-  ctx->pending_clear.valid = false;
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Clear, pc.target, pc.fmt, pc.y0, pc.rows, &op)) return e;
-  op->clear_packed = pc.packed;
-  return submit_fill(ctx, *op);
-}
-
-int finish_pending(SvrContext* ctx) {  // the fence
-  if (int e = flush_clear(ctx)) return e;
-  return retire_ops(ctx, true);
-}
-int poll_pending(SvrContext* ctx) { return (ctx->tuning & TUNE_NO_POLL) ? SVR_OK : retire_ops(ctx, false); }
-
-// the scissor's 32-row tile rows this context renders (svr_set_row_interleave: index % rstride == roff)
-uint32_t owned_tile_rows(const SvrContext* ctx) {
-  const uint32_t all = (ctx->sh + TILE - 1) / TILE;
-  return all > ctx->roff ? (all - ctx->roff + ctx->rstride - 1) / ctx->rstride : 0u;
-}
-
+// ---------------------------------------------------------------- from a drawing call to a pass
 // A multiview pass (include/svr_views.h): its layered targets, and the clear its layers start from
 struct MultiView {
   uint32_t n_views = 0;
@@ -1047,7 +212,7 @@ uint2* id_target(const SvrContext* ctx, const PassRequest& rq) { return (!rq.ids
 // Every parameter of the pass that the request and the context decide, final: the buffers of its set, the log slot and
 // the pyramid are submit_pass's.  A multiview pass has every layer's tile rows, layer-major, and its layers' own clear
 // rides in it like a deferred one.
-int fill_frame_params(SvrContext* ctx, const PassRequest& rq, SvrContext::PassInput input, FrameParams& P) {
+int fill_frame_params(SvrContext* ctx, const PassRequest& rq, PassInput input, FrameParams& P) {
   if (rq.n_tris >= 0x3ffffff0ull) return fail(SVR_ERR_UNSUPPORTED, "more than 2^30 triangles in one pass");
   const MultiView* mv = rq.mv;
   std::memset(&P, 0, sizeof(P));
@@ -1071,7 +236,7 @@ int fill_frame_params(SvrContext* ctx, const PassRequest& rq, SvrContext::PassIn
   P.n_tiles = P.tiles_x * P.tiles_y;
   P.n_tris = (uint32_t)rq.n_tris;
   P.n_chunks = (uint32_t)rq.n_chunks;
-  P.flatten = input != SvrContext::PassInput::Draws ? 1u : 0u;
+  P.flatten = input != PassInput::Draws ? 1u : 0u;
   P.tex = (const TexBinding*)ctx->tex_table.p;
   P.tex_arena = ctx->tex_arena.get();
   P.instrument = ctx->instrument ? 1u : 0u;
@@ -1140,32 +305,19 @@ int upload_flatten_tables(SvrContext* ctx, ClearMode clear) {
 }
 
 // Enqueue the pass rq asks for.  `in` holds its input (in.input and the draws, objects or list version it names).
-int enqueue_pass(SvrContext* ctx, const PassRequest& rq, SvrContext::LoggedOp&& in) {
+int enqueue_pass(SvrContext* ctx, const PassRequest& rq, PassOp&& in) {
   if (int e = poll_pending(ctx)) return e;
   if (in.flattened())  // before fill_frame_params: it can fence, and so flush the deferred clear
     if (int e = upload_flatten_tables(ctx, clear_mode(rq))) return e;
-  FrameParams P;
   const SvrContext::PendingClear asked = ctx->pending_clear;  // folded into P.lazy_clear below: put back if the pass is not enqueued
-  if (int e = fill_frame_params(ctx, rq, in.input, P)) return e;
-  int slot = 0;
-  int e = log_slot(ctx, &slot);
-  if (e == SVR_OK) {
-    ctx->log.push_back(std::move(in));
-    SvrContext::LoggedOp& op = ctx->log.back();
-    op.seq = ctx->next_seq++;
-    if (ctx->next_seq == 0) ctx->next_seq = 1;
-    op.slot = slot;
-    op.timed = ctx->kernel_timing == 1;
-    op.shape.depth_only = rq.depth_only;
-    op.shape.multiview = rq.mv != nullptr;
-    op.shape.depth_load = rq.depth_load;
-    op.P = P;
-    if (ctx->occl_bound && !rq.mv) op.pyr = ctx->pyramids[ctx->occl_bound - 1];  // (multiview passes refuse a bound pyramid)
-    std::memset(&ctx->h_counters[slot], 0, sizeof(Counters));
-    e = submit_pass(ctx, op, !(ctx->tuning & TUNE_NO_PIPELINE));
-    if (e) ctx->log.pop_back();
-  }
-  if (e && P.lazy_clear && !rq.mv) ctx->pending_clear = asked;
+  if (int e = fill_frame_params(ctx, rq, in.input, in.P)) return e;
+  const bool took_clear = in.P.lazy_clear && !rq.mv;
+  in.shape.depth_only = rq.depth_only;
+  in.shape.multiview = rq.mv != nullptr;
+  in.shape.depth_load = rq.depth_load;
+  if (ctx->occl_bound && !rq.mv) in.pyr = ctx->pyramids[ctx->occl_bound - 1];  // (multiview passes refuse a bound pyramid)
+  const int e = log_pass(ctx, std::move(in));
+  if (e && took_clear) ctx->pending_clear = asked;
   return e;
 }
 
@@ -1178,7 +330,7 @@ int run_pass(SvrContext* ctx, PassRequest& rq, std::vector<DrawDesc>& draws) {
     rq.n_tris += d.tri_count;
     rq.n_chunks += chunk_count(d.first_index, d.tri_count);
   }
-  SvrContext::LoggedOp in;
+  PassOp in;
   in.draws.swap(draws);
   return enqueue_pass(ctx, rq, std::move(in));
 }
@@ -1544,11 +696,16 @@ int svr_draw_background(SvrContext* ctx, int effect, const float data[16]) {
   if (int e = use_device(ctx)) return e;
   if (int e = poll_pending(ctx)) return e;
   if (int e = flush_clear(ctx)) return e;
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Background, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
-  op->bg_effect = effect;
-  std::memcpy(op->bg_data, data, sizeof(op->bg_data));
-  return submit_fill(ctx, *op);
+  BackgroundOp op;
+  op.target = ctx->color;
+  op.fmt = ctx->fmt;
+  op.w = ctx->W;
+  op.h = ctx->H;
+  op.y_first = ctx->sy;
+  op.n_rows = ctx->sh;
+  op.effect = effect;
+  std::memcpy(op.data, data, sizeof(op.data));
+  return log_op(ctx, std::move(op));
 }
 
 static int blit_checks(SvrContext* ctx, const void* dst, uint32_t dw, uint32_t dh, int fmt, const char* who) {
@@ -1565,20 +722,25 @@ int svr_copy_to_swapchain(SvrContext* ctx, void* dst_dev, uint32_t dw, uint32_t 
   if (int e = flush_clear(ctx)) return e;
   // identity extent: the rows of the scissor (a rank of the multi-GPU path presents its band); scaled: everything
   const bool identity = dw == ctx->W && dh == ctx->H;
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Blit, ctx->color, ctx->fmt, identity ? ctx->sy : 0u, identity ? ctx->sh : dh, &op)) return e;
-  op->blit_dst = dst_dev;
-  op->blit_w = dw;
-  op->blit_h = dh;
-  op->blit_fmt = fmt;
-  op->blit_row_end = op->y_first + op->n_rows;
+  BlitOp op;
+  op.src = ctx->color;
+  op.src_fmt = ctx->fmt;
+  op.src_w = ctx->W;
+  op.src_h = ctx->H;
+  op.dst = dst_dev;
+  op.dst_w = dw;
+  op.dst_h = dh;
+  op.dst_fmt = fmt;
+  op.y_first = identity ? ctx->sy : 0u;
+  op.n_rows = identity ? ctx->sh : dh;
+  op.row_end = op.y_first + op.n_rows;
   if (identity && ctx->rstride > 1u) {  // a rank of the interleaved form presents its own tile rows, in place
-    op->blit_rstride = ctx->rstride;
-    op->blit_roff = ctx->roff;
-    op->n_rows = owned_tile_rows(ctx) * TILE;
+    op.rstride = ctx->rstride;
+    op.roff = ctx->roff;
+    op.n_rows = owned_tile_rows(ctx) * TILE;
   }
-  op->blit_status = ctx->present_status;
-  return submit_fill(ctx, *op);
+  op.status = ctx->present_status;
+  return log_op(ctx, std::move(op));
 }
 
 int svr_read_swapchain(SvrContext* ctx, uint32_t dw, uint32_t dh, int fmt, void* dst_host, size_t bytes) {
@@ -1743,8 +905,8 @@ static int draw_geometry(SvrContext* ctx, PassRequest rq, const SvrRenderObject*
   const size_t n_objects = n_opaque + n_transparent;
   const bool fits = n_objects <= FLATTEN_MAX_OBJECTS && ctx->meshes.size() < (1u << 20) && ctx->materials.size() < (1u << 20);
   if (fits && n_objects > 0 && (ctx->device_flatten == 1 || (ctx->device_flatten == 0 && n_objects >= 2048))) {
-    SvrContext::LoggedOp in;
-    in.input = SvrContext::PassInput::Objects;
+    PassOp in;
+    in.input = PassInput::Objects;
     in.objects.reserve(n_objects);
     in.objects.insert(in.objects.end(), opaque, opaque + n_opaque);
     in.objects.insert(in.objects.end(), transparent, transparent + n_transparent);
@@ -2240,7 +1402,7 @@ struct ListViews {
 // validity — looked at again if a mesh was destroyed since — and the device.  Then the pass over the list's current
 // version: `in` names it as the List input, unless the pass draws no object, and rq gets the bounds of one view (a
 // depth-only pass: of the opaque objects alone, the only ones its flatten walks).
-static int list_pass(SvrContext* ctx, SvrDrawList list, PassRequest& rq, ListViews* views, SvrContext::LoggedOp& in) {
+static int list_pass(SvrContext* ctx, SvrDrawList list, PassRequest& rq, ListViews* views, PassOp& in) {
   const std::string fn(rq.who);
   DrawListRes* L = get_list(ctx, list);
   if (!L) return fail(SVR_ERR_BAD_HANDLE, fn + ": bad list handle");
@@ -2253,7 +1415,7 @@ static int list_pass(SvrContext* ctx, SvrDrawList list, PassRequest& rq, ListVie
   const ListVersion& v = *L->cur;
   const uint32_t n_transparent = rq.depth_only ? 0u : v.n_transparent;
   if (v.n_opaque + (size_t)n_transparent > 0) {
-    in.input = SvrContext::PassInput::List;
+    in.input = PassInput::List;
     in.list = L->cur;
     in.n_opaque_obj = v.n_opaque;
     in.n_transparent_obj = n_transparent;
@@ -2271,7 +1433,7 @@ static int draw_list(SvrContext* ctx, SvrDrawList list, PassRequest rq, SvrStats
   if (!ctx || !rq.scene) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(rq.who) + ": null argument");
   if (int e = take_depth_load_op(ctx, rq, false)) return e;
   auto t0 = std::chrono::steady_clock::now();
-  SvrContext::LoggedOp in;  // no objects: svr_draw_geometry's host path, a pass of no draws
+  PassOp in;  // no objects: svr_draw_geometry's host path, a pass of no draws
   if (int e = list_pass(ctx, list, rq, nullptr, in)) return e;
   if (owns_nothing(ctx, out_stats, rq)) return SVR_OK;
   if (int e = upload_tex_table(ctx, nullptr)) return e;
@@ -2290,11 +1452,11 @@ static int draw_list_views(SvrContext* ctx, SvrDrawList list, PassRequest rq, co
   if (int e = take_depth_load_op(ctx, rq, true)) return e;
   auto t0 = std::chrono::steady_clock::now();
   ListViews views{va, MultiView{}, nullptr};
-  SvrContext::LoggedOp in;
+  PassOp in;
   if (int e = list_pass(ctx, list, rq, &views, in)) return e;
   const DrawListRes* L = views.list;
   if (int e = upload_tex_table(ctx, nullptr)) return e;
-  if (in.input == SvrContext::PassInput::List && (size_t)in.n_opaque_obj + in.n_transparent_obj <= LIST_FUSED_MAX && ctx->device_flatten != 2) {
+  if (in.input == PassInput::List && (size_t)in.n_opaque_obj + in.n_transparent_obj <= LIST_FUSED_MAX && ctx->device_flatten != 2) {
     // the device copy in draw order, culled and turned into records view by view by one workgroup (list_views_kernel)
     in.viewprojs.resize((size_t)va.n_views * 16);
     for (uint32_t k = 0; k < va.n_views; k++) std::memcpy(&in.viewprojs[(size_t)k * 16], va.scenes[k].viewproj, 64);
@@ -2329,102 +1491,6 @@ int svr_draw_depth_views(SvrContext* ctx, uint32_t n_views, const SvrSceneData* 
 int svr_draw_list_depth_views(SvrContext* ctx, SvrDrawList list, uint32_t n_views, const SvrSceneData* scenes,
                               const SvrViewTargets* targets, SvrStats* out_stats) {
   return draw_list_views(ctx, list, geometry_request("svr_draw_list_depth_views", nullptr, true), {n_views, scenes, targets}, out_stats);
-}
-
-// ---------------------------------------------------------------- occlusion culling (include/svr_occlusion.h)
-static std::shared_ptr<PyramidMem> get_pyramid(SvrContext* ctx, SvrDepthPyramid h) {
-  if (h == 0 || h > ctx->pyramids.size()) return nullptr;
-  return ctx->pyramids[h - 1];
-}
-
-int svr_create_depth_pyramid(SvrContext* ctx, SvrDepthPyramid* out) {
-  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_create_depth_pyramid: null argument");
-  if (int e = use_device(ctx)) return e;
-  auto m = std::make_shared<PyramidMem>();
-  m->levels = pyramid_levels(ctx->W, ctx->H);
-  m->words = pyramid_offsets(ctx->W, ctx->H, m->off);
-  DEV_ALLOC(m->p, m->words * sizeof(uint32_t));
-  HIPCHK_AS(make_event(m->ev_built, hipEventDisableTiming), "hipEventCreateWithFlags(&m->ev_built, hipEventDisableTiming)");
-  // all texels 0.0 until the first build: a pass culls nothing against it
-  HIPCHK(hipMemsetAsync(m->p.get(), 0, m->words * sizeof(uint32_t), ctx->stream));
-  HIPCHK(hipEventRecord(m->ev_built.get(), ctx->stream));
-  ctx->pyramids.push_back(m);
-  *out = (SvrDepthPyramid)ctx->pyramids.size();
-  return SVR_OK;
-}
-
-int svr_destroy_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr) {
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_destroy_depth_pyramid: null context");
-  if (!get_pyramid(ctx, pyr)) return fail(SVR_ERR_BAD_HANDLE, "svr_destroy_depth_pyramid: bad pyramid handle");
-  if (int e = use_device(ctx)) return e;
-  ctx->pyramids[pyr - 1].reset();  // the memory goes with the last logged operation that holds it
-  if (ctx->occl_bound == pyr) ctx->occl_bound = 0;
-  return SVR_OK;
-}
-
-int svr_build_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr, const float* depth_dev) {
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_build_depth_pyramid: null context");
-  std::shared_ptr<PyramidMem> m = get_pyramid(ctx, pyr);
-  if (!m) return fail(SVR_ERR_BAD_HANDLE, "svr_build_depth_pyramid: bad pyramid handle");
-  const float* src = depth_dev ? depth_dev : ctx->depth;
-  if (!src) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_build_depth_pyramid: no depth target");
-  if (int e = use_device(ctx)) return e;
-  if (int e = poll_pending(ctx)) return e;
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Pyramid, nullptr, 0, 0, ctx->H, &op)) return e;
-  op->pyr = m;
-  op->pyr_src = src;
-  return submit_fill(ctx, *op);
-}
-
-int svr_set_occlusion_pyramid(SvrContext* ctx, SvrDepthPyramid pyr) {
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_set_occlusion_pyramid: null context");
-  if (pyr != 0 && !get_pyramid(ctx, pyr)) return fail(SVR_ERR_BAD_HANDLE, "svr_set_occlusion_pyramid: bad pyramid handle");
-  ctx->occl_bound = pyr;
-  return SVR_OK;
-}
-
-int svr_read_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr, uint32_t level, void* dst, size_t bytes, uint32_t* n_levels) {
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: null context");
-  std::shared_ptr<PyramidMem> m = get_pyramid(ctx, pyr);
-  if (!m) return fail(SVR_ERR_BAD_HANDLE, "svr_read_depth_pyramid: bad pyramid handle");
-  if (n_levels) *n_levels = m->levels;
-  if (level < 1 || level > m->levels)
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: level out of range (1.." + std::to_string(m->levels) + ")");
-  const size_t need = (size_t)(((ctx->W - 1u) >> level) + 1u) * (((ctx->H - 1u) >> level) + 1u) * sizeof(uint32_t);
-  if (!dst || bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: destination too small");
-  if (int e = svr_sync(ctx)) return e;
-  HIPCHK(hipMemcpy(dst, m->p.get() + m->off[level], need, hipMemcpyDeviceToHost));
-  return SVR_OK;
-}
-
-int svr_get_occlusion_stats(SvrContext* ctx, SvrOcclusionStats* out) {
-  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_occlusion_stats: null argument");
-  if (int e = svr_sync(ctx)) return e;
-  *out = ctx->occl_stats;
-  return SVR_OK;
-}
-
-int svr_debug_read_occlusion(SvrContext* ctx, uint32_t* bits, size_t capacity, uint32_t* n_chunks) {
-  if (!ctx || !n_chunks) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: null argument");
-  if (int e = svr_sync(ctx)) return e;
-  const FrameParams& P = ctx->last;
-  if (!P.draws) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: no pass yet");
-  uint32_t nc = P.n_chunks;
-  if (P.flatten) {  // the device knows the count
-    Counters c;
-    HIPCHK(hipMemcpy(&c, P.counters, sizeof(Counters), hipMemcpyDeviceToHost));
-    nc = c.flat_chunks;
-  }
-  *n_chunks = nc;
-  if (!bits) return SVR_OK;
-  if (capacity < ((size_t)nc + 31u) / 32u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: bit buffer too small");
-  std::vector<uint8_t> flags(nc, 0);
-  if (P.occl_flags && nc) HIPCHK(hipMemcpy(flags.data(), P.occl_flags, nc, hipMemcpyDeviceToHost));
-  std::memset(bits, 0, ((size_t)nc + 31u) / 32u * sizeof(uint32_t));
-  for (uint32_t i = 0; i < nc; i++)
-    if (flags[i]) bits[i / 32u] |= 1u << (i % 32u);
-  return SVR_OK;
 }
 
 // ---------------------------------------------------------------- the ID target (include/svr_ids.h)
@@ -2562,288 +1628,6 @@ int svr_read_attribute(SvrContext* ctx, int attr, void* dst_host, size_t bytes) 
   if (bytes != attr_bytes(ctx, i)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_attribute: the size is not the plane's");
   if (int e = svr_sync(ctx)) return e;
   HIPCHK(hipMemcpy(dst_host, ctx->attr[i], bytes, hipMemcpyDeviceToHost));
-  return SVR_OK;
-}
-
-// ---------------------------------------------------------------- the deferred lighting pass (include/svr_lighting.h)
-int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
-  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: null argument");
-  if (pass->n_lights > SVR_MAX_LIGHTS) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: more than SVR_MAX_LIGHTS lights");
-  if (pass->n_lights && !pass->lights) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: null light array");
-  for (uint32_t i = 0; i < pass->n_lights; i++)
-    if (!(std::isfinite(pass->lights[i].radius) && pass->lights[i].radius > 0.0f))
-      return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: light " + std::to_string(i) + ": the radius must be finite and greater than 0");
-  if (pass->shadow_depth && (pass->shadow_width == 0 || pass->shadow_height == 0 || pass->shadow_width > (1u << 24) || pass->shadow_height > (1u << 24)))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: the shadow map's extent must be 1 .. 2^24 each way");
-  if (!ctx->attr[2] || !ctx->attr[3])
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: needs the SVR_ATTR_NORMAL and SVR_ATTR_ALBEDO planes (svr_enable_attributes / svr_bind_attribute_target)");
-  const float* ao = nullptr;  // include/svr_ambient.h: the ambient target current at this call
-  if (ctx->light_ao) {
-    ao = ctx->ambient_bound ? ctx->ambient_bound : ctx->d_ambient_own.get();
-    if (!ao) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: svr_set_light_ambient_occlusion is on and there is no ambient target (svr_ambient_pass / svr_bind_ambient_target)");
-  }
-  if (int e = use_device(ctx)) return e;
-  if (int e = poll_pending(ctx)) return e;
-  if (!ctx->d_lights) DEV_ALLOC(ctx->d_lights, SVR_MAX_LIGHTS * sizeof(SvrPointLight));
-  if (!ctx->d_light_tiles) DEV_ALLOC(ctx->d_light_tiles, (size_t)((ctx->W + TILE - 1) / TILE) * ((ctx->H + TILE - 1) / TILE) * sizeof(uint32_t));
-  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Light, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
-  op->lights.assign(pass->lights, pass->lights + pass->n_lights);
-  op->light_tiles_y = owned_tile_rows(ctx);
-  LightLaunch& L = op->light;
-  L.color = ctx->color;
-  L.depth = ctx->depth;
-  L.normal = (const float4*)ctx->attr[2];
-  L.albedo = (const float4*)ctx->attr[3];
-  L.W = ctx->W;
-  L.H = ctx->H;
-  L.sx = ctx->sx;
-  L.sy = ctx->sy;
-  L.sw = ctx->sw;
-  L.sh = ctx->sh;
-  L.tiles_x = (ctx->sw + TILE - 1) / TILE;
-  L.rstride = ctx->rstride;
-  L.roff = ctx->roff;
-  L.two_over_w = 2.0f / (float)ctx->W;
-  L.two_over_h = 2.0f / (float)ctx->H;
-  std::memcpy(L.inv_viewproj, pass->inv_viewproj, sizeof(L.inv_viewproj));
-  std::memcpy(L.ambient_color, pass->ambient_color, sizeof(L.ambient_color));
-  std::memcpy(L.sunlight_direction, pass->sunlight_direction, sizeof(L.sunlight_direction));
-  std::memcpy(L.sunlight_color, pass->sunlight_color, sizeof(L.sunlight_color));
-  L.lights = ctx->d_lights.get();
-  L.n_lights = pass->n_lights;
-  L.shadow_depth = pass->shadow_depth;
-  if (pass->shadow_depth) {
-    L.shadow_w = pass->shadow_width;
-    L.shadow_h = pass->shadow_height;
-    L.shadow_half_w = (float)pass->shadow_width * 0.5f;
-    L.shadow_half_h = (float)pass->shadow_height * 0.5f;
-    std::memcpy(L.shadow_viewproj, pass->shadow_viewproj, sizeof(L.shadow_viewproj));
-    L.shadow_bias = pass->shadow_bias;
-  }
-  L.tile_counts = ctx->d_light_tiles.get();
-  L.poison = ctx->d_poison.get();
-  L.ao = ao;
-  ctx->light_tiles_n = L.tiles_x * op->light_tiles_y;
-  return submit_fill(ctx, *op);
-}
-
-int svr_debug_read_light_tiles(SvrContext* ctx, uint32_t* counts, size_t capacity, uint32_t* n_tiles) {
-  if (!ctx || !n_tiles) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: null argument");
-  if (int e = svr_sync(ctx)) return e;
-  *n_tiles = ctx->light_tiles_n;
-  if (!counts) return SVR_OK;
-  if (!ctx->d_light_tiles) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: no lighting pass yet");
-  if (capacity < ctx->light_tiles_n) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: buffer too small");
-  if (ctx->light_tiles_n) HIPCHK(hipMemcpy(counts, ctx->d_light_tiles.get(), (size_t)ctx->light_tiles_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return SVR_OK;
-}
-
-// ---------------------------------------------------------------- the HDR post pass (include/svr_post.h)
-int svr_post_pass(SvrContext* ctx, const SvrPostPass* pass) {
-  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: null argument");
-  if (!(std::isfinite(pass->exposure) && pass->exposure > 0.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the exposure must be finite and greater than 0");
-  if (!(std::isfinite(pass->bloom_threshold) && pass->bloom_threshold >= 0.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the bloom threshold must be finite and at least 0");
-  if (!(std::isfinite(pass->bloom_intensity) && pass->bloom_intensity >= 0.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the bloom intensity must be finite and at least 0");
-  if (pass->bloom_levels > SVR_POST_MAX_LEVELS) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: more than SVR_POST_MAX_LEVELS bloom levels");
-  if (pass->tonemap > SVR_TONEMAP_ACES) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: unknown tone-mapping operator");
-  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_post_pass: the colour target must be RGBA16F (an RGBA8 target holds no HDR values)");
-  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_post_pass: not under svr_set_row_interleave with a stride above 1");
-  if (int e = use_device(ctx)) return e;
-  if (int e = poll_pending(ctx)) return e;
-  uint32_t off[SVR_POST_MAX_LEVELS], lw[SVR_POST_MAX_LEVELS], lh[SVR_POST_MAX_LEVELS];
-  // (the extents grow with the image's, so the levels of any scissor fit in those of the whole target)
-  if (!ctx->d_post_levels) DEV_ALLOC(ctx->d_post_levels, post_level_layout(ctx->W, ctx->H, SVR_POST_MAX_LEVELS, off, lw, lh) * sizeof(uint2));
-  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Post, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
-  PostLaunch& P = op->post;
-  P.color = (uint2*)ctx->color;
-  P.W = ctx->W;
-  P.sx = ctx->sx;
-  P.sy = ctx->sy;
-  P.sw = ctx->sw;
-  P.sh = ctx->sh;
-  P.levels = ctx->d_post_levels.get();
-  P.n_levels = pass->bloom_levels;
-  post_level_layout(ctx->sw, ctx->sh, pass->bloom_levels, P.off, P.lw, P.lh);
-  P.exposure = pass->exposure;
-  P.threshold = pass->bloom_threshold;
-  P.intensity = pass->bloom_intensity;
-  P.tonemap = pass->tonemap;
-  P.poison = ctx->d_poison.get();
-  return submit_fill(ctx, *op);
-}
-
-// ---------------------------------------------------------------- temporal antialiasing (include/svr_temporal.h)
-static bool temporal_history_usable(const SvrContext* ctx) {
-  return ctx->temporal_has && ctx->temporal_scissor[0] == ctx->sx && ctx->temporal_scissor[1] == ctx->sy &&
-         ctx->temporal_scissor[2] == ctx->sw && ctx->temporal_scissor[3] == ctx->sh;
-}
-
-int svr_temporal_resolve(SvrContext* ctx, const SvrTemporalPass* pass) {
-  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: null argument");
-  if (!(std::isfinite(pass->blend) && pass->blend > 0.0f && pass->blend <= 1.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: the blend must be finite, greater than 0 and at most 1");
-  if (pass->flags & ~(uint32_t)(SVR_TEMPORAL_RESET | SVR_TEMPORAL_NO_CLAMP)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: unknown flag bits");
-  for (int i = 0; i < 16; i++)
-    if (!std::isfinite(pass->reproject[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: reproject[" + std::to_string(i) + "] is not finite");
-  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: the colour target must be RGBA16F");
-  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: not under svr_set_row_interleave with a stride above 1");
-  if (int e = use_device(ctx)) return e;
-  if (int e = poll_pending(ctx)) return e;
-  const size_t hist_bytes = (size_t)ctx->W * ctx->H * sizeof(uint2);
-  for (int i = 0; i < 2; i++)
-    if (!ctx->d_temporal[i]) {  // zeroed once: the read-back hook shows the whole extent, the kernels read the scissor only
-      DEV_ALLOC(ctx->d_temporal[i], hist_bytes);
-      HIPCHK(hipMemsetAsync(ctx->d_temporal[i].get(), 0, hist_bytes, ctx->stream));
-    }
-  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Temporal, ctx->color, ctx->fmt, ctx->sy, ctx->sh, &op)) return e;
-  TemporalLaunch& T = op->temporal;
-  T.color = (uint2*)ctx->color;
-  T.depth = ctx->depth;
-  T.W = ctx->W;
-  T.H = ctx->H;
-  T.sx = ctx->sx;
-  T.sy = ctx->sy;
-  T.sw = ctx->sw;
-  T.sh = ctx->sh;
-  // the roles and the validity are decided here, in call order, and travel with the operation: a replay finds them as they were
-  T.hist_in = ctx->d_temporal[ctx->temporal_read].get();
-  T.hist_out = ctx->d_temporal[ctx->temporal_read ^ 1].get();
-  T.history_valid = temporal_history_usable(ctx) && !(pass->flags & SVR_TEMPORAL_RESET) ? 1u : 0u;
-  T.clamp = (pass->flags & SVR_TEMPORAL_NO_CLAMP) ? 0u : 1u;
-  std::memcpy(T.reproject, pass->reproject, sizeof(T.reproject));
-  T.blend = pass->blend;
-  T.two_over_w = 2.0f / (float)ctx->W;
-  T.two_over_h = 2.0f / (float)ctx->H;
-  T.half_w = (float)ctx->W * 0.5f;
-  T.half_h = (float)ctx->H * 0.5f;
-  T.poison = ctx->d_poison.get();
-  ctx->temporal_read ^= 1;
-  ctx->temporal_has = true;
-  ctx->temporal_scissor[0] = ctx->sx;
-  ctx->temporal_scissor[1] = ctx->sy;
-  ctx->temporal_scissor[2] = ctx->sw;
-  ctx->temporal_scissor[3] = ctx->sh;
-  return submit_fill(ctx, *op);
-}
-
-int svr_debug_read_temporal_history(SvrContext* ctx, void* dst, size_t bytes, uint32_t* valid) {
-  if (!ctx || !valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_temporal_history: null argument");
-  const size_t need = (size_t)ctx->W * ctx->H * sizeof(uint2);
-  if (dst && bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_temporal_history: buffer too small");
-  if (int e = svr_sync(ctx)) return e;
-  *valid = temporal_history_usable(ctx) ? 1u : 0u;
-  if (!dst) return SVR_OK;
-  if (ctx->d_temporal[ctx->temporal_read])
-    HIPCHK(hipMemcpy(dst, ctx->d_temporal[ctx->temporal_read].get(), need, hipMemcpyDeviceToHost));
-  else
-    std::memset(dst, 0, need);
-  return SVR_OK;
-}
-
-// ---------------------------------------------------------------- ambient occlusion (include/svr_ambient.h)
-static float* ambient_target(const SvrContext* ctx) { return ctx->ambient_bound ? ctx->ambient_bound : ctx->d_ambient_own.get(); }
-
-int svr_ambient_pass(SvrContext* ctx, const SvrAmbientPass* pass) {
-  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: null argument");
-  if (!(std::isfinite(pass->radius) && pass->radius > 0.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the radius must be finite and greater than 0");
-  if (!(std::isfinite(pass->pixels_per_unit) && pass->pixels_per_unit > 0.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: pixels_per_unit must be finite and greater than 0");
-  if (!(std::isfinite(pass->bias) && pass->bias >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the bias must be finite and at least 0");
-  if (!(std::isfinite(pass->intensity) && pass->intensity >= 0.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the intensity must be finite and at least 0");
-  if (!(std::isfinite(pass->sharpness) && pass->sharpness >= 0.0f && pass->sharpness < 1.0f))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the sharpness must be finite, at least 0 and less than 1");
-  if (pass->flags & ~(uint32_t)SVR_AMBIENT_NO_BLUR) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: unknown flag bits");
-  for (int i = 0; i < 16; i++)
-    if (!std::isfinite(pass->inv_viewproj[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: inv_viewproj[" + std::to_string(i) + "] is not finite");
-  if (!ctx->attr[2]) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: needs the SVR_ATTR_NORMAL plane (svr_enable_attributes / svr_bind_attribute_target)");
-  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_ambient_pass: not under svr_set_row_interleave with a stride above 1");
-  if (int e = use_device(ctx)) return e;
-  if (int e = poll_pending(ctx)) return e;
-  const size_t n = (size_t)ctx->W * ctx->H;
-  // zeroed once: the read-backs show the whole extent, the kernels touch the scissor only
-  if (!ctx->d_ambient_raw) {
-    DEV_ALLOC(ctx->d_ambient_raw, n * sizeof(float2));
-    HIPCHK(hipMemsetAsync(ctx->d_ambient_raw.get(), 0, n * sizeof(float2), ctx->stream));
-  }
-  if (!ctx->ambient_bound && !ctx->d_ambient_own) {
-    DEV_ALLOC(ctx->d_ambient_own, n * sizeof(float));
-    HIPCHK(hipMemsetAsync(ctx->d_ambient_own.get(), 0, n * sizeof(float), ctx->stream));
-  }
-  // (no flush_clear: the pass neither reads nor writes colour)
-  SvrContext::LoggedOp* op = nullptr;
-  if (int e = log_fill(ctx, SvrContext::OpKind::Ambient, nullptr, 0, ctx->sy, ctx->sh, &op)) return e;
-  AmbientLaunch& T = op->ambient;
-  T.depth = ctx->depth;
-  T.normal = (const float4*)ctx->attr[2];
-  T.raw = ctx->d_ambient_raw.get();
-  T.out = ambient_target(ctx);
-  T.W = ctx->W;
-  T.H = ctx->H;
-  T.sx = ctx->sx;
-  T.sy = ctx->sy;
-  T.sw = ctx->sw;
-  T.sh = ctx->sh;
-  std::memcpy(T.inv_viewproj, pass->inv_viewproj, sizeof(T.inv_viewproj));
-  T.two_over_w = 2.0f / (float)ctx->W;
-  T.two_over_h = 2.0f / (float)ctx->H;
-  T.radius_px = pass->radius * pass->pixels_per_unit;
-  T.radius2 = pass->radius * pass->radius;
-  T.bias = pass->bias;
-  T.coef = (pass->intensity * pass->radius) * 0.125f;
-  T.sharpness = pass->sharpness;
-  T.blur = (pass->flags & SVR_AMBIENT_NO_BLUR) ? 0u : 1u;
-  T.poison = ctx->d_poison.get();
-  return submit_fill(ctx, *op);
-}
-
-int svr_bind_ambient_target(SvrContext* ctx, float* dev) {
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
-  if (((uintptr_t)dev & 15u) != 0u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_bind_ambient_target: the target must be 16-byte aligned");
-  if (int e = use_device(ctx)) return e;
-  // no fence: passes already enqueued carry their own planes (also for a replay), as with svr_bind_attribute_target
-  if (int e = poll_pending(ctx)) return e;
-  ctx->ambient_bound = dev;
-  return SVR_OK;
-}
-
-int svr_get_ambient_target(SvrContext* ctx, float** dev) {
-  if (!ctx || !dev) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_ambient_target: null argument");
-  *dev = ambient_target(ctx);
-  return SVR_OK;
-}
-
-int svr_read_ambient(SvrContext* ctx, void* dst_host, size_t bytes) {
-  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: null argument");
-  if (!ambient_target(ctx)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: no ambient target (svr_ambient_pass / svr_bind_ambient_target)");
-  if (bytes != (size_t)ctx->W * ctx->H * sizeof(float)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: the size is not the plane's");
-  if (int e = svr_sync(ctx)) return e;
-  HIPCHK(hipMemcpy(dst_host, ambient_target(ctx), bytes, hipMemcpyDeviceToHost));
-  return SVR_OK;
-}
-
-int svr_set_light_ambient_occlusion(SvrContext* ctx, int on) {
-  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
-  ctx->light_ao = on != 0;
-  return SVR_OK;
-}
-
-int svr_debug_read_ambient_raw(SvrContext* ctx, void* dst_host, size_t bytes) {
-  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: null argument");
-  if (!ctx->d_ambient_raw) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: no ambient pass yet");
-  if (bytes != (size_t)ctx->W * ctx->H * sizeof(float2)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: the size is not the plane's");
-  if (int e = svr_sync(ctx)) return e;
-  HIPCHK(hipMemcpy(dst_host, ctx->d_ambient_raw.get(), bytes, hipMemcpyDeviceToHost));
   return SVR_OK;
 }
 

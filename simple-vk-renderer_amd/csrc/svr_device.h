@@ -292,7 +292,7 @@ struct FrameParams {
   // SVR_OPT_KERNEL_TIMING level 1 (pinned host memory; NULL = off): the tile kernel stamps the 100 MHz wall clock itself.
   // Word 0: the start of the workgroup with launch index 0; word (1 + ((blockIdx.x >> 3) & 63)) * CLOCK_STRIDE: the end of the
   // workgroup that stored there last — every workgroup of a pass of up to SPLIT_TILES_MAX tiles, every eighth of a larger
-  // one.  The host takes the largest of the 64 at retirement (svr_api.hip retire_ops).
+  // one.  The host takes the largest of the 64 at retirement (svr_log.hip retire_ops).
   unsigned long long* host_clock;
 };
 constexpr uint32_t CLOCK_STRIDE = 16;                 // one 128-byte line per word: stores to one line of host memory go one at a time

@@ -1,0 +1,383 @@
+// svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
+// culling's calls, the deferred lighting pass, the HDR post pass, temporal antialiasing and ambient occlusion, with
+// their targets and read-backs.  Each validates its arguments, allocates what its first call needs, records its
+// kernels' parameters in a payload of its kind and logs it (svr_context.h, svr_log.hip).
+#include <cmath>
+
+#include "svr_context.h"
+
+using namespace svr;
+
+extern "C" {
+
+// ---------------------------------------------------------------- occlusion culling (include/svr_occlusion.h)
+static std::shared_ptr<PyramidMem> get_pyramid(SvrContext* ctx, SvrDepthPyramid h) {
+  if (h == 0 || h > ctx->pyramids.size()) return nullptr;
+  return ctx->pyramids[h - 1];
+}
+
+int svr_create_depth_pyramid(SvrContext* ctx, SvrDepthPyramid* out) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_create_depth_pyramid: null argument");
+  if (int e = use_device(ctx)) return e;
+  auto m = std::make_shared<PyramidMem>();
+  m->levels = pyramid_levels(ctx->W, ctx->H);
+  m->words = pyramid_offsets(ctx->W, ctx->H, m->off);
+  DEV_ALLOC(m->p, m->words * sizeof(uint32_t));
+  HIPCHK_AS(make_event(m->ev_built, hipEventDisableTiming), "hipEventCreateWithFlags(&m->ev_built, hipEventDisableTiming)");
+  // all texels 0.0 until the first build: a pass culls nothing against it
+  HIPCHK(hipMemsetAsync(m->p.get(), 0, m->words * sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipEventRecord(m->ev_built.get(), ctx->stream));
+  ctx->pyramids.push_back(m);
+  *out = (SvrDepthPyramid)ctx->pyramids.size();
+  return SVR_OK;
+}
+
+int svr_destroy_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_destroy_depth_pyramid: null context");
+  if (!get_pyramid(ctx, pyr)) return fail(SVR_ERR_BAD_HANDLE, "svr_destroy_depth_pyramid: bad pyramid handle");
+  if (int e = use_device(ctx)) return e;
+  ctx->pyramids[pyr - 1].reset();  // the memory goes with the last logged operation that holds it
+  if (ctx->occl_bound == pyr) ctx->occl_bound = 0;
+  return SVR_OK;
+}
+
+int svr_build_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr, const float* depth_dev) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_build_depth_pyramid: null context");
+  std::shared_ptr<PyramidMem> m = get_pyramid(ctx, pyr);
+  if (!m) return fail(SVR_ERR_BAD_HANDLE, "svr_build_depth_pyramid: bad pyramid handle");
+  const float* src = depth_dev ? depth_dev : ctx->depth;
+  if (!src) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_build_depth_pyramid: no depth target");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  return log_op(ctx, PyramidOp{std::move(m), src, ctx->W, ctx->H});
+}
+
+int svr_set_occlusion_pyramid(SvrContext* ctx, SvrDepthPyramid pyr) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_set_occlusion_pyramid: null context");
+  if (pyr != 0 && !get_pyramid(ctx, pyr)) return fail(SVR_ERR_BAD_HANDLE, "svr_set_occlusion_pyramid: bad pyramid handle");
+  ctx->occl_bound = pyr;
+  return SVR_OK;
+}
+
+int svr_read_depth_pyramid(SvrContext* ctx, SvrDepthPyramid pyr, uint32_t level, void* dst, size_t bytes, uint32_t* n_levels) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: null context");
+  std::shared_ptr<PyramidMem> m = get_pyramid(ctx, pyr);
+  if (!m) return fail(SVR_ERR_BAD_HANDLE, "svr_read_depth_pyramid: bad pyramid handle");
+  if (n_levels) *n_levels = m->levels;
+  if (level < 1 || level > m->levels)
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: level out of range (1.." + std::to_string(m->levels) + ")");
+  const size_t need = (size_t)(((ctx->W - 1u) >> level) + 1u) * (((ctx->H - 1u) >> level) + 1u) * sizeof(uint32_t);
+  if (!dst || bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_depth_pyramid: destination too small");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst, m->p.get() + m->off[level], need, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+int svr_get_occlusion_stats(SvrContext* ctx, SvrOcclusionStats* out) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_occlusion_stats: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  *out = ctx->occl_stats;
+  return SVR_OK;
+}
+
+int svr_debug_read_occlusion(SvrContext* ctx, uint32_t* bits, size_t capacity, uint32_t* n_chunks) {
+  if (!ctx || !n_chunks) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  const FrameParams& P = ctx->last;
+  if (!P.draws) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: no pass yet");
+  uint32_t nc = P.n_chunks;
+  if (P.flatten) {  // the device knows the count
+    Counters c;
+    HIPCHK(hipMemcpy(&c, P.counters, sizeof(Counters), hipMemcpyDeviceToHost));
+    nc = c.flat_chunks;
+  }
+  *n_chunks = nc;
+  if (!bits) return SVR_OK;
+  if (capacity < ((size_t)nc + 31u) / 32u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_occlusion: bit buffer too small");
+  std::vector<uint8_t> flags(nc, 0);
+  if (P.occl_flags && nc) HIPCHK(hipMemcpy(flags.data(), P.occl_flags, nc, hipMemcpyDeviceToHost));
+  std::memset(bits, 0, ((size_t)nc + 31u) / 32u * sizeof(uint32_t));
+  for (uint32_t i = 0; i < nc; i++)
+    if (flags[i]) bits[i / 32u] |= 1u << (i % 32u);
+  return SVR_OK;
+}
+// ---------------------------------------------------------------- the deferred lighting pass (include/svr_lighting.h)
+int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: null argument");
+  if (pass->n_lights > SVR_MAX_LIGHTS) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: more than SVR_MAX_LIGHTS lights");
+  if (pass->n_lights && !pass->lights) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: null light array");
+  for (uint32_t i = 0; i < pass->n_lights; i++)
+    if (!(std::isfinite(pass->lights[i].radius) && pass->lights[i].radius > 0.0f))
+      return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: light " + std::to_string(i) + ": the radius must be finite and greater than 0");
+  if (pass->shadow_depth && (pass->shadow_width == 0 || pass->shadow_height == 0 || pass->shadow_width > (1u << 24) || pass->shadow_height > (1u << 24)))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: the shadow map's extent must be 1 .. 2^24 each way");
+  if (!ctx->attr[2] || !ctx->attr[3])
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: needs the SVR_ATTR_NORMAL and SVR_ATTR_ALBEDO planes (svr_enable_attributes / svr_bind_attribute_target)");
+  const float* ao = nullptr;  // include/svr_ambient.h: the ambient target current at this call
+  if (ctx->light_ao) {
+    ao = ctx->ambient_bound ? ctx->ambient_bound : ctx->d_ambient_own.get();
+    if (!ao) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: svr_set_light_ambient_occlusion is on and there is no ambient target (svr_ambient_pass / svr_bind_ambient_target)");
+  }
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  if (!ctx->d_lights) DEV_ALLOC(ctx->d_lights, SVR_MAX_LIGHTS * sizeof(SvrPointLight));
+  if (!ctx->d_light_tiles) DEV_ALLOC(ctx->d_light_tiles, (size_t)((ctx->W + TILE - 1) / TILE) * ((ctx->H + TILE - 1) / TILE) * sizeof(uint32_t));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  LightOp op;
+  op.color_fmt = ctx->fmt;
+  op.lights.assign(pass->lights, pass->lights + pass->n_lights);
+  op.tiles_y = owned_tile_rows(ctx);
+  LightLaunch& L = op.launch;
+  L.color = ctx->color;
+  L.depth = ctx->depth;
+  L.normal = (const float4*)ctx->attr[2];
+  L.albedo = (const float4*)ctx->attr[3];
+  L.W = ctx->W;
+  L.H = ctx->H;
+  L.sx = ctx->sx;
+  L.sy = ctx->sy;
+  L.sw = ctx->sw;
+  L.sh = ctx->sh;
+  L.tiles_x = (ctx->sw + TILE - 1) / TILE;
+  L.rstride = ctx->rstride;
+  L.roff = ctx->roff;
+  L.two_over_w = 2.0f / (float)ctx->W;
+  L.two_over_h = 2.0f / (float)ctx->H;
+  std::memcpy(L.inv_viewproj, pass->inv_viewproj, sizeof(L.inv_viewproj));
+  std::memcpy(L.ambient_color, pass->ambient_color, sizeof(L.ambient_color));
+  std::memcpy(L.sunlight_direction, pass->sunlight_direction, sizeof(L.sunlight_direction));
+  std::memcpy(L.sunlight_color, pass->sunlight_color, sizeof(L.sunlight_color));
+  L.lights = ctx->d_lights.get();
+  L.n_lights = pass->n_lights;
+  L.shadow_depth = pass->shadow_depth;
+  if (pass->shadow_depth) {
+    L.shadow_w = pass->shadow_width;
+    L.shadow_h = pass->shadow_height;
+    L.shadow_half_w = (float)pass->shadow_width * 0.5f;
+    L.shadow_half_h = (float)pass->shadow_height * 0.5f;
+    std::memcpy(L.shadow_viewproj, pass->shadow_viewproj, sizeof(L.shadow_viewproj));
+    L.shadow_bias = pass->shadow_bias;
+  }
+  L.tile_counts = ctx->d_light_tiles.get();
+  L.poison = ctx->d_poison.get();
+  L.ao = ao;
+  const uint32_t n_tiles = L.tiles_x * op.tiles_y;
+  if (int e = log_op(ctx, std::move(op))) return e;
+  ctx->light_tiles_n = n_tiles;
+  return SVR_OK;
+}
+
+int svr_debug_read_light_tiles(SvrContext* ctx, uint32_t* counts, size_t capacity, uint32_t* n_tiles) {
+  if (!ctx || !n_tiles) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  *n_tiles = ctx->light_tiles_n;
+  if (!counts) return SVR_OK;
+  if (!ctx->d_light_tiles) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: no lighting pass yet");
+  if (capacity < ctx->light_tiles_n) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_light_tiles: buffer too small");
+  if (ctx->light_tiles_n) HIPCHK(hipMemcpy(counts, ctx->d_light_tiles.get(), (size_t)ctx->light_tiles_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- the HDR post pass (include/svr_post.h)
+int svr_post_pass(SvrContext* ctx, const SvrPostPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: null argument");
+  if (!(std::isfinite(pass->exposure) && pass->exposure > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the exposure must be finite and greater than 0");
+  if (!(std::isfinite(pass->bloom_threshold) && pass->bloom_threshold >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the bloom threshold must be finite and at least 0");
+  if (!(std::isfinite(pass->bloom_intensity) && pass->bloom_intensity >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: the bloom intensity must be finite and at least 0");
+  if (pass->bloom_levels > SVR_POST_MAX_LEVELS) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: more than SVR_POST_MAX_LEVELS bloom levels");
+  if (pass->tonemap > SVR_TONEMAP_ACES) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: unknown tone-mapping operator");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_post_pass: the colour target must be RGBA16F (an RGBA8 target holds no HDR values)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_post_pass: not under svr_set_row_interleave with a stride above 1");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  uint32_t off[SVR_POST_MAX_LEVELS], lw[SVR_POST_MAX_LEVELS], lh[SVR_POST_MAX_LEVELS];
+  // (the extents grow with the image's, so the levels of any scissor fit in those of the whole target)
+  if (!ctx->d_post_levels) DEV_ALLOC(ctx->d_post_levels, post_level_layout(ctx->W, ctx->H, SVR_POST_MAX_LEVELS, off, lw, lh) * sizeof(uint2));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  PostOp P{};
+  P.color = (uint2*)ctx->color;
+  P.W = ctx->W;
+  P.sx = ctx->sx;
+  P.sy = ctx->sy;
+  P.sw = ctx->sw;
+  P.sh = ctx->sh;
+  P.levels = ctx->d_post_levels.get();
+  P.n_levels = pass->bloom_levels;
+  post_level_layout(ctx->sw, ctx->sh, pass->bloom_levels, P.off, P.lw, P.lh);
+  P.exposure = pass->exposure;
+  P.threshold = pass->bloom_threshold;
+  P.intensity = pass->bloom_intensity;
+  P.tonemap = pass->tonemap;
+  P.poison = ctx->d_poison.get();
+  return log_op(ctx, std::move(P));
+}
+
+// ---------------------------------------------------------------- temporal antialiasing (include/svr_temporal.h)
+static bool temporal_history_usable(const SvrContext* ctx) {
+  return ctx->temporal_has && ctx->temporal_scissor[0] == ctx->sx && ctx->temporal_scissor[1] == ctx->sy &&
+         ctx->temporal_scissor[2] == ctx->sw && ctx->temporal_scissor[3] == ctx->sh;
+}
+
+int svr_temporal_resolve(SvrContext* ctx, const SvrTemporalPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: null argument");
+  if (!(std::isfinite(pass->blend) && pass->blend > 0.0f && pass->blend <= 1.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: the blend must be finite, greater than 0 and at most 1");
+  if (pass->flags & ~(uint32_t)(SVR_TEMPORAL_RESET | SVR_TEMPORAL_NO_CLAMP)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: unknown flag bits");
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(pass->reproject[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: reproject[" + std::to_string(i) + "] is not finite");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: the colour target must be RGBA16F");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: not under svr_set_row_interleave with a stride above 1");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  const size_t hist_bytes = (size_t)ctx->W * ctx->H * sizeof(uint2);
+  for (int i = 0; i < 2; i++)
+    if (!ctx->d_temporal[i]) {  // zeroed once: the read-back hook shows the whole extent, the kernels read the scissor only
+      DEV_ALLOC(ctx->d_temporal[i], hist_bytes);
+      HIPCHK(hipMemsetAsync(ctx->d_temporal[i].get(), 0, hist_bytes, ctx->stream));
+    }
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  TemporalOp T{};
+  T.color = (uint2*)ctx->color;
+  T.depth = ctx->depth;
+  T.W = ctx->W;
+  T.H = ctx->H;
+  T.sx = ctx->sx;
+  T.sy = ctx->sy;
+  T.sw = ctx->sw;
+  T.sh = ctx->sh;
+  // the roles and the validity are decided here, in call order, and travel with the operation: a replay finds them as they were
+  T.hist_in = ctx->d_temporal[ctx->temporal_read].get();
+  T.hist_out = ctx->d_temporal[ctx->temporal_read ^ 1].get();
+  T.history_valid = temporal_history_usable(ctx) && !(pass->flags & SVR_TEMPORAL_RESET) ? 1u : 0u;
+  T.clamp = (pass->flags & SVR_TEMPORAL_NO_CLAMP) ? 0u : 1u;
+  std::memcpy(T.reproject, pass->reproject, sizeof(T.reproject));
+  T.blend = pass->blend;
+  T.two_over_w = 2.0f / (float)ctx->W;
+  T.two_over_h = 2.0f / (float)ctx->H;
+  T.half_w = (float)ctx->W * 0.5f;
+  T.half_h = (float)ctx->H * 0.5f;
+  T.poison = ctx->d_poison.get();
+  if (int e = log_op(ctx, std::move(T))) return e;
+  ctx->temporal_read ^= 1;
+  ctx->temporal_has = true;
+  ctx->temporal_scissor[0] = ctx->sx;
+  ctx->temporal_scissor[1] = ctx->sy;
+  ctx->temporal_scissor[2] = ctx->sw;
+  ctx->temporal_scissor[3] = ctx->sh;
+  return SVR_OK;
+}
+
+int svr_debug_read_temporal_history(SvrContext* ctx, void* dst, size_t bytes, uint32_t* valid) {
+  if (!ctx || !valid) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_temporal_history: null argument");
+  const size_t need = (size_t)ctx->W * ctx->H * sizeof(uint2);
+  if (dst && bytes < need) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_temporal_history: buffer too small");
+  if (int e = svr_sync(ctx)) return e;
+  *valid = temporal_history_usable(ctx) ? 1u : 0u;
+  if (!dst) return SVR_OK;
+  if (ctx->d_temporal[ctx->temporal_read])
+    HIPCHK(hipMemcpy(dst, ctx->d_temporal[ctx->temporal_read].get(), need, hipMemcpyDeviceToHost));
+  else
+    std::memset(dst, 0, need);
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- ambient occlusion (include/svr_ambient.h)
+static float* ambient_target(const SvrContext* ctx) { return ctx->ambient_bound ? ctx->ambient_bound : ctx->d_ambient_own.get(); }
+
+int svr_ambient_pass(SvrContext* ctx, const SvrAmbientPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: null argument");
+  if (!(std::isfinite(pass->radius) && pass->radius > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the radius must be finite and greater than 0");
+  if (!(std::isfinite(pass->pixels_per_unit) && pass->pixels_per_unit > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: pixels_per_unit must be finite and greater than 0");
+  if (!(std::isfinite(pass->bias) && pass->bias >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the bias must be finite and at least 0");
+  if (!(std::isfinite(pass->intensity) && pass->intensity >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the intensity must be finite and at least 0");
+  if (!(std::isfinite(pass->sharpness) && pass->sharpness >= 0.0f && pass->sharpness < 1.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the sharpness must be finite, at least 0 and less than 1");
+  if (pass->flags & ~(uint32_t)SVR_AMBIENT_NO_BLUR) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: unknown flag bits");
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(pass->inv_viewproj[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: inv_viewproj[" + std::to_string(i) + "] is not finite");
+  if (!ctx->attr[2]) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: needs the SVR_ATTR_NORMAL plane (svr_enable_attributes / svr_bind_attribute_target)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_ambient_pass: not under svr_set_row_interleave with a stride above 1");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  const size_t n = (size_t)ctx->W * ctx->H;
+  // zeroed once: the read-backs show the whole extent, the kernels touch the scissor only
+  if (!ctx->d_ambient_raw) {
+    DEV_ALLOC(ctx->d_ambient_raw, n * sizeof(float2));
+    HIPCHK(hipMemsetAsync(ctx->d_ambient_raw.get(), 0, n * sizeof(float2), ctx->stream));
+  }
+  if (!ctx->ambient_bound && !ctx->d_ambient_own) {
+    DEV_ALLOC(ctx->d_ambient_own, n * sizeof(float));
+    HIPCHK(hipMemsetAsync(ctx->d_ambient_own.get(), 0, n * sizeof(float), ctx->stream));
+  }
+  // (no flush_clear: the pass neither reads nor writes colour)
+  AmbientOp T{};
+  T.depth = ctx->depth;
+  T.normal = (const float4*)ctx->attr[2];
+  T.raw = ctx->d_ambient_raw.get();
+  T.out = ambient_target(ctx);
+  T.W = ctx->W;
+  T.H = ctx->H;
+  T.sx = ctx->sx;
+  T.sy = ctx->sy;
+  T.sw = ctx->sw;
+  T.sh = ctx->sh;
+  std::memcpy(T.inv_viewproj, pass->inv_viewproj, sizeof(T.inv_viewproj));
+  T.two_over_w = 2.0f / (float)ctx->W;
+  T.two_over_h = 2.0f / (float)ctx->H;
+  T.radius_px = pass->radius * pass->pixels_per_unit;
+  T.radius2 = pass->radius * pass->radius;
+  T.bias = pass->bias;
+  T.coef = (pass->intensity * pass->radius) * 0.125f;
+  T.sharpness = pass->sharpness;
+  T.blur = (pass->flags & SVR_AMBIENT_NO_BLUR) ? 0u : 1u;
+  T.poison = ctx->d_poison.get();
+  return log_op(ctx, std::move(T));
+}
+
+int svr_bind_ambient_target(SvrContext* ctx, float* dev) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  if (((uintptr_t)dev & 15u) != 0u) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_bind_ambient_target: the target must be 16-byte aligned");
+  if (int e = use_device(ctx)) return e;
+  // no fence: passes already enqueued carry their own planes (also for a replay), as with svr_bind_attribute_target
+  if (int e = poll_pending(ctx)) return e;
+  ctx->ambient_bound = dev;
+  return SVR_OK;
+}
+
+int svr_get_ambient_target(SvrContext* ctx, float** dev) {
+  if (!ctx || !dev) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_ambient_target: null argument");
+  *dev = ambient_target(ctx);
+  return SVR_OK;
+}
+
+int svr_read_ambient(SvrContext* ctx, void* dst_host, size_t bytes) {
+  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: null argument");
+  if (!ambient_target(ctx)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: no ambient target (svr_ambient_pass / svr_bind_ambient_target)");
+  if (bytes != (size_t)ctx->W * ctx->H * sizeof(float)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_ambient: the size is not the plane's");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst_host, ambient_target(ctx), bytes, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+int svr_set_light_ambient_occlusion(SvrContext* ctx, int on) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "null context");
+  ctx->light_ao = on != 0;
+  return SVR_OK;
+}
+
+int svr_debug_read_ambient_raw(SvrContext* ctx, void* dst_host, size_t bytes) {
+  if (!ctx || !dst_host) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: null argument");
+  if (!ctx->d_ambient_raw) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: no ambient pass yet");
+  if (bytes != (size_t)ctx->W * ctx->H * sizeof(float2)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: the size is not the plane's");
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(dst_host, ctx->d_ambient_raw.get(), bytes, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+}  // extern "C"

@@ -106,6 +106,37 @@ def test_overflow_inside_an_unfenced_sequence(hip, oracle):
     assert a["stats"].replayed_passes == 0
 
 
+def _unfenced_background(lib, caps):
+    cam1, cam2 = ((2.5, 1.0, -5.5), 0.2, 1.0), ((30.0, 8.0, 9.7), -0.3, 3.0)
+    r, scene1, opaque, transparent = T.setup_sponza(lib, 320, 180, lod=4, tex_size=64, camera=cam1)
+    scene2 = S.scene_data_struct(*cam2, 320, 180)
+    if caps is not None:
+        r.set_option(A.OPT_QUEUE_CAPS, caps)
+    r.clear_color((1, 1, 1, 1))
+    r.draw_geometry(scene1, opaque, transparent)
+    r.set_scissor(0, 60, 320, 64)
+    r.draw_background(A.BACKGROUND_SKY, A.SKY_DEFAULT)
+    r.set_scissor(40, 30, 200, 100)
+    r.draw_geometry(scene2, opaque, transparent)
+    out = T._finish(r)
+    r.close()
+    return out
+
+
+def test_overflow_in_front_of_an_unfenced_background(hip, oracle):
+    """A background between two passes, enqueued without a fence behind a pass that overflows its queues: it writes
+    nothing until the replay runs it again, in its place between the replayed passes (operation log)."""
+    b = _unfenced_background(oracle, None)
+    a = _unfenced_background(hip, 64)
+    T.assert_images_identical(a["color"], b["color"], "unfenced background, caps 64 colour")
+    T.assert_images_identical(a["depth"], b["depth"], "unfenced background, caps 64 depth")
+    assert a["stats"].replayed_passes >= 1
+    a = _unfenced_background(hip, None)
+    T.assert_images_identical(a["color"], b["color"], "unfenced background, default caps colour")
+    T.assert_images_identical(a["depth"], b["depth"], "unfenced background, default caps depth")
+    assert a["stats"].replayed_passes == 0
+
+
 def _background_and_blit(lib, w, h, fmt, effect, data, blits):
     r = lib.create(w, h, fmt)
     r.clear_color((0.2, 0.4, 0.6, 1.0))

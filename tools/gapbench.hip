@@ -3,7 +3,7 @@
 // Chains of fixed-duration kernels (every workgroup spins on the 100 MHz wall clock), timed by the host over the whole
 // chain; per-boundary overhead = chain time / links - kernel duration.  Variants: a completion event riding on every
 // kernel (hipExtLaunchKernelGGL stopEvent), a cross-stream event wait in front of every kernel (the tile kernel's
-// wait for its pass's bins), the full two-stream pipeline of svr_api.hip's submit_pass, kernels that use scratch,
+// wait for its pass's bins), the full two-stream pipeline of svr_log.hip's submit_pass, kernels that use scratch,
 // kernels that leave 100 MB of dirty lines behind (plain and non-temporal stores).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
