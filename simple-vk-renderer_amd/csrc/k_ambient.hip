@@ -8,12 +8,13 @@
 //                         is staged into LDS, 16 bytes a lane where the row allows, with 0 for every texel outside the
 //                         scissor — a depth of 0 contributes nothing (C34), so the LDS image is the edge-tested image
 //                         and no tap needs a test of its own.  A lane then takes 4 pixels of one column: the centre's
-//                         position and normal, and eight scattered depths out of LDS, each unprojected in full (C35).
+//                         position and normal, and eight scattered depths out of LDS, each unprojected in full (C17, C35).
 //   ambient_blur_kernel   stages the 36 x 36 window of the scratch plane at clamped coordinates, takes the 25 taps out of
 //                         LDS (C37) and stores the ambient target; under SVR_AMBIENT_NO_BLUR it copies a.
 // Ordinary vector loads and stores only; nothing is handed between workgroups of one launch, and neither kernel reads a
 // plane the same launch writes.  Both kernels read the context's poison flag first: after an overflow they write nothing.
 #include "svr_launch.h"
+#include "svr_pixel.h"
 
 #define SVR_AMBIENT_TABLE __device__ const
 #include "svr_ambient_tables.h"
@@ -28,22 +29,6 @@ constexpr uint32_t AW = AT + 2u * REACH;        // the staged depth window, per 
 constexpr uint32_t BR = 2;                      // the blur's reach
 constexpr uint32_t BW = AT + 2u * BR;           // the staged raw window, per side
 
-struct Vec4 {
-  float x, y, z, w;
-};
-
-// inv_viewproj (column-major) times (xn, yn, z, 1), the C0 chain as C17 spells it
-__device__ __forceinline__ Vec4 unproject(const float* m, float xn, float yn, float z) {
-  Vec4 r;
-  r.x = m[0] * xn; r.y = m[1] * xn; r.z = m[2] * xn; r.w = m[3] * xn;
-  r.x = fmaf(m[4], yn, r.x); r.y = fmaf(m[5], yn, r.y); r.z = fmaf(m[6], yn, r.z); r.w = fmaf(m[7], yn, r.w);
-  r.x = fmaf(m[8], z, r.x); r.y = fmaf(m[9], z, r.y); r.z = fmaf(m[10], z, r.z); r.w = fmaf(m[11], z, r.w);
-  r.x = fmaf(m[12], 1.0f, r.x); r.y = fmaf(m[13], 1.0f, r.y); r.z = fmaf(m[14], 1.0f, r.z); r.w = fmaf(m[15], 1.0f, r.w);
-  return r;
-}
-
-__device__ __forceinline__ bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1u)) == 0u; }
-__device__ __forceinline__ uint32_t clamp_to(int v, uint32_t n) { return v < 0 ? 0u : ((uint32_t)v > n - 1u ? n - 1u : (uint32_t)v); }
 __device__ __forceinline__ int clamp_reach(int v) { return v < -REACH ? -REACH : (v > REACH ? REACH : v); }
 
 }  // namespace
@@ -90,7 +75,7 @@ __global__ __launch_bounds__(256) void ambient_raw_kernel(AmbientLaunch A) {
     const float z = s_z[r0 + i + REACH][c + REACH];
     const float4 n = A.normal[at];
     const float yn = fmaf((float)py + 0.5f, A.two_over_h, -1.0f);
-    const Vec4 h = unproject(A.inv_viewproj, xn, yn, z);
+    const Vec4 h = mat_vec(A.inv_viewproj, xn, yn, z, 1.0f);
     const float nn = fmaf(n.z, n.z, fmaf(n.y, n.y, n.x * n.x));
     if (!(z > 0.0f && f2u(n.w) != 0u && nn > 0.0f)) {
       A.raw[at] = make_float2(1.0f, 0.0f);
@@ -126,7 +111,7 @@ __global__ __launch_bounds__(256) void ambient_raw_kernel(AmbientLaunch A) {
       // C35: the tap's own position, in full
       const float xt = fmaf((float)((int)px + ox) + 0.5f, A.two_over_w, -1.0f);
       const float yt = fmaf((float)((int)py + oy) + 0.5f, A.two_over_h, -1.0f);
-      const Vec4 g = unproject(A.inv_viewproj, xt, yt, zt);
+      const Vec4 g = mat_vec(A.inv_viewproj, xt, yt, zt, 1.0f);
       const float gw = rcp_ieee(g.w);
       const float vx = g.x * gw - Px, vy = g.y * gw - Py, vz = g.z * gw - Pz;
       const float vv = fmaf(vz, vz, fmaf(vy, vy, vx * vx));

@@ -8,9 +8,8 @@
 //   background      draw_background's two compute effects (gradient_color.comp, sky.comp)
 //   blit            vkutil::copy_image in general: LINEAR-filter scaling blit to the swapchain format
 // All are pure streaming kernels, grid-stride, HBM-bound.
-#include <hip/hip_fp16.h>
-
 #include "svr_launch.h"
+#include "svr_pixel.h"
 
 namespace svr {
 
@@ -106,10 +105,7 @@ void launch_retile(bool to_tiled, void* linear, uint8_t* tiled, uint32_t w, uint
   else hipLaunchKernelGGL(retile_kernel<false>, grid, block, 0, s, (uint32_t*)linear, (uint32_t*)tiled, w, h, plw);
 }
 
-__device__ __forceinline__ uint32_t h2un8(uint32_t hbits) {
-  float f = __half2float(__ushort_as_half((unsigned short)hbits));
-  return (uint32_t)__float2int_rn(fminf(fmaxf(f, 0.0f), 1.0f) * 255.0f);
-}
+__device__ __forceinline__ uint32_t h2un8(uint32_t hbits) { return un8(half_bits_to_float(hbits)); }
 // two pixels (16 bytes in, 8 bytes out) per lane
 __global__ __launch_bounds__(256) void cvt16f_to_8_kernel(const uint2* src, uint32_t* dst, uint32_t n_pixels) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pixels; i += gridDim.x * blockDim.x) {
@@ -120,20 +116,9 @@ __global__ __launch_bounds__(256) void cvt16f_to_8_kernel(const uint2* src, uint
 // ------------------------------------------------------------------------------------------------
 // draw_background (src/vk_engine.cpp:1341-1355): gradient_color.comp and sky.comp  (contract C14, C15).
 // One lane per pixel of the scissor's rows, 8 (RGBA16F) or 4 (RGBA8) bytes written per lane.
-__device__ __forceinline__ float pin32(float x) {  // keep "fp32 result, then the store's rounding" apart (see Codec)
-  asm volatile("" : "+v"(x));
-  return x;
-}
 __device__ __forceinline__ void store_target(void* color, int fmt, size_t p, float r, float g, float b, float a) {
-  if (fmt == SVR_COLOR_RGBA16F) {
-    r = pin32(r); g = pin32(g); b = pin32(b); a = pin32(a);
-    uint32_t hr = __half_as_ushort(__float2half_rn(r)), hg = __half_as_ushort(__float2half_rn(g));
-    uint32_t hb = __half_as_ushort(__float2half_rn(b)), ha = __half_as_ushort(__float2half_rn(a));
-    reinterpret_cast<uint2*>(color)[p] = make_uint2(hr | (hg << 16), hb | (ha << 16));
-  } else {
-    auto un8 = [](float f) { return (uint32_t)__float2int_rn(fminf(fmaxf(f, 0.0f), 1.0f) * 255.0f); };
-    reinterpret_cast<uint32_t*>(color)[p] = un8(r) | (un8(g) << 8) | (un8(b) << 16) | (un8(a) << 24);
-  }
+  if (fmt == SVR_COLOR_RGBA16F) reinterpret_cast<uint2*>(color)[p] = Codec<SVR_COLOR_RGBA16F>::encode(make_float4(r, g, b, a));
+  else reinterpret_cast<uint32_t*>(color)[p] = Codec<SVR_COLOR_RGBA8>::encode(make_float4(r, g, b, a));
 }
 
 // cos for sky.comp's hash, operation by operation as the oracle's sky_cos (three-term Cody-Waite by
@@ -209,14 +194,8 @@ void launch_background(void* color, int color_format, uint32_t W, uint32_t H, ui
 // format and extent (contract C16).  One lane per destination pixel; identity extent degenerates to
 // weights 0 and is exactly the plain format conversion.
 __device__ __forceinline__ float4 load_target(const void* color, int fmt, size_t p) {
-  if (fmt == SVR_COLOR_RGBA16F) {
-    uint2 e = reinterpret_cast<const uint2*>(color)[p];
-    return make_float4(__half2float(__ushort_as_half((unsigned short)(e.x & 0xffffu))), __half2float(__ushort_as_half((unsigned short)(e.x >> 16))),
-                       __half2float(__ushort_as_half((unsigned short)(e.y & 0xffffu))), __half2float(__ushort_as_half((unsigned short)(e.y >> 16))));
-  }
-  uint32_t t = reinterpret_cast<const uint32_t*>(color)[p];
-  const float k = 0x1.010102p-8f;
-  return make_float4((float)(t & 0xffu) * k, (float)((t >> 8) & 0xffu) * k, (float)((t >> 16) & 0xffu) * k, (float)(t >> 24) * k);
+  if (fmt == SVR_COLOR_RGBA16F) return Codec<SVR_COLOR_RGBA16F>::decode(reinterpret_cast<const uint2*>(color)[p]);
+  return Codec<SVR_COLOR_RGBA8>::decode(reinterpret_cast<const uint32_t*>(color)[p]);
 }
 // rstride > 1 (identity extent only): of the 32-row tile rows counted from row_first, those with index % rstride == roff
 // (svr_set_row_interleave) — n_rows is then 32 x the number of such tile rows and row_end the first row not to write.
@@ -251,7 +230,6 @@ __global__ __launch_bounds__(256) void blit_kernel(const void* color, int fmt, u
       float top = fmaf(a, c10 - c00, c00), bot = fmaf(a, c11 - c01, c01);
       return fmaf(b, bot - top, top);
     };
-    auto un8 = [](float f) { return (uint32_t)__float2int_rn(fminf(fmaxf(f, 0.0f), 1.0f) * 255.0f); };
     uint32_t r = un8(filt(t00.x, t10.x, t01.x, t11.x)), g = un8(filt(t00.y, t10.y, t01.y, t11.y));
     uint32_t bl = un8(filt(t00.z, t10.z, t01.z, t11.z)), al = un8(filt(t00.w, t10.w, t01.w, t11.w));
     dst[idx] = dst_format == SVR_SWAPCHAIN_B8G8R8A8 ? (bl | (g << 8) | (r << 16) | (al << 24)) : (r | (g << 8) | (bl << 16) | (al << 24));

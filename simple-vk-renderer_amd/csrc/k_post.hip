@@ -13,9 +13,8 @@
 // Staged texels are fetched at clamped coordinates, so the LDS arrays hold the edge-clamped image and no tap needs a test.
 // Ordinary vector loads and stores only; nothing is handed between workgroups of one launch.  Every kernel reads the
 // context's poison flag first: after an overflow it writes nothing.
-#include <hip/hip_fp16.h>
-
 #include "svr_launch.h"
+#include "svr_pixel.h"
 
 namespace svr {
 
@@ -23,26 +22,15 @@ namespace {
 
 constexpr uint32_t PT = 32;       // the tile of a level image a workgroup writes
 constexpr uint32_t PS = PT + 4;   // ... and the staged texels per side: two more each way for the five taps
-constexpr float HALF_MAX = 65504.0f;
 
 struct Rgb {
   float r, g, b;
 };
 
-__device__ __forceinline__ float san(float v) { return v > 0.0f ? (v < HALF_MAX ? v : HALF_MAX) : 0.0f; }
-__device__ __forceinline__ float half_bits_to_float(uint32_t h) { return __half2float(__ushort_as_half((unsigned short)h)); }
 __device__ __forceinline__ Rgb decode(uint2 t) { return {half_bits_to_float(t.x & 0xffffu), half_bits_to_float(t.x >> 16), half_bits_to_float(t.y & 0xffffu)}; }
-// the fp32 value is pinned in a VGPR so that "fma -> cvt" is not fused into one rounding (as k_light.hip's stores)
-__device__ __forceinline__ uint32_t h16(float x) {
-  asm volatile("" : "+v"(x));
-  return __half_as_ushort(__float2half_rn(x));
-}
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
-__device__ __forceinline__ uint32_t clamp_to(int v, uint32_t n) { return v < 0 ? 0u : ((uint32_t)v > n - 1u ? n - 1u : (uint32_t)v); }
-
 // texels x0 and x1 (x1 == x0 + 1 or x1 == x0) of one row: one 16-byte load where the address allows
 __device__ __forceinline__ void load_pair(const uint2* row, uint32_t x0, uint32_t x1, uint2& a, uint2& b) {
-  if (x1 != x0 && aligned16(row + x0)) {
+  if (x1 != x0 && aligned_to(row + x0, 16u)) {
     const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
     a = make_uint2(q.x, q.y);
     b = make_uint2(q.z, q.w);
@@ -212,7 +200,7 @@ __global__ __launch_bounds__(256) void post_composite_kernel(CompositeArgs A) {
   const uint32_t x = (blockIdx.x * 64u + (threadIdx.x & 63u)) * 2u, y = blockIdx.y * 4u + (threadIdx.x >> 6);
   if (x >= A.sw || y >= A.sh) return;
   uint2* at = A.color + (size_t)y * A.pitch + x;
-  if (x + 1u < A.sw && aligned16(at)) {
+  if (x + 1u < A.sw && aligned_to(at, 16u)) {
     const uint4 q = *reinterpret_cast<const uint4*>(at);
     const uint2 a = composite_pixel<OP>(A, make_uint2(q.x, q.y), x, y), b = composite_pixel<OP>(A, make_uint2(q.z, q.w), x + 1u, y);
     *reinterpret_cast<uint4*>(at) = make_uint4(a.x, a.y, b.x, b.y);

@@ -14,9 +14,8 @@
 //                             (16 bytes) where the address allows, else one at a time.
 // Ordinary vector loads and stores only; nothing is handed between workgroups of one launch.  Both kernels read the
 // context's poison flag first: after an overflow they write nothing.
-#include <hip/hip_fp16.h>
-
 #include "svr_launch.h"
+#include "svr_pixel.h"
 
 namespace svr {
 
@@ -26,17 +25,7 @@ constexpr uint32_t TT = 32;      // the tile of the scissor a workgroup resolves
 constexpr uint32_t TS = TT + 2;  // ... and the staged texels per side: one more each way
 constexpr uint32_t TP = 36;      // floats per staged row: window column c sits at index c + 1, so the texel pairs that
                                  // start at window column 1 (the tile's own first column) are 8-byte aligned in LDS
-constexpr float HALF_MAX = 65504.0f;
 
-__device__ __forceinline__ float san(float v) { return v > 0.0f ? (v < HALF_MAX ? v : HALF_MAX) : 0.0f; }
-__device__ __forceinline__ float half_bits_to_float(uint32_t h) { return __half2float(__ushort_as_half((unsigned short)h)); }
-// the fp32 value is pinned in a VGPR so that "fma -> cvt" is not fused into one rounding (as k_post.hip's stores)
-__device__ __forceinline__ uint32_t h16(float x) {
-  asm volatile("" : "+v"(x));
-  return __half_as_ushort(__float2half_rn(x));
-}
-__device__ __forceinline__ bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1u)) == 0u; }
-__device__ __forceinline__ uint32_t clamp_to(int v, uint32_t n) { return v < 0 ? 0u : ((uint32_t)v > n - 1u ? n - 1u : (uint32_t)v); }
 __device__ __forceinline__ float min2(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float max2(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float lerp(float t, float a, float b) { return fmaf(t, b - a, a); }
@@ -117,15 +106,11 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalLaunch A)
     const float z = max2(max2(hz[i], hz[i + 1u]), hz[i + 2u]);
     // C29: the C0 chain, one matrix, no intermediate divide
     const float yn = fmaf((float)py + 0.5f, A.two_over_h, -1.0f);
-    const float* m = A.reproject;
-    float qx = m[0] * xn, qy = m[1] * xn, qw = m[3] * xn;
-    qx = fmaf(m[4], yn, qx); qy = fmaf(m[5], yn, qy); qw = fmaf(m[7], yn, qw);
-    qx = fmaf(m[8], z, qx); qy = fmaf(m[9], z, qy); qw = fmaf(m[11], z, qw);
-    qx = fmaf(m[12], 1.0f, qx); qy = fmaf(m[13], 1.0f, qy); qw = fmaf(m[15], 1.0f, qw);
-    bool valid = A.history_valid != 0u && qw > 0.0f;
+    const Vec4 q = mat_vec(A.reproject, xn, yn, z, 1.0f);  // (q.z is not used)
+    bool valid = A.history_valid != 0u && q.w > 0.0f;
     if (valid) {
-      const float r = rcp_ieee(qw);
-      const float hx = fmaf(qx * r, A.half_w, A.half_w), hy = fmaf(qy * r, A.half_h, A.half_h);
+      const float r = rcp_ieee(q.w);
+      const float hx = fmaf(q.x * r, A.half_w, A.half_w), hy = fmaf(q.y * r, A.half_h, A.half_h);
       valid = hx >= x_lo && hx < x_hi && hy >= y_lo && hy < y_hi;  // on the floats, before any conversion (NaN fails)
       if (valid) {
         // C30: hx - 0.5 lies in [sx - 0.5, sx + sw - 0.5), so the floors fit an int and the taps clamp into the scissor

@@ -26,14 +26,13 @@
 // Heavy tiles of small passes are rendered as four 8-row quarters by four workgroups (tile_kernel<.., SPLIT>).
 // What bounds it is memory latency and VALU issue (the fragment stage is ~350 instructions per pixel), not HBM:
 // DESIGN.md "Tile kernel".  <= 96 VGPRs and < 32 KiB of LDS = 5 workgroups per CU (round 3; 124 / 37 KiB = 4 before).
-#include <hip/hip_fp16.h>
-
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
 #include <type_traits>
 
 #include "svr_launch.h"
+#include "svr_pixel.h"
 
 namespace svr {
 
@@ -50,7 +49,6 @@ constexpr uint32_t SREC = 7;  // pieces (uint4) per staged record
 
 // ------------------------------------------------------------------------------------------------
 // texture unit (C8, C9)
-constexpr float kInv255 = 0x1.010102p-8f;
 constexpr float kG0 = 0x1.c51282p-2f, kG1 = -0x1.14a3a2p-2f, kG2 = 0x1.37536ap-3f, kG3 = -0x1.778474p-5f;
 
 __device__ __forceinline__ float lod_from_rho2(float rho2) {
@@ -121,7 +119,6 @@ __device__ __forceinline__ Taps level_taps(int wl, int hl, uint32_t plw, uint32_
 __device__ __forceinline__ uint32_t texel(const uint8_t* arena, uint32_t off) {
   return *reinterpret_cast<const uint32_t*>(arena + off);
 }
-__device__ __forceinline__ float chan(uint32_t t, int c) { return (float)((t >> (8 * c)) & 0xffu) * kInv255; }
 __device__ __forceinline__ float bilerp(uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11, int c, float a, float b) {
   return lerpf(lerpf(chan(t00, c), chan(t10, c), a), lerpf(chan(t01, c), chan(t11, c), a), b);
 }
@@ -306,47 +303,6 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   if (ATTR) { fa->nx = nx; fa->ny = ny; fa->nz = nz; fa->light = light; fa->cr = cr; fa->cg = cg; fa->cb = cb; }
   return o;
 }
-
-// ------------------------------------------------------------------------------------------------
-// colour target codecs: the attachment holds fp16 (reference) or unorm8
-template <int FMT>
-struct Codec;
-template <>
-struct Codec<SVR_COLOR_RGBA16F> {
-  typedef uint2 enc_t;
-  // The fp32 result must exist before it is rounded to fp16 (two roundings, as an attachment store
-  // after an fp32 shader does): without the barrier hipcc fuses "fma -> cvt" into v_fma_mixlo_f16,
-  // which rounds once and differs from the contract on fp16 ties.
-  static __device__ __forceinline__ float pin(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-  }
-  static __device__ __forceinline__ enc_t encode(float4 c) {
-    c.x = pin(c.x); c.y = pin(c.y); c.z = pin(c.z); c.w = pin(c.w);
-    uint32_t r = __half_as_ushort(__float2half_rn(c.x)), g = __half_as_ushort(__float2half_rn(c.y));
-    uint32_t b = __half_as_ushort(__float2half_rn(c.z)), a = __half_as_ushort(__float2half_rn(c.w));
-    return make_uint2(r | (g << 16), b | (a << 16));
-  }
-  static __device__ __forceinline__ float4 decode(enc_t e) {
-    return make_float4(__half2float(__ushort_as_half((unsigned short)(e.x & 0xffffu))),
-                       __half2float(__ushort_as_half((unsigned short)(e.x >> 16))),
-                       __half2float(__ushort_as_half((unsigned short)(e.y & 0xffffu))),
-                       __half2float(__ushort_as_half((unsigned short)(e.y >> 16))));
-  }
-};
-template <>
-struct Codec<SVR_COLOR_RGBA8> {
-  typedef uint32_t enc_t;
-  static __device__ __forceinline__ uint32_t un8(float f) {
-    return (uint32_t)__float2int_rn(fminf(fmaxf(f, 0.0f), 1.0f) * 255.0f);
-  }
-  static __device__ __forceinline__ enc_t encode(float4 c) {
-    return un8(c.x) | (un8(c.y) << 8) | (un8(c.z) << 16) | (un8(c.w) << 24);
-  }
-  static __device__ __forceinline__ float4 decode(enc_t e) {
-    return make_float4(chan(e, 0), chan(e, 1), chan(e, 2), chan(e, 3));
-  }
-};
 
 // ------------------------------------------------------------------------------------------------
 // Phase A, column scan.  A heavy bin is mostly slivers (a distant column's quads are ~3 x 26 pixels)

@@ -421,6 +421,19 @@ __device__ __forceinline__ void matvec4(const float* m, float x, float y, float 
     out[r] = acc;
   }
 }
+// ... and the same chain by value, a column at a time, for the screen-space passes.  Both spellings stay: either one
+// written through the other gives the same values but another instruction order in the kernels that use it.
+struct Vec4 {
+  float x, y, z, w;
+};
+__device__ __forceinline__ Vec4 mat_vec(const float* m, float x, float y, float z, float w) {
+  Vec4 r;
+  r.x = m[0] * x; r.y = m[1] * x; r.z = m[2] * x; r.w = m[3] * x;
+  r.x = fmaf(m[4], y, r.x); r.y = fmaf(m[5], y, r.y); r.z = fmaf(m[6], y, r.z); r.w = fmaf(m[7], y, r.w);
+  r.x = fmaf(m[8], z, r.x); r.y = fmaf(m[9], z, r.y); r.z = fmaf(m[10], z, r.z); r.w = fmaf(m[11], z, r.w);
+  r.x = fmaf(m[12], w, r.x); r.y = fmaf(m[13], w, r.y); r.z = fmaf(m[14], w, r.z); r.w = fmaf(m[15], w, r.w);
+  return r;
+}
 __device__ __forceinline__ void matmul4(const float* a, const float* b, float* out) {
 #pragma unroll
   for (int j = 0; j < 4; j++) matvec4(a, b[4 * j + 0], b[4 * j + 1], b[4 * j + 2], b[4 * j + 3], out + 4 * j);

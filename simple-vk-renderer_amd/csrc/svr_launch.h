@@ -76,7 +76,7 @@ struct LightLaunch {
   float shadow_bias;
   uint32_t* tile_counts;        // [tiles_x * tiles_y]: the lights each tile kept (svr_debug_read_light_tiles)
   const uint32_t* poison;
-  const float* ao;              // the ambient target (include/svr_ambient.h), or null: light_ao_kernel / light_kernel
+  const float* ao;              // the ambient target (include/svr_ambient.h), or null: light_kernel<FMT, true> / <FMT, false>
 };
 void launch_light(const LightLaunch& L, int color_format, uint32_t tiles_y, hipStream_t s);
 // k_post.hip: the HDR post pass (include/svr_post.h)
