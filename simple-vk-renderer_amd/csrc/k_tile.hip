@@ -171,6 +171,7 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   e2 = fma(A2, dx, fma(B2, dy, C2)) + ((flags & F_T2) ? 1.0 : 0.0);
   TexD t;
   t.base_off = (uint32_t)(unsigned long long)__double_as_longlong(c6.y);
+  const uint32_t tk = (uint32_t)((unsigned long long)__double_as_longlong(c6.y) >> 32);  // tex_consts (svr_device.h): COMMON reads its levels out of these bytes
   t.w = td.x & 0xffffu;
   t.h = td.x >> 16;
   t.lw = td.y & 0xffu;
@@ -183,19 +184,18 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   float b1 = (float)e1 * inv_area, b2 = (float)e2 * inv_area;
   float q0 = s0.x, dq1 = s0.y, dq2 = s0.z;
   const float qq = fmaf(b2, dq2, fmaf(b1, dq1, q0));
-  float hb1 = 0.0f, hb2 = 0.0f, vb1 = 0.0f, vb2 = 0.0f, hq = 1.0f, vq = 1.0f;
-  if (!quads) {
+  float hb1 = 0.0f, hb2 = 0.0f, vb1 = 0.0f, vb2 = 0.0f, hq = 1.0f, vq = 1.0f, hr = 0.0f, vr = 0.0f;
+  // the quad partners' barycentrics and 1/w by the pixel's own chain, one edge step away
+  auto partners = [&]() {
     double sxp = (px & 1) ? -1.0 : 1.0, syp = (py & 1) ? -1.0 : 1.0;
     hb1 = (float)fma(sxp, A1, e1) * inv_area, hb2 = (float)fma(sxp, A2, e2) * inv_area;
     vb1 = (float)fma(syp, B1, e1) * inv_area, vb2 = (float)fma(syp, B2, e2) * inv_area;
     hq = fmaf(hb2, dq2, fmaf(hb1, dq1, q0)), vq = fmaf(vb2, dq2, fmaf(vb1, dq1, q0));
-  }
-  float r, hr = 0.0f, vr = 0.0f;
-  if (COMMON && !quads) {
-    rcp3_ieee(qq, hq, vq, r, hr, vr);  // one exponent-window test for the three
-  } else {
-    r = rcp_ieee(qq);
-  }
+  };
+  if (!COMMON && !quads) partners();  // (the generic stage keeps the order it was compiled in: its instances' code stays)
+  // COMMON: setup_triangle proved per triangle (frag_ranges_ok; a failing one gives up key bit 1) that 1/w at the pixel and
+  // at its quad partners lies in the reciprocal's exponent window and that |u|, |v| < 2^23: no test, no branch, no select
+  const float r = COMMON ? rcp_in_window(qq) : rcp_ieee(qq);
   const uint32_t kind = COMMON ? (uint32_t)PIPE_MESH : ((flags >> F_KIND_SHIFT) & 3u);
   float cr = interp3(s1.z, s3.z, s5.z, b1, b2, r);
   float cg = interp3(s1.w, s3.w, s5.w, b1, b2, r);
@@ -213,6 +213,11 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
     uh = quad_partner_x(u), vh = quad_partner_x(v);
     uv_ = quad_partner_y(u), vv_ = quad_partner_y(v);
   } else {
+    if (COMMON) {  // the whole of the partners' chain inside this branch: nothing of it is live where quads holds
+      partners();
+      hr = rcp_in_window(hq);
+      vr = rcp_in_window(vq);
+    }
     uh = interp3(s2.y, s4.y, s6.y, hb1, hb2, hr), vh = interp3(s2.z, s4.z, s6.z, hb1, hb2, hr);
     uv_ = interp3(s2.y, s4.y, s6.y, vb1, vb2, vr), vv_ = interp3(s2.z, s4.z, s6.z, vb1, vb2, vr);
   }
@@ -227,7 +232,7 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   float rho2 = fmaxf(fmaf(mx, mx, my * my), fmaf(nx_, nx_, ny_ * ny_));
   float lambda = fminf(fmaxf(lod_from_rho2(rho2), t.min_lod), t.max_lod);
   const bool linear = COMMON ? true : (((lambda <= 0.0f) ? (t.filters & 1u) : ((t.filters >> 1) & 1u)) != 0u);
-  int q = (int)t.levels - 1;
+  int q = COMMON ? (int)(tk >> 24) : (int)t.levels - 1;
   const bool mip_linear = COMMON ? true : (((t.filters >> 2) & 1u) != 0u);
   int dn = min(max((int)ceilf(lambda + 0.5f) - 1, 0), q);
   float lc = fminf(fmaxf(lambda, 0.0f), (float)q);
@@ -235,12 +240,14 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   int dhi = mip_linear ? (int)fl : dn;
   float delta = mip_linear ? lc - fl : 0.0f;
   int dlo = mip_linear ? min(dhi + 1, q) : dn;
-  float us = (fabsf(u) < 8388608.0f) ? u : 0.0f, vs = (fabsf(v) < 8388608.0f) ? v : 0.0f;
+  float us = (COMMON || fabsf(u) < 8388608.0f) ? u : 0.0f, vs = (COMMON || fabsf(v) < 8388608.0f) ? v : 0.0f;
   // level extents and arena offsets.  The layout pads every level to powers of two and whole tiles (svr_device.h
   // mip_offset), so the next level starts one padded level further on: no second evaluation of the closed form.
+  // COMMON: the same figures from the texture's constants, computed once per texture (svr_device.h tex_consts)
   const int whi = (int)max(t.w >> dhi, 1u), hhi = (int)max(t.h >> dhi, 1u);
-  const uint32_t bhi = t.base_off + mip_offset(t.lw, t.lh, (uint32_t)dhi);
-  Taps th = level_taps<COMMON>(whi, hhi, level_lw(t.lw, (uint32_t)dhi), bhi, linear, us, vs);
+  const uint32_t bhi = t.base_off + (COMMON ? packed_mip_offset(tk, (uint32_t)dhi) : mip_offset(t.lw, t.lh, (uint32_t)dhi));
+  const uint32_t plw_hi = COMMON ? packed_level_lw(td.y, (uint32_t)dhi) : level_lw(t.lw, (uint32_t)dhi);
+  Taps th = level_taps<COMMON>(whi, hhi, plw_hi, bhi, linear, us, vs);
   const uint8_t* tb = P.tex_arena;
   uint32_t h00 = texel(tb, th.o00), h10 = texel(tb, th.o10), h01 = texel(tb, th.o01), h11 = texel(tb, th.o11);
   // The second level only matters where delta != 0 (lerp(H, L, 0) == H exactly): magnified and
@@ -251,9 +258,10 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   uint32_t l00 = 0, l10 = 0, l01 = 0, l11 = 0;
   if (two_levels) {
     const int wlo = (int)max(t.w >> dlo, 1u), hlo = (int)max(t.h >> dlo, 1u);
-    const uint32_t step = level_bytes(t.lw, t.lh, (uint32_t)dhi);  // padded bytes of level dhi
+    const uint32_t step = COMMON ? packed_level_bytes(tk, (uint32_t)dhi) : level_bytes(t.lw, t.lh, (uint32_t)dhi);  // padded bytes of level dhi
     const uint32_t blo = dlo != dhi ? bhi + step : bhi;
-    tl = level_taps<COMMON>(wlo, hlo, level_lw(t.lw, (uint32_t)dlo), blo, linear, us, vs);
+    const uint32_t plw_lo = COMMON ? packed_level_lw(td.y, (uint32_t)dlo) : level_lw(t.lw, (uint32_t)dlo);
+    tl = level_taps<COMMON>(wlo, hlo, plw_lo, blo, linear, us, vs);
     l00 = texel(tb, tl.o00);
     l10 = texel(tb, tl.o10);
     l01 = texel(tb, tl.o01);

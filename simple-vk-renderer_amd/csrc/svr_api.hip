@@ -63,6 +63,7 @@ TexBinding make_binding(const ImageRes& im, const SvrSamplerDesc& s) {
   std::memset(&tb, 0, sizeof(tb));
   uint32_t filters = (uint32_t)s.mag_filter | ((uint32_t)s.min_filter << 1) | ((uint32_t)s.mipmap_mode << 2);
   tb.base_off = im.arena_off;
+  tb.pad0 = tex_consts(im.lw, im.lh, im.levels);
   tb.wh = im.w | (im.h << 16);
   tb.info = im.lw | (im.lh << 8) | (im.levels << 16) | (filters << 24);
   tb.min_lod = s.min_lod;

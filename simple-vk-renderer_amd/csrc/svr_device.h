@@ -107,7 +107,7 @@ struct WaveChunk {
 // were padded to 2^lw x 2^lh and every level to whole tiles, so offset and pitch are closed forms of (lw, lh, l).
 struct TexBinding {
   uint32_t base_off;        // RGBA8 texels of level 0: byte offset in the context's texel arena (FrameParams::tex_arena)
-  uint32_t pad0;
+  uint32_t pad0;            // tex_consts(lw, lh, levels): the layout's level-independent constants, four bytes (below)
   uint32_t wh;              // w | h << 16   (extent <= 16384 each)
   uint32_t info;            // lw | lh << 8 | levels << 16 | filters << 24; filters = mag | min<<1 | mip<<2
   float min_lod, max_lod;
@@ -146,6 +146,70 @@ __host__ __device__ inline uint32_t texel_offset_y(uint32_t plw, uint32_t y) {
 }
 __host__ __device__ inline uint32_t texel_offset(uint32_t plw, uint32_t x, uint32_t y) { return texel_offset_x(x) + texel_offset_y(plw, y); }
 
+// The level-independent half of the closed forms above, once per TEXTURE instead of once per pixel: four bytes in
+// TexBinding::pad0 (the host's make_binding), copied into TriRec::tex_pad by setup_triangle.  The common-case fragment
+// stage reads its levels' offset, pitch and size out of these bytes and TexBinding::info's (a byte is an operand select).
+//   byte 0  a = min(nw, nh)      byte 1  b = max(nw, nh)      byte 2  cw + ch      byte 3  levels - 1
+__host__ __device__ inline uint32_t tex_consts(uint32_t lw, uint32_t lh, uint32_t levels) {
+  const uint32_t cw = level_lw(lw, 0), ch = level_lh(lh, 0), nw = cw - TEX_TILE_LW, nh = ch - TEX_TILE_LH;
+  return (nw < nh ? nw : nh) | ((nw < nh ? nh : nw) << 8) | ((cw + ch) << 16) | ((levels ? levels - 1u : 0u) << 24);
+}
+// == level_lw(lw, level), level_lh(lh, level) with lw, lh out of TexBinding::info: a signed max in place of compare and select
+__host__ __device__ inline uint32_t packed_level_lw(uint32_t info, uint32_t level) {
+  const int d = (int)(info & 0xffu) - (int)level;
+  return (uint32_t)(d > (int)TEX_TILE_LW ? d : (int)TEX_TILE_LW);
+}
+__host__ __device__ inline uint32_t packed_level_lh(uint32_t info, uint32_t level) {
+  const int d = (int)((info >> 8) & 0xffu) - (int)level;
+  return (uint32_t)(d > (int)TEX_TILE_LH ? d : (int)TEX_TILE_LH);
+}
+// == level_bytes(lw, lh, level): each extent has halved min(level, n) times
+__host__ __device__ inline uint32_t packed_level_bytes(uint32_t k, uint32_t level) {
+  const uint32_t a = k & 0xffu, b = (k >> 8) & 0xffu, cc = (k >> 16) & 0xffu;
+  return 4u << (cc - (level < a ? level : a) - (level < b ? level : b));
+}
+// == mip_offset(lw, lh, level).  (0x2aaaaaaa >> (31 - 2 l1) is 0x55555555 >> (32 - 2 l1) for l1 >= 1 and 0 for l1 == 0.)
+__host__ __device__ inline uint32_t packed_mip_offset(uint32_t k, uint32_t level) {
+  const uint32_t a = k & 0xffu, b = (k >> 8) & 0xffu, cc = (k >> 16) & 0xffu;
+  const uint32_t l1 = level < a ? level : a, l2 = level < b ? level : b;
+  uint32_t off = (0x2aaaaaaau >> (31u - 2u * l1)) << ((cc + 4u - 2u * l1) & 31u);
+  if (level > a) off += (8u << (cc - 2u * a)) - (8u << (cc - a - l2));
+  if (level > b) off += (level - b) * TEX_TILE_BYTES;
+  return off;
+}
+
+// Range proofs of the common-case fragment stage, once per TRIANGLE (setup_triangle; DESIGN.md C10a has the derivation).
+// True: at every pixel centre the triangle covers, (i) the 1/w plane at the pixel and at its two quad partners, as
+// shade_pixel's fp32 chain computes them, lies inside rcp_fast_ok's exponent window, and (ii) |u|, |v| < 2^23.  The
+// key's common-case bit is cleared where this is false, and the specialised stage runs without either guard.
+//   q0, dq1, dq2: the record's 1/w plane; A1, B1, A2, B2: the per-pixel steps of edges 1 and 2 (exact integers);
+//   inv_area: the record's; uv: the six vertex values of u and v (any order).
+// Exactly: the plane at a covered pixel is a convex combination of q0, q0 + dq1, q0 + dq2 (both barycentrics and their
+// complement are >= 0 there), a quad partner's differs from it by the plane's signed step per pixel gx or gy (the two
+// products all but cancel across a sliver: the SIGNED sum, not a sum of magnitudes), and the fp32 chain's rounding is below
+// 2^-22 of the magnitude sum of its terms.  A binade of margin on either side of the window.  Everything here is fp32 (an
+// fp64 form cost the setup kernels eight registers and the 1080p frame 3-9 %: DESIGN.md section 5): the edge steps are
+// exact in it (integers below 2^24, times 256), the two products and their sum round to 2^-24 each of `steps`, which is
+// part of `mag`, and the allowance is 2^-19 mag — four times the chain's rounding and the bound's own together.  u = N / q is a convex combination of the vertex values once q > 0, up to the
+// rounding of N (relative to hi / lo, the spread of 1 / w); the six |u|, |v| are summed, not compared: a sum is no smaller
+// than its largest term and carries a NaN or an infinity to the comparison, which they fail like every other here.
+__host__ __device__ inline bool frag_ranges_ok(float q0, float dq1, float dq2, double A1, double B1, double A2, double B2, float inv_area,
+                                               const float (&uv)[6]) {
+  const float fa1 = (float)A1, fb1 = (float)B1, fa2 = (float)A2, fb2 = (float)B2;  // exact: integers below 2^24, times 256
+  const float gx = (fa1 * dq1 + fa2 * dq2) * inv_area, gy = (fb1 * dq1 + fb2 * dq2) * inv_area;
+  const float a1 = fa1 < 0.0f ? -fa1 : fa1, b1 = fb1 < 0.0f ? -fb1 : fb1, a2 = fa2 < 0.0f ? -fa2 : fa2, b2 = fb2 < 0.0f ? -fb2 : fb2;
+  const float steps = ((a1 > b1 ? a1 : b1) * (dq1 < 0.0f ? -dq1 : dq1) + (a2 > b2 ? a2 : b2) * (dq2 < 0.0f ? -dq2 : dq2)) * inv_area;
+  const float q1 = q0 + dq1, q2 = q0 + dq2;
+  const float lo0 = q0 < q1 ? (q0 < q2 ? q0 : q2) : (q1 < q2 ? q1 : q2), hi0 = q0 > q1 ? (q0 > q2 ? q0 : q2) : (q1 > q2 ? q1 : q2);
+  const float ax = gx < 0.0f ? -gx : gx, ay = gy < 0.0f ? -gy : gy, G = ax > ay ? ax : ay;
+  const float mag = steps + (q0 < 0.0f ? -q0 : q0) + (dq1 < 0.0f ? -dq1 : dq1) + (dq2 < 0.0f ? -dq2 : dq2);
+  const float allow = mag * 0x1p-19f + 0x1p-100f;
+  const float lo = lo0 - G - allow, hi = hi0 + G + allow;
+  float sum = 0.0f;
+  for (int i = 0; i < 6; i++) sum += uv[i] < 0.0f ? -uv[i] : uv[i];
+  return lo >= 0x1p-94f && hi <= 0x1p95f && mag <= 0x1p100f && sum * (lo + 0x1p-18f * hi) < 4194304.0f * lo;
+}
+
 // A set-up triangle, 256 bytes: first half is all the coverage/depth loop reads, second half only
 // the winners' shading reads.  Edge functions are evaluated at integer pixel indices (px,py):
 // e_i = A[i]*px + B[i]*py + C[i]  (C already carries the top-left bias); everything is an exact
@@ -158,7 +222,7 @@ struct TriRec {
   uint32_t flags;
   float z0, dz1, dz2, inv_area;
   double A[3], B[3], C[3];
-  uint32_t tex_off, tex_pad;       // the draw's TexBinding, copied in (offset 104): arena offset of level 0
+  uint32_t tex_off, tex_pad;       // the draw's TexBinding, copied in (offset 104): arena offset of level 0, tex_consts
   uint32_t tex_wh, tex_info;
   float tex_min_lod, tex_max_lod;
   // ---- shading half
@@ -385,23 +449,14 @@ __device__ __forceinline__ float rcp_ieee(float x) {
   if (__builtin_expect(!rcp_fast_ok(x), 0)) return 1.0f / x;
   return rcp_refined<SVR_RCP_VARIANT>(x);
 }
-
-// three at once (the fragment stage's 1/q at the pixel and at its two quad partners): one window test, one branch
-__device__ __forceinline__ void rcp3_ieee(float a, float b, float c, float& ra, float& rb, float& rc) {
+// rcp_ieee(x) for an x the caller knows to pass rcp_fast_ok (the common-case fragment stage: setup proved it per
+// triangle, frag_ranges_ok): the same value with no test and no branch
+__device__ __forceinline__ float rcp_in_window(float x) {
 #ifdef SVR_AB_PLAIN_DIV
-  const bool window = false;
+  return 1.0f / x;
 #else
-  const bool window = rcp_fast_ok(a) && rcp_fast_ok(b) && rcp_fast_ok(c);
+  return rcp_refined<SVR_RCP_VARIANT>(x);
 #endif
-  if (__builtin_expect(!window, 0)) {
-    ra = 1.0f / a;
-    rb = 1.0f / b;
-    rc = 1.0f / c;
-    return;
-  }
-  ra = rcp_refined<SVR_RCP_VARIANT>(a);
-  rb = rcp_refined<SVR_RCP_VARIANT>(b);
-  rc = rcp_refined<SVR_RCP_VARIANT>(c);
 }
 
 // post-vertex-shader vertex: gl_Position + 8 varying floats
@@ -538,7 +593,8 @@ __device__ __forceinline__ void store_invalid(TriRec* rec) {
 //   bit 0  the record came through the clipper: the main slot only links to the pieces
 //   bit 1  the fragment stage is the common case — mesh.frag, a LINEAR/LINEAR/MIPMAP_LINEAR sampler, an image
 //          with power-of-two extents —
-//          for which the tile kernel has a specialised instance (a wave whose pixels all carry it takes it)
+//          for which the tile kernel has a specialised instance (a wave whose pixels all carry it takes it).
+//          setup_triangle clears it again for a triangle that fails the stage's range proofs (frag_ranges_ok)
 __device__ __forceinline__ uint32_t make_key(uint32_t seq, uint32_t draw_flags, const TexBinding& tex, bool clipped) {
   bool pow2 = (tex.wh & 0xffffu) == (1u << (tex.info & 0xffu)) && (tex.wh >> 16) == (1u << ((tex.info >> 8) & 0xffu));
   bool common = ((draw_flags >> F_KIND_SHIFT) & 3u) == PIPE_MESH && (tex.info >> 24) == 7u && pow2;
@@ -610,6 +666,14 @@ __device__ inline bool setup_triangle(const FrameParams& P, const VOut* v0, cons
     }
   }
 
+  // The key's common-case bit also promises the fragment stage its operands' ranges (frag_ranges_ok): a triangle — or a
+  // clipper piece — that cannot be shown to keep them gives the bit up, in its own record only.
+  const float rw0 = s0.rw;
+  if (key & 2u) {
+    const float uv[6] = {v0->attr[6], v0->attr[7], v1->attr[6], v1->attr[7], v2->attr[6], v2->attr[7]};
+    if (!frag_ranges_ok(rw0, rw1 - rw0, rw2 - rw0, A[1], B[1], A[2], B[2], inv_area, uv)) key &= ~2u;
+  }
+
   // the record, as its sixteen 16-byte pieces (struct TriRec); the caller stores it
   uint4 h;
   h.x = ((uint32_t)(uint16_t)pminx) | ((uint32_t)(uint16_t)pminy << 16);
@@ -628,11 +692,10 @@ __device__ inline bool setup_triangle(const FrameParams& P, const VOut* v0, cons
   rec[5] = pack2(C[0], C[1]);
   {
     unsigned long long uc = (unsigned long long)__double_as_longlong(C[2]);
-    rec[6] = make_uint4((uint32_t)uc, (uint32_t)(uc >> 32), tex.base_off, 0u);
+    rec[6] = make_uint4((uint32_t)uc, (uint32_t)(uc >> 32), tex.base_off, tex.pad0);
   }
   rec[7] = make_uint4(tex.wh, tex.info, f2u(tex.min_lod), f2u(tex.max_lod));
   // shading half
-  float rw0 = s0.rw;
   float sh[32];
   sh[0] = rw0;
   sh[1] = rw1 - rw0;
