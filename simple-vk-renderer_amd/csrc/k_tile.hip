@@ -66,6 +66,10 @@ __device__ __forceinline__ float lod_from_rho2(float rho2) {
 }
 
 __device__ __forceinline__ float lerpf(float a, float b, float t) { return fmaf(t, b - a, a); }
+// x clamped into [lo, hi] for lo <= hi and x not a NaN: the value of fminf(fmaxf(x, lo), hi), in one instruction
+__device__ __forceinline__ float clamp_med3(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
+// 1.0 where the edge carries the top-left bias (flag bit F_T1 or F_T2 set), else 0.0: the bit itself, converted
+__device__ __forceinline__ double top_left_bias(uint32_t flags, uint32_t bit) { return (double)((flags / bit) & 1u); }
 
 struct TexD {
   uint32_t base_off;  // level 0 in the texel arena
@@ -80,8 +84,6 @@ struct Taps {
   float alpha, beta;
 };
 // wl, hl: the level's extent; plw: log2 of its padded width (level_lw); base: its byte offset in the arena.
-// POW2: the image's extents are powers of two (part of the COMMON case): REPEAT is a mask
-template <bool POW2 = false>
 __device__ __forceinline__ Taps level_taps(int wl, int hl, uint32_t plw, uint32_t base, bool linear, float u, float v) {
   float U = (u - floorf(u)) * (float)wl;
   float V = (v - floorf(v)) * (float)hl;
@@ -92,22 +94,35 @@ __device__ __forceinline__ Taps level_taps(int wl, int hl, uint32_t plw, uint32_
   tp.beta = linear ? Vh - fv : 0.0f;
   int i0 = (int)fu, j0 = (int)fv;
   int i1 = linear ? i0 + 1 : i0, j1 = linear ? j0 + 1 : j0;
-  if (POW2) {  // indices are in [-1, extent]: one wrap either way == the mask
-    i0 &= wl - 1;
-    i1 &= wl - 1;
-    j0 &= hl - 1;
-    j1 &= hl - 1;
-  } else {
-    if (i0 < 0) i0 += wl;
-    if (i0 >= wl) i0 -= wl;
-    if (i1 >= wl) i1 -= wl;
-    if (j0 < 0) j0 += hl;
-    if (j0 >= hl) j0 -= hl;
-    if (j1 >= hl) j1 -= hl;
-  }
+  if (i0 < 0) i0 += wl;
+  if (i0 >= wl) i0 -= wl;
+  if (i1 >= wl) i1 -= wl;
+  if (j0 < 0) j0 += hl;
+  if (j0 >= hl) j0 -= hl;
+  if (j1 >= hl) j1 -= hl;
   // tiled texels (svr_device.h texel_offset): shifts and masks once per axis, one three-operand add per tap
   const uint32_t x0 = texel_offset_x((uint32_t)i0), x1 = texel_offset_x((uint32_t)i1);
   const uint32_t y0 = base + texel_offset_y(plw, (uint32_t)j0), y1 = base + texel_offset_y(plw, (uint32_t)j1);
+  tp.o00 = y0 + x0;
+  tp.o10 = y0 + x1;
+  tp.o01 = y1 + x0;
+  tp.o11 = y1 + x1;
+  return tp;
+}
+// The COMMON case's level (LINEAR on power-of-two extents 2^kw x 2^kh): the extent is never formed.  frac * 2^k is an
+// exact scaling either way, so ldexpf gives the product's own bits (tests/test_frag_exact.py), and the REPEAT mask is k ones.
+__device__ __forceinline__ Taps level_taps_exp(int kw, int kh, uint32_t plw, uint32_t base, float u, float v) {
+  float U = ldexpf(u - floorf(u), kw);
+  float V = ldexpf(v - floorf(v), kh);
+  float Uh = U - 0.5f, Vh = V - 0.5f;
+  float fu = floorf(Uh), fv = floorf(Vh);
+  Taps tp;
+  tp.alpha = Uh - fu;
+  tp.beta = Vh - fv;
+  const int i0 = (int)fu, j0 = (int)fv;
+  const uint32_t mw = (1u << kw) - 1u, mh = (1u << kh) - 1u;  // indices are in [-1, extent]: one wrap either way == the mask
+  const uint32_t x0 = texel_offset_x((uint32_t)i0 & mw), x1 = texel_offset_x((uint32_t)(i0 + 1) & mw);
+  const uint32_t y0 = base + texel_offset_y(plw, (uint32_t)j0 & mh), y1 = base + texel_offset_y(plw, (uint32_t)(j0 + 1) & mh);
   tp.o00 = y0 + x0;
   tp.o10 = y0 + x1;
   tp.o01 = y1 + x0;
@@ -121,6 +136,42 @@ __device__ __forceinline__ uint32_t texel(const uint8_t* arena, uint32_t off) {
 }
 __device__ __forceinline__ float bilerp(uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11, int c, float a, float b) {
   return lerpf(lerpf(chan(t00, c), chan(t10, c), a), lerpf(chan(t01, c), chan(t11, c), a), b);
+}
+
+// texture(colorTex, uv).rgb of the COMMON case, between levels dhi and dlo: (base_off, tk, info) are the binding's arena
+// offset, tex_consts and lw | lh << 8 | ..  The second level only matters where delta != 0 (lerp(H, L, 0) == H exactly):
+// magnified pixels skip its four taps when no lane of the wave needs them.  Its loads are issued before anything consumes
+// the first level's texels, so both batches are in flight together — which is why the level sits in TWO branches, its
+// loads in front of the first level's bilerp and its blend behind.  (In one branch, with the first level's bilerp in both
+// arms, the compiler hoists that bilerp in front of the branch and waits for its texels before the second level's loads
+// go out: five instructions fewer and the 4K frame 1.7 % slower)
+__device__ __forceinline__ float4 common_texture(const uint8_t* tb, uint32_t base_off, uint32_t tk, uint32_t info, int dhi, int dlo,
+                                                 float delta, float u, float v) {
+  // level d of a 2^lw x 2^lh image is 2^max(lw - d, 0) x 2^max(lh - d, 0): exponents, never extents (level_taps_exp)
+  const uint32_t lw = info & 0xffu, lh = (info >> 8) & 0xffu;
+  auto kexp = [](uint32_t l, int d) { return (int)__builtin_elementwise_sub_sat(l, (uint32_t)d); };
+  const uint32_t bhi = base_off + packed_mip_offset(tk, (uint32_t)dhi);
+  const Taps th = level_taps_exp(kexp(lw, dhi), kexp(lh, dhi), packed_level_lw(info, (uint32_t)dhi), bhi, u, v);
+  const uint32_t h00 = texel(tb, th.o00), h10 = texel(tb, th.o10), h01 = texel(tb, th.o01), h11 = texel(tb, th.o11);
+  float4 tx;
+  tx.w = 1.0f;
+  const bool two_levels = __any(delta != 0.0f);
+  Taps tl = th;
+  uint32_t l00 = 0, l10 = 0, l01 = 0, l11 = 0;
+  if (two_levels) {
+    const uint32_t blo = dlo != dhi ? bhi + packed_level_bytes(tk, (uint32_t)dhi) : bhi;  // the next level starts one padded level further on
+    tl = level_taps_exp(kexp(lw, dlo), kexp(lh, dlo), packed_level_lw(info, (uint32_t)dlo), blo, u, v);
+    l00 = texel(tb, tl.o00), l10 = texel(tb, tl.o10), l01 = texel(tb, tl.o01), l11 = texel(tb, tl.o11);
+  }
+  tx.x = bilerp(h00, h10, h01, h11, 0, th.alpha, th.beta);
+  tx.y = bilerp(h00, h10, h01, h11, 1, th.alpha, th.beta);
+  tx.z = bilerp(h00, h10, h01, h11, 2, th.alpha, th.beta);
+  if (two_levels) {
+    tx.x = lerpf(tx.x, bilerp(l00, l10, l01, l11, 0, tl.alpha, tl.beta), delta);
+    tx.y = lerpf(tx.y, bilerp(l00, l10, l01, l11, 1, tl.alpha, tl.beta), delta);
+    tx.z = lerpf(tx.z, bilerp(l00, l10, l01, l11, 2, tl.alpha, tl.beta), delta);
+  }
+  return tx;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -167,8 +218,8 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   double C1 = c5.y, C2 = c6.x;
   A1 = c2.y; B1 = c4.x; A2 = c3.x; B2 = c4.y;
   double dx = (double)px, dy = (double)py;
-  e1 = fma(A1, dx, fma(B1, dy, C1)) + ((flags & F_T1) ? 1.0 : 0.0);
-  e2 = fma(A2, dx, fma(B2, dy, C2)) + ((flags & F_T2) ? 1.0 : 0.0);
+  e1 = fma(A1, dx, fma(B1, dy, C1)) + top_left_bias(flags, F_T1);
+  e2 = fma(A2, dx, fma(B2, dy, C2)) + top_left_bias(flags, F_T2);
   TexD t;
   t.base_off = (uint32_t)(unsigned long long)__double_as_longlong(c6.y);
   const uint32_t tk = (uint32_t)((unsigned long long)__double_as_longlong(c6.y) >> 32);  // tex_consts (svr_device.h): COMMON reads its levels out of these bytes
@@ -187,9 +238,16 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   float hb1 = 0.0f, hb2 = 0.0f, vb1 = 0.0f, vb2 = 0.0f, hq = 1.0f, vq = 1.0f, hr = 0.0f, vr = 0.0f;
   // the quad partners' barycentrics and 1/w by the pixel's own chain, one edge step away
   auto partners = [&]() {
-    double sxp = (px & 1) ? -1.0 : 1.0, syp = (py & 1) ? -1.0 : 1.0;
-    hb1 = (float)fma(sxp, A1, e1) * inv_area, hb2 = (float)fma(sxp, A2, e2) * inv_area;
-    vb1 = (float)fma(syp, B1, e1) * inv_area, vb2 = (float)fma(syp, B2, e2) * inv_area;
+    if (COMMON) {  // e +- A is fma(+-1, A, e)'s exactly rounded value: the parity goes into the step's sign bit
+      const int sx = (int)((uint32_t)px << 31), sy = (int)((uint32_t)py << 31);
+      auto flip = [](double a, int s) { return __hiloint2double(__double2hiint(a) ^ s, __double2loint(a)); };
+      hb1 = (float)(e1 + flip(A1, sx)) * inv_area, hb2 = (float)(e2 + flip(A2, sx)) * inv_area;
+      vb1 = (float)(e1 + flip(B1, sy)) * inv_area, vb2 = (float)(e2 + flip(B2, sy)) * inv_area;
+    } else {
+      double sxp = (px & 1) ? -1.0 : 1.0, syp = (py & 1) ? -1.0 : 1.0;
+      hb1 = (float)fma(sxp, A1, e1) * inv_area, hb2 = (float)fma(sxp, A2, e2) * inv_area;
+      vb1 = (float)fma(syp, B1, e1) * inv_area, vb2 = (float)fma(syp, B2, e2) * inv_area;
+    }
     hq = fmaf(hb2, dq2, fmaf(hb1, dq1, q0)), vq = fmaf(vb2, dq2, fmaf(vb1, dq1, q0));
   };
   if (!COMMON && !quads) partners();  // (the generic stage keeps the order it was compiled in: its instances' code stays)
@@ -221,21 +279,24 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
     uh = interp3(s2.y, s4.y, s6.y, hb1, hb2, hr), vh = interp3(s2.z, s4.z, s6.z, hb1, hb2, hr);
     uv_ = interp3(s2.y, s4.y, s6.y, vb1, vb2, vr), vv_ = interp3(s2.z, s4.z, s6.z, vb1, vb2, vr);
   }
-  float dudx = (px & 1) ? (u - uh) : (uh - u);
-  float dvdx = (px & 1) ? (v - vh) : (vh - v);
-  float dudy = (py & 1) ? (u - uv_) : (uv_ - u);
-  float dvdy = (py & 1) ? (v - vv_) : (vv_ - v);
+  // COMMON: the derivatives reach only rho2, through squares: u - uh is -(uh - u) exactly, so the parity selects are not made
+  float dudx = (COMMON || !(px & 1)) ? (uh - u) : (u - uh);
+  float dvdx = (COMMON || !(px & 1)) ? (vh - v) : (v - vh);
+  float dudy = (COMMON || !(py & 1)) ? (uv_ - u) : (u - uv_);
+  float dvdy = (COMMON || !(py & 1)) ? (vv_ - v) : (v - vv_);
   // ---- texture(colorTex, uv): implicit LOD, then one unified 2-level x 4-tap footprint
+  // COMMON: the extents are 2^lw x 2^lh, and a product with a power of two is ldexpf's value (the same exact value, rounded once)
   float W0 = (float)t.w, H0 = (float)t.h;
-  float mx = dudx * W0, my = dvdx * H0;
-  float nx_ = dudy * W0, ny_ = dvdy * H0;
+  float mx = COMMON ? ldexpf(dudx, (int)t.lw) : dudx * W0, my = COMMON ? ldexpf(dvdx, (int)t.lh) : dvdx * H0;
+  float nx_ = COMMON ? ldexpf(dudy, (int)t.lw) : dudy * W0, ny_ = COMMON ? ldexpf(dvdy, (int)t.lh) : dvdy * H0;
   float rho2 = fmaxf(fmaf(mx, mx, my * my), fmaf(nx_, nx_, ny_ * ny_));
-  float lambda = fminf(fmaxf(lod_from_rho2(rho2), t.min_lod), t.max_lod);
+  // (lod_from_rho2 returns no NaN and a binding's min_lod <= max_lod, svr_api.hip make_binding: the chain is a median)
+  float lambda = COMMON ? clamp_med3(lod_from_rho2(rho2), t.min_lod, t.max_lod) : fminf(fmaxf(lod_from_rho2(rho2), t.min_lod), t.max_lod);
   const bool linear = COMMON ? true : (((lambda <= 0.0f) ? (t.filters & 1u) : ((t.filters >> 1) & 1u)) != 0u);
   int q = COMMON ? (int)(tk >> 24) : (int)t.levels - 1;
   const bool mip_linear = COMMON ? true : (((t.filters >> 2) & 1u) != 0u);
   int dn = min(max((int)ceilf(lambda + 0.5f) - 1, 0), q);
-  float lc = fminf(fmaxf(lambda, 0.0f), (float)q);
+  float lc = COMMON ? clamp_med3(lambda, 0.0f, (float)q) : fminf(fmaxf(lambda, 0.0f), (float)q);
   float fl = floorf(lc);
   int dhi = mip_linear ? (int)fl : dn;
   float delta = mip_linear ? lc - fl : 0.0f;
@@ -244,49 +305,53 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   // level extents and arena offsets.  The layout pads every level to powers of two and whole tiles (svr_device.h
   // mip_offset), so the next level starts one padded level further on: no second evaluation of the closed form.
   // COMMON: the same figures from the texture's constants, computed once per texture (svr_device.h tex_consts)
-  const int whi = (int)max(t.w >> dhi, 1u), hhi = (int)max(t.h >> dhi, 1u);
-  const uint32_t bhi = t.base_off + (COMMON ? packed_mip_offset(tk, (uint32_t)dhi) : mip_offset(t.lw, t.lh, (uint32_t)dhi));
-  const uint32_t plw_hi = COMMON ? packed_level_lw(td.y, (uint32_t)dhi) : level_lw(t.lw, (uint32_t)dhi);
-  Taps th = level_taps<COMMON>(whi, hhi, plw_hi, bhi, linear, us, vs);
-  const uint8_t* tb = P.tex_arena;
-  uint32_t h00 = texel(tb, th.o00), h10 = texel(tb, th.o10), h01 = texel(tb, th.o01), h11 = texel(tb, th.o11);
-  // The second level only matters where delta != 0 (lerp(H, L, 0) == H exactly): magnified and
-  // NEAREST-mip pixels skip its four taps when no lane of the wave needs them.  Its loads are issued
-  // before anything consumes the first level's texels, so both batches are in flight together.
-  const bool two_levels = __any(delta != 0.0f);
-  Taps tl = th;
-  uint32_t l00 = 0, l10 = 0, l01 = 0, l11 = 0;
-  if (two_levels) {
-    const int wlo = (int)max(t.w >> dlo, 1u), hlo = (int)max(t.h >> dlo, 1u);
-    const uint32_t step = COMMON ? packed_level_bytes(tk, (uint32_t)dhi) : level_bytes(t.lw, t.lh, (uint32_t)dhi);  // padded bytes of level dhi
-    const uint32_t blo = dlo != dhi ? bhi + step : bhi;
-    const uint32_t plw_lo = COMMON ? packed_level_lw(td.y, (uint32_t)dlo) : level_lw(t.lw, (uint32_t)dlo);
-    tl = level_taps<COMMON>(wlo, hlo, plw_lo, blo, linear, us, vs);
-    l00 = texel(tb, tl.o00);
-    l10 = texel(tb, tl.o10);
-    l01 = texel(tb, tl.o01);
-    l11 = texel(tb, tl.o11);
-  }
   float4 tx;
-  tx.x = bilerp(h00, h10, h01, h11, 0, th.alpha, th.beta);
-  tx.y = bilerp(h00, h10, h01, h11, 1, th.alpha, th.beta);
-  tx.z = bilerp(h00, h10, h01, h11, 2, th.alpha, th.beta);
-  tx.w = 1.0f;
-  if (two_levels) {
-    tx.x = lerpf(tx.x, bilerp(l00, l10, l01, l11, 0, tl.alpha, tl.beta), delta);
-    tx.y = lerpf(tx.y, bilerp(l00, l10, l01, l11, 1, tl.alpha, tl.beta), delta);
-    tx.z = lerpf(tx.z, bilerp(l00, l10, l01, l11, 2, tl.alpha, tl.beta), delta);
-  }
-  if (TRACE) {  // slots shared with the oracle's trace (tests/tools only)
-    trace[0] = (float)(hdr.z >> 2); trace[1] = b1; trace[2] = b2; trace[3] = r; trace[4] = u; trace[5] = v;
-    trace[6] = dudx; trace[7] = dvdx; trace[8] = dudy; trace[9] = dvdy; trace[10] = lambda;
-    trace[11] = tx.x; trace[12] = tx.y; trace[13] = tx.z;
-    trace[26] = hb1; trace[27] = hb2; trace[28] = vb1; trace[29] = vb2; trace[30] = hr; trace[31] = vr;
-  }
-  if (kind == PIPE_TEX_IMAGE) {  // shaders/tex_image.frag:10-12 — the only consumer of texture alpha
-    tx.w = bilerp(h00, h10, h01, h11, 3, th.alpha, th.beta);
-    if (two_levels) tx.w = lerpf(tx.w, bilerp(l00, l10, l01, l11, 3, tl.alpha, tl.beta), delta);
-    return tx;
+  if constexpr (COMMON) {
+    tx = common_texture(P.tex_arena, t.base_off, tk, td.y, dhi, dlo, delta, us, vs);
+  } else {
+    const int whi = (int)max(t.w >> dhi, 1u), hhi = (int)max(t.h >> dhi, 1u);
+    const uint32_t bhi = t.base_off + mip_offset(t.lw, t.lh, (uint32_t)dhi);
+    const uint32_t plw_hi = level_lw(t.lw, (uint32_t)dhi);
+    Taps th = level_taps(whi, hhi, plw_hi, bhi, linear, us, vs);
+    const uint8_t* tb = P.tex_arena;
+    uint32_t h00 = texel(tb, th.o00), h10 = texel(tb, th.o10), h01 = texel(tb, th.o01), h11 = texel(tb, th.o11);
+    // The second level only matters where delta != 0 (lerp(H, L, 0) == H exactly): magnified and
+    // NEAREST-mip pixels skip its four taps when no lane of the wave needs them.  Its loads are issued
+    // before anything consumes the first level's texels, so both batches are in flight together.
+    const bool two_levels = __any(delta != 0.0f);
+    Taps tl = th;
+    uint32_t l00 = 0, l10 = 0, l01 = 0, l11 = 0;
+    if (two_levels) {
+      const int wlo = (int)max(t.w >> dlo, 1u), hlo = (int)max(t.h >> dlo, 1u);
+      const uint32_t step = level_bytes(t.lw, t.lh, (uint32_t)dhi);  // padded bytes of level dhi
+      const uint32_t blo = dlo != dhi ? bhi + step : bhi;
+      const uint32_t plw_lo = level_lw(t.lw, (uint32_t)dlo);
+      tl = level_taps(wlo, hlo, plw_lo, blo, linear, us, vs);
+      l00 = texel(tb, tl.o00);
+      l10 = texel(tb, tl.o10);
+      l01 = texel(tb, tl.o01);
+      l11 = texel(tb, tl.o11);
+    }
+    tx.x = bilerp(h00, h10, h01, h11, 0, th.alpha, th.beta);
+    tx.y = bilerp(h00, h10, h01, h11, 1, th.alpha, th.beta);
+    tx.z = bilerp(h00, h10, h01, h11, 2, th.alpha, th.beta);
+    tx.w = 1.0f;
+    if (two_levels) {
+      tx.x = lerpf(tx.x, bilerp(l00, l10, l01, l11, 0, tl.alpha, tl.beta), delta);
+      tx.y = lerpf(tx.y, bilerp(l00, l10, l01, l11, 1, tl.alpha, tl.beta), delta);
+      tx.z = lerpf(tx.z, bilerp(l00, l10, l01, l11, 2, tl.alpha, tl.beta), delta);
+    }
+    if (TRACE) {  // slots shared with the oracle's trace (tests/tools only)
+      trace[0] = (float)(hdr.z >> 2); trace[1] = b1; trace[2] = b2; trace[3] = r; trace[4] = u; trace[5] = v;
+      trace[6] = dudx; trace[7] = dvdx; trace[8] = dudy; trace[9] = dvdy; trace[10] = lambda;
+      trace[11] = tx.x; trace[12] = tx.y; trace[13] = tx.z;
+      trace[26] = hb1; trace[27] = hb2; trace[28] = vb1; trace[29] = vb2; trace[30] = hr; trace[31] = vr;
+    }
+    if (kind == PIPE_TEX_IMAGE) {  // shaders/tex_image.frag:10-12 — the only consumer of texture alpha
+      tx.w = bilerp(h00, h10, h01, h11, 3, th.alpha, th.beta);
+      if (two_levels) tx.w = lerpf(tx.w, bilerp(l00, l10, l01, l11, 3, tl.alpha, tl.beta), delta);
+      return tx;
+    }
   }
   // shaders/mesh.frag:12-19
   float nx = interp3(s0.w, s2.w, s4.w, b1, b2, r);
@@ -527,7 +592,7 @@ __device__ __forceinline__ void scan_columns(const FrameParams& P, uint4* s_cov,
       const double2* d = reinterpret_cast<const double2*>(rec);
       double2 c2 = d[2], c3 = d[3], c4 = d[4], c5 = d[5], c6 = d[6];
       double B0 = c3.y, B1 = c4.x, B2 = c4.y;
-      double u1 = (flags & F_T1) ? 1.0 : 0.0, u2 = (flags & F_T2) ? 1.0 : 0.0;
+      double u1 = top_left_bias(flags, F_T1), u2 = top_left_bias(flags, F_T2);
       double dx = (double)col, dy = (double)y0;
       double f0 = fma(c2.x, dx, fma(B0, dy, c5.x));
       double f1 = fma(c2.y, dx, fma(B1, dy, c5.y));
@@ -769,7 +834,7 @@ __device__ __forceinline__ void scan_columns_ordered(const FrameParams& P, uint4
         // holding the two 1.0 / 0.0 in registers across walk and flush cost four VGPRs and an add per row
         // (walking edges 1 and 2 unbiased, with "g > 0" / "g >= 0" picked per lane, saves the two adds and four
         // registers below but pays more in the compares' mask logic: +4 % on the curtain tiles)
-        const double u1 = (flags & F_T1) ? 1.0 : 0.0, u2 = (flags & F_T2) ? 1.0 : 0.0;
+        const double u1 = top_left_bias(flags, F_T1), u2 = top_left_bias(flags, F_T2);
         double g1 = fma(c2.y, dx, fma(B1, dy, c5.y));
         double g2 = fma(c3.x, dx, fma(B2, dy, c6.x));
 #pragma unroll 1

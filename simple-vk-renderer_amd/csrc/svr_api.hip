@@ -66,7 +66,7 @@ TexBinding make_binding(const ImageRes& im, const SvrSamplerDesc& s) {
   tb.pad0 = tex_consts(im.lw, im.lh, im.levels);
   tb.wh = im.w | (im.h << 16);
   tb.info = im.lw | (im.lh << 8) | (im.levels << 16) | (filters << 24);
-  tb.min_lod = s.min_lod;
+  tb.min_lod = binding_min_lod(s.min_lod, s.max_lod);  // min_lod <= max_lod from here on: the fragment stage's median relies on it
   tb.max_lod = s.max_lod;
   return tb;
 }

@@ -178,6 +178,11 @@ __host__ __device__ inline uint32_t packed_mip_offset(uint32_t k, uint32_t level
   return off;
 }
 
+// The lower LOD clamp a binding carries (the host's make_binding).  The common-case fragment stage clamps with a median,
+// which is fminf(fmaxf(lod, lo), hi) only for lo <= hi.  For lo > hi that chain gives hi whatever lod is, and so does either
+// form with lo = hi.  (svr_create_sampler admits no such pair: this is the guarantee stated where the pair is made.)
+__host__ __device__ inline float binding_min_lod(float lo, float hi) { return lo <= hi ? lo : hi; }
+
 // Range proofs of the common-case fragment stage, once per TRIANGLE (setup_triangle; DESIGN.md C10a has the derivation).
 // True: at every pixel centre the triangle covers, (i) the 1/w plane at the pixel and at its two quad partners, as
 // shade_pixel's fp32 chain computes them, lies inside rcp_fast_ok's exponent window, and (ii) |u|, |v| < 2^23.  The

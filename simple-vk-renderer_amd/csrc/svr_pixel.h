@@ -36,11 +36,14 @@ struct Codec;
 template <>
 struct Codec<SVR_COLOR_RGBA16F> {
   typedef uint2 enc_t;
-  static __device__ __forceinline__ enc_t encode(float4 c) {  // four pins, then four conversions
+  // four pins, then the four round-to-nearest-even conversions as the two pairs the words hold, (r, g) and (b, a): a
+  // packed conversion leaves each word as it is stored, nothing is shifted or ORed together afterwards
+  static __device__ __forceinline__ enc_t encode(float4 c) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     c.x = pin(c.x); c.y = pin(c.y); c.z = pin(c.z); c.w = pin(c.w);
-    uint32_t r = __half_as_ushort(__float2half_rn(c.x)), g = __half_as_ushort(__float2half_rn(c.y));
-    uint32_t b = __half_as_ushort(__float2half_rn(c.z)), a = __half_as_ushort(__float2half_rn(c.w));
-    return make_uint2(r | (g << 16), b | (a << 16));
+    const f16x2 rg = __builtin_convertvector((f32x2){c.x, c.y}, f16x2), ba = __builtin_convertvector((f32x2){c.z, c.w}, f16x2);
+    return make_uint2(__builtin_bit_cast(uint32_t, rg), __builtin_bit_cast(uint32_t, ba));
   }
   static __device__ __forceinline__ float4 decode(enc_t e) {
     return make_float4(half_bits_to_float(e.x & 0xffffu), half_bits_to_float(e.x >> 16), half_bits_to_float(e.y & 0xffffu),
