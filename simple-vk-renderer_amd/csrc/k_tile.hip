@@ -33,6 +33,7 @@
 
 #include "svr_launch.h"
 #include "svr_pixel.h"
+#include "svr_span.h"
 
 namespace svr {
 
@@ -381,7 +382,8 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
 // Phase A, column scan.  A heavy bin is mostly slivers (a distant column's quads are ~3 x 26 pixels)
 // and a whole-wave pass per triangle leaves 95 % of the lanes idle on them.  Instead every triangle of
 // a staged batch is expanded into one work item per pixel column of its tile-clamped bbox (wave prefix
-// sum over the 64 column counts); one lane takes one item, walks its rows and resolves visibility with
+// sum over the 64 column counts); one lane takes one item, walks its covered rows (one interval, found once per item:
+// svr_span.h) and resolves visibility with
 // one LDS ds_max_u64 per covered pixel on a (depth bits << 32 | key) tile.  Lanes are busy whatever
 // the triangle shapes are; the four waves take alternate chunks of 64 items.  max over (depth, key)
 // is what in-order GREATER_OR_EQUAL with depth write leaves behind, so no order is needed.  The
@@ -597,19 +599,24 @@ __device__ __forceinline__ void scan_columns(const FrameParams& P, uint4* s_cov,
       double f0 = fma(c2.x, dx, fma(B0, dy, c5.x));
       double f1 = fma(c2.y, dx, fma(B1, dy, c5.y));
       double f2 = fma(c3.x, dx, fma(B2, dy, c6.x));
-      unsigned long long* cell = s_depth + (y0 - ty0) * TILE + (col - tx0);
-      for (int y = y0; y <= y1; y++) {
-        if (f0 >= 0.0 && f1 >= 0.0 && f2 >= 0.0) {
-          if (INSTR) n_raster++;
-          float b1 = (float)(f1 + u1) * zr.w, b2 = (float)(f2 + u2) * zr.w;
-          float z = fmaf(b2, zr.z, fmaf(b1, zr.y, zr.x));
-          z = fminf(fmaxf(z, 0.0f), 1.0f) + 0.0f;
-          if (INSTR && (flags >> 31) && f2u(z) >= (uint32_t)(*cell >> 32)) n_hiz_bad++;  // (cells only grow: no false alarm)
-          atomicMax(cell, ((unsigned long long)f2u(z) << 32) | key);
-        }
-        f0 += B0;  // exact: integers below 2^53
-        f1 += B1;
-        f2 += B2;
+      // The rows of the column on which all three edges are >= 0 are one interval (the triangle is convex), found once
+      // and exactly (svr_span.h) instead of by three compares on every row of the box: an item that covers nothing -- two
+      // in five -- ends here, and the others walk their covered rows only, without edge 0 and without a compare.
+      int k0, kn;
+      svr_span::column_span(f0, f1, f2, B0, B1, B2, y1 - y0 + 1, k0, kn);
+      if (kn == 0) continue;
+      if (INSTR) n_raster += (uint32_t)kn;
+      const double dk = (double)k0;
+      double g1 = fma(B1, dk, f1) + u1, g2 = fma(B2, dk, f2) + u2;  // unbiased at the span's first row (exact: integers below 2^53)
+      unsigned long long* cell = s_depth + (y0 + k0 - ty0) * TILE + (col - tx0);
+      for (; kn > 0; kn--) {
+        float b1 = (float)g1 * zr.w, b2 = (float)g2 * zr.w;
+        float z = fmaf(b2, zr.z, fmaf(b1, zr.y, zr.x));
+        z = fminf(fmaxf(z, 0.0f), 1.0f) + 0.0f;
+        if (INSTR && (flags >> 31) && f2u(z) >= (uint32_t)(*cell >> 32)) n_hiz_bad++;  // (cells only grow: no false alarm)
+        atomicMax(cell, ((unsigned long long)f2u(z) << 32) | key);
+        g1 += B1;  // exact: integers below 2^53
+        g2 += B2;
         cell += TILE;
       }
     }
