@@ -39,7 +39,10 @@
  * Out of scope
  *   - Multiview layers, RGBA8 targets, interleaved row ownership.
  *   - The sharded frame (svr_dist.h): a band rank blooms its own rows only, so the bloom has seams at band edges.
- *   - An sRGB or gamma transfer (the swapchain formats are UNORM), auto-exposure.
+ *   - An sRGB or gamma transfer (the swapchain formats are UNORM).
+ *
+ * Auto-exposure is include/svr_exposure.h: under svr_set_post_auto_exposure this pass multiplies `exposure` by the exposure
+ * metered on the device (e = exposure * state.exposure, one fp32 multiply), and `exposure` acts as a compensation.
  *
  * HIP library only: the CPU oracle has no post pass.
  */

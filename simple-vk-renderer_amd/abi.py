@@ -121,6 +121,10 @@ AMBIENT_SYMBOLS = ["svr_ambient_pass", "svr_bind_ambient_target", "svr_get_ambie
                    "svr_set_light_ambient_occlusion", "svr_debug_read_ambient_raw"]
 AMBIENT_NO_BLUR = 1
 AMBIENT_MAX_REACH, AMBIENT_TAPS = 16, 8
+# include/svr_exposure.h: auto-exposure (a luminance histogram and an adapted exposure in device memory), HIP library only
+EXPOSURE_SYMBOLS = ["svr_meter_exposure", "svr_reset_exposure", "svr_set_post_auto_exposure", "svr_read_exposure",
+                    "svr_debug_read_exposure_histogram", "svr_get_exposure_state"]
+EXPOSURE_BINS = 256
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -155,6 +159,16 @@ class SvrTemporalPass(C.Structure):  # include/svr_temporal.h
 class SvrAmbientPass(C.Structure):  # include/svr_ambient.h
     _fields_ = [("inv_viewproj", C.c_float * 16), ("radius", C.c_float), ("pixels_per_unit", C.c_float), ("bias", C.c_float),
                 ("intensity", C.c_float), ("sharpness", C.c_float), ("flags", C.c_uint32)]
+
+
+class SvrExposureMeter(C.Structure):  # include/svr_exposure.h
+    _fields_ = [("key", C.c_float), ("low_fraction", C.c_float), ("high_fraction", C.c_float), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("adapt", C.c_float)]
+
+
+class SvrExposureState(C.Structure):  # include/svr_exposure.h
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("mean_log2", C.c_float), ("counted", C.c_uint32),
+                ("black", C.c_uint32), ("meters", C.c_uint32)]
 
 
 POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("intensity", "<f4")])
@@ -283,6 +297,14 @@ class SvrLib:
             L.svr_read_ambient.argtypes = [P, P, C.c_size_t]
             L.svr_set_light_ambient_occlusion.argtypes = [P, C.c_int]
             L.svr_debug_read_ambient_raw.argtypes = [P, P, C.c_size_t]
+        self.has_exposure = hasattr(L, "svr_meter_exposure")
+        if self.has_exposure:
+            L.svr_meter_exposure.argtypes = [P, C.POINTER(SvrExposureMeter)]
+            L.svr_reset_exposure.argtypes = [P]
+            L.svr_set_post_auto_exposure.argtypes = [P, C.c_int]
+            L.svr_read_exposure.argtypes = [P, C.POINTER(SvrExposureState)]
+            L.svr_debug_read_exposure_histogram.argtypes = [P, P, C.c_size_t]
+            L.svr_get_exposure_state.argtypes = [P, C.POINTER(P)]
         self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
         if self.has_depth_load:
             L.svr_set_depth_load_op.argtypes = [P, C.c_int]
@@ -881,6 +903,49 @@ class Renderer:
         """later light_pass calls scale their ambient term by the ambient target current at their enqueue"""
         self._need_ambient()
         self.lib.check(self.lib.lib.svr_set_light_ambient_occlusion(self.h, 1 if on else 0))
+
+    # ---- auto-exposure (include/svr_exposure.h)
+    def _need_exposure(self):
+        if not getattr(self.lib, "has_exposure", False):
+            raise SvrError(-5, f"{self.lib.backend} has no auto-exposure (include/svr_exposure.h)")
+
+    def meter_exposure(self, key=0.18, low_fraction=0.0, high_fraction=1.0, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10, adapt=1.0):
+        """svr_meter_exposure: histogram the luminance of the scissor's pixels of the RGBA16F colour target and move the
+        device-resident exposure towards key / (the geometric mean of the pixels between the two fractions)"""
+        self._need_exposure()
+        m = SvrExposureMeter(float(key), float(low_fraction), float(high_fraction), float(min_exposure), float(max_exposure), float(adapt))
+        self.lib.check(self.lib.lib.svr_meter_exposure(self.h, C.byref(m)))
+
+    def reset_exposure(self):
+        """svr_reset_exposure: the next accepted meter snaps, whatever its adapt"""
+        self._need_exposure()
+        self.lib.check(self.lib.lib.svr_reset_exposure(self.h))
+
+    def set_post_auto_exposure(self, on=True):
+        """later post_pass calls use their exposure times the state's, read on the device"""
+        self._need_exposure()
+        self.lib.check(self.lib.lib.svr_set_post_auto_exposure(self.h, 1 if on else 0))
+
+    def read_exposure(self):
+        """svr_read_exposure -> SvrExposureState behind everything enqueued so far (fences)"""
+        self._need_exposure()
+        st = SvrExposureState()
+        self.lib.check(self.lib.lib.svr_read_exposure(self.h, C.byref(st)))
+        return st
+
+    def read_exposure_histogram(self):
+        """svr_debug_read_exposure_histogram -> uint32 [EXPOSURE_BINS]: the last applied meter's bins (fences)"""
+        self._need_exposure()
+        out = np.zeros(EXPOSURE_BINS, dtype=np.uint32)
+        self.lib.check(self.lib.lib.svr_debug_read_exposure_histogram(self.h, out.ctypes.data, out.nbytes))
+        return out
+
+    def exposure_state_ptr(self):
+        """svr_get_exposure_state: the device address of the SvrExposureState, stable for the context's life"""
+        self._need_exposure()
+        p = C.c_void_p()
+        self.lib.check(self.lib.lib.svr_get_exposure_state(self.h, C.byref(p)))
+        return p.value
 
     # ---- the depth loadOp (include/svr_load.h)
     def _need_depth_load(self):

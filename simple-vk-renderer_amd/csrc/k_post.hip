@@ -10,6 +10,8 @@
 //   bloom_up_kernel             U_i in place over B_i: a lane reads its own texel and the four taps of U_{i+1}.
 //   post_composite_kernel<OP>   two pixels (16 bytes in, 16 bytes out) per lane where the address allows, else one at a
 //                               time; the taps of U_0 are re-reads of the half-resolution level, served by the caches.
+// Under svr_set_post_auto_exposure (include/svr_exposure.h) the two kernels that use the exposure run as the instances
+// that multiply it by the state's exposure, read through a pointer; the others' machine code is the parent's.
 // Staged texels are fetched at clamped coordinates, so the LDS arrays hold the edge-clamped image and no tap needs a test.
 // Ordinary vector loads and stores only; nothing is handed between workgroups of one launch.  Every kernel reads the
 // context's poison flag first: after an overflow it writes nothing.
@@ -80,9 +82,15 @@ __device__ __forceinline__ float box(float a00, float a10, float a01, float a11,
   return FIRST ? san(v * exposure - threshold) : v;
 }
 
-template <bool FIRST>
-__global__ __launch_bounds__(256) void bloom_level_kernel(LevelArgs A) {
+// State: nothing, or, under svr_set_post_auto_exposure, one `const float*` to the state's exposure (include/svr_exposure.h):
+// e = pass.exposure * state.exposure then stands for the exposure.  The state is read behind the poison flag, like
+// everything else.  (One kernel with its body in place: the instances without a state are the parent's machine code, which a
+// body shared through an inlined function was not, by the operand order of four multiplies.)
+template <bool FIRST, class... State>
+__global__ __launch_bounds__(256) void bloom_level_kernel(LevelArgs A, State... state) {
   if (*A.poison) return;
+  float exposure = A.exposure;
+  if constexpr (sizeof...(State) != 0) exposure = exposure * *(state, ...);
   __shared__ float s_d[3][PS][PS];  // D_i at clamped coordinates
   __shared__ float s_h[3][PS][PT];  // its horizontal blur
   const uint32_t t = threadIdx.x;
@@ -96,9 +104,9 @@ __global__ __launch_bounds__(256) void bloom_level_kernel(LevelArgs A) {
     load_pair(A.src + (size_t)y0 * A.src_pitch, x0, x1, q00, q10);
     load_pair(A.src + (size_t)y1 * A.src_pitch, x0, x1, q01, q11);
     const Rgb a = decode(q00), b = decode(q10), cc = decode(q01), d = decode(q11);
-    s_d[0][r][c] = box<FIRST>(a.r, b.r, cc.r, d.r, A.exposure, A.threshold);
-    s_d[1][r][c] = box<FIRST>(a.g, b.g, cc.g, d.g, A.exposure, A.threshold);
-    s_d[2][r][c] = box<FIRST>(a.b, b.b, cc.b, d.b, A.exposure, A.threshold);
+    s_d[0][r][c] = box<FIRST>(a.r, b.r, cc.r, d.r, exposure, A.threshold);
+    s_d[1][r][c] = box<FIRST>(a.g, b.g, cc.g, d.g, exposure, A.threshold);
+    s_d[2][r][c] = box<FIRST>(a.b, b.b, cc.b, d.b, exposure, A.threshold);
   }
   __syncthreads();
 
@@ -194,9 +202,9 @@ __device__ __forceinline__ uint2 composite_pixel(const CompositeArgs& A, uint2 t
   return make_uint2(h16(r) | (h16(g) << 16), h16(b) | (texel.y & 0xffff0000u));  // the alpha half as it was
 }
 
+// the body of post_composite_kernel<OP> and of post_composite_auto_kernel<OP>
 template <int OP>
-__global__ __launch_bounds__(256) void post_composite_kernel(CompositeArgs A) {
-  if (*A.poison) return;
+__device__ __forceinline__ void post_composite(const CompositeArgs& A) {
   const uint32_t x = (blockIdx.x * 64u + (threadIdx.x & 63u)) * 2u, y = blockIdx.y * 4u + (threadIdx.x >> 6);
   if (x >= A.sw || y >= A.sh) return;
   uint2* at = A.color + (size_t)y * A.pitch + x;
@@ -208,6 +216,20 @@ __global__ __launch_bounds__(256) void post_composite_kernel(CompositeArgs A) {
     at[0] = composite_pixel<OP>(A, at[0], x, y);
     if (x + 1u < A.sw) at[1] = composite_pixel<OP>(A, at[1], x + 1u, y);
   }
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void post_composite_kernel(CompositeArgs A) {
+  if (*A.poison) return;
+  post_composite<OP>(A);
+}
+
+// post_composite_kernel<OP> under svr_set_post_auto_exposure: e in the exposure's place, as in bloom_level_kernel<true, const float*>
+template <int OP>
+__global__ __launch_bounds__(256) void post_composite_auto_kernel(CompositeArgs A, const float* state_exposure) {
+  if (*A.poison) return;
+  A.exposure = A.exposure * *state_exposure;
+  post_composite<OP>(A);
 }
 
 size_t post_level_layout(uint32_t sw, uint32_t sh, uint32_t n_levels, uint32_t* off, uint32_t* lw, uint32_t* lh) {
@@ -242,7 +264,10 @@ void launch_post(const PostLaunch& P, hipStream_t s) {
       A.src_pitch = P.W;
       A.ws = P.sw;
       A.hs = P.sh;
-      hipLaunchKernelGGL(bloom_level_kernel<true>, grid, block, 0, s, A);
+      if (P.auto_exposure)
+        hipLaunchKernelGGL(bloom_level_kernel<true>, grid, block, 0, s, A, P.auto_exposure);
+      else
+        hipLaunchKernelGGL(bloom_level_kernel<true>, grid, block, 0, s, A);
     } else {
       A.src = P.levels + P.off[i - 1u];
       A.src_pitch = A.ws = P.lw[i - 1u];
@@ -276,7 +301,14 @@ void launch_post(const PostLaunch& P, hipStream_t s) {
   C.intensity = P.intensity;
   C.poison = P.poison;
   const dim3 grid(((P.sw + 1u) / 2u + 63u) / 64u, (P.sh + 3u) / 4u);
-  if (P.tonemap == SVR_TONEMAP_CLAMP)
+  if (P.auto_exposure) {
+    if (P.tonemap == SVR_TONEMAP_CLAMP)
+      hipLaunchKernelGGL(post_composite_auto_kernel<SVR_TONEMAP_CLAMP>, grid, block, 0, s, C, P.auto_exposure);
+    else if (P.tonemap == SVR_TONEMAP_REINHARD)
+      hipLaunchKernelGGL(post_composite_auto_kernel<SVR_TONEMAP_REINHARD>, grid, block, 0, s, C, P.auto_exposure);
+    else
+      hipLaunchKernelGGL(post_composite_auto_kernel<SVR_TONEMAP_ACES>, grid, block, 0, s, C, P.auto_exposure);
+  } else if (P.tonemap == SVR_TONEMAP_CLAMP)
     hipLaunchKernelGGL(post_composite_kernel<SVR_TONEMAP_CLAMP>, grid, block, 0, s, C);
   else if (P.tonemap == SVR_TONEMAP_REINHARD)
     hipLaunchKernelGGL(post_composite_kernel<SVR_TONEMAP_REINHARD>, grid, block, 0, s, C);

@@ -25,6 +25,7 @@
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
+#include "../../include/svr_exposure.h"
 #include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
@@ -236,10 +237,12 @@ struct LightOp {
 using PostOp = PostLaunch;
 using TemporalOp = TemporalLaunch;
 using AmbientOp = AmbientLaunch;
+// svr_meter_exposure: the kernels' parameters as recorded, whether it snaps among them
+using ExposureOp = ExposureLaunch;
 
 struct LoggedOp {
   int slot;  // index into h_counters / op_done / h_stage
-  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp> what;
+  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp> what;
   template <class Op> LoggedOp(int slot_, Op&& op) : slot(slot_), what(std::forward<Op>(op)) {}
   const PassOp* as_pass() const { return std::get_if<PassOp>(&what); }
 };
@@ -371,6 +374,12 @@ struct Context {
   DevPtr<float> d_ambient_own;
   float* ambient_bound = nullptr;
   bool light_ao = false;
+  // include/svr_exposure.h: the state, the working bins and the last histogram (EXPOSURE_WORDS words), allocated and
+  // initialised by the first call of the group.  exposure_snap: the next accepted meter snaps; it changes at an accepted
+  // meter and at svr_reset_exposure only, in call order.  post_auto: svr_set_post_auto_exposure.
+  DevPtr<uint32_t> d_exposure;
+  bool exposure_snap = true;
+  bool post_auto = false;
   SvrStats stats{};
   // Declared last, so it goes first: its entries hold draw-list versions and pyramids, and name the memory above.
   std::deque<LoggedOp> log;
@@ -421,6 +430,7 @@ int submit(SvrContext* ctx, const LightOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const PostOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const TemporalOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const AmbientOp& op, int slot, bool replaying);
+int submit(SvrContext* ctx, const ExposureOp& op, int slot, bool replaying);
 // log the finished payload of any of those kinds in a free slot and submit it; the entry stays in the log if the submit
 // fails
 template <class Op> int log_op(SvrContext* ctx, Op&& op) {

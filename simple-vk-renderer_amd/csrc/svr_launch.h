@@ -1,6 +1,7 @@
 // svr_launch.h — host-callable launchers of the HIP kernels (one per kernel file).
 #pragma once
 #include "../../include/svr_ambient.h"
+#include "../../include/svr_exposure.h"
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
@@ -90,6 +91,7 @@ struct PostLaunch {
   float exposure, threshold, intensity;
   uint32_t tonemap;             // SVR_TONEMAP_*
   const uint32_t* poison;
+  const float* auto_exposure;   // svr_set_post_auto_exposure: the state's exposure (include/svr_exposure.h), null when off
 };
 // C22: the level extents of a sw x sh image and their packed offsets (each level starts on 16 bytes); returns the texels
 size_t post_level_layout(uint32_t sw, uint32_t sh, uint32_t n_levels, uint32_t* off, uint32_t* lw, uint32_t* lh);
@@ -133,6 +135,23 @@ struct AmbientLaunch {
 };
 // one ambient_raw_kernel and one ambient_blur_kernel, on s
 void launch_ambient(const AmbientLaunch& A, hipStream_t s);
+// k_exposure.hip: auto-exposure (include/svr_exposure.h)
+constexpr uint32_t EXPOSURE_STATE_WORDS = 8;   // SvrExposureState (6 words), padded to 32 bytes
+constexpr uint32_t EXPOSURE_BINS_WORDS = 264;  // the working bins: SVR_EXPOSURE_BINS, then the black counter, padded
+constexpr uint32_t EXPOSURE_WORDS = EXPOSURE_STATE_WORDS + EXPOSURE_BINS_WORDS + SVR_EXPOSURE_BINS;  // ... then the last histogram
+struct ExposureLaunch {
+  const uint2* color;           // the RGBA16F colour target, W texels per row: read only
+  uint32_t W;
+  uint32_t sx, sy, sw, sh;      // the scissor: the pixels metered
+  uint32_t* mem;                // the context's EXPOSURE_WORDS words: state, working bins (all 0 between meters), last histogram
+  SvrExposureMeter meter;
+  uint32_t snap;                // decided at the call (include/svr_exposure.h)
+  const uint32_t* poison;
+};
+// C38's grid rule: the workgroups of exposure_histogram_kernel for a scissor of sw x sh
+uint32_t exposure_grid(uint32_t sw, uint32_t sh);
+// one exposure_histogram_kernel (none for an empty scissor) and one exposure_resolve_kernel, on s
+void launch_exposure(const ExposureLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

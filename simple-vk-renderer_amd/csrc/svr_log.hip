@@ -347,6 +347,10 @@ int submit(SvrContext* ctx, const AmbientOp& op, int, bool) {
   launch_ambient(op, ctx->stream);
   return launched();
 }
+int submit(SvrContext* ctx, const ExposureOp& op, int, bool) {
+  launch_exposure(op, ctx->stream);
+  return launched();
+}
 
 namespace {
 

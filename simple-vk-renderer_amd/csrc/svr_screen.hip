@@ -1,8 +1,9 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, temporal antialiasing and ambient occlusion, with
+// culling's calls, the deferred lighting pass, the HDR post pass, auto-exposure, temporal antialiasing and ambient occlusion, with
 // their targets and read-backs.  Each validates its arguments, allocates what its first call needs, records its
 // kernels' parameters in a payload of its kind and logs it (svr_context.h, svr_log.hip).
 #include <cmath>
+#include <cstddef>
 
 #include "svr_context.h"
 
@@ -179,6 +180,8 @@ int svr_debug_read_light_tiles(SvrContext* ctx, uint32_t* counts, size_t capacit
 }
 
 // ---------------------------------------------------------------- the HDR post pass (include/svr_post.h)
+static int exposure_memory(SvrContext* ctx);  // include/svr_exposure.h, below
+
 int svr_post_pass(SvrContext* ctx, const SvrPostPass* pass) {
   if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_post_pass: null argument");
   if (!(std::isfinite(pass->exposure) && pass->exposure > 0.0f))
@@ -212,7 +215,99 @@ int svr_post_pass(SvrContext* ctx, const SvrPostPass* pass) {
   P.intensity = pass->bloom_intensity;
   P.tonemap = pass->tonemap;
   P.poison = ctx->d_poison.get();
+  if (ctx->post_auto) {  // include/svr_exposure.h: e = exposure * the state's, formed on the device
+    if (int e = exposure_memory(ctx)) return e;
+    P.auto_exposure = reinterpret_cast<const float*>(ctx->d_exposure.get());  // SvrExposureState::exposure is the first word
+  }
   return log_op(ctx, std::move(P));
+}
+
+// ---------------------------------------------------------------- auto-exposure (include/svr_exposure.h)
+static_assert(sizeof(SvrExposureMeter) == 24 && sizeof(SvrExposureState) == 24 && offsetof(SvrExposureState, exposure) == 0, "include/svr_exposure.h");
+static_assert(sizeof(SvrExposureState) <= EXPOSURE_STATE_WORDS * sizeof(uint32_t), "the state's words");
+
+// the state, the working bins and the last histogram: allocated and initialised by the first call that needs them
+static int exposure_memory(SvrContext* ctx) {
+  if (ctx->d_exposure) return SVR_OK;
+  static const SvrExposureState first = {1.0f, 1.0f, 0.0f, 0u, 0u, 0u};
+  if (int e = use_device(ctx)) return e;
+  DevPtr<uint32_t> mem;
+  DEV_ALLOC(mem, EXPOSURE_WORDS * sizeof(uint32_t));
+  HIPCHK(hipMemsetAsync(mem.get(), 0, EXPOSURE_WORDS * sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipMemcpyAsync(mem.get(), &first, sizeof(first), hipMemcpyHostToDevice, ctx->stream));
+  ctx->d_exposure = std::move(mem);
+  return SVR_OK;
+}
+
+int svr_meter_exposure(SvrContext* ctx, const SvrExposureMeter* meter) {
+  if (!ctx || !meter) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_meter_exposure: null argument");
+  if (!(std::isfinite(meter->key) && meter->key > 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_meter_exposure: the key must be finite and greater than 0");
+  if (!(meter->low_fraction >= 0.0f && meter->low_fraction < 1.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_meter_exposure: low_fraction must be at least 0 and less than 1");
+  if (!(meter->high_fraction > meter->low_fraction && meter->high_fraction <= 1.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_meter_exposure: high_fraction must be greater than low_fraction and at most 1");
+  if (!(std::isfinite(meter->min_exposure) && meter->min_exposure > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_meter_exposure: min_exposure must be finite and greater than 0");
+  if (!(std::isfinite(meter->max_exposure) && meter->max_exposure >= meter->min_exposure))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_meter_exposure: max_exposure must be finite and at least min_exposure");
+  if (!(meter->adapt >= 0.0f && meter->adapt <= 1.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_meter_exposure: adapt must be at least 0 and at most 1");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_meter_exposure: the colour target must be RGBA16F");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_meter_exposure: not under svr_set_row_interleave with a stride above 1");
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  if (int e = exposure_memory(ctx)) return e;
+  if (int e = flush_clear(ctx)) return e;  // this call reads colour: a deferred clear lands first
+  ExposureOp E{};
+  E.color = (const uint2*)ctx->color;
+  E.W = ctx->W;
+  E.sx = ctx->sx;
+  E.sy = ctx->sy;
+  E.sw = ctx->sw;
+  E.sh = ctx->sh;
+  E.mem = ctx->d_exposure.get();
+  E.meter = *meter;
+  // decided here, in call order, and it travels with the operation: a replay finds it as it was
+  E.snap = ctx->exposure_snap ? 1u : 0u;
+  E.poison = ctx->d_poison.get();
+  if (int e = log_op(ctx, std::move(E))) return e;
+  ctx->exposure_snap = false;
+  return SVR_OK;
+}
+
+int svr_reset_exposure(SvrContext* ctx) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_reset_exposure: null context");
+  ctx->exposure_snap = true;
+  return SVR_OK;
+}
+
+int svr_set_post_auto_exposure(SvrContext* ctx, int on) {
+  if (!ctx) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_set_post_auto_exposure: null context");
+  ctx->post_auto = on != 0;
+  return SVR_OK;
+}
+
+int svr_read_exposure(SvrContext* ctx, SvrExposureState* out) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_exposure: null argument");
+  if (int e = exposure_memory(ctx)) return e;
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(out, ctx->d_exposure.get(), sizeof(SvrExposureState), hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+int svr_debug_read_exposure_histogram(SvrContext* ctx, uint32_t* out, size_t bytes) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_exposure_histogram: null argument");
+  if (bytes != SVR_EXPOSURE_BINS * sizeof(uint32_t)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_exposure_histogram: the size is not SVR_EXPOSURE_BINS * 4");
+  if (int e = exposure_memory(ctx)) return e;
+  if (int e = svr_sync(ctx)) return e;
+  HIPCHK(hipMemcpy(out, ctx->d_exposure.get() + EXPOSURE_STATE_WORDS + EXPOSURE_BINS_WORDS, bytes, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+int svr_get_exposure_state(SvrContext* ctx, const void** device) {
+  if (!ctx || !device) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_get_exposure_state: null argument");
+  if (int e = exposure_memory(ctx)) return e;
+  *device = ctx->d_exposure.get();
+  return SVR_OK;
 }
 
 // ---------------------------------------------------------------- temporal antialiasing (include/svr_temporal.h)

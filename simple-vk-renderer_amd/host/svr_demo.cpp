@@ -22,6 +22,10 @@
 //       --ao <radius>:<intensity>: screen-space ambient occlusion (include/svr_ambient.h, HIP library only) with --deferred 1:
 //           svr_ambient_pass between the G-buffer pass and the lighting pass, which scales its ambient term by the result
 //           (bias 0.02 radius, sharpness 0.05); an intensity of 0 gives the frame without the flag; not with --views or --ranks
+//       --auto-exposure <key>:<adapt>: auto-exposure (include/svr_exposure.h, HIP library only) with --post: svr_meter_exposure
+//           behind every frame's last pass and in front of the post pass, which multiplies --exposure (then a compensation)
+//           by the metered exposure on the device; the final state is printed as
+//           "exposure E target T mean_log2 M counted C black B meters N"
 //       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
 //           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
 //           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
@@ -91,7 +95,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false;
-  std::string occlusion = "off", post_arg, taa_arg, ao_arg;
+  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg;
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -119,6 +123,7 @@ int main(int argc, char** argv) {
     else if (a == "--post") post_arg = argv[i + 1];  // <operator>:<levels> (include/svr_post.h)
     else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
     else if (a == "--ao") ao_arg = argv[i + 1];  // <radius>:<intensity> (include/svr_ambient.h)
+    else if (a == "--auto-exposure") ae_arg = argv[i + 1];  // <key>:<adapt> (include/svr_exposure.h)
     else if (a == "--exposure") post.exposure = (float)atof(argv[i + 1]);
     else if (a == "--bloom-threshold") post.bloom_threshold = (float)atof(argv[i + 1]);
     else if (a == "--bloom-intensity") post.bloom_intensity = (float)atof(argv[i + 1]);
@@ -156,7 +161,7 @@ int main(int argc, char** argv) {
                     "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1] [--deferred 1]\n"
                     "                [--occlusion off|last|prepass]\n"
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
-                    "                [--taa blend] [--ao radius:intensity]\n");
+                    "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -218,6 +223,22 @@ int main(int argc, char** argv) {
     }
     if (ranks > 1) {
       fprintf(stderr, "--post: not with --ranks (a band rank would bloom its own rows only)\n");
+      return 1;
+    }
+  }
+  float ae_key = 0.f, ae_adapt = 0.f;
+  if (!ae_arg.empty()) {
+    const size_t colon = ae_arg.find(':');
+    char *end_k = nullptr, *end_a = nullptr;
+    ae_key = strtof(ae_arg.c_str(), &end_k);
+    if (colon != std::string::npos) ae_adapt = strtof(ae_arg.c_str() + colon + 1, &end_a);
+    if (colon == std::string::npos || colon == 0 || end_k != ae_arg.c_str() + colon || !end_a || *end_a || end_a == ae_arg.c_str() + colon + 1 ||
+        !(ae_key > 0.f && ae_key < INFINITY) || !(ae_adapt >= 0.f && ae_adapt <= 1.f)) {
+      fprintf(stderr, "--auto-exposure: expected <key > 0>:<adapt 0..1>, got '%s'\n", ae_arg.c_str());
+      return 2;
+    }
+    if (post_arg.empty()) {
+      fprintf(stderr, "--auto-exposure: needs --post (the post pass is what applies the metered exposure)\n");
       return 1;
     }
   }
@@ -513,6 +534,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--deferred: not with --views, --depth-only, --retained or --occlusion\n");
     return 1;
   }
+  if (!ae_arg.empty() && !(eng.api.svr_meter_exposure && eng.api.svr_set_post_auto_exposure && eng.api.svr_read_exposure)) {
+    fprintf(stderr, "--auto-exposure: the library has no auto-exposure (include/svr_exposure.h)\n");
+    return 1;
+  }
   if (!post_arg.empty() && !eng.api.svr_post_pass) {
     fprintf(stderr, "--post: the library has no post pass (include/svr_post.h)\n");
     return 1;
@@ -547,6 +572,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n", eng.error.rfind("--taa", 0) == 0 ? eng.error.c_str() : ("--taa: " + eng.error).c_str());
       return 1;
     }
+    if (!ae_arg.empty() && !eng.meter_exposure(ae_key, ae_adapt)) {  // behind the frame's last pass, in front of the post pass
+      fprintf(stderr, "%s\n", eng.error.rfind("--auto-exposure", 0) == 0 ? eng.error.c_str() : ("--auto-exposure: " + eng.error).c_str());
+      return 1;
+    }
     if (!post_arg.empty() && !eng.post_pass(post)) {  // behind the frame's last pass, before the swapchain copy
       fprintf(stderr, "%s\n", eng.error.rfind("--post", 0) == 0 ? eng.error.c_str() : ("--post: " + eng.error).c_str());
       return 1;
@@ -555,6 +584,15 @@ int main(int argc, char** argv) {
   eng.api.svr_sync(eng.ctx);
   printf("draws %d triangles %d update %.3f ms record %.3f ms\n", eng.stats.drawcall_count, eng.stats.triangle_count,
          eng.stats.scene_update_time, eng.stats.mesh_draw_time);
+  if (!ae_arg.empty()) {
+    SvrExposureState st{};
+    if (!eng.read_exposure(st)) {
+      fprintf(stderr, "%s\n", eng.error.c_str());
+      return 1;
+    }
+    printf("exposure %.9g target %.9g mean_log2 %.9g counted %u black %u meters %u\n", (double)st.exposure, (double)st.target, (double)st.mean_log2,
+           st.counted, st.black, st.meters);
+  }
   if (select) {
     SvrEngine::Pick p;
     if (!eng.pick(sel_x, sel_y, p)) {

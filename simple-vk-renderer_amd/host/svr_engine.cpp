@@ -51,6 +51,9 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_temporal_resolve = reinterpret_cast<decltype(svr_temporal_resolve)>(dlsym(handle, "svr_temporal_resolve"));
   svr_ambient_pass = reinterpret_cast<decltype(svr_ambient_pass)>(dlsym(handle, "svr_ambient_pass"));
   svr_set_light_ambient_occlusion = reinterpret_cast<decltype(svr_set_light_ambient_occlusion)>(dlsym(handle, "svr_set_light_ambient_occlusion"));
+  svr_meter_exposure = reinterpret_cast<decltype(svr_meter_exposure)>(dlsym(handle, "svr_meter_exposure"));
+  svr_set_post_auto_exposure = reinterpret_cast<decltype(svr_set_post_auto_exposure)>(dlsym(handle, "svr_set_post_auto_exposure"));
+  svr_read_exposure = reinterpret_cast<decltype(svr_read_exposure)>(dlsym(handle, "svr_read_exposure"));
   return ok;
 }
 void SvrApi::unload() {
@@ -409,6 +412,36 @@ bool SvrEngine::post_pass(const SvrPostPass& pass) {
     return false;
   }
   if (api.svr_post_pass(ctx, &pass)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::meter_exposure(float key, float adapt) {
+  if (!api.svr_meter_exposure || !api.svr_set_post_auto_exposure) {
+    error = "--auto-exposure: the library has no auto-exposure (include/svr_exposure.h)";
+    return false;
+  }
+  if (!auto_exposure_on && api.svr_set_post_auto_exposure(ctx, 1)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  auto_exposure_on = true;
+  const SvrExposureMeter m{key, 0.0f, 1.0f, 0x1p-10f, 0x1p10f, adapt};
+  if (api.svr_meter_exposure(ctx, &m)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::read_exposure(SvrExposureState& out) {
+  if (!api.svr_read_exposure) {
+    error = "--auto-exposure: the library has no auto-exposure (include/svr_exposure.h)";
+    return false;
+  }
+  if (api.svr_read_exposure(ctx, &out)) {
     error = api.svr_last_error();
     return false;
   }

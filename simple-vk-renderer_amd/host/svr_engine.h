@@ -25,6 +25,7 @@
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
+#include "../../include/svr_exposure.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -60,6 +61,8 @@ struct SvrApi {
   SVR_FN(svr_temporal_resolve)
   // include/svr_ambient.h: optional (HIP library only), needed by SvrEngine::draw_deferred with ao_radius > 0
   SVR_FN(svr_ambient_pass) SVR_FN(svr_set_light_ambient_occlusion)
+  // include/svr_exposure.h: optional (HIP library only), needed by SvrEngine::meter_exposure
+  SVR_FN(svr_meter_exposure) SVR_FN(svr_set_post_auto_exposure) SVR_FN(svr_read_exposure)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -182,6 +185,12 @@ struct SvrEngine {
   // The HDR post pass (svr_demo --post <operator>:<levels>, include/svr_post.h): exposure, bloom and the operator over the
   // colour target, after the frame's last pass and before the swapchain copy.
   bool post_pass(const SvrPostPass& pass);
+  // Auto-exposure (svr_demo --auto-exposure <key>:<adapt>, include/svr_exposure.h): meter the colour target behind the
+  // frame's last pass and in front of the post pass, which then multiplies its exposure (a compensation) by the state's.
+  // The first call turns svr_set_post_auto_exposure on.  Whole window, exposures clamped to [2^-10, 2^10].
+  bool auto_exposure_on = false;
+  bool meter_exposure(float key, float adapt);
+  bool read_exposure(SvrExposureState& out);
   // Temporal antialiasing (svr_demo --taa <blend>, include/svr_temporal.h).  With taa_blend > 0 update_scene shifts the
   // projection by Halton(2, 3) - 0.5 pixels, a period of 16 frames, and keeps the unjittered viewproj; temporal_resolve,
   // called behind the frame's last geometry or lighting pass and in front of the post pass, reprojects with
