@@ -125,6 +125,11 @@ AMBIENT_MAX_REACH, AMBIENT_TAPS = 16, 8
 EXPOSURE_SYMBOLS = ["svr_meter_exposure", "svr_reset_exposure", "svr_set_post_auto_exposure", "svr_read_exposure",
                     "svr_debug_read_exposure_histogram", "svr_get_exposure_state"]
 EXPOSURE_BINS = 256
+# include/svr_overlay.h: the UI overlay pass (2D triangle lists blended over the swapchain image), HIP library only
+OVERLAY_SYMBOLS = ["svr_draw_overlay", "svr_debug_read_overlay_stats", "svr_overlay_font"]
+OVERLAY_MAX_TRIANGLES, OVERLAY_MAX_CMDS, OVERLAY_MAX_TEXTURES, OVERLAY_MAX_TEXTURE_EXTENT = 65536, 4096, 16, 16384
+OVERLAY_TEX_RGBA8, OVERLAY_TEX_A8 = 0, 1
+OVERLAY_FONT_WHITE_X, OVERLAY_FONT_WHITE_Y = 92, 43
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -170,6 +175,33 @@ class SvrExposureState(C.Structure):  # include/svr_exposure.h
     _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("mean_log2", C.c_float), ("counted", C.c_uint32),
                 ("black", C.c_uint32), ("meters", C.c_uint32)]
 
+
+class SvrOverlayVertex(C.Structure):  # include/svr_overlay.h
+    _fields_ = [("pos", C.c_float * 2), ("uv", C.c_float * 2), ("col", C.c_uint32)]
+
+
+class SvrOverlayCmd(C.Structure):  # include/svr_overlay.h
+    _fields_ = [("clip_rect", C.c_float * 4), ("texture", C.c_uint32), ("vtx_offset", C.c_uint32), ("idx_offset", C.c_uint32),
+                ("elem_count", C.c_uint32)]
+
+
+class SvrOverlayTexture(C.Structure):  # include/svr_overlay.h
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SvrOverlayList(C.Structure):  # include/svr_overlay.h
+    _fields_ = [("vertices", C.c_void_p), ("indices", C.c_void_p), ("cmds", C.c_void_p), ("textures", C.c_void_p),
+                ("n_vertices", C.c_uint32), ("n_indices", C.c_uint32), ("n_cmds", C.c_uint32), ("n_textures", C.c_uint32),
+                ("display_pos", C.c_float * 2), ("scale", C.c_float * 2)]
+
+
+class SvrOverlayStats(C.Structure):  # include/svr_overlay.h
+    _fields_ = [("triangles", C.c_uint32), ("kept", C.c_uint32), ("tiles", C.c_uint32)]
+
+
+OVERLAY_VERTEX_DTYPE = np.dtype([("pos", "<f4", 2), ("uv", "<f4", 2), ("col", "<u4")])
+OVERLAY_CMD_DTYPE = np.dtype([("clip_rect", "<f4", 4), ("texture", "<u4"), ("vtx_offset", "<u4"), ("idx_offset", "<u4"), ("elem_count", "<u4")])
+assert OVERLAY_VERTEX_DTYPE.itemsize == C.sizeof(SvrOverlayVertex) == 20 and OVERLAY_CMD_DTYPE.itemsize == C.sizeof(SvrOverlayCmd) == 32
 
 POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("intensity", "<f4")])
 assert POINT_LIGHT_DTYPE.itemsize == C.sizeof(SvrPointLight) == 32
@@ -305,6 +337,11 @@ class SvrLib:
             L.svr_read_exposure.argtypes = [P, C.POINTER(SvrExposureState)]
             L.svr_debug_read_exposure_histogram.argtypes = [P, P, C.c_size_t]
             L.svr_get_exposure_state.argtypes = [P, C.POINTER(P)]
+        self.has_overlay = hasattr(L, "svr_draw_overlay")
+        if self.has_overlay:
+            L.svr_draw_overlay.argtypes = [P, P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(SvrOverlayList)]
+            L.svr_debug_read_overlay_stats.argtypes = [P, C.POINTER(SvrOverlayStats)]
+            L.svr_overlay_font.argtypes = [C.POINTER(C.POINTER(C.c_uint8))] + [C.POINTER(C.c_uint32)] * 6
         self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
         if self.has_depth_load:
             L.svr_set_depth_load_op.argtypes = [P, C.c_int]
@@ -320,6 +357,24 @@ class SvrLib:
 
     def create(self, width, height, color_format=COLOR_RGBA16F, device=0):
         return Renderer(self, width, height, color_format, device)
+
+
+def overlay_device_ptr(x):
+    """a device address: an int, None, or anything with data_ptr() (a torch tensor)"""
+    if x is None:
+        return None
+    return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
+
+
+def overlay_font(lib):
+    """svr_overlay_font -> (uint8 [height, width] A8 atlas, cell_w, cell_h, first_char, n_chars); needs no device"""
+    if not getattr(lib, "has_overlay", False):
+        raise SvrError(-5, f"{lib.backend} has no overlay pass (include/svr_overlay.h)")
+    a8 = C.POINTER(C.c_uint8)()
+    v = [C.c_uint32() for _ in range(6)]
+    lib.check(lib.lib.svr_overlay_font(C.byref(a8), *[C.byref(x) for x in v]))
+    w, h, cw, ch, first, n = [x.value for x in v]
+    return np.ctypeslib.as_array(a8, shape=(h, w)).copy(), cw, ch, first, n
 
 
 def _f4(a):
@@ -946,6 +1001,35 @@ class Renderer:
         p = C.c_void_p()
         self.lib.check(self.lib.lib.svr_get_exposure_state(self.h, C.byref(p)))
         return p.value
+
+    # ---- the UI overlay pass (include/svr_overlay.h)
+    def _need_overlay(self):
+        if not getattr(self.lib, "has_overlay", False):
+            raise SvrError(-5, f"{self.lib.backend} has no overlay pass (include/svr_overlay.h)")
+
+    def draw_overlay(self, dst, width, height, fmt, vertices, indices, cmds, textures, display_pos=(0, 0), scale=(1, 1)):
+        """svr_draw_overlay: blend a 2D triangle list over the width x height UNORM8 image at dst (a device pointer or a
+        torch tensor), in submission order.  vertices: OVERLAY_VERTEX_DTYPE records; indices: uint16; cmds: OVERLAY_CMD_DTYPE
+        records; textures: a sequence of (device pointer or torch tensor, width, height, OVERLAY_TEX_*)"""
+        self._need_overlay()
+        vertices = np.ascontiguousarray(vertices, dtype=OVERLAY_VERTEX_DTYPE)
+        indices = np.ascontiguousarray(indices, dtype=np.uint16)
+        cmds = np.ascontiguousarray(cmds, dtype=OVERLAY_CMD_DTYPE)
+        table = (SvrOverlayTexture * max(len(textures), 1))()
+        for i, (texels, w, h, f) in enumerate(textures):
+            table[i] = SvrOverlayTexture(overlay_device_ptr(texels), int(w), int(h), int(f), 0)
+        lst = SvrOverlayList(vertices.ctypes.data if vertices.size else None, indices.ctypes.data if indices.size else None,
+                             cmds.ctypes.data if cmds.size else None, C.cast(table, C.c_void_p) if len(textures) else None,
+                             vertices.size, indices.size, cmds.size, len(textures),
+                             (C.c_float * 2)(*[float(v) for v in display_pos]), (C.c_float * 2)(*[float(v) for v in scale]))
+        self.lib.check(self.lib.lib.svr_draw_overlay(self.h, overlay_device_ptr(dst), int(width), int(height), int(fmt), C.byref(lst)))
+
+    def read_overlay_stats(self):
+        """svr_debug_read_overlay_stats -> SvrOverlayStats of the last overlay that enqueued work (fences)"""
+        self._need_overlay()
+        st = SvrOverlayStats()
+        self.lib.check(self.lib.lib.svr_debug_read_overlay_stats(self.h, C.byref(st)))
+        return st
 
     # ---- the depth loadOp (include/svr_load.h)
     def _need_depth_load(self):

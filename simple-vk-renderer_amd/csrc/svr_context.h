@@ -26,6 +26,7 @@
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
+#include "../../include/svr_overlay.h"
 #include "../../include/svr_load.h"
 #include "../../include/svr_occlusion.h"
 #include "../../include/svr_views.h"
@@ -239,10 +240,20 @@ using TemporalOp = TemporalLaunch;
 using AmbientOp = AmbientLaunch;
 // svr_meter_exposure: the kernels' parameters as recorded, whether it snaps among them
 using ExposureOp = ExposureLaunch;
+// svr_draw_overlay: the kernels' parameters as recorded (the device pointers of the copies are filled in at submit) and
+// the call's arrays, owned: what a replay uploads again
+struct OverlayOp {
+  OverlayLaunch launch{};
+  uint32_t submitted = 0;  // triangles of every command, for the statistics
+  std::vector<SvrOverlayVertex> vertices;
+  std::vector<uint16_t> indices;
+  std::vector<OverlayCmdDev> cmds;  // those with triangles and a clip box that is not empty
+  std::vector<SvrOverlayTexture> textures;
+};
 
 struct LoggedOp {
   int slot;  // index into h_counters / op_done / h_stage
-  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp> what;
+  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp> what;
   template <class Op> LoggedOp(int slot_, Op&& op) : slot(slot_), what(std::forward<Op>(op)) {}
   const PassOp* as_pass() const { return std::get_if<PassOp>(&what); }
 };
@@ -380,6 +391,10 @@ struct Context {
   DevPtr<uint32_t> d_exposure;
   bool exposure_snap = true;
   bool post_auto = false;
+  // include/svr_overlay.h: the device copy of an overlay's arrays (the statistics at its head) and its triangle records
+  // and boxes; allocated by the first overlay, grown when one needs more, refilled in stream order in front of every
+  // overlay's kernels
+  DevBuf d_overlay_in, d_overlay_recs;
   SvrStats stats{};
   // Declared last, so it goes first: its entries hold draw-list versions and pyramids, and name the memory above.
   std::deque<LoggedOp> log;
@@ -431,6 +446,7 @@ int submit(SvrContext* ctx, const PostOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const TemporalOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const AmbientOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const ExposureOp& op, int slot, bool replaying);
+int submit(SvrContext* ctx, const OverlayOp& op, int slot, bool replaying);
 // log the finished payload of any of those kinds in a free slot and submit it; the entry stays in the log if the submit
 // fails
 template <class Op> int log_op(SvrContext* ctx, Op&& op) {

@@ -3,6 +3,7 @@
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
 #include "../../include/svr_lighting.h"
+#include "../../include/svr_overlay.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
 #include "svr_device.h"
@@ -152,6 +153,36 @@ struct ExposureLaunch {
 uint32_t exposure_grid(uint32_t sw, uint32_t sh);
 // one exposure_histogram_kernel (none for an empty scissor) and one exposure_resolve_kernel, on s
 void launch_exposure(const ExposureLaunch& A, hipStream_t s);
+// k_overlay.hip: the UI overlay pass (include/svr_overlay.h)
+constexpr uint32_t OVERLAY_REC_WORDS = 36;  // a triangle's record (k_overlay.hip "the record"), 144 bytes
+// a command as the kernels read it: the clip box in whole pixels (C45), already cut to the image, and where its
+// triangles stand among those of the launch
+struct OverlayCmdDev {
+  int32_t x0, y0, x1, y1;  // pixel i passes iff x0 <= i < x1
+  uint32_t texture, vtx_offset, idx_offset;
+  uint32_t tri_first, tri_count;  // among the triangles of the commands that reached the device, in order
+  uint32_t pad[3];
+};
+static_assert(sizeof(OverlayCmdDev) == 48, "16-byte records");
+struct OverlayLaunch {
+  uint32_t* dst;                     // dw x dh UNORM8 texels, the caller's
+  uint32_t dw, dh;
+  int dst_fmt;                       // SVR_SWAPCHAIN_*
+  float display_pos[2], scale[2];
+  const SvrOverlayVertex* vertices;  // the context's device copies, valid for this launch
+  const uint16_t* indices;
+  const OverlayCmdDev* cmds;
+  const SvrOverlayTexture* textures;
+  uint32_t n_cmds, n_tris;           // commands and triangles that reached the device (n_tris > 0)
+  uint32_t n_textures;               // entries of the texture table (<= SVR_OVERLAY_MAX_TEXTURES)
+  uint32_t tile_x0, tile_y0, tiles_w, tiles_h;  // the 32 x 32 tiles the commands' clip boxes reach: the tile kernel's grid
+  uint2* boxes;                      // [n_tris] the records' boxes alone, for the tile kernel's scan
+  uint32_t* recs;                    // [n_tris][OVERLAY_REC_WORDS]
+  uint32_t* stats;                   // SvrOverlayStats, written {submitted, 0, 0} by the copy in front of the kernels
+  const uint32_t* poison;
+};
+// one overlay_setup_kernel and one overlay_tile_kernel, on s
+void launch_overlay(const OverlayLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

@@ -351,6 +351,40 @@ int submit(SvrContext* ctx, const ExposureOp& op, int, bool) {
   launch_exposure(op, ctx->stream);
   return launched();
 }
+// One copy through the slot's staging buffer: the statistics {submitted, 0, 0, -}, then the commands, the texture table,
+// the vertices and the indices, each on 16 bytes.  The device buffers only grow; growing frees the old one, which waits
+// for the device, so an overlay still in flight has finished with it.
+int submit(SvrContext* ctx, const OverlayOp& op, int slot, bool) {
+  auto up16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
+  const size_t o_cmds = 16, o_tex = o_cmds + up16(op.cmds.size() * sizeof(OverlayCmdDev));
+  const size_t o_vtx = o_tex + up16(op.textures.size() * sizeof(SvrOverlayTexture));
+  const size_t o_idx = o_vtx + up16(op.vertices.size() * sizeof(SvrOverlayVertex));
+  const size_t bytes = o_idx + up16(op.indices.size() * sizeof(uint16_t));
+  void* stage = nullptr;
+  if (int e = stage_buffer(ctx, slot, bytes, &stage)) return e;
+  if (int e = ctx->d_overlay_in.ensure(bytes)) return e;
+  const size_t box_bytes = up16((size_t)op.launch.n_tris * sizeof(uint2));
+  if (int e = ctx->d_overlay_recs.ensure(box_bytes + (size_t)op.launch.n_tris * OVERLAY_REC_WORDS * sizeof(uint32_t))) return e;
+  char* h = static_cast<char*>(stage);
+  const uint32_t head[4] = {op.submitted, 0u, 0u, 0u};
+  std::memcpy(h, head, sizeof(head));
+  std::memcpy(h + o_cmds, op.cmds.data(), op.cmds.size() * sizeof(OverlayCmdDev));
+  std::memcpy(h + o_tex, op.textures.data(), op.textures.size() * sizeof(SvrOverlayTexture));
+  std::memcpy(h + o_vtx, op.vertices.data(), op.vertices.size() * sizeof(SvrOverlayVertex));
+  std::memcpy(h + o_idx, op.indices.data(), op.indices.size() * sizeof(uint16_t));
+  char* d = static_cast<char*>(ctx->d_overlay_in.p);
+  HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+  OverlayLaunch L = op.launch;
+  L.stats = reinterpret_cast<uint32_t*>(d);
+  L.cmds = reinterpret_cast<const OverlayCmdDev*>(d + o_cmds);
+  L.textures = reinterpret_cast<const SvrOverlayTexture*>(d + o_tex);
+  L.vertices = reinterpret_cast<const SvrOverlayVertex*>(d + o_vtx);
+  L.indices = reinterpret_cast<const uint16_t*>(d + o_idx);
+  L.boxes = static_cast<uint2*>(ctx->d_overlay_recs.p);
+  L.recs = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->d_overlay_recs.p) + box_bytes);
+  launch_overlay(L, ctx->stream);
+  return launched();
+}
 
 namespace {
 

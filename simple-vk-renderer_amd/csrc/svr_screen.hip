@@ -1,11 +1,12 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, auto-exposure, temporal antialiasing and ambient occlusion, with
+// culling's calls, the deferred lighting pass, the HDR post pass, auto-exposure, temporal antialiasing, ambient occlusion and the UI overlay, with
 // their targets and read-backs.  Each validates its arguments, allocates what its first call needs, records its
 // kernels' parameters in a payload of its kind and logs it (svr_context.h, svr_log.hip).
 #include <cmath>
 #include <cstddef>
 
 #include "svr_context.h"
+#include "svr_overlay_font.h"
 
 using namespace svr;
 
@@ -472,6 +473,139 @@ int svr_debug_read_ambient_raw(SvrContext* ctx, void* dst_host, size_t bytes) {
   if (bytes != (size_t)ctx->W * ctx->H * sizeof(float2)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_ambient_raw: the size is not the plane's");
   if (int e = svr_sync(ctx)) return e;
   HIPCHK(hipMemcpy(dst_host, ctx->d_ambient_raw.get(), bytes, hipMemcpyDeviceToHost));
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- the UI overlay pass (include/svr_overlay.h)
+static_assert(sizeof(SvrOverlayVertex) == 20 && sizeof(SvrOverlayCmd) == 32 && sizeof(SvrOverlayTexture) == 24 && sizeof(SvrOverlayStats) == 12,
+              "include/svr_overlay.h");
+
+int svr_draw_overlay(SvrContext* ctx, void* dst_dev, uint32_t dw, uint32_t dh, int fmt, const SvrOverlayList* list) {
+  const std::string who = "svr_draw_overlay: ";
+  if (!ctx || !dst_dev || !list) return fail(SVR_ERR_INVALID_ARGUMENT, who + "null argument");
+  if (dw == 0 || dh == 0 || dw > 16384 || dh > 16384) return fail(SVR_ERR_INVALID_ARGUMENT, who + "extent must be in 1..16384");
+  if (fmt != SVR_SWAPCHAIN_B8G8R8A8 && fmt != SVR_SWAPCHAIN_R8G8B8A8) return fail(SVR_ERR_INVALID_ARGUMENT, who + "unknown format");
+  if (list->n_cmds > SVR_OVERLAY_MAX_CMDS) return fail(SVR_ERR_INVALID_ARGUMENT, who + "n_cmds is above SVR_OVERLAY_MAX_CMDS");
+  if (list->n_textures > SVR_OVERLAY_MAX_TEXTURES) return fail(SVR_ERR_INVALID_ARGUMENT, who + "n_textures is above SVR_OVERLAY_MAX_TEXTURES");
+  if ((list->n_cmds && !list->cmds) || (list->n_vertices && !list->vertices) || (list->n_indices && !list->indices) || (list->n_textures && !list->textures))
+    return fail(SVR_ERR_INVALID_ARGUMENT, who + "null array with a count above 0");
+  for (int k = 0; k < 2; k++) {
+    if (!std::isfinite(list->display_pos[k])) return fail(SVR_ERR_INVALID_ARGUMENT, who + "display_pos must be finite");
+    if (!(std::isfinite(list->scale[k]) && list->scale[k] > 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, who + "scale must be finite and greater than 0");
+  }
+  for (uint32_t i = 0; i < list->n_textures; i++) {
+    const SvrOverlayTexture& t = list->textures[i];
+    const std::string which = "texture " + std::to_string(i);
+    if (!t.texels) return fail(SVR_ERR_INVALID_ARGUMENT, who + which + " has a null pointer");
+    if (t.width == 0 || t.height == 0 || t.width > SVR_OVERLAY_MAX_TEXTURE_EXTENT || t.height > SVR_OVERLAY_MAX_TEXTURE_EXTENT)
+      return fail(SVR_ERR_INVALID_ARGUMENT, who + which + ": extent must be in 1..16384");
+    if (t.format != SVR_OVERLAY_TEX_RGBA8 && t.format != SVR_OVERLAY_TEX_A8) return fail(SVR_ERR_INVALID_ARGUMENT, who + which + ": unknown format");
+  }
+  uint64_t submitted = 0;
+  for (uint32_t c = 0; c < list->n_cmds; c++) {
+    const SvrOverlayCmd& cmd = list->cmds[c];
+    const std::string which = "command " + std::to_string(c);
+    if (cmd.elem_count % 3u) return fail(SVR_ERR_INVALID_ARGUMENT, who + which + ": elem_count is not divisible by 3");
+    if ((uint64_t)cmd.idx_offset + cmd.elem_count > list->n_indices) return fail(SVR_ERR_INVALID_ARGUMENT, who + which + ": idx_offset + elem_count is above n_indices");
+    if (cmd.elem_count == 0) continue;
+    if (cmd.texture >= list->n_textures) return fail(SVR_ERR_INVALID_ARGUMENT, who + which + ": texture is not below n_textures");
+    for (uint32_t i = 0; i < cmd.elem_count; i++)
+      if ((uint64_t)cmd.vtx_offset + list->indices[cmd.idx_offset + i] >= list->n_vertices)
+        return fail(SVR_ERR_INVALID_ARGUMENT, who + which + ": index out of range (vtx_offset + index >= n_vertices)");
+    submitted += cmd.elem_count / 3u;
+    if (submitted > SVR_OVERLAY_MAX_TRIANGLES) return fail(SVR_ERR_INVALID_ARGUMENT, who + "more than SVR_OVERLAY_MAX_TRIANGLES triangles");
+  }
+  // C45: the clip boxes, in whole pixels; a command without triangles or with an empty box does not reach the device
+  OverlayOp op;
+  uint32_t n_tris = 0, vtx_end = 0, idx_end = 0;
+  int32_t reach[4] = {(int32_t)dw, (int32_t)dh, 0, 0};  // the union of the live commands' clip boxes
+  const float ext[2] = {(float)dw, (float)dh};
+  for (uint32_t c = 0; c < list->n_cmds; c++) {
+    const SvrOverlayCmd& cmd = list->cmds[c];
+    if (cmd.elem_count == 0) continue;
+    int32_t lo[2];
+    uint32_t span[2];
+    bool empty = false;
+    for (int k = 0; k < 2; k++) {
+      float cmin = (cmd.clip_rect[k] - list->display_pos[k]) * list->scale[k], cmax = (cmd.clip_rect[2 + k] - list->display_pos[k]) * list->scale[k];
+      if (cmin < 0.0f) cmin = 0.0f;
+      if (cmax > ext[k]) cmax = ext[k];
+      if (!(cmax > cmin)) {  // also where one of them is NaN
+        empty = true;
+        break;
+      }
+      lo[k] = (int32_t)cmin;
+      span[k] = (uint32_t)(cmax - cmin);
+    }
+    if (empty) continue;
+    OverlayCmdDev d{};
+    d.x0 = lo[0];
+    d.y0 = lo[1];
+    d.x1 = std::min<int32_t>(lo[0] + (int32_t)span[0], (int32_t)dw);  // (the min never binds: DESIGN.md C45)
+    d.y1 = std::min<int32_t>(lo[1] + (int32_t)span[1], (int32_t)dh);
+    if (d.x1 <= d.x0 || d.y1 <= d.y0) continue;  // a box narrower than a pixel passes none
+    d.texture = cmd.texture;
+    d.vtx_offset = cmd.vtx_offset;
+    d.idx_offset = cmd.idx_offset;
+    d.tri_first = n_tris;
+    d.tri_count = cmd.elem_count / 3u;
+    n_tris += d.tri_count;
+    idx_end = std::max(idx_end, cmd.idx_offset + cmd.elem_count);
+    for (uint32_t i = 0; i < cmd.elem_count; i++) vtx_end = std::max(vtx_end, cmd.vtx_offset + list->indices[cmd.idx_offset + i] + 1u);
+    reach[0] = std::min(reach[0], d.x0);
+    reach[1] = std::min(reach[1], d.y0);
+    reach[2] = std::max(reach[2], d.x1);
+    reach[3] = std::max(reach[3], d.y1);
+    op.cmds.push_back(d);
+  }
+  if (n_tris == 0) return SVR_OK;  // nothing to draw: nothing is enqueued
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  // (the colour target is not touched: a deferred svr_clear_color stays deferred)
+  op.submitted = (uint32_t)submitted;
+  op.vertices.assign(list->vertices, list->vertices + vtx_end);  // what the live commands can name
+  op.indices.assign(list->indices, list->indices + idx_end);
+  op.textures.assign(list->textures, list->textures + list->n_textures);
+  OverlayLaunch& L = op.launch;
+  L.dst = static_cast<uint32_t*>(dst_dev);
+  L.dw = dw;
+  L.dh = dh;
+  L.dst_fmt = fmt;
+  for (int k = 0; k < 2; k++) {
+    L.display_pos[k] = list->display_pos[k];
+    L.scale[k] = list->scale[k];
+  }
+  L.n_cmds = (uint32_t)op.cmds.size();
+  L.n_tris = n_tris;
+  L.n_textures = list->n_textures;
+  // no tile outside every clip box has work: they are not launched (0 <= x0 < x1 <= dw for every live command)
+  L.tile_x0 = (uint32_t)reach[0] / 32u;
+  L.tile_y0 = (uint32_t)reach[1] / 32u;
+  L.tiles_w = ((uint32_t)reach[2] + 31u) / 32u - L.tile_x0;
+  L.tiles_h = ((uint32_t)reach[3] + 31u) / 32u - L.tile_y0;
+  L.poison = ctx->d_poison.get();
+  return log_op(ctx, std::move(op));
+}
+
+int svr_debug_read_overlay_stats(SvrContext* ctx, SvrOverlayStats* out) {
+  if (!ctx || !out) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_debug_read_overlay_stats: null argument");
+  if (int e = svr_sync(ctx)) return e;
+  SvrOverlayStats st = {0u, 0u, 0u};
+  if (ctx->d_overlay_in.p) HIPCHK(hipMemcpy(&st, ctx->d_overlay_in.p, sizeof(st), hipMemcpyDeviceToHost));
+  *out = st;
+  return SVR_OK;
+}
+
+int svr_overlay_font(const uint8_t** a8, uint32_t* width, uint32_t* height, uint32_t* cell_w, uint32_t* cell_h, uint32_t* first_char, uint32_t* n_chars) {
+  static const std::vector<uint8_t> atlas = build_font_atlas();
+  static_assert(SVR_OVERLAY_FONT_WHITE_X == FONT_W - FONT_CELL_W + 2 && SVR_OVERLAY_FONT_WHITE_Y == FONT_H - FONT_CELL_H + 3, "the opaque texel lies inside the filled cell");
+  if (a8) *a8 = atlas.data();
+  if (width) *width = FONT_W;
+  if (height) *height = FONT_H;
+  if (cell_w) *cell_w = FONT_CELL_W;
+  if (cell_h) *cell_h = FONT_CELL_H;
+  if (first_char) *first_char = FONT_FIRST;
+  if (n_chars) *n_chars = FONT_CHARS;
   return SVR_OK;
 }
 

@@ -26,6 +26,10 @@
 //           behind every frame's last pass and in front of the post pass, which multiplies --exposure (then a compensation)
 //           by the metered exposure on the device; the final state is printed as
 //           "exposure E target T mean_log2 M counted C black B meters N"
+//       --stats-overlay 1: the UI overlay pass (include/svr_overlay.h, HIP library only): behind the last frame the colour
+//           target is copied to a swapchain image in device memory and the reference's stats window (frametime, draw time,
+//           update time, triangles, draws) is drawn onto it by svr_draw_overlay; <prefix>.swapchain is then that image and
+//           <prefix>.overlay.txt the calls that built the list; not with --views or --ranks
 //       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
 //           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
 //           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
@@ -94,7 +98,7 @@ int main(int argc, char** argv) {
   uint32_t w = 160, h = 90;
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
-  bool depth_only = false, deferred = false;
+  bool depth_only = false, deferred = false, stats_overlay = false;
   std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg;
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
@@ -124,6 +128,7 @@ int main(int argc, char** argv) {
     else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
     else if (a == "--ao") ao_arg = argv[i + 1];  // <radius>:<intensity> (include/svr_ambient.h)
     else if (a == "--auto-exposure") ae_arg = argv[i + 1];  // <key>:<adapt> (include/svr_exposure.h)
+    else if (a == "--stats-overlay") stats_overlay = atoi(argv[i + 1]) != 0;  // include/svr_overlay.h
     else if (a == "--exposure") post.exposure = (float)atof(argv[i + 1]);
     else if (a == "--bloom-threshold") post.bloom_threshold = (float)atof(argv[i + 1]);
     else if (a == "--bloom-intensity") post.bloom_intensity = (float)atof(argv[i + 1]);
@@ -161,7 +166,7 @@ int main(int argc, char** argv) {
                     "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1] [--deferred 1]\n"
                     "                [--occlusion off|last|prepass]\n"
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
-                    "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt]\n");
+                    "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt] [--stats-overlay 1]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -225,6 +230,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "--post: not with --ranks (a band rank would bloom its own rows only)\n");
       return 1;
     }
+  }
+  if (stats_overlay && (views || ranks > 1)) {
+    fprintf(stderr, "--stats-overlay: not with --views or --ranks\n");
+    return 1;
   }
   float ae_key = 0.f, ae_adapt = 0.f;
   if (!ae_arg.empty()) {
@@ -538,6 +547,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--auto-exposure: the library has no auto-exposure (include/svr_exposure.h)\n");
     return 1;
   }
+  if (stats_overlay && !(eng.api.svr_draw_overlay && eng.api.svr_overlay_font)) {
+    fprintf(stderr, "--stats-overlay: the library has no overlay pass (include/svr_overlay.h)\n");
+    return 1;
+  }
   if (!post_arg.empty() && !eng.api.svr_post_pass) {
     fprintf(stderr, "--post: the library has no post pass (include/svr_post.h)\n");
     return 1;
@@ -614,11 +627,13 @@ int main(int argc, char** argv) {
     dump(prefix + ".color", color.data(), color.size());
     dump(prefix + ".depth", depth.data(), depth.size());
     std::vector<uint8_t> swap;  // what copy_image leaves in the swapchain image (src/vk_engine.cpp:1277)
-    if (!eng.read_swapchain(swap)) {
+    std::string drawn;  // --stats-overlay: ... and what draw_imgui then draws onto it (src/vk_engine.cpp:1282)
+    if (!(stats_overlay ? eng.stats_overlay(swap, drawn) : eng.read_swapchain(swap))) {
       fprintf(stderr, "swapchain readback failed: %s\n", eng.error.c_str());
       return 1;
     }
     dump(prefix + ".swapchain", swap.data(), swap.size());
+    if (stats_overlay) dump(prefix + ".overlay.txt", drawn.data(), drawn.size());
   }
   if (views) {  // --views: layer k is what a run with --yaw <view k's yaw> leaves in the colour and depth targets
     std::vector<uint16_t> color;

@@ -1,11 +1,13 @@
 // svr_engine.cpp — see svr_engine.h.  Every function names the reference code it stands for.
 #include "svr_engine.h"
+#include "svr_overlay_text.h"
 
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 namespace svrhost {
@@ -54,6 +56,8 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_meter_exposure = reinterpret_cast<decltype(svr_meter_exposure)>(dlsym(handle, "svr_meter_exposure"));
   svr_set_post_auto_exposure = reinterpret_cast<decltype(svr_set_post_auto_exposure)>(dlsym(handle, "svr_set_post_auto_exposure"));
   svr_read_exposure = reinterpret_cast<decltype(svr_read_exposure)>(dlsym(handle, "svr_read_exposure"));
+  svr_draw_overlay = reinterpret_cast<decltype(svr_draw_overlay)>(dlsym(handle, "svr_draw_overlay"));
+  svr_overlay_font = reinterpret_cast<decltype(svr_overlay_font)>(dlsym(handle, "svr_overlay_font"));
   return ok;
 }
 void SvrApi::unload() {
@@ -701,5 +705,66 @@ bool SvrEngine::read_view_layers(std::vector<uint16_t>& color, std::vector<float
     return false;
   }
   return true;
+}
+
+// ---------------------------------------------------------------- the stats window (include/svr_overlay.h)
+bool SvrEngine::stats_overlay(std::vector<uint8_t>& image, std::string& drawn) {
+  if (!api.svr_draw_overlay || !api.svr_overlay_font) {
+    error = "--stats-overlay: the library has no overlay pass (include/svr_overlay.h)";
+    return false;
+  }
+  if (!g_hip.load()) {
+    error = "--stats-overlay: no HIP runtime to allocate the swapchain image";
+    return false;
+  }
+  const uint32_t sw = swapchain_width ? swapchain_width : width, sh = swapchain_height ? swapchain_height : height;
+  const uint8_t* atlas = nullptr;
+  uint32_t aw = 0, ah = 0, cw = 0, ch = 0, first = 0, n = 0;
+  api.svr_overlay_font(&atlas, &aw, &ah, &cw, &ch, &first, &n);
+  void *d_image = nullptr, *d_atlas = nullptr;
+  bool ok = false;
+  do {
+    if (g_hip.malloc_(&d_image, (size_t)sw * sh * 4) || g_hip.malloc_(&d_atlas, (size_t)aw * ah) || g_hip.memcpy_(d_atlas, atlas, (size_t)aw * ah, HIP_H2D)) {
+      error = "--stats-overlay: hipMalloc or hipMemcpy failed";
+      break;
+    }
+    if (api.svr_copy_to_swapchain(ctx, d_image, sw, sh, SVR_SWAPCHAIN_B8G8R8A8)) {  // src/vk_engine.cpp:1276
+      error = api.svr_last_error();
+      break;
+    }
+    // draw_imgui (src/vk_engine.cpp:1282): the stats window of src/vk_engine.cpp:1186-1190
+    OverlayListBuilder b(aw, ah, cw, ch, first, n);
+    static const uint8_t ink[4] = {255, 255, 255, 255};
+    char line[5][96];
+    snprintf(line[0], sizeof(line[0]), "frametime %f ms", (double)stats.frame_time);
+    snprintf(line[1], sizeof(line[1]), "draw time %f ms", (double)stats.mesh_draw_time);
+    snprintf(line[2], sizeof(line[2]), "update time %f ms", (double)stats.scene_update_time);
+    snprintf(line[3], sizeof(line[3]), "triangles %i", stats.triangle_count);
+    snprintf(line[4], sizeof(line[4]), "draws %i", stats.drawcall_count);
+    const int wx = 10, wy = 10, ww = 150, wh = 64;
+    b.window((float)wx, (float)wy, (float)ww, (float)wh, "stats");
+    drawn = "window " + std::to_string(wx) + " " + std::to_string(wy) + " " + std::to_string(ww) + " " + std::to_string(wh) + " stats\n";
+    for (int k = 0; k < 5; k++) {
+      const int tx = wx + 4, ty = wy + 16 + 9 * k;
+      b.text((float)tx, (float)ty, line[k], ink);
+      drawn += "text " + std::to_string(tx) + " " + std::to_string(ty) + " " + line[k] + "\n";
+    }
+    const SvrOverlayTexture tex = {d_atlas, aw, ah, SVR_OVERLAY_TEX_A8, 0u};
+    const SvrOverlayList list = b.list(&tex, 1);
+    if (api.svr_draw_overlay(ctx, d_image, sw, sh, SVR_SWAPCHAIN_B8G8R8A8, &list) || api.svr_sync(ctx)) {
+      error = api.svr_last_error();
+      break;
+    }
+    image.resize((size_t)sw * sh * 4);
+    if (g_hip.memcpy_(image.data(), d_image, image.size(), HIP_D2H)) {
+      error = "--stats-overlay: hipMemcpy failed";
+      break;
+    }
+    ok = true;
+  } while (false);
+  if (ctx) api.svr_sync(ctx);  // nothing in flight names the image or the atlas
+  if (d_image) g_hip.free_(d_image);
+  if (d_atlas) g_hip.free_(d_atlas);
+  return ok;
 }
 }  // namespace svrhost

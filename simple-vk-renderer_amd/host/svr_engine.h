@@ -26,6 +26,7 @@
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
+#include "../../include/svr_overlay.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -63,6 +64,8 @@ struct SvrApi {
   SVR_FN(svr_ambient_pass) SVR_FN(svr_set_light_ambient_occlusion)
   // include/svr_exposure.h: optional (HIP library only), needed by SvrEngine::meter_exposure
   SVR_FN(svr_meter_exposure) SVR_FN(svr_set_post_auto_exposure) SVR_FN(svr_read_exposure)
+  // include/svr_overlay.h: optional (HIP library only), needed by SvrEngine::stats_overlay
+  SVR_FN(svr_draw_overlay) SVR_FN(svr_overlay_font)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -218,7 +221,12 @@ struct SvrEngine {
   SvrDrawList draw_list = 0;
   DrawContext list_context;  // what draw_list holds
   bool sync_draw_list();
-  bool draw();  // update_scene -> draw_background -> draw_geometry (ImGui/present have no counterpart)
+  bool draw();  // update_scene -> draw_background -> draw_geometry (the present has no counterpart; draw_imgui: stats_overlay)
+  // The stats window (svr_demo --stats-overlay 1, include/svr_overlay.h): what draw() does behind draw_geometry
+  // (src/vk_engine.cpp:1276-1282) — the copy to a swapchain image, then draw_imgui's window with the five lines of
+  // src/vk_engine.cpp:1186-1190 onto that image by svr_draw_overlay.  image: the swapchain image afterwards (B8G8R8A8);
+  // drawn: the builder calls it made, a line each ("window x y w h title", "text x y string").
+  bool stats_overlay(std::vector<uint8_t>& image, std::string& drawn);
   // Multiview (svr_demo --views N, include/svr_views.h): N cameras at main_camera's position, yaw stepped by 2 pi / N.
   // The layers live in device memory of the HIP runtime the library runs on; each starts as the context's colour
   // target (the background just drawn) and gets view k of the draw context, immediate or retained.
