@@ -130,6 +130,9 @@ OVERLAY_SYMBOLS = ["svr_draw_overlay", "svr_debug_read_overlay_stats", "svr_over
 OVERLAY_MAX_TRIANGLES, OVERLAY_MAX_CMDS, OVERLAY_MAX_TEXTURES, OVERLAY_MAX_TEXTURE_EXTENT = 65536, 4096, 16, 16384
 OVERLAY_TEX_RGBA8, OVERLAY_TEX_A8 = 0, 1
 OVERLAY_FONT_WHITE_X, OVERLAY_FONT_WHITE_Y = 92, 43
+# include/svr_upscale.h: the upscaled present (bicubic magnification, anti-ringing clamp, adaptive sharpen), HIP library only
+UPSCALE_SYMBOLS = ["svr_upscale_to_swapchain", "svr_read_upscaled"]
+UPSCALE_NO_SHARPEN = 1
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -197,6 +200,10 @@ class SvrOverlayList(C.Structure):  # include/svr_overlay.h
 
 class SvrOverlayStats(C.Structure):  # include/svr_overlay.h
     _fields_ = [("triangles", C.c_uint32), ("kept", C.c_uint32), ("tiles", C.c_uint32)]
+
+
+class SvrUpscalePass(C.Structure):  # include/svr_upscale.h
+    _fields_ = [("sharpness", C.c_float), ("flags", C.c_uint32)]
 
 
 OVERLAY_VERTEX_DTYPE = np.dtype([("pos", "<f4", 2), ("uv", "<f4", 2), ("col", "<u4")])
@@ -342,6 +349,10 @@ class SvrLib:
             L.svr_draw_overlay.argtypes = [P, P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(SvrOverlayList)]
             L.svr_debug_read_overlay_stats.argtypes = [P, C.POINTER(SvrOverlayStats)]
             L.svr_overlay_font.argtypes = [C.POINTER(C.POINTER(C.c_uint8))] + [C.POINTER(C.c_uint32)] * 6
+        self.has_upscale = hasattr(L, "svr_upscale_to_swapchain")
+        if self.has_upscale:
+            L.svr_upscale_to_swapchain.argtypes = [P, C.POINTER(SvrUpscalePass), P, C.c_uint32, C.c_uint32, C.c_int]
+            L.svr_read_upscaled.argtypes = [P, C.POINTER(SvrUpscalePass), C.c_uint32, C.c_uint32, C.c_int, P, C.c_size_t]
         self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
         if self.has_depth_load:
             L.svr_set_depth_load_op.argtypes = [P, C.c_int]
@@ -1030,6 +1041,27 @@ class Renderer:
         st = SvrOverlayStats()
         self.lib.check(self.lib.lib.svr_debug_read_overlay_stats(self.h, C.byref(st)))
         return st
+
+    # ---- the upscaled present (include/svr_upscale.h)
+    def _need_upscale(self):
+        if not getattr(self.lib, "has_upscale", False):
+            raise SvrError(-5, f"{self.lib.backend} has no upscaled present (include/svr_upscale.h)")
+
+    def upscale_to_swapchain(self, dst, width, height, fmt=0, sharpness=0.5, flags=0):
+        """svr_upscale_to_swapchain: magnify the colour target into the width x height UNORM8 image at dst (a device
+        pointer or a torch tensor) with a Catmull-Rom filter, an anti-ringing clamp and, unless UPSCALE_NO_SHARPEN, a
+        contrast-adaptive sharpen"""
+        self._need_upscale()
+        p = SvrUpscalePass(float(sharpness), int(flags))
+        self.lib.check(self.lib.lib.svr_upscale_to_swapchain(self.h, C.byref(p), overlay_device_ptr(dst), int(width), int(height), int(fmt)))
+
+    def read_upscaled(self, width, height, fmt=0, sharpness=0.5, flags=0):
+        """svr_read_upscaled -> uint8 [height, width, 4]: the same image, behind everything enqueued so far (fences)"""
+        self._need_upscale()
+        p = SvrUpscalePass(float(sharpness), int(flags))
+        out = np.empty((height, width, 4), dtype=np.uint8)
+        self.lib.check(self.lib.lib.svr_read_upscaled(self.h, C.byref(p), int(width), int(height), int(fmt), out.ctypes.data, out.nbytes))
+        return out
 
     # ---- the depth loadOp (include/svr_load.h)
     def _need_depth_load(self):

@@ -709,13 +709,6 @@ int svr_draw_background(SvrContext* ctx, int effect, const float data[16]) {
   return log_op(ctx, std::move(op));
 }
 
-static int blit_checks(SvrContext* ctx, const void* dst, uint32_t dw, uint32_t dh, int fmt, const char* who) {
-  if (!ctx || !dst) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
-  if (dw == 0 || dh == 0 || dw > 16384 || dh > 16384) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": extent must be in 1..16384");
-  if (fmt != SVR_SWAPCHAIN_B8G8R8A8 && fmt != SVR_SWAPCHAIN_R8G8B8A8) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown format");
-  return SVR_OK;
-}
-
 int svr_copy_to_swapchain(SvrContext* ctx, void* dst_dev, uint32_t dw, uint32_t dh, int fmt) {
   if (int e = blit_checks(ctx, dst_dev, dw, dh, fmt, "svr_copy_to_swapchain")) return e;
   if (int e = use_device(ctx)) return e;

@@ -251,9 +251,12 @@ struct OverlayOp {
   std::vector<SvrOverlayTexture> textures;
 };
 
+// svr_upscale_to_swapchain: the kernel's parameters as recorded, the sharpen's peak by value among them
+using UpscaleOp = UpscaleLaunch;
+
 struct LoggedOp {
   int slot;  // index into h_counters / op_done / h_stage
-  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp> what;
+  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp> what;
   template <class Op> LoggedOp(int slot_, Op&& op) : slot(slot_), what(std::forward<Op>(op)) {}
   const PassOp* as_pass() const { return std::get_if<PassOp>(&what); }
 };
@@ -425,6 +428,14 @@ inline uint32_t owned_tile_rows(const SvrContext* ctx) {
   return all > ctx->roff ? (all - ctx->roff + ctx->rstride - 1) / ctx->rstride : 0u;
 }
 
+// what every present into a swapchain image checks first (svr_copy_to_swapchain, svr_read_swapchain, include/svr_upscale.h)
+inline int blit_checks(SvrContext* ctx, const void* dst, uint32_t dw, uint32_t dh, int fmt, const char* who) {
+  if (!ctx || !dst) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+  if (dw == 0 || dh == 0 || dw > 16384 || dh > 16384) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": extent must be in 1..16384");
+  if (fmt != SVR_SWAPCHAIN_B8G8R8A8 && fmt != SVR_SWAPCHAIN_R8G8B8A8) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown format");
+  return SVR_OK;
+}
+
 // ---------------------------------------------------------------- svr_log.hip
 int harvest_timing(SvrContext* ctx, int slot);  // fold one finished slot of the timing ring into the running means
 int retire_ops(SvrContext* ctx, bool blocking);
@@ -447,6 +458,7 @@ int submit(SvrContext* ctx, const TemporalOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const AmbientOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const ExposureOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const OverlayOp& op, int slot, bool replaying);
+int submit(SvrContext* ctx, const UpscaleOp& op, int slot, bool replaying);
 // log the finished payload of any of those kinds in a free slot and submit it; the entry stays in the log if the submit
 // fails
 template <class Op> int log_op(SvrContext* ctx, Op&& op) {

@@ -6,6 +6,7 @@
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
+#include "../../include/svr_upscale.h"
 #include "svr_device.h"
 
 namespace svr {
@@ -183,6 +184,22 @@ struct OverlayLaunch {
 };
 // one overlay_setup_kernel and one overlay_tile_kernel, on s
 void launch_overlay(const OverlayLaunch& A, hipStream_t s);
+// k_upscale.hip: the upscaled present (include/svr_upscale.h)
+struct UpscaleLaunch {
+  const void* src;              // the colour target, W x H texels of src_fmt: read only
+  int src_fmt;                  // SVR_COLOR_*
+  uint32_t W, H;
+  uint32_t* dst;                // dw x dh UNORM8 texels, the caller's (W <= dw, H <= dh)
+  uint32_t dw, dh;
+  int dst_fmt;                  // SVR_SWAPCHAIN_*
+  float su, sv;                 // C51: (float)W / (float)dw and (float)H / (float)dh, divided once, on the host
+  float peak;                   // C53: -1.0f / (8.0f - 3.0f * sharpness), computed once, at the call
+  uint32_t sharpen;             // 0 under SVR_UPSCALE_NO_SHARPEN
+  const uint32_t* poison;
+  uint32_t* status;             // svr_set_present_status (may be null): 1 when void, else status_ok
+};
+// one upscale_kernel, on s
+void launch_upscale(const UpscaleLaunch& A, uint32_t status_ok, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

@@ -385,6 +385,10 @@ int submit(SvrContext* ctx, const OverlayOp& op, int slot, bool) {
   launch_overlay(L, ctx->stream);
   return launched();
 }
+int submit(SvrContext* ctx, const UpscaleOp& op, int, bool replaying) {
+  launch_upscale(op, replaying ? 2u : 0u, ctx->stream);
+  return launched();
+}
 
 namespace {
 

@@ -1,5 +1,5 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, auto-exposure, temporal antialiasing, ambient occlusion and the UI overlay, with
+// culling's calls, the deferred lighting pass, the HDR post pass, auto-exposure, temporal antialiasing, ambient occlusion, the UI overlay and the upscaled present, with
 // their targets and read-backs.  Each validates its arguments, allocates what its first call needs, records its
 // kernels' parameters in a payload of its kind and logs it (svr_context.h, svr_log.hip).
 #include <cmath>
@@ -606,6 +606,62 @@ int svr_overlay_font(const uint8_t** a8, uint32_t* width, uint32_t* height, uint
   if (cell_h) *cell_h = FONT_CELL_H;
   if (first_char) *first_char = FONT_FIRST;
   if (n_chars) *n_chars = FONT_CHARS;
+  return SVR_OK;
+}
+
+// ---------------------------------------------------------------- the upscaled present (include/svr_upscale.h)
+static_assert(sizeof(SvrUpscalePass) == 8, "include/svr_upscale.h");
+
+// the checks of both entry points, then the kernel's parameters; nothing of the context changes
+static int upscale_launch(SvrContext* ctx, const SvrUpscalePass* pass, void* dst, uint32_t dw, uint32_t dh, int fmt, const char* who, UpscaleLaunch* out) {
+  const std::string fn(who);
+  if (!pass) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": null argument");
+  if (int e = blit_checks(ctx, dst, dw, dh, fmt, who)) return e;
+  if (!(std::isfinite(pass->sharpness) && pass->sharpness >= 0.0f && pass->sharpness <= 1.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": the sharpness must be finite, at least 0 and at most 1");
+  if (pass->flags & ~(uint32_t)SVR_UPSCALE_NO_SHARPEN) return fail(SVR_ERR_INVALID_ARGUMENT, fn + ": unknown flag bits");
+  if (dw < ctx->W || dh < ctx->H) return fail(SVR_ERR_UNSUPPORTED, fn + ": the destination is smaller than the colour target (svr_copy_to_swapchain minifies)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, fn + ": not under svr_set_row_interleave with a stride above 1");
+  UpscaleLaunch& U = *out;
+  U = UpscaleLaunch{};
+  U.src = ctx->color;
+  U.src_fmt = ctx->fmt;
+  U.W = ctx->W;
+  U.H = ctx->H;
+  U.dst = static_cast<uint32_t*>(dst);
+  U.dw = dw;
+  U.dh = dh;
+  U.dst_fmt = fmt;
+  U.su = (float)ctx->W / (float)dw;  // C51
+  U.sv = (float)ctx->H / (float)dh;
+  U.peak = -1.0f / (8.0f - 3.0f * pass->sharpness);  // C53: computed once, here; it travels in the operation by value
+  U.sharpen = (pass->flags & SVR_UPSCALE_NO_SHARPEN) ? 0u : 1u;
+  U.poison = ctx->d_poison.get();
+  return SVR_OK;
+}
+
+int svr_upscale_to_swapchain(SvrContext* ctx, const SvrUpscalePass* pass, void* dst_dev, uint32_t dw, uint32_t dh, int fmt) {
+  UpscaleOp op;
+  if (int e = upscale_launch(ctx, pass, dst_dev, dw, dh, fmt, "svr_upscale_to_swapchain", &op)) return e;
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  if (int e = flush_clear(ctx)) return e;  // this call reads colour: a deferred clear lands first
+  op.status = ctx->present_status;
+  return log_op(ctx, std::move(op));
+}
+
+int svr_read_upscaled(SvrContext* ctx, const SvrUpscalePass* pass, uint32_t dw, uint32_t dh, int fmt, void* dst_host, size_t bytes) {
+  UpscaleLaunch U;
+  if (int e = upscale_launch(ctx, pass, dst_host, dw, dh, fmt, "svr_read_upscaled", &U)) return e;
+  if (bytes < (size_t)dw * dh * 4) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_read_upscaled: buffer too small");
+  if (int e = use_device(ctx)) return e;
+  if (int e = finish_pending(ctx)) return e;  // the read-back is a fence
+  if (int e = ctx->d_cvt.ensure((size_t)dw * dh * 4)) return e;
+  U.dst = static_cast<uint32_t*>(ctx->d_cvt.p);
+  launch_upscale(U, 0u, ctx->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(dst_host, ctx->d_cvt.p, (size_t)dw * dh * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return SVR_OK;
 }
 

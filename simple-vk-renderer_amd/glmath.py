@@ -270,3 +270,11 @@ def temporal_reproject(prev_viewproj, viewproj):
 def pixels_per_unit(proj, height):
     """SvrAmbientPass.pixels_per_unit: the pixels one world unit spans at clip w = 1 in a target of the given height"""
     return (f32(0.5) * f32(height)) * abs(f32(np.asarray(proj, dtype=f32)[1][1]))
+
+
+# ---- the upscaled present (include/svr_upscale.h): the caller's side, host/svr_math.h's render_extent
+def render_extent(window_w, window_h, scale):
+    """(width, height) a frame is rendered at under a render scale: the reference's expression (src/vk_engine.cpp:1220-1222),
+    a float product truncated to uint32, each way; at least 1"""
+    s = f32(scale)
+    return max(int(f32(window_w) * s), 1), max(int(f32(window_h) * s), 1)

@@ -30,6 +30,12 @@
 //           target is copied to a swapchain image in device memory and the reference's stats window (frametime, draw time,
 //           update time, triangles, draws) is drawn onto it by svr_draw_overlay; <prefix>.swapchain is then that image and
 //           <prefix>.overlay.txt the calls that built the list; not with --views or --ranks
+//       --render-scale <s> [--upscale <sharpness>|off]: the reference's _render_scale (src/vk_engine.h:121), bound: --width and
+//           --height are the window's; the frame is rendered at the reference's render extent (the float product truncated,
+//           src/vk_engine.cpp:1220-1222) and <prefix>.color / .depth have that extent.  <prefix>.swapchain is the window-sized
+//           image: with --upscale <sharpness 0..1> the upscaled present's (include/svr_upscale.h, HIP library only), with
+//           --upscale off (the default) the scaled svr_copy_to_swapchain's, the reference's stretch.  --stats-overlay 1 draws
+//           over either at the window's resolution.  s in (0, 1]; not with --views or --ranks
 //       --occlusion off|last|prepass: occlusion culling (include/svr_occlusion.h, HIP library only): against the pyramid of
 //           the previous frame's depth, or of a depth-only pass of the occluders (the opaque default material's objects;
 //           with --gltf every opaque material's) drawn first; the dumps are those of --occlusion off
@@ -99,7 +105,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false, stats_overlay = false;
-  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg;
+  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, scale_arg, upscale_arg = "off";
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -129,6 +135,8 @@ int main(int argc, char** argv) {
     else if (a == "--ao") ao_arg = argv[i + 1];  // <radius>:<intensity> (include/svr_ambient.h)
     else if (a == "--auto-exposure") ae_arg = argv[i + 1];  // <key>:<adapt> (include/svr_exposure.h)
     else if (a == "--stats-overlay") stats_overlay = atoi(argv[i + 1]) != 0;  // include/svr_overlay.h
+    else if (a == "--render-scale") scale_arg = argv[i + 1];  // <s> (include/svr_upscale.h)
+    else if (a == "--upscale") upscale_arg = argv[i + 1];  // <sharpness> | off
     else if (a == "--exposure") post.exposure = (float)atof(argv[i + 1]);
     else if (a == "--bloom-threshold") post.bloom_threshold = (float)atof(argv[i + 1]);
     else if (a == "--bloom-intensity") post.bloom_intensity = (float)atof(argv[i + 1]);
@@ -166,7 +174,8 @@ int main(int argc, char** argv) {
                     "                [--retained 1] [--views N] [--yaw radians] [--depth-only 1] [--deferred 1]\n"
                     "                [--occlusion off|last|prepass]\n"
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
-                    "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt] [--stats-overlay 1]\n");
+                    "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt] [--stats-overlay 1]\n"
+                    "                [--render-scale s --upscale sharpness|off]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -228,6 +237,32 @@ int main(int argc, char** argv) {
     }
     if (ranks > 1) {
       fprintf(stderr, "--post: not with --ranks (a band rank would bloom its own rows only)\n");
+      return 1;
+    }
+  }
+  float render_scale = 1.f, upscale_sharpness = 0.f;
+  const bool upscale = upscale_arg != "off";
+  if (!scale_arg.empty()) {
+    char* end = nullptr;
+    render_scale = strtof(scale_arg.c_str(), &end);
+    if (!end || *end || end == scale_arg.c_str() || !(render_scale > 0.f && render_scale <= 1.f)) {
+      fprintf(stderr, "--render-scale: expected a scale in (0, 1], got '%s'\n", scale_arg.c_str());
+      return 2;
+    }
+    if (views || ranks > 1) {
+      fprintf(stderr, "--render-scale: not with --views or --ranks\n");
+      return 1;
+    }
+  }
+  if (upscale) {
+    char* end = nullptr;
+    upscale_sharpness = strtof(upscale_arg.c_str(), &end);
+    if (!end || *end || end == upscale_arg.c_str() || !(upscale_sharpness >= 0.f && upscale_sharpness <= 1.f)) {
+      fprintf(stderr, "--upscale: expected a sharpness in [0, 1] or off, got '%s'\n", upscale_arg.c_str());
+      return 2;
+    }
+    if (views || ranks > 1) {
+      fprintf(stderr, "--upscale: not with --views or --ranks\n");
       return 1;
     }
   }
@@ -309,11 +344,15 @@ int main(int argc, char** argv) {
   }
   SvrEngine eng;
   eng.device = transport == "rccl" ? rank : 0;
+  eng.render_scale = render_scale;
+  eng.upscale = upscale;
+  eng.upscale_sharpness = upscale_sharpness;
   if (!eng.init(lib, w, h)) {
-    fprintf(stderr, "init failed: %s\n", eng.error.c_str());
+    fprintf(stderr, "%s%s\n", eng.error.rfind("--", 0) == 0 ? "" : "init failed: ", eng.error.c_str());
     return 1;
   }
   printf("backend %s, %ux%u\n", eng.api.svr_backend_name(), w, h);
+  if (!scale_arg.empty()) printf("render extent %ux%u\n", eng.width, eng.height);
 
   eng.current_background_effect = background;
   eng.retained = retained != 0;

@@ -58,6 +58,8 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_read_exposure = reinterpret_cast<decltype(svr_read_exposure)>(dlsym(handle, "svr_read_exposure"));
   svr_draw_overlay = reinterpret_cast<decltype(svr_draw_overlay)>(dlsym(handle, "svr_draw_overlay"));
   svr_overlay_font = reinterpret_cast<decltype(svr_overlay_font)>(dlsym(handle, "svr_overlay_font"));
+  svr_upscale_to_swapchain = reinterpret_cast<decltype(svr_upscale_to_swapchain)>(dlsym(handle, "svr_upscale_to_swapchain"));
+  svr_read_upscaled = reinterpret_cast<decltype(svr_read_upscaled)>(dlsym(handle, "svr_read_upscaled"));
   return ok;
 }
 void SvrApi::unload() {
@@ -134,12 +136,17 @@ SvrBounds loader_bounds(const std::vector<SvrVertex>& v, size_t initial_vtx) {  
 
 // ---------------------------------------------------------------- engine
 bool SvrEngine::init(const std::string& library_path, uint32_t w, uint32_t h) {
-  width = w;
-  height = h;
+  window_width = w;
+  window_height = h;
+  svrm::render_extent(w, h, render_scale, &width, &height);  // src/vk_engine.cpp:1220-1222
   if (!api.load(library_path, &error)) return false;
+  if (upscale && !(api.svr_upscale_to_swapchain && api.svr_read_upscaled)) {
+    error = "--upscale: the library has no upscaled present (include/svr_upscale.h)";
+    return false;
+  }
   SvrConfig cfg{};
-  cfg.width = w;
-  cfg.height = h;
+  cfg.width = width;
+  cfg.height = height;
   cfg.color_format = SVR_COLOR_RGBA16F;  // _draw_image format, src/vk_engine.cpp:749
   cfg.device = device;
   if (api.svr_create(&cfg, &ctx)) {
@@ -265,9 +272,11 @@ bool SvrEngine::draw_background() {  // src/vk_engine.cpp:1341-1355: dispatch th
 }
 
 bool SvrEngine::read_swapchain(std::vector<uint8_t>& out) {
-  uint32_t sw = swapchain_width ? swapchain_width : width, sh = swapchain_height ? swapchain_height : height;
+  uint32_t sw = swapchain_width ? swapchain_width : window_width, sh = swapchain_height ? swapchain_height : window_height;
   out.resize((size_t)sw * sh * 4);
-  if (api.svr_read_swapchain(ctx, sw, sh, SVR_SWAPCHAIN_B8G8R8A8, out.data(), out.size())) {
+  const SvrUpscalePass up = {upscale_sharpness, 0u};
+  if (upscale ? api.svr_read_upscaled(ctx, &up, sw, sh, SVR_SWAPCHAIN_B8G8R8A8, out.data(), out.size())
+              : api.svr_read_swapchain(ctx, sw, sh, SVR_SWAPCHAIN_B8G8R8A8, out.data(), out.size())) {
     error = api.svr_last_error();
     return false;
   }
@@ -717,7 +726,7 @@ bool SvrEngine::stats_overlay(std::vector<uint8_t>& image, std::string& drawn) {
     error = "--stats-overlay: no HIP runtime to allocate the swapchain image";
     return false;
   }
-  const uint32_t sw = swapchain_width ? swapchain_width : width, sh = swapchain_height ? swapchain_height : height;
+  const uint32_t sw = swapchain_width ? swapchain_width : window_width, sh = swapchain_height ? swapchain_height : window_height;
   const uint8_t* atlas = nullptr;
   uint32_t aw = 0, ah = 0, cw = 0, ch = 0, first = 0, n = 0;
   api.svr_overlay_font(&atlas, &aw, &ah, &cw, &ch, &first, &n);
@@ -728,7 +737,9 @@ bool SvrEngine::stats_overlay(std::vector<uint8_t>& image, std::string& drawn) {
       error = "--stats-overlay: hipMalloc or hipMemcpy failed";
       break;
     }
-    if (api.svr_copy_to_swapchain(ctx, d_image, sw, sh, SVR_SWAPCHAIN_B8G8R8A8)) {  // src/vk_engine.cpp:1276
+    // src/vk_engine.cpp:1276, or the upscaled present in its place (include/svr_upscale.h)
+    const SvrUpscalePass up = {upscale_sharpness, 0u};
+    if (upscale ? api.svr_upscale_to_swapchain(ctx, &up, d_image, sw, sh, SVR_SWAPCHAIN_B8G8R8A8) : api.svr_copy_to_swapchain(ctx, d_image, sw, sh, SVR_SWAPCHAIN_B8G8R8A8)) {
       error = api.svr_last_error();
       break;
     }

@@ -27,6 +27,7 @@
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
 #include "../../include/svr_overlay.h"
+#include "../../include/svr_upscale.h"
 #include "../../include/svr_views.h"
 #include "svr_math.h"
 
@@ -66,6 +67,8 @@ struct SvrApi {
   SVR_FN(svr_meter_exposure) SVR_FN(svr_set_post_auto_exposure) SVR_FN(svr_read_exposure)
   // include/svr_overlay.h: optional (HIP library only), needed by SvrEngine::stats_overlay
   SVR_FN(svr_draw_overlay) SVR_FN(svr_overlay_font)
+  // include/svr_upscale.h: optional (HIP library only), needed by SvrEngine::upscale
+  SVR_FN(svr_upscale_to_swapchain) SVR_FN(svr_read_upscaled)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -146,7 +149,16 @@ std::shared_ptr<LoadedScene> load_gltf_meshes(SvrEngine* engine, const std::stri
 struct SvrEngine {
   SvrApi api;
   SvrContext* ctx = nullptr;
-  uint32_t width = 1700, height = 900;  // _window_extent, src/vk_engine.h:219
+  uint32_t width = 1700, height = 900;  // _draw_extent: the context's extent, render_extent(window, render_scale)
+  // Render scale (svr_demo --render-scale <s> [--upscale <sharpness>|off], include/svr_upscale.h): _render_scale of
+  // src/vk_engine.h:121, bound.  Set before init, which takes the window's extent (_window_extent, src/vk_engine.h:219) and
+  // creates the context at svrm::render_extent of it; the swapchain image stays at the window's extent.  upscale: read_swapchain
+  // and stats_overlay present with svr_upscale_to_swapchain at upscale_sharpness; without it with the scaled
+  // svr_copy_to_swapchain, the reference's stretch.
+  float render_scale = 1.f;
+  bool upscale = false;
+  float upscale_sharpness = 0.5f;
+  uint32_t window_width = 1700, window_height = 900;
   int device = 0;                        // SvrConfig.device: the rank's GPU in the sharded form (svr_dist.h)
   int frame_number = 0;
   EngineStats stats;
@@ -170,7 +182,7 @@ struct SvrEngine {
   // init_background_pipelines (src/vk_engine.cpp:920-1000): gradient (white, white) and sky (0.1,0.2,0.4,0.97)
   std::vector<ComputeEffect> background_effects;
   int current_background_effect = 0;
-  uint32_t swapchain_width = 0, swapchain_height = 0;  // _swap_chain_extent; 0 = the draw extent
+  uint32_t swapchain_width = 0, swapchain_height = 0;  // _swap_chain_extent; 0 = the window's extent
   bool draw_background();
   bool draw_geometry();
   // Depth-only frames (svr_demo --depth-only 1, include/svr_depth.h): the draw context's opaque surfaces (or the draw

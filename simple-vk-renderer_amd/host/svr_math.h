@@ -5,6 +5,7 @@
 // Column-major like glm::mat4: m[c][r].
 #pragma once
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 
 namespace svrm {
@@ -201,5 +202,14 @@ inline mat4 temporal_reproject(const mat4& prev_viewproj, const mat4& viewproj) 
 // (tests/test_ambient_math.py).
 // SvrAmbientPass.pixels_per_unit: the pixels one world unit spans at clip w = 1 in a target of the given height.
 inline float pixels_per_unit(const mat4& proj, float height) { return (0.5f * height) * std::fabs(proj.m[1][1]); }
+
+// ---- the upscaled present (include/svr_upscale.h): the caller's side; glmath.py's render_extent is the same
+// The extent a frame is rendered at under a render scale: the reference's expression (src/vk_engine.cpp:1220-1222), a float
+// product truncated to uint32, each way; at least 1.
+inline void render_extent(uint32_t window_w, uint32_t window_h, float scale, uint32_t* w, uint32_t* h) {
+  const uint32_t rw = (uint32_t)((float)window_w * scale), rh = (uint32_t)((float)window_h * scale);
+  *w = rw < 1u ? 1u : rw;
+  *h = rh < 1u ? 1u : rh;
+}
 
 }  // namespace svrm
