@@ -133,6 +133,9 @@ OVERLAY_FONT_WHITE_X, OVERLAY_FONT_WHITE_Y = 92, 43
 # include/svr_upscale.h: the upscaled present (bicubic magnification, anti-ringing clamp, adaptive sharpen), HIP library only
 UPSCALE_SYMBOLS = ["svr_upscale_to_swapchain", "svr_read_upscaled"]
 UPSCALE_NO_SHARPEN = 1
+# include/svr_fog.h: the fog pass (height fog and sun shafts marched through the shadow map), HIP library only
+FOG_SYMBOLS = ["svr_fog_pass"]
+FOG_MAX_STEPS = 64
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -204,6 +207,15 @@ class SvrOverlayStats(C.Structure):  # include/svr_overlay.h
 
 class SvrUpscalePass(C.Structure):  # include/svr_upscale.h
     _fields_ = [("sharpness", C.c_float), ("flags", C.c_uint32)]
+
+
+class SvrFogPass(C.Structure):  # include/svr_fog.h
+    _fields_ = [("inv_viewproj", C.c_float * 16), ("camera_position", C.c_float * 3), ("density", C.c_float),
+                ("height_falloff", C.c_float), ("height_base", C.c_float), ("max_distance", C.c_float), ("steps", C.c_uint32),
+                ("fog_color", C.c_float * 3), ("anisotropy", C.c_float), ("sunlight_direction", C.c_float * 4),
+                ("sun_color", C.c_float * 3), ("edge_sharpness", C.c_float), ("shadow_depth", C.c_void_p),
+                ("shadow_width", C.c_uint32), ("shadow_height", C.c_uint32), ("shadow_viewproj", C.c_float * 16),
+                ("shadow_bias", C.c_float), ("frame_index", C.c_uint32)]
 
 
 OVERLAY_VERTEX_DTYPE = np.dtype([("pos", "<f4", 2), ("uv", "<f4", 2), ("col", "<u4")])
@@ -353,6 +365,9 @@ class SvrLib:
         if self.has_upscale:
             L.svr_upscale_to_swapchain.argtypes = [P, C.POINTER(SvrUpscalePass), P, C.c_uint32, C.c_uint32, C.c_int]
             L.svr_read_upscaled.argtypes = [P, C.POINTER(SvrUpscalePass), C.c_uint32, C.c_uint32, C.c_int, P, C.c_size_t]
+        self.has_fog = hasattr(L, "svr_fog_pass")
+        if self.has_fog:
+            L.svr_fog_pass.argtypes = [P, C.POINTER(SvrFogPass)]
         self.has_depth_load = hasattr(L, "svr_set_depth_load_op")
         if self.has_depth_load:
             L.svr_set_depth_load_op.argtypes = [P, C.c_int]
@@ -395,6 +410,29 @@ def _f4(a):
 def _f16m(a):
     a = np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(16))
     return (C.c_float * 16)(*a.tolist())
+
+
+def fog_struct(inv_viewproj, camera_position, density, height_falloff=0.0, height_base=0.0, max_distance=100.0, steps=16,
+               fog_color=(0.5, 0.6, 0.7), sun_dir=(0.0, 1.0, 0.0, 0.0), sun_color=(0.0, 0.0, 0.0), anisotropy=0.0, shadow_ptr=None,
+               shadow_size=(0, 0), shadow_viewproj=None, shadow_bias=0.0, edge_sharpness=1.0, frame_index=0):
+    """an SvrFogPass (include/svr_fog.h) from Python values; sun_dir may have 3 or 4 components"""
+    p = SvrFogPass()
+    p.inv_viewproj = _f16m(inv_viewproj)
+    p.camera_position = (C.c_float * 3)(*[float(x) for x in camera_position])
+    p.density, p.height_falloff, p.height_base, p.max_distance = float(density), float(height_falloff), float(height_base), float(max_distance)
+    p.steps = int(steps)
+    p.fog_color = (C.c_float * 3)(*[float(x) for x in fog_color])
+    p.anisotropy = float(anisotropy)
+    p.sunlight_direction = _f4((list(sun_dir) + [0.0])[:4])
+    p.sun_color = (C.c_float * 3)(*[float(x) for x in list(sun_color)[:3]])
+    p.edge_sharpness = float(edge_sharpness)
+    if shadow_ptr:
+        p.shadow_depth = C.c_void_p(shadow_ptr)
+        p.shadow_width, p.shadow_height = int(shadow_size[0]), int(shadow_size[1])
+        p.shadow_viewproj = _f16m(shadow_viewproj)
+        p.shadow_bias = float(shadow_bias)
+    p.frame_index = int(frame_index) & 0xffffffff
+    return p
 
 
 def scene_struct(view, proj, viewproj, ambient, sun_dir, sun_color):
@@ -900,6 +938,18 @@ class Renderer:
             raise SvrError(-5, f"{self.lib.backend} has no post pass (include/svr_post.h)")
         p = SvrPostPass(float(exposure), float(bloom_threshold), float(bloom_intensity), int(bloom_levels), int(tonemap))
         self.lib.check(self.lib.lib.svr_post_pass(self.h, C.byref(p)))
+
+    # ---- the fog pass (include/svr_fog.h)
+    def fog_pass(self, inv_viewproj, camera_position, density, height_falloff=0.0, height_base=0.0, max_distance=100.0, steps=16,
+                 fog_color=(0.5, 0.6, 0.7), sun_dir=(0.0, 1.0, 0.0, 0.0), sun_color=(0.0, 0.0, 0.0), anisotropy=0.0, shadow_ptr=None,
+                 shadow_size=(0, 0), shadow_viewproj=None, shadow_bias=0.0, edge_sharpness=1.0, frame_index=0):
+        """svr_fog_pass: height fog and sun shafts over the scissor's pixels of the RGBA16F colour target, in place.
+        shadow_ptr: a device depth map of shadow_size = (width, height) drawn with shadow_viewproj, or None"""
+        if not getattr(self.lib, "has_fog", False):
+            raise SvrError(-5, f"{self.lib.backend} has no fog pass (include/svr_fog.h)")
+        p = fog_struct(inv_viewproj, camera_position, density, height_falloff, height_base, max_distance, steps, fog_color, sun_dir,
+                       sun_color, anisotropy, shadow_ptr, shadow_size, shadow_viewproj, shadow_bias, edge_sharpness, frame_index)
+        self.lib.check(self.lib.lib.svr_fog_pass(self.h, C.byref(p)))
 
     # ---- temporal antialiasing (include/svr_temporal.h)
     def _need_temporal(self):

@@ -15,6 +15,7 @@
 // Plain vector loads, LDS atomics and global integer atomics only; nothing is handed between workgroups of one launch.
 // Both kernels read the context's poison flag first: after an overflow they change nothing, so the working bins stay
 // zero across a void meter.
+#include "svr_exp2.h"
 #include "svr_launch.h"
 #include "svr_pixel.h"
 
@@ -144,18 +145,7 @@ struct ResolveArgs {
 __device__ const double kSubLog2[8] = {0x1.663f6fac91316p-4, 0x1.fbc16b902680ap-3, 0x1.91bba891f1709p-2, 0x1.0c10500d63aa6p-1,
                                        0x1.49a784bcd1b8bp-1, 0x1.82809d5be7073p-1, 0x1.b74948f5532dap-1, 0x1.e88c6b3626a73p-1};
 
-// C41: 2^x for |x| <= 16
-__device__ __forceinline__ float exp2_poly(float x) {
-  const float n = floorf(x), f = x - n;  // f in [0, 1], exact
-  float p = 0x1.ca8f0ap-13f;
-  p = fmaf(p, f, 0x1.44d4d2p-10f);
-  p = fmaf(p, f, 0x1.3d54d8p-7f);
-  p = fmaf(p, f, 0x1.c67f5p-5f);
-  p = fmaf(p, f, 0x1.ebfdf2p-3f);
-  p = fmaf(p, f, 0x1.62e428p-1f);
-  p = fmaf(p, f, 1.0f);
-  return __uint_as_float(__float_as_uint(p) + ((uint32_t)(int)n << 23));  // p in [1, 2.0000003]: the exponent takes n
-}
+// C41's 2^x for |x| <= 16: exp2_poly of svr_exp2.h
 
 __global__ __launch_bounds__(256) void exposure_resolve_kernel(ResolveArgs A) {
   if (*A.poison) return;

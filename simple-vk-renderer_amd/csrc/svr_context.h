@@ -22,6 +22,7 @@
 #include "../../include/svr_attributes.h"
 #include "../../include/svr_ids.h"
 #include "../../include/svr_lighting.h"
+#include "../../include/svr_fog.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
@@ -253,10 +254,14 @@ struct OverlayOp {
 
 // svr_upscale_to_swapchain: the kernel's parameters as recorded, the sharpen's peak by value among them
 using UpscaleOp = UpscaleLaunch;
+// svr_fog_pass: the kernels' parameters as recorded, by value (the shadow map and the scratch images by address)
+struct FogOp {
+  FogLaunch launch{};
+};
 
 struct LoggedOp {
   int slot;  // index into h_counters / op_done / h_stage
-  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp> what;
+  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp, FogOp> what;
   template <class Op> LoggedOp(int slot_, Op&& op) : slot(slot_), what(std::forward<Op>(op)) {}
   const PassOp* as_pass() const { return std::get_if<PassOp>(&what); }
 };
@@ -374,6 +379,9 @@ struct Context {
   // svr_post_pass: the level images of the bloom (4 halves per texel), sized for the context's extent; allocated once, by
   // the first post pass
   DevPtr<uint2> d_post_levels;
+  // svr_fog_pass: the half-resolution images, (S.rgb, T) per block and then t_end per block (fog_blocks of the context's
+  // extent each); allocated once, by the first fog pass
+  DevPtr<float4> d_fog;
   // svr_temporal_resolve: the two history images (4 halves per texel, the context's extent), allocated and zeroed by the
   // first resolve.  temporal_read names the one the next resolve reads; temporal_has: a resolve was accepted, with the
   // scissor temporal_scissor.  All three change at an accepted call only, in call order.
@@ -459,6 +467,7 @@ int submit(SvrContext* ctx, const AmbientOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const ExposureOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const OverlayOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const UpscaleOp& op, int slot, bool replaying);
+int submit(SvrContext* ctx, const FogOp& op, int slot, bool replaying);
 // log the finished payload of any of those kinds in a free slot and submit it; the entry stays in the log if the submit
 // fails
 template <class Op> int log_op(SvrContext* ctx, Op&& op) {

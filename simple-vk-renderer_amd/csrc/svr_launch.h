@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
+#include "../../include/svr_fog.h"
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_post.h"
@@ -200,6 +201,38 @@ struct UpscaleLaunch {
 };
 // one upscale_kernel, on s
 void launch_upscale(const UpscaleLaunch& A, uint32_t status_ok, hipStream_t s);
+// k_fog.hip: the fog pass (include/svr_fog.h)
+struct FogLaunch {
+  uint2* color;                 // the RGBA16F colour target, W texels per row: the scissor's RGB halves are rewritten in place
+  const float* depth;           // the depth target, read as it stands in stream order
+  uint32_t W;
+  uint32_t sx, sy, sw, sh;      // the scissor: the image of the pass
+  uint32_t gw, gh;              // C55: the half-resolution grid, (sw + 1) / 2 by (sh + 1) / 2
+  float4* st;                   // the context's scratch: (S.rgb, T) per block, gw per row
+  float* te;                    // ... and t_end per block
+  float two_over_w, two_over_h; // C17: divided once, on the host
+  float inv_viewproj[16];
+  float cam[3];
+  float density;
+  float kh;                     // C57: height_falloff * log2(e), one product at the call
+  float height_base, max_distance;
+  uint32_t steps;
+  float fog_color[3], sun_color[3];
+  float sun[3];                 // C58: L / |L| (zero for a direction without a length)
+  float one_plus_g2, minus_2g, one_minus_g2;  // C58: 1 + g g, -2 g, 1 - g g, computed once, at the call
+  const float* shadow_depth;    // null: unshadowed
+  uint32_t shadow_w, shadow_h;
+  float shadow_half_w, shadow_half_h;  // C18: Ws / 2, Hs / 2 (exact)
+  float shadow_viewproj[16];
+  float shadow_bias;
+  float edge;                   // C59: edge_sharpness
+  uint32_t frame;
+  const uint32_t* poison;
+};
+// C55: the blocks a context of W x H needs scratch for
+inline size_t fog_blocks(uint32_t w, uint32_t h) { return (size_t)((w + 1u) / 2u) * ((h + 1u) / 2u); }
+// one fog_march_kernel and one fog_composite_kernel, on s
+void launch_fog(const FogLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

@@ -389,6 +389,10 @@ int submit(SvrContext* ctx, const UpscaleOp& op, int, bool replaying) {
   launch_upscale(op, replaying ? 2u : 0u, ctx->stream);
   return launched();
 }
+int submit(SvrContext* ctx, const FogOp& op, int, bool) {
+  launch_fog(op.launch, ctx->stream);
+  return launched();
+}
 
 namespace {
 

@@ -1,5 +1,5 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, auto-exposure, temporal antialiasing, ambient occlusion, the UI overlay and the upscaled present, with
+// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, auto-exposure, temporal antialiasing, ambient occlusion, the UI overlay and the upscaled present, with
 // their targets and read-backs.  Each validates its arguments, allocates what its first call needs, records its
 // kernels' parameters in a payload of its kind and logs it (svr_context.h, svr_log.hip).
 #include <cmath>
@@ -221,6 +221,80 @@ int svr_post_pass(SvrContext* ctx, const SvrPostPass* pass) {
     P.auto_exposure = reinterpret_cast<const float*>(ctx->d_exposure.get());  // SvrExposureState::exposure is the first word
   }
   return log_op(ctx, std::move(P));
+}
+
+// ---------------------------------------------------------------- the fog pass (include/svr_fog.h)
+static_assert(sizeof(SvrFogPass) == 232 && offsetof(SvrFogPass, shadow_depth) == 144 && offsetof(SvrFogPass, frame_index) == 228, "include/svr_fog.h");
+
+int svr_fog_pass(SvrContext* ctx, const SvrFogPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: null argument");
+  if (!(std::isfinite(pass->density) && pass->density >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the density must be finite and at least 0");
+  if (!(std::isfinite(pass->height_falloff) && pass->height_falloff >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the height falloff must be finite and at least 0");
+  if (!(std::isfinite(pass->max_distance) && pass->max_distance > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: max_distance must be finite and greater than 0");
+  if (pass->steps < 1u || pass->steps > SVR_FOG_MAX_STEPS) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: steps must be in 1..SVR_FOG_MAX_STEPS");
+  if (!(std::fabs(pass->anisotropy) < 1.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the anisotropy must be greater than -1 and less than 1");
+  if (!(std::isfinite(pass->edge_sharpness) && pass->edge_sharpness >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the edge sharpness must be finite and at least 0");
+  if (pass->shadow_depth && (pass->shadow_width == 0 || pass->shadow_height == 0 || pass->shadow_width > (1u << 24) || pass->shadow_height > (1u << 24)))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the shadow map's extent must be 1 .. 2^24 each way");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_fog_pass: the colour target must be RGBA16F (the pass works in scene-linear HDR)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_fog_pass: not under svr_set_row_interleave with a stride above 1");
+  if (pass->density == 0.0f) return SVR_OK;  // no medium: the target keeps its bits, and no kernel is enqueued to rewrite them
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  // (the grid's extents grow with the image's, so the blocks of any scissor fit in those of the whole target)
+  const size_t cap = fog_blocks(ctx->W, ctx->H);
+  if (!ctx->d_fog) DEV_ALLOC(ctx->d_fog, cap * (sizeof(float4) + sizeof(float)));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  FogOp op;
+  FogLaunch& F = op.launch;
+  F.color = (uint2*)ctx->color;
+  F.depth = ctx->depth;
+  F.W = ctx->W;
+  F.sx = ctx->sx;
+  F.sy = ctx->sy;
+  F.sw = ctx->sw;
+  F.sh = ctx->sh;
+  F.gw = (ctx->sw + 1u) / 2u;
+  F.gh = (ctx->sh + 1u) / 2u;
+  F.st = ctx->d_fog.get();
+  F.te = reinterpret_cast<float*>(ctx->d_fog.get() + cap);
+  F.two_over_w = 2.0f / (float)ctx->W;
+  F.two_over_h = 2.0f / (float)ctx->H;
+  std::memcpy(F.inv_viewproj, pass->inv_viewproj, sizeof(F.inv_viewproj));
+  std::memcpy(F.cam, pass->camera_position, sizeof(F.cam));
+  F.density = pass->density;
+  F.kh = pass->height_falloff * 0x1.715476p+0f;  // C57
+  F.height_base = pass->height_base;
+  F.max_distance = pass->max_distance;
+  F.steps = pass->steps;
+  std::memcpy(F.fog_color, pass->fog_color, sizeof(F.fog_color));
+  std::memcpy(F.sun_color, pass->sun_color, sizeof(F.sun_color));
+  {  // C58: L / |L|, and the phase function's constants
+    const float* L = pass->sunlight_direction;
+    const float l2 = std::fma(L[2], L[2], std::fma(L[1], L[1], L[0] * L[0]));
+    const float inv = (std::isfinite(l2) && l2 > 0.0f) ? 1.0f / std::sqrt(l2) : 0.0f;
+    for (int k = 0; k < 3; k++) F.sun[k] = (std::isfinite(l2) && l2 > 0.0f) ? L[k] * inv : 0.0f;
+    const float g = pass->anisotropy, g2 = g * g;
+    F.one_plus_g2 = 1.0f + g2;
+    F.minus_2g = -2.0f * g;
+    F.one_minus_g2 = 1.0f - g2;
+  }
+  F.shadow_depth = pass->shadow_depth;
+  if (pass->shadow_depth) {
+    F.shadow_w = pass->shadow_width;
+    F.shadow_h = pass->shadow_height;
+    F.shadow_half_w = (float)pass->shadow_width * 0.5f;
+    F.shadow_half_h = (float)pass->shadow_height * 0.5f;
+    std::memcpy(F.shadow_viewproj, pass->shadow_viewproj, sizeof(F.shadow_viewproj));
+    F.shadow_bias = pass->shadow_bias;
+  }
+  F.edge = pass->edge_sharpness;
+  F.frame = pass->frame_index;
+  F.poison = ctx->d_poison.get();
+  return log_op(ctx, std::move(op));
 }
 
 // ---------------------------------------------------------------- auto-exposure (include/svr_exposure.h)

@@ -15,6 +15,10 @@
 //       --post clamp|reinhard|aces:<levels> [--exposure E] [--bloom-threshold T] [--bloom-intensity I]: the HDR post pass
 //           (include/svr_post.h, HIP library only) behind every frame's last pass and before the swapchain copy: the
 //           .color and .swapchain dumps are taken after it
+//       --fog <density>:<falloff>[:<g>]: the fog pass (include/svr_fog.h, HIP library only) with --deferred 1: height fog and sun
+//           shafts from the scene's sun behind the transparent objects, in front of --taa and --post (16 steps, no shadow
+//           map); the pass as handed to the library is dumped as <prefix>.fog.  With --taa, frame_index advances per
+//           frame, so the resolve averages the dither away; without, it stays 0.  Not with --views or --ranks
 //       --taa <blend>: temporal antialiasing (include/svr_temporal.h, HIP library only): every frame is drawn with a sub-pixel
 //           jitter (Halton(2, 3) - 0.5 pixels, a period of 16 frames) and resolved against the reprojected, clamped history
 //           with the given weight of the current frame, behind the frame's last geometry or lighting pass and in front of
@@ -105,7 +109,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false, stats_overlay = false;
-  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, scale_arg, upscale_arg = "off";
+  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, fog_arg, scale_arg, upscale_arg = "off";
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -132,6 +136,7 @@ int main(int argc, char** argv) {
     else if (a == "--deferred") deferred = atoi(argv[i + 1]) != 0;  // G-buffer pass, lighting pass, transparent objects under LOAD
     else if (a == "--post") post_arg = argv[i + 1];  // <operator>:<levels> (include/svr_post.h)
     else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
+    else if (a == "--fog") fog_arg = argv[i + 1];  // <density>:<falloff>[:<g>] (include/svr_fog.h)
     else if (a == "--ao") ao_arg = argv[i + 1];  // <radius>:<intensity> (include/svr_ambient.h)
     else if (a == "--auto-exposure") ae_arg = argv[i + 1];  // <key>:<adapt> (include/svr_exposure.h)
     else if (a == "--stats-overlay") stats_overlay = atoi(argv[i + 1]) != 0;  // include/svr_overlay.h
@@ -175,7 +180,7 @@ int main(int argc, char** argv) {
                     "                [--occlusion off|last|prepass]\n"
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
                     "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt] [--stats-overlay 1]\n"
-                    "                [--render-scale s --upscale sharpness|off]\n");
+                    "                [--render-scale s --upscale sharpness|off] [--fog density:falloff[:g]]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -216,6 +221,30 @@ int main(int argc, char** argv) {
     }
     if (ranks > 1) {
       fprintf(stderr, "--ao: not with --ranks (a band rank would cut taps at its band's edge)\n");
+      return 1;
+    }
+  }
+  float fog_density = 0.f, fog_falloff = 0.f, fog_g = 0.f;
+  if (!fog_arg.empty()) {
+    char tail = 0;
+    const int n = sscanf(fog_arg.c_str(), "%f:%f:%f%c", &fog_density, &fog_falloff, &fog_g, &tail);
+    char tail2 = 0;
+    const int n2 = n == 2 ? sscanf(fog_arg.c_str(), "%f:%f%c", &fog_density, &fog_falloff, &tail2) : 0;
+    const bool shape = n == 3 || (n == 2 && n2 == 2);
+    if (!shape || !(fog_density >= 0.f && fog_density < INFINITY) || !(fog_falloff >= 0.f && fog_falloff < INFINITY) || !(fog_g > -1.f && fog_g < 1.f)) {
+      fprintf(stderr, "--fog: expected <density >= 0>:<falloff >= 0>[:<g in (-1, 1)>], got '%s'\n", fog_arg.c_str());
+      return 2;
+    }
+    if (!deferred) {
+      fprintf(stderr, "--fog: needs --deferred 1 (the pass runs behind the lighting pass and the transparent objects)\n");
+      return 1;
+    }
+    if (views) {
+      fprintf(stderr, "--fog: not with --views (the pass works on the context's own targets)\n");
+      return 1;
+    }
+    if (ranks > 1) {
+      fprintf(stderr, "--fog: not with --ranks (a band rank would clamp the upsample's taps at its band's edge)\n");
       return 1;
     }
   }
@@ -594,6 +623,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--post: the library has no post pass (include/svr_post.h)\n");
     return 1;
   }
+  if (!fog_arg.empty() && !eng.api.svr_fog_pass) {
+    fprintf(stderr, "--fog: the library has no fog pass (include/svr_fog.h)\n");
+    return 1;
+  }
   if (!taa_arg.empty() && !eng.api.svr_temporal_resolve) {
     fprintf(stderr, "--taa: the library has no temporal pass (include/svr_temporal.h)\n");
     return 1;
@@ -618,6 +651,11 @@ int main(int argc, char** argv) {
     }
     if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : (depth_only ? eng.draw_depth() : (deferred ? eng.draw_deferred() : eng.draw_geometry())))) {
       fprintf(stderr, "draw failed: %s\n", eng.error.c_str());
+      return 1;
+    }
+    // behind the deferred frame's transparents, in front of the resolve (which averages the per-frame dither) and the post pass
+    if (!fog_arg.empty() && !eng.fog_pass(fog_density, fog_falloff, fog_g, taa_blend > 0.f ? (uint32_t)f : 0u)) {
+      fprintf(stderr, "%s\n", eng.error.rfind("--fog", 0) == 0 ? eng.error.c_str() : ("--fog: " + eng.error).c_str());
       return 1;
     }
     if (taa_blend > 0.f && !eng.temporal_resolve()) {  // behind the frame's last pass, in front of the post pass
@@ -665,6 +703,7 @@ int main(int argc, char** argv) {
     }
     dump(prefix + ".color", color.data(), color.size());
     dump(prefix + ".depth", depth.data(), depth.size());
+    if (!fog_arg.empty()) dump(prefix + ".fog", &eng.last_fog, 1);
     std::vector<uint8_t> swap;  // what copy_image leaves in the swapchain image (src/vk_engine.cpp:1277)
     std::string drawn;  // --stats-overlay: ... and what draw_imgui then draws onto it (src/vk_engine.cpp:1282)
     if (!(stats_overlay ? eng.stats_overlay(swap, drawn) : eng.read_swapchain(swap))) {

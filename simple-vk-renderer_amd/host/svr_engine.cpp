@@ -60,6 +60,7 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_overlay_font = reinterpret_cast<decltype(svr_overlay_font)>(dlsym(handle, "svr_overlay_font"));
   svr_upscale_to_swapchain = reinterpret_cast<decltype(svr_upscale_to_swapchain)>(dlsym(handle, "svr_upscale_to_swapchain"));
   svr_read_upscaled = reinterpret_cast<decltype(svr_read_upscaled)>(dlsym(handle, "svr_read_upscaled"));
+  svr_fog_pass = reinterpret_cast<decltype(svr_fog_pass)>(dlsym(handle, "svr_fog_pass"));
   return ok;
 }
 void SvrApi::unload() {
@@ -425,6 +426,40 @@ bool SvrEngine::post_pass(const SvrPostPass& pass) {
     return false;
   }
   if (api.svr_post_pass(ctx, &pass)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::fog_pass(float density, float falloff, float anisotropy, uint32_t frame_index) {
+  if (!api.svr_fog_pass) {
+    error = "--fog: the library has no fog pass (include/svr_fog.h)";
+    return false;
+  }
+  SvrFogPass fp{};
+  mat4 viewproj;
+  std::memcpy(viewproj.data(), scene_data.viewproj, 64);
+  const mat4 inv = svrm::inverse(viewproj);
+  std::memcpy(fp.inv_viewproj, inv.data(), 64);
+  fp.camera_position[0] = main_camera.position.x;
+  fp.camera_position[1] = main_camera.position.y;
+  fp.camera_position[2] = main_camera.position.z;
+  fp.density = density;
+  fp.height_falloff = falloff;
+  fp.height_base = 0.f;
+  fp.max_distance = 200.f;
+  fp.steps = 16;
+  fp.anisotropy = anisotropy;
+  std::memcpy(fp.sunlight_direction, scene_data.sunlight_direction, 16);
+  for (int k = 0; k < 3; k++) {
+    fp.fog_color[k] = scene_data.ambient_color[k];
+    fp.sun_color[k] = scene_data.sunlight_color[k] * scene_data.sunlight_color[3];
+  }
+  fp.edge_sharpness = 1.f;
+  fp.frame_index = frame_index;
+  last_fog = fp;
+  if (api.svr_fog_pass(ctx, &fp)) {
     error = api.svr_last_error();
     return false;
   }

@@ -26,6 +26,7 @@
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
+#include "../../include/svr_fog.h"
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_upscale.h"
 #include "../../include/svr_views.h"
@@ -69,6 +70,8 @@ struct SvrApi {
   SVR_FN(svr_draw_overlay) SVR_FN(svr_overlay_font)
   // include/svr_upscale.h: optional (HIP library only), needed by SvrEngine::upscale
   SVR_FN(svr_upscale_to_swapchain) SVR_FN(svr_read_upscaled)
+  // include/svr_fog.h: optional (HIP library only), needed by SvrEngine::fog_pass
+  SVR_FN(svr_fog_pass)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -200,6 +203,13 @@ struct SvrEngine {
   // The HDR post pass (svr_demo --post <operator>:<levels>, include/svr_post.h): exposure, bloom and the operator over the
   // colour target, after the frame's last pass and before the swapchain copy.
   bool post_pass(const SvrPostPass& pass);
+  // The fog pass (svr_demo --deferred 1 --fog <density>:<falloff>[:<g>], include/svr_fog.h): behind the deferred frame's
+  // transparents, in front of the temporal resolve and the post pass.  The camera is the scene's: the inverse of its
+  // viewproj and the main camera's position; the sun is the scene's direction and colour (rgb times w), the fog's own
+  // colour the scene's ambient; no shadow map.  height_base 0, max_distance 200, 16 steps, edge_sharpness 1.
+  // last_fog: the pass as it was handed to the library (svr_demo dumps it as <prefix>.fog).
+  SvrFogPass last_fog{};
+  bool fog_pass(float density, float falloff, float anisotropy, uint32_t frame_index);
   // Auto-exposure (svr_demo --auto-exposure <key>:<adapt>, include/svr_exposure.h): meter the colour target behind the
   // frame's last pass and in front of the post pass, which then multiplies its exposure (a compensation) by the state's.
   // The first call turns svr_set_post_auto_exposure on.  Whole window, exposures clamped to [2^-10, 2^10].
