@@ -412,6 +412,15 @@ def _f16m(a):
     return (C.c_float * 16)(*a.tolist())
 
 
+def _set_shadow(p, shadow_ptr, shadow_size, shadow_viewproj, shadow_bias):
+    """the five shadow fields of an SvrLightPass or SvrFogPass; without a map they stay zero"""
+    if shadow_ptr:
+        p.shadow_depth = C.c_void_p(shadow_ptr)
+        p.shadow_width, p.shadow_height = int(shadow_size[0]), int(shadow_size[1])
+        p.shadow_viewproj = _f16m(shadow_viewproj)
+        p.shadow_bias = float(shadow_bias)
+
+
 def fog_struct(inv_viewproj, camera_position, density, height_falloff=0.0, height_base=0.0, max_distance=100.0, steps=16,
                fog_color=(0.5, 0.6, 0.7), sun_dir=(0.0, 1.0, 0.0, 0.0), sun_color=(0.0, 0.0, 0.0), anisotropy=0.0, shadow_ptr=None,
                shadow_size=(0, 0), shadow_viewproj=None, shadow_bias=0.0, edge_sharpness=1.0, frame_index=0):
@@ -426,11 +435,7 @@ def fog_struct(inv_viewproj, camera_position, density, height_falloff=0.0, heigh
     p.sunlight_direction = _f4((list(sun_dir) + [0.0])[:4])
     p.sun_color = (C.c_float * 3)(*[float(x) for x in list(sun_color)[:3]])
     p.edge_sharpness = float(edge_sharpness)
-    if shadow_ptr:
-        p.shadow_depth = C.c_void_p(shadow_ptr)
-        p.shadow_width, p.shadow_height = int(shadow_size[0]), int(shadow_size[1])
-        p.shadow_viewproj = _f16m(shadow_viewproj)
-        p.shadow_bias = float(shadow_bias)
+    _set_shadow(p, shadow_ptr, shadow_size, shadow_viewproj, shadow_bias)
     p.frame_index = int(frame_index) & 0xffffffff
     return p
 
@@ -912,11 +917,7 @@ class Renderer:
         p.ambient_color, p.sunlight_direction, p.sunlight_color = _f4(ambient), _f4(sun_dir), _f4(sun_color)
         arr = np.ascontiguousarray(lights if lights is not None else np.zeros(0, POINT_LIGHT_DTYPE), dtype=POINT_LIGHT_DTYPE).reshape(-1)
         p.lights, p.n_lights = (arr.ctypes.data if arr.size else None), arr.size
-        if shadow_ptr:
-            p.shadow_depth = C.c_void_p(shadow_ptr)
-            p.shadow_width, p.shadow_height = int(shadow_size[0]), int(shadow_size[1])
-            p.shadow_viewproj = _f16m(shadow_viewproj)
-            p.shadow_bias = float(shadow_bias)
+        _set_shadow(p, shadow_ptr, shadow_size, shadow_viewproj, shadow_bias)
         self.lib.check(self.lib.lib.svr_light_pass(self.h, C.byref(p)))
 
     def read_light_tiles(self):

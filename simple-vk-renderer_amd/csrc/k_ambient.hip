@@ -15,6 +15,7 @@
 // plane the same launch writes.  Both kernels read the context's poison flag first: after an overflow they write nothing.
 #include "svr_launch.h"
 #include "svr_pixel.h"
+#include "svr_screen_math.h"
 
 #define SVR_AMBIENT_TABLE __device__ const
 #include "svr_ambient_tables.h"
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(256) void ambient_raw_kernel(AmbientLaunch A) {
   const uint32_t x = tx0 + c;
   if (x >= A.sw) return;
   const uint32_t px = A.sx + x;
-  const float xn = fmaf((float)px + 0.5f, A.two_over_w, -1.0f);  // C17
+  const float xn = pixel_ndc(px, A.two_over_w);
 #pragma unroll
   for (uint32_t i = 0; i < 4u; i++) {
     const uint32_t y = ty0 + r0 + i;
@@ -74,8 +75,7 @@ __global__ __launch_bounds__(256) void ambient_raw_kernel(AmbientLaunch A) {
     // C32
     const float z = s_z[r0 + i + REACH][c + REACH];
     const float4 n = A.normal[at];
-    const float yn = fmaf((float)py + 0.5f, A.two_over_h, -1.0f);
-    const Vec4 h = mat_vec(A.inv_viewproj, xn, yn, z, 1.0f);
+    const Vec4 h = unproject(A.inv_viewproj, xn, pixel_ndc(py, A.two_over_h), z);  // C17's first step: h.w is looked at below
     const float nn = fmaf(n.z, n.z, fmaf(n.y, n.y, n.x * n.x));
     if (!(z > 0.0f && f2u(n.w) != 0u && nn > 0.0f)) {
       A.raw[at] = make_float2(1.0f, 0.0f);
@@ -88,8 +88,7 @@ __global__ __launch_bounds__(256) void ambient_raw_kernel(AmbientLaunch A) {
       A.raw[at] = make_float2(1.0f, h.w);
       continue;
     }
-    const float rw = rcp_ieee(h.w);
-    const float Px = h.x * rw, Py = h.y * rw, Pz = h.z * rw;
+    const Point P = point_of(h);
     // `/` and sqrtf are correctly rounded: the file is built with -fhip-fp32-correctly-rounded-divide-sqrt
     const float rl = 1.0f / sqrtf(nn);
     const float nx = n.x * rl, ny = n.y * rl, nz = n.z * rl;
@@ -109,11 +108,13 @@ __global__ __launch_bounds__(256) void ambient_raw_kernel(AmbientLaunch A) {
       const float zt = s_z[(int)(r0 + i) + REACH + oy][(int)c + REACH + ox];
       if (!(zt > 0.0f)) continue;  // a cleared texel, or one outside the scissor
       // C35: the tap's own position, in full
+      // (two things stay spelled here, profiles/screen_math_isa.txt: the tap's coordinate is an int, whose conversion is
+      // not pixel_ndc's instruction, and C17's second step, each product next to its difference)
       const float xt = fmaf((float)((int)px + ox) + 0.5f, A.two_over_w, -1.0f);
       const float yt = fmaf((float)((int)py + oy) + 0.5f, A.two_over_h, -1.0f);
-      const Vec4 g = mat_vec(A.inv_viewproj, xt, yt, zt, 1.0f);
+      const Vec4 g = unproject(A.inv_viewproj, xt, yt, zt);
       const float gw = rcp_ieee(g.w);
-      const float vx = g.x * gw - Px, vy = g.y * gw - Py, vz = g.z * gw - Pz;
+      const float vx = g.x * gw - P.x, vy = g.y * gw - P.y, vz = g.z * gw - P.z;
       const float vv = fmaf(vz, vz, fmaf(vy, vy, vx * vx));
       if (!(vv < A.radius2)) continue;
       const float vn = fmaf(vz, nz, fmaf(vy, ny, vx * nx)) - A.bias;

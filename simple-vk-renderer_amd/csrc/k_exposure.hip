@@ -43,7 +43,8 @@ constexpr uint32_t BATCH = 8u;            // chunks whose loads are issued befor
 // (bits(L) >> 20) - 888 <= 142 * 8 + 7 - 888 = 255.  The min() of the contract never binds; it is kept, as one v_min.
 // The bottom: L >= 2^-16 has an exponent field of 111 at least, and 111 * 8 = 888.  L is never NaN or negative.
 __device__ __forceinline__ uint32_t bin_of(uint2 t) {
-  const float r = san(half_bits_to_float(t.x & 0xffffu)), g = san(half_bits_to_float(t.x >> 16)), b = san(half_bits_to_float(t.y & 0xffffu));
+  const Rgb c = decode_rgb(t);
+  const float r = san(c.r), g = san(c.g), b = san(c.b);
   const float L = fmaf(0.0722f, b, fmaf(0.7152f, g, 0.2126f * r));
   if (L < 0x1p-16f) return BLACK;
   return min((__float_as_uint(L) >> 20) - 888u, BINS - 1u);

@@ -18,6 +18,7 @@
 #include "svr_exp2.h"
 #include "svr_launch.h"
 #include "svr_pixel.h"
+#include "svr_screen_math.h"
 
 namespace svr {
 
@@ -32,8 +33,9 @@ constexpr uint32_t CS_W = CT_W / 2 + 2, CS_H = CT_H / 2 + 2;  // ... and the blo
 // (bits 0) and a distance that is no number count as max_distance.  x, y: the pixel in the target.
 __device__ __forceinline__ float pixel_t(const FogLaunch& A, uint32_t x, uint32_t y, float z) {
   if (f2u(z) == 0u) return A.max_distance;
-  const float xn = fmaf((float)x + 0.5f, A.two_over_w, -1.0f), yn = fmaf((float)y + 0.5f, A.two_over_h, -1.0f);
-  const Vec4 h = mat_vec(A.inv_viewproj, xn, yn, z, 1.0f);
+  // (C17's second step is spelled here and below, each product next to its difference: through point_of the compiler
+  // schedules the three products otherwise, profiles/screen_math_isa.txt)
+  const Vec4 h = unproject(A.inv_viewproj, pixel_ndc(x, A.two_over_w), pixel_ndc(y, A.two_over_h), z);
   const float rw = rcp_ieee(h.w);
   const float vx = h.x * rw - A.cam[0], vy = h.y * rw - A.cam[1], vz = h.z * rw - A.cam[2];
   // sqrtf is correctly rounded: the file is built with -fhip-fp32-correctly-rounded-divide-sqrt
@@ -87,8 +89,9 @@ __global__ __launch_bounds__(256) void fog_march_kernel(FogLaunch A) {
   const float t_end = m;
   float dx, dy, dz;
   {
+    // (the block's centre, not a pixel's: + 1.0f)
     const float xn = fmaf((float)x0 + 1.0f, A.two_over_w, -1.0f), yn = fmaf((float)y0 + 1.0f, A.two_over_h, -1.0f);
-    const Vec4 h = mat_vec(A.inv_viewproj, xn, yn, 1.0f, 1.0f);
+    const Vec4 h = unproject(A.inv_viewproj, xn, yn, 1.0f);
     const float rw = rcp_ieee(h.w);
     const float vx = h.x * rw - A.cam[0], vy = h.y * rw - A.cam[1], vz = h.z * rw - A.cam[2];
     // `/` and sqrtf are correctly rounded: the file is built with -fhip-fp32-correctly-rounded-divide-sqrt
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(256) void fog_march_kernel(FogLaunch A) {
   // the shadow matrix, applied once: to the origin as a point, to the direction as a vector
   Vec4 q0 = {0.0f, 0.0f, 0.0f, 0.0f}, dq = {0.0f, 0.0f, 0.0f, 0.0f};
   if (SHADOW) {
-    const float* M = A.shadow_viewproj;
+    const float* M = A.shadow.viewproj;
     q0 = mat_vec(M, A.cam[0], A.cam[1], A.cam[2], 1.0f);
     dq.x = fmaf(M[8], dz, fmaf(M[4], dy, M[0] * dx));
     dq.y = fmaf(M[9], dz, fmaf(M[5], dy, M[1] * dx));
@@ -127,13 +130,7 @@ __global__ __launch_bounds__(256) void fog_march_kernel(FogLaunch A) {
     bool shadowed = false;
     if (SHADOW) {  // C18's lookup at the sample
       const float qx = fmaf(ti, dq.x, q0.x), qy = fmaf(ti, dq.y, q0.y), qz = fmaf(ti, dq.z, q0.z), qw = fmaf(ti, dq.w, q0.w);
-      const float rq = rcp_ieee(qw);
-      const float sx = fmaf(qx * rq, A.shadow_half_w, A.shadow_half_w), sy = fmaf(qy * rq, A.shadow_half_h, A.shadow_half_h);
-      const float sz = qz * rq;
-      const float fx = floorf(sx), fy = floorf(sy);
-      // (the extents are at most 2^24, so they are exact as floats and a passing floor is an index inside the map)
-      if (qw > 0.0f && fx >= 0.0f && fx < (float)A.shadow_w && fy >= 0.0f && fy < (float)A.shadow_h)
-        shadowed = sz + A.shadow_bias < A.shadow_depth[(size_t)(uint32_t)fy * A.shadow_w + (uint32_t)fx];
+      shadowed = shadow_occluded(A.shadow, qx, qy, qz, qw);
     }
     const float w = T * (1.0f - a);
     Sr = fmaf(w, shadowed ? dark_r : lit_r, Sr);
@@ -173,9 +170,8 @@ __device__ __forceinline__ uint2 fog_pixel(const FogLaunch& A, uint2 texel, floa
   }
   const float rd = 1.0f / den;
   const float Sr = nr * rd, Sg = ng * rd, Sb = nb * rd, T = nt * rd;
-  const float ir = half_bits_to_float(texel.x & 0xffffu), ig = half_bits_to_float(texel.x >> 16), ib = half_bits_to_float(texel.y & 0xffffu);
-  const float r = san(fmaf(ir, T, Sr)), g = san(fmaf(ig, T, Sg)), bl = san(fmaf(ib, T, Sb));
-  return make_uint2(h16(r) | (h16(g) << 16), h16(bl) | (texel.y & 0xffff0000u));  // the alpha half as it was
+  const Rgb in = decode_rgb(texel);
+  return encode_rgb({san(fmaf(in.r, T, Sr)), san(fmaf(in.g, T, Sg)), san(fmaf(in.b, T, Sb))}, texel);
 }
 
 }  // namespace
@@ -214,7 +210,7 @@ void launch_fog(const FogLaunch& A, hipStream_t s) {
   if (A.sw == 0u || A.sh == 0u) return;
   const dim3 block(256);
   const dim3 march((A.gw + 31u) / 32u, (A.gh + 7u) / 8u);
-  if (A.shadow_depth)
+  if (A.shadow.depth)
     hipLaunchKernelGGL(fog_march_kernel<true>, march, block, 0, s, A);
   else
     hipLaunchKernelGGL(fog_march_kernel<false>, march, block, 0, s, A);

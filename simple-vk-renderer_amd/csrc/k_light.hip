@@ -14,6 +14,7 @@
 // after an overflow it writes nothing.
 #include "svr_launch.h"
 #include "svr_pixel.h"
+#include "svr_screen_math.h"
 
 namespace svr {
 
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void light_kernel(LightLaunch L) {
     }
   }
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  const float yn = fmaf((float)py + 0.5f, L.two_over_h, -1.0f);
+  const float yn = pixel_ndc(py, L.two_over_h);
 #pragma unroll
   for (uint32_t k = 0; k < 4u; k++) {
     nx[k] = ny[k] = nz[k] = cr[k] = cg[k] = cb[k] = X[k] = Y[k] = Z[k] = 0.0f;
@@ -83,11 +84,8 @@ __global__ __launch_bounds__(256) void light_kernel(LightLaunch L) {
     const float4 n = L.normal[at + k];
     nx[k] = n.x; ny[k] = n.y; nz[k] = n.z;
     cr[k] = a.x; cg[k] = a.y; cb[k] = a.z;
-    // C17
-    const float xn = fmaf((float)(px0 + k) + 0.5f, L.two_over_w, -1.0f);
-    const Vec4 h = mat_vec(L.inv_viewproj, xn, yn, z[k], 1.0f);
-    const float rw = rcp_ieee(h.w);
-    X[k] = h.x * rw; Y[k] = h.y * rw; Z[k] = h.z * rw;
+    const Point p = point_of(unproject(L.inv_viewproj, pixel_ndc(px0 + k, L.two_over_w), yn, z[k]));  // C17
+    X[k] = p.x; Y[k] = p.y; Z[k] = p.z;
     if (finite3(X[k], Y[k], Z[k])) {
       lo[0] = fminf(lo[0], X[k]); hi[0] = fmaxf(hi[0], X[k]);
       lo[1] = fminf(lo[1], Y[k]); hi[1] = fmaxf(hi[1], Y[k]);
@@ -141,15 +139,9 @@ __global__ __launch_bounds__(256) void light_kernel(LightLaunch L) {
     if (!win[k]) continue;
     const float d = fmaf(nz[k], L.sunlight_direction[2], fmaf(ny[k], L.sunlight_direction[1], nx[k] * L.sunlight_direction[0]));
     bool shadowed = false;
-    if (L.shadow_depth) {
-      const Vec4 q = mat_vec(L.shadow_viewproj, X[k], Y[k], Z[k], 1.0f);
-      const float rq = rcp_ieee(q.w);
-      const float sx = fmaf(q.x * rq, L.shadow_half_w, L.shadow_half_w), sy = fmaf(q.y * rq, L.shadow_half_h, L.shadow_half_h);
-      const float sz = q.z * rq;
-      const float fx = floorf(sx), fy = floorf(sy);
-      // (the extents are at most 2^24, so they are exact as floats and a passing floor is an index inside the map)
-      if (q.w > 0.0f && fx >= 0.0f && fx < (float)L.shadow_w && fy >= 0.0f && fy < (float)L.shadow_h)
-        shadowed = sz + L.shadow_bias < L.shadow_depth[(size_t)(uint32_t)fy * L.shadow_w + (uint32_t)fx];
+    if (L.shadow.depth) {
+      const Vec4 q = mat_vec(L.shadow.viewproj, X[k], Y[k], Z[k], 1.0f);
+      shadowed = shadow_occluded(L.shadow, q.x, q.y, q.z, q.w);
     }
     const float light = shadowed ? 0.1f : fmaxf(d, 0.1f);
     if (AO) {

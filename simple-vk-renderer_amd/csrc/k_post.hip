@@ -25,11 +25,6 @@ namespace {
 constexpr uint32_t PT = 32;       // the tile of a level image a workgroup writes
 constexpr uint32_t PS = PT + 4;   // ... and the staged texels per side: two more each way for the five taps
 
-struct Rgb {
-  float r, g, b;
-};
-
-__device__ __forceinline__ Rgb decode(uint2 t) { return {half_bits_to_float(t.x & 0xffffu), half_bits_to_float(t.x >> 16), half_bits_to_float(t.y & 0xffffu)}; }
 // texels x0 and x1 (x1 == x0 + 1 or x1 == x0) of one row: one 16-byte load where the address allows
 __device__ __forceinline__ void load_pair(const uint2* row, uint32_t x0, uint32_t x1, uint2& a, uint2& b) {
   if (x1 != x0 && aligned_to(row + x0, 16u)) {
@@ -54,7 +49,7 @@ __device__ __forceinline__ Rgb upsample(const uint2* S, uint32_t ws, uint32_t hs
   uint2 q00, q10, q01, q11;
   load_pair(r0, x0, x1, q00, q10);
   load_pair(r1, x0, x1, q01, q11);
-  const Rgb a = decode(q00), b = decode(q10), c = decode(q01), d = decode(q11);
+  const Rgb a = decode_rgb(q00), b = decode_rgb(q10), c = decode_rgb(q01), d = decode_rgb(q11);
   const Rgb top = {fmaf(tx, b.r - a.r, a.r), fmaf(tx, b.g - a.g, a.g), fmaf(tx, b.b - a.b, a.b)};
   const Rgb bot = {fmaf(tx, d.r - c.r, c.r), fmaf(tx, d.g - c.g, c.g), fmaf(tx, d.b - c.b, c.b)};
   return {fmaf(ty, bot.r - top.r, top.r), fmaf(ty, bot.g - top.g, top.g), fmaf(ty, bot.b - top.b, top.b)};
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(256) void bloom_level_kernel(LevelArgs A, State... 
     uint2 q00, q10, q01, q11;
     load_pair(A.src + (size_t)y0 * A.src_pitch, x0, x1, q00, q10);
     load_pair(A.src + (size_t)y1 * A.src_pitch, x0, x1, q01, q11);
-    const Rgb a = decode(q00), b = decode(q10), cc = decode(q01), d = decode(q11);
+    const Rgb a = decode_rgb(q00), b = decode_rgb(q10), cc = decode_rgb(q01), d = decode_rgb(q11);
     s_d[0][r][c] = box<FIRST>(a.r, b.r, cc.r, d.r, exposure, A.threshold);
     s_d[1][r][c] = box<FIRST>(a.g, b.g, cc.g, d.g, exposure, A.threshold);
     s_d[2][r][c] = box<FIRST>(a.b, b.b, cc.b, d.b, exposure, A.threshold);
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(256) void bloom_up_kernel(UpArgs A) {
   const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
   if (x >= A.w || y >= A.h) return;
   uint2* at = A.dst + (size_t)y * A.w + x;
-  const Rgb b = decode(*at);
+  const Rgb b = decode_rgb(*at);
   const Rgb u = upsample(A.src, A.ws, A.hs, x, y);
   *at = make_uint2(h16(add_clamped(b.r, u.r)) | (h16(add_clamped(b.g, u.g)) << 16), h16(add_clamped(b.b, u.b)));
 }
@@ -195,11 +190,11 @@ template <int OP>
 __device__ __forceinline__ uint2 composite_pixel(const CompositeArgs& A, uint2 texel, uint32_t x, uint32_t y) {
   Rgb bloom = {0.0f, 0.0f, 0.0f};
   if (A.levels) bloom = upsample(A.u0, A.w0, A.h0, x, y);
-  const Rgb in = decode(texel);
+  const Rgb in = decode_rgb(texel);
   const float r = tonemap<OP>(san(fmaf(A.intensity, bloom.r, A.exposure * in.r)));
   const float g = tonemap<OP>(san(fmaf(A.intensity, bloom.g, A.exposure * in.g)));
   const float b = tonemap<OP>(san(fmaf(A.intensity, bloom.b, A.exposure * in.b)));
-  return make_uint2(h16(r) | (h16(g) << 16), h16(b) | (texel.y & 0xffff0000u));  // the alpha half as it was
+  return encode_rgb({r, g, b}, texel);
 }
 
 // the body of post_composite_kernel<OP> and of post_composite_auto_kernel<OP>

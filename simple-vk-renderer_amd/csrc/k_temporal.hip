@@ -16,6 +16,7 @@
 // context's poison flag first: after an overflow they write nothing.
 #include "svr_launch.h"
 #include "svr_pixel.h"
+#include "svr_screen_math.h"
 
 namespace svr {
 
@@ -51,17 +52,18 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalLaunch A)
     if (pair && xa + 1u < A.sw && aligned_to(crow + xa, 16u) && aligned_to(zrow + xa, 8u)) {
       const uint4 q = *reinterpret_cast<const uint4*>(crow + xa);
       const float2 z = *reinterpret_cast<const float2*>(zrow + xa);
-      *reinterpret_cast<float2*>(&s_c[0][wr][wc + 1u]) = make_float2(san(half_bits_to_float(q.x & 0xffffu)), san(half_bits_to_float(q.z & 0xffffu)));
-      *reinterpret_cast<float2*>(&s_c[1][wr][wc + 1u]) = make_float2(san(half_bits_to_float(q.x >> 16)), san(half_bits_to_float(q.z >> 16)));
-      *reinterpret_cast<float2*>(&s_c[2][wr][wc + 1u]) = make_float2(san(half_bits_to_float(q.y & 0xffffu)), san(half_bits_to_float(q.w & 0xffffu)));
+      const Rgb a = decode_rgb(make_uint2(q.x, q.y)), b = decode_rgb(make_uint2(q.z, q.w));
+      *reinterpret_cast<float2*>(&s_c[0][wr][wc + 1u]) = make_float2(san(a.r), san(b.r));
+      *reinterpret_cast<float2*>(&s_c[1][wr][wc + 1u]) = make_float2(san(a.g), san(b.g));
+      *reinterpret_cast<float2*>(&s_c[2][wr][wc + 1u]) = make_float2(san(a.b), san(b.b));
       *reinterpret_cast<float2*>(&s_z[wr][wc + 1u]) = z;
     } else {
       for (uint32_t k = 0; k < (pair ? 2u : 1u); k++) {
         const uint32_t x = clamp_to((int)(tx0 + wc + k) - 1, A.sw);
-        const uint2 q = crow[x];
-        s_c[0][wr][wc + k + 1u] = san(half_bits_to_float(q.x & 0xffffu));
-        s_c[1][wr][wc + k + 1u] = san(half_bits_to_float(q.x >> 16));
-        s_c[2][wr][wc + k + 1u] = san(half_bits_to_float(q.y & 0xffffu));
+        const Rgb q = decode_rgb(crow[x]);
+        s_c[0][wr][wc + k + 1u] = san(q.r);
+        s_c[1][wr][wc + k + 1u] = san(q.g);
+        s_c[2][wr][wc + k + 1u] = san(q.b);
         s_z[wr][wc + k + 1u] = zrow[x];
       }
     }
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalLaunch A)
   const uint32_t x = tx0 + c;
   if (x >= A.sw) return;
   const uint32_t px = A.sx + x;
-  const float xn = fmaf((float)px + 0.5f, A.two_over_w, -1.0f);  // C17
+  const float xn = pixel_ndc(px, A.two_over_w);
   const float x_lo = (float)A.sx, x_hi = (float)(A.sx + A.sw), y_lo = (float)A.sy, y_hi = (float)(A.sy + A.sh);
 #pragma unroll
   for (uint32_t i = 0; i < 4u; i++) {
@@ -105,8 +107,7 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalLaunch A)
     }
     const float z = max2(max2(hz[i], hz[i + 1u]), hz[i + 2u]);
     // C29: the C0 chain, one matrix, no intermediate divide
-    const float yn = fmaf((float)py + 0.5f, A.two_over_h, -1.0f);
-    const Vec4 q = mat_vec(A.reproject, xn, yn, z, 1.0f);  // (q.z is not used)
+    const Vec4 q = mat_vec(A.reproject, xn, pixel_ndc(py, A.two_over_h), z, 1.0f);  // (q.z is not used)
     bool valid = A.history_valid != 0u && q.w > 0.0f;
     if (valid) {
       const float r = rcp_ieee(q.w);
@@ -157,10 +158,10 @@ __global__ __launch_bounds__(256) void temporal_copy_kernel(TemporalLaunch A) {
   if (x + 1u < A.sw && aligned_to(at, 16u) && aligned_to(h, 16u)) {
     const uint4 q = *reinterpret_cast<const uint4*>(at);
     const uint4 n = *reinterpret_cast<const uint4*>(h);
-    *reinterpret_cast<uint4*>(at) = make_uint4(n.x, (n.y & 0xffffu) | (q.y & 0xffff0000u), n.z, (n.w & 0xffffu) | (q.w & 0xffff0000u));
+    *reinterpret_cast<uint4*>(at) = make_uint4(n.x, keep_alpha(n.y, q.y), n.z, keep_alpha(n.w, q.w));
   } else {
-    at[0] = make_uint2(h[0].x, (h[0].y & 0xffffu) | (at[0].y & 0xffff0000u));  // the alpha half as it was
-    if (x + 1u < A.sw) at[1] = make_uint2(h[1].x, (h[1].y & 0xffffu) | (at[1].y & 0xffff0000u));
+    at[0] = make_uint2(h[0].x, keep_alpha(h[0].y, at[0].y));
+    if (x + 1u < A.sw) at[1] = make_uint2(h[1].x, keep_alpha(h[1].y, at[1].y));
   }
 }
 

@@ -2,7 +2,8 @@
 // the payload of each kind of logged operation, SvrContext itself, and the internal functions that cross files.
 //   svr_api.hip     context life cycle, resources, targets, options, read-backs, every geometry entry point
 //   svr_log.hip     a pass's submit and retirement, the operation log and its replay
-//   svr_screen.hip  the operations over finished targets: depth pyramid, lighting, post, temporal, ambient
+//   svr_screen.hip  the operations over finished targets: depth pyramid, lighting, post, fog, exposure, temporal, ambient,
+//                   overlay, upscaled present
 // Host code only.  The C ABI is the extern "C" functions of those files; everything here is internal (namespace svr).
 #pragma once
 #include <hip/hip_runtime.h>

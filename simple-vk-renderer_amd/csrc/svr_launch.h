@@ -1,5 +1,7 @@
 // svr_launch.h — host-callable launchers of the HIP kernels (one per kernel file).
 #pragma once
+#include <cstddef>
+
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
 #include "../../include/svr_fog.h"
@@ -59,6 +61,15 @@ uint32_t pyramid_levels(uint32_t W, uint32_t H);
 size_t pyramid_offsets(uint32_t W, uint32_t H, uint32_t* off);  // off[1 .. levels]: word offset of each level; returns the words
 void launch_pyramid(const float* depth, uint32_t W, uint32_t H, uint32_t* pyr, const uint32_t* off, uint32_t n_levels,
                     const uint32_t* poison, hipStream_t s);
+// the shadow map of a pass that takes one (C18; the lookup: svr_screen_math.h shadow_occluded)
+struct ShadowMap {
+  const float* depth;           // null: unshadowed, and nothing below is read
+  uint32_t w, h;
+  float half_w, half_h;         // Ws / 2, Hs / 2 (exact)
+  float viewproj[16];
+  float bias;
+};
+static_assert(sizeof(ShadowMap) == 96, "kernel arguments: the layout is part of the machine code");
 // k_light.hip: the deferred lighting pass (include/svr_lighting.h)
 struct LightLaunch {
   void* color;                  // the colour target (W x H), written where the albedo texel names an opaque winner
@@ -73,15 +84,12 @@ struct LightLaunch {
   float ambient_color[4], sunlight_direction[4], sunlight_color[4];
   const SvrPointLight* lights;  // device copy
   uint32_t n_lights;
-  const float* shadow_depth;    // null: unshadowed
-  uint32_t shadow_w, shadow_h;
-  float shadow_half_w, shadow_half_h;  // C18: Ws / 2, Hs / 2 (exact)
-  float shadow_viewproj[16];
-  float shadow_bias;
+  ShadowMap shadow;
   uint32_t* tile_counts;        // [tiles_x * tiles_y]: the lights each tile kept (svr_debug_read_light_tiles)
   const uint32_t* poison;
   const float* ao;              // the ambient target (include/svr_ambient.h), or null: light_kernel<FMT, true> / <FMT, false>
 };
+static_assert(sizeof(LightLaunch) == 328 && offsetof(LightLaunch, shadow) == 208, "where the flat shadow fields stood");
 void launch_light(const LightLaunch& L, int color_format, uint32_t tiles_y, hipStream_t s);
 // k_post.hip: the HDR post pass (include/svr_post.h)
 struct PostLaunch {
@@ -220,11 +228,7 @@ struct FogLaunch {
   float fog_color[3], sun_color[3];
   float sun[3];                 // C58: L / |L| (zero for a direction without a length)
   float one_plus_g2, minus_2g, one_minus_g2;  // C58: 1 + g g, -2 g, 1 - g g, computed once, at the call
-  const float* shadow_depth;    // null: unshadowed
-  uint32_t shadow_w, shadow_h;
-  float shadow_half_w, shadow_half_h;  // C18: Ws / 2, Hs / 2 (exact)
-  float shadow_viewproj[16];
-  float shadow_bias;
+  ShadowMap shadow;
   float edge;                   // C59: edge_sharpness
   uint32_t frame;
   const uint32_t* poison;

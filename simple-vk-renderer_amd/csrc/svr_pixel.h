@@ -1,5 +1,5 @@
-// svr_pixel.h — how a kernel reads and writes a render target's texels, and the two small index
-// helpers every screen-space pass needs.  Stated once: a kernel file includes this header and restates none of it.
+// svr_pixel.h — how a kernel reads and writes a render target's texels, the RGB rewrite of the
+// in-place HDR passes among it, and the two small index helpers every screen-space pass needs.  Stated once: a kernel file includes this header and restates none of it.
 // There is no division and no square root in here, so the header means the same in the files built with
 // -fhip-fp32-correctly-rounded-divide-sqrt and in those built without.
 #pragma once
@@ -24,6 +24,15 @@ __device__ __forceinline__ float half_bits_to_float(uint32_t h) { return __half2
 constexpr float HALF_MAX = 65504.0f;
 // what an HDR pass takes a stored half for: NaN and negatives are 0, +inf is the largest half
 __device__ __forceinline__ float san(float v) { return v > 0.0f ? (v < HALF_MAX ? v : HALF_MAX) : 0.0f; }
+
+// ---- the in-place HDR passes over an RGBA16F target: RGB halves in, RGB halves out, the alpha half as it was
+struct Rgb {
+  float r, g, b;
+};
+__device__ __forceinline__ Rgb decode_rgb(uint2 t) { return {half_bits_to_float(t.x & 0xffffu), half_bits_to_float(t.x >> 16), half_bits_to_float(t.y & 0xffffu)}; }
+// a texel's second word: the blue half of b_word, the alpha half of old_word
+__device__ __forceinline__ uint32_t keep_alpha(uint32_t b_word, uint32_t old_word) { return (b_word & 0xffffu) | (old_word & 0xffff0000u); }
+__device__ __forceinline__ uint2 encode_rgb(Rgb c, uint2 old) { return make_uint2(h16(c.r) | (h16(c.g) << 16), keep_alpha(h16(c.b), old.y)); }
 
 // ---- unorm8 (RGBA8 targets, the swapchain, texels)
 constexpr float kInv255 = 0x1.010102p-8f;

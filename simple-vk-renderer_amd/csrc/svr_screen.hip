@@ -1,7 +1,8 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, auto-exposure, temporal antialiasing, ambient occlusion, the UI overlay and the upscaled present, with
-// their targets and read-backs.  Each validates its arguments, allocates what its first call needs, records its
-// kernels' parameters in a payload of its kind and logs it (svr_context.h, svr_log.hip).
+// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, auto-exposure, temporal antialiasing,
+// ambient occlusion, the UI overlay and the upscaled present, with their targets and read-backs.  Each validates its
+// arguments, allocates what its first call needs, records its kernels' parameters in a payload of its kind and logs it
+// (svr_context.h, svr_log.hip).
 #include <cmath>
 #include <cstddef>
 
@@ -11,6 +12,30 @@
 using namespace svr;
 
 extern "C" {
+
+// ---------------------------------------------------------------- what several passes check and fill alike
+// the shadow map a pass was handed (C18), as its kernels read it; depth == null: none, and S stays empty
+static int shadow_map(const char* who, const float* depth, uint32_t w, uint32_t h, const float* viewproj, float bias, ShadowMap& S) {
+  S = ShadowMap{};
+  if (!depth) return SVR_OK;
+  if (w == 0 || h == 0 || w > (1u << 24) || h > (1u << 24))
+    return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": the shadow map's extent must be 1 .. 2^24 each way");
+  S.depth = depth;
+  S.w = w;
+  S.h = h;
+  S.half_w = (float)w * 0.5f;
+  S.half_h = (float)h * 0.5f;
+  std::memcpy(S.viewproj, viewproj, sizeof(S.viewproj));
+  S.bias = bias;
+  return SVR_OK;
+}
+
+// a matrix a pass divides by: 16 finite floats
+static int finite_matrix(const char* who, const char* name, const float* m) {
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(m[i])) return fail(SVR_ERR_INVALID_ARGUMENT, std::string(who) + ": " + name + "[" + std::to_string(i) + "] is not finite");
+  return SVR_OK;
+}
 
 // ---------------------------------------------------------------- occlusion culling (include/svr_occlusion.h)
 static std::shared_ptr<PyramidMem> get_pyramid(SvrContext* ctx, SvrDepthPyramid h) {
@@ -111,8 +136,8 @@ int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
   for (uint32_t i = 0; i < pass->n_lights; i++)
     if (!(std::isfinite(pass->lights[i].radius) && pass->lights[i].radius > 0.0f))
       return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: light " + std::to_string(i) + ": the radius must be finite and greater than 0");
-  if (pass->shadow_depth && (pass->shadow_width == 0 || pass->shadow_height == 0 || pass->shadow_width > (1u << 24) || pass->shadow_height > (1u << 24)))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: the shadow map's extent must be 1 .. 2^24 each way");
+  ShadowMap shadow;
+  if (int e = shadow_map("svr_light_pass", pass->shadow_depth, pass->shadow_width, pass->shadow_height, pass->shadow_viewproj, pass->shadow_bias, shadow)) return e;
   if (!ctx->attr[2] || !ctx->attr[3])
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_light_pass: needs the SVR_ATTR_NORMAL and SVR_ATTR_ALBEDO planes (svr_enable_attributes / svr_bind_attribute_target)");
   const float* ao = nullptr;  // include/svr_ambient.h: the ambient target current at this call
@@ -151,15 +176,7 @@ int svr_light_pass(SvrContext* ctx, const SvrLightPass* pass) {
   std::memcpy(L.sunlight_color, pass->sunlight_color, sizeof(L.sunlight_color));
   L.lights = ctx->d_lights.get();
   L.n_lights = pass->n_lights;
-  L.shadow_depth = pass->shadow_depth;
-  if (pass->shadow_depth) {
-    L.shadow_w = pass->shadow_width;
-    L.shadow_h = pass->shadow_height;
-    L.shadow_half_w = (float)pass->shadow_width * 0.5f;
-    L.shadow_half_h = (float)pass->shadow_height * 0.5f;
-    std::memcpy(L.shadow_viewproj, pass->shadow_viewproj, sizeof(L.shadow_viewproj));
-    L.shadow_bias = pass->shadow_bias;
-  }
+  L.shadow = shadow;
   L.tile_counts = ctx->d_light_tiles.get();
   L.poison = ctx->d_poison.get();
   L.ao = ao;
@@ -237,8 +254,8 @@ int svr_fog_pass(SvrContext* ctx, const SvrFogPass* pass) {
   if (!(std::fabs(pass->anisotropy) < 1.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the anisotropy must be greater than -1 and less than 1");
   if (!(std::isfinite(pass->edge_sharpness) && pass->edge_sharpness >= 0.0f))
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the edge sharpness must be finite and at least 0");
-  if (pass->shadow_depth && (pass->shadow_width == 0 || pass->shadow_height == 0 || pass->shadow_width > (1u << 24) || pass->shadow_height > (1u << 24)))
-    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_fog_pass: the shadow map's extent must be 1 .. 2^24 each way");
+  ShadowMap shadow;
+  if (int e = shadow_map("svr_fog_pass", pass->shadow_depth, pass->shadow_width, pass->shadow_height, pass->shadow_viewproj, pass->shadow_bias, shadow)) return e;
   if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_fog_pass: the colour target must be RGBA16F (the pass works in scene-linear HDR)");
   if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_fog_pass: not under svr_set_row_interleave with a stride above 1");
   if (pass->density == 0.0f) return SVR_OK;  // no medium: the target keeps its bits, and no kernel is enqueued to rewrite them
@@ -282,15 +299,7 @@ int svr_fog_pass(SvrContext* ctx, const SvrFogPass* pass) {
     F.minus_2g = -2.0f * g;
     F.one_minus_g2 = 1.0f - g2;
   }
-  F.shadow_depth = pass->shadow_depth;
-  if (pass->shadow_depth) {
-    F.shadow_w = pass->shadow_width;
-    F.shadow_h = pass->shadow_height;
-    F.shadow_half_w = (float)pass->shadow_width * 0.5f;
-    F.shadow_half_h = (float)pass->shadow_height * 0.5f;
-    std::memcpy(F.shadow_viewproj, pass->shadow_viewproj, sizeof(F.shadow_viewproj));
-    F.shadow_bias = pass->shadow_bias;
-  }
+  F.shadow = shadow;
   F.edge = pass->edge_sharpness;
   F.frame = pass->frame_index;
   F.poison = ctx->d_poison.get();
@@ -396,8 +405,7 @@ int svr_temporal_resolve(SvrContext* ctx, const SvrTemporalPass* pass) {
   if (!(std::isfinite(pass->blend) && pass->blend > 0.0f && pass->blend <= 1.0f))
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: the blend must be finite, greater than 0 and at most 1");
   if (pass->flags & ~(uint32_t)(SVR_TEMPORAL_RESET | SVR_TEMPORAL_NO_CLAMP)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: unknown flag bits");
-  for (int i = 0; i < 16; i++)
-    if (!std::isfinite(pass->reproject[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_temporal_resolve: reproject[" + std::to_string(i) + "] is not finite");
+  if (int e = finite_matrix("svr_temporal_resolve", "reproject", pass->reproject)) return e;
   if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: the colour target must be RGBA16F");
   if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_temporal_resolve: not under svr_set_row_interleave with a stride above 1");
   if (int e = use_device(ctx)) return e;
@@ -469,8 +477,7 @@ int svr_ambient_pass(SvrContext* ctx, const SvrAmbientPass* pass) {
   if (!(std::isfinite(pass->sharpness) && pass->sharpness >= 0.0f && pass->sharpness < 1.0f))
     return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: the sharpness must be finite, at least 0 and less than 1");
   if (pass->flags & ~(uint32_t)SVR_AMBIENT_NO_BLUR) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: unknown flag bits");
-  for (int i = 0; i < 16; i++)
-    if (!std::isfinite(pass->inv_viewproj[i])) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: inv_viewproj[" + std::to_string(i) + "] is not finite");
+  if (int e = finite_matrix("svr_ambient_pass", "inv_viewproj", pass->inv_viewproj)) return e;
   if (!ctx->attr[2]) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_ambient_pass: needs the SVR_ATTR_NORMAL plane (svr_enable_attributes / svr_bind_attribute_target)");
   if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_ambient_pass: not under svr_set_row_interleave with a stride above 1");
   if (int e = use_device(ctx)) return e;

@@ -179,6 +179,21 @@ def slab_map(n, M_light, seed, lo_y=2.0, hi_y=8.0, open_share=0.5):
     return depth.astype(f32)
 
 
+def spot_light(eye=(0.0, 4.0, -6.0), fov=2.0, near=0.5):
+    """a perspective light looking straight down from eye: clip w is the distance below it, so a sample above the light has
+    w < 0 and C18's `q.w > 0` decides.  Returns (viewproj float64 4x4, its direction towards the light)"""
+    return perspective(fov, 1.0, near) @ look_at(eye, (eye[0], 0.0, eye[2]), up=(0.0, 0.0, -1.0)), (0.0, 1.0, 0.0, 0.0)
+
+
+def spot_map(n, seed, eye_y=4.0, near=0.5, lo_y=1.0, hi_y=3.5, open_share=0.5):
+    """a coarse n x n map under spot_light: each texel either open (depth 0) or an occluder at a seeded height in
+    [lo_y, hi_y], reversed-Z: near / (eye_y - y); float32 [n, n]"""
+    rng = np.random.default_rng(seed)
+    depth = near / (eye_y - rng.uniform(lo_y, hi_y, (n, n)))
+    depth[rng.random((n, n)) < open_share] = 0.0
+    return depth.astype(f32)
+
+
 # ---------------------------------------------------------------- the fp64 statement, from the definitions
 def fog_hash(bx, by, frame):
     M = 0xffffffff
@@ -260,3 +275,31 @@ def march64(depth, inv_viewproj, camera, scissor=None, shadow=None, pin_o=None, 
                 tr = tr * a
             S[by, bx], T[by, bx], TE[by, bx] = s, tr, t_end
     return dict(S=S, T=T, t_end=TE, edge=EDGE, gap=GAP)
+
+
+def sample_points64(depth, inv_viewproj, camera, steps, frame_index, max_distance):
+    """float64 [gh, gw, steps, 3]: the world positions the march of the whole target samples, by march64's definitions
+    (the inputs must hold no NaN)"""
+    h, w = depth.shape
+    Minv = np.asarray(inv_viewproj, f32).astype(np.float64).reshape(4, 4).T
+    cam = np.asarray(camera, f32).astype(np.float64)
+    maxd = float(f32(max_distance))
+
+    def unproject(px, py, z):
+        q = np.stack([px * 2.0 / w - 1.0, py * 2.0 / h - 1.0, z, np.ones_like(z)], -1) @ Minv.T
+        return q[..., :3] / q[..., 3:]
+
+    gw, gh = (w + 1) // 2, (h + 1) // 2
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.minimum(np.linalg.norm(unproject(x + 0.5, y + 0.5, depth.astype(np.float64)) - cam, axis=-1), maxd)
+    t[depth.view(np.uint32) == 0] = maxd
+    padded = np.full((2 * gh, 2 * gw), -np.inf)
+    padded[:h, :w] = t
+    t_end = padded.reshape(gh, 2, gw, 2).max(axis=(1, 3))
+    by, bx = np.mgrid[0:gh, 0:gw]
+    v = unproject(2.0 * bx + 1.0, 2.0 * by + 1.0, np.ones((gh, gw))) - cam
+    d = v / np.linalg.norm(v, axis=-1, keepdims=True)
+    o = np.array([[(fog_hash(int(b), int(a), frame_index & 0xffffffff) >> 24) / 256.0 for b in range(gw)] for a in range(gh)])
+    ti = (np.arange(steps)[None, None, :] + o[..., None]) * (t_end / steps)[..., None]
+    return cam + ti[..., None] * d[:, :, None, :]

@@ -133,6 +133,24 @@ def test_odd_scissor(hip):
     b.close()
 
 
+def test_perspective_light(hip):
+    """the case test_fog_ref.py's test_perspective_light_outside_or_behind_is_lit classifies: an eighth of the samples lie
+    behind the light, where C18's `q.w > 0` decides, and half outside the map"""
+    pytest.importorskip("torch")
+    w, h = 33, 17
+    cam, color, depth = scene(w, h, seed=61)
+    M_spot, sun = FR.spot_light()
+    smap = FR.spot_map(16, seed=5)
+    kw = dict(FOG, sun_dir=sun)
+    b = Bound(hip, color, depth, smap)
+    b.r.fog_pass(cam.inv, cam.eye, **kw, **b.shadow_args(M_spot))
+    got = b.read()
+    want = FR.run_ref(color, depth, cam.inv, cam.eye, shadow=smap, shadow_viewproj=FR.colmajor(M_spot), **ref_kw(kw, False))["color"]
+    assert_color(got, want, "a perspective light")
+    assert not np.array_equal(want, FR.run_ref(color, depth, cam.inv, cam.eye, **ref_kw(kw, False))["color"]), "the map must matter"
+    b.close()
+
+
 # ---------------------------------------------------------------- 2. invariants, library against library
 def test_invariants(hip):
     pytest.importorskip("torch")

@@ -248,3 +248,43 @@ def test_every_variant_changes_the_picture():
     good = FR.run_ref(color, depth, CAM.inv, CAM.eye, shadow=COARSE, **kw)["color"]
     for variant in FR.WRONG_VARIANTS:
         assert not np.array_equal(FR.run_ref(color, depth, CAM.inv, CAM.eye, shadow=COARSE, variant=variant, **kw)["color"], good), variant
+
+
+# ---------------------------------------------------------------- a perspective light: C18's `q.w > 0`
+def test_perspective_light_outside_or_behind_is_lit():
+    """Under an orthographic light clip w is 1, and C18's `q.w > 0` never decides.  Under FR.spot_light, hung inside the fog,
+    a float64 classification of every sample finds each of C18's four outcomes on at least 5 % of them; and on the blocks
+    whose samples are all clearly behind the light (w < -0.05) or clearly outside the map (w > 0.05 and more than 0.05 texel
+    from it) the restatement with the map gives (S, T) bit-equal to its run without one: a sample outside the map or behind
+    the light is lit.  The margins are four orders of magnitude above fp32's error at these coordinates (|q| < 64, u = 2^-24),
+    so the fp32 march decides those samples as float64 does."""
+    w, h, steps, n = 33, 17, 7, 16
+    cam = FR.Camera(w, h)
+    color, depth = FR.random_hdr(w, h, 61, specials=True), cam.depth_of(FR.rolling_depth(w, h, 62))
+    M, sun = FR.spot_light()
+    smap = FR.spot_map(n, seed=5)
+    p = dict(BASE, density=0.06, height_falloff=0.15, height_base=1.0, max_distance=45.0, sun_dir=sun, shadow_bias=0.002, edge_sharpness=2.0,
+             frame_index=3, steps=steps)
+    pos = FR.sample_points64(depth, cam.inv, cam.eye, steps, p["frame_index"], p["max_distance"])
+    q = np.concatenate([pos, np.ones(pos.shape[:-1] + (1,))], -1) @ FR.colmajor(M).astype(np.float64).reshape(4, 4)
+    qw = q[..., 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v, sz = (q[..., 0] / qw * 0.5 + 0.5) * n, (q[..., 1] / qw * 0.5 + 0.5) * n, q[..., 2] / qw
+    behind = qw <= 0
+    inside = ~behind & (np.floor(u) >= 0) & (np.floor(u) < n) & (np.floor(v) >= 0) & (np.floor(v) < n)
+    texel = smap.astype(np.float64)[np.clip(np.floor(v), 0, n - 1).astype(int), np.clip(np.floor(u), 0, n - 1).astype(int)]
+    dark = inside & (sz + float(f32(p["shadow_bias"])) < texel)
+    shares = {"behind the light": behind.mean(), "outside the map": (~behind & ~inside).mean(), "inside, lit": (inside & ~dark).mean(),
+              "inside, shadowed": dark.mean()}
+    print(", ".join(f"{k} {s:.3f}" for k, s in shares.items()))
+    assert all(s >= 0.05 for s in shares.values()), shares
+
+    clearly_behind = qw < -0.05
+    clearly_outside = (qw > 0.05) & ((u < -0.05) | (u > n + 0.05) | (v < -0.05) | (v > n + 0.05))
+    blocks = (clearly_behind | clearly_outside).all(-1)
+    print(f"{int(blocks.sum())} of {blocks.size} blocks qualify, {int((blocks & clearly_behind.any(-1)).sum())} of them hold a behind sample")
+    assert blocks.sum() >= 20 and (blocks & clearly_behind.any(-1)).sum() >= 10
+    with_map = FR.run_ref(color, depth, cam.inv, cam.eye, shadow=smap, shadow_viewproj=FR.colmajor(M), **p)
+    without = FR.run_ref(color, depth, cam.inv, cam.eye, **p)
+    assert np.array_equal(with_map["st"][blocks].view(np.uint32), without["st"][blocks].view(np.uint32))
+    assert not np.array_equal(with_map["st"][~blocks].view(np.uint32), without["st"][~blocks].view(np.uint32)), "elsewhere the map must matter"
