@@ -136,6 +136,9 @@ UPSCALE_NO_SHARPEN = 1
 # include/svr_fog.h: the fog pass (height fog and sun shafts marched through the shadow map), HIP library only
 FOG_SYMBOLS = ["svr_fog_pass"]
 FOG_MAX_STEPS = 64
+# include/svr_dof.h: the depth of field pass (a thin-lens blur gathered over the HDR colour target), HIP library only
+DOF_SYMBOLS = ["svr_dof_pass"]
+DOF_MAX_RADIUS = 16
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -207,6 +210,11 @@ class SvrOverlayStats(C.Structure):  # include/svr_overlay.h
 
 class SvrUpscalePass(C.Structure):  # include/svr_upscale.h
     _fields_ = [("sharpness", C.c_float), ("flags", C.c_uint32)]
+
+
+class SvrDofPass(C.Structure):  # include/svr_dof.h
+    _fields_ = [("inv_z_scale", C.c_float), ("inv_z_bias", C.c_float), ("focus_distance", C.c_float), ("blur_scale", C.c_float),
+                ("max_radius", C.c_float)]
 
 
 class SvrFogPass(C.Structure):  # include/svr_fog.h
@@ -365,6 +373,9 @@ class SvrLib:
         if self.has_upscale:
             L.svr_upscale_to_swapchain.argtypes = [P, C.POINTER(SvrUpscalePass), P, C.c_uint32, C.c_uint32, C.c_int]
             L.svr_read_upscaled.argtypes = [P, C.POINTER(SvrUpscalePass), C.c_uint32, C.c_uint32, C.c_int, P, C.c_size_t]
+        self.has_dof = hasattr(L, "svr_dof_pass")
+        if self.has_dof:
+            L.svr_dof_pass.argtypes = [P, C.POINTER(SvrDofPass)]
         self.has_fog = hasattr(L, "svr_fog_pass")
         if self.has_fog:
             L.svr_fog_pass.argtypes = [P, C.POINTER(SvrFogPass)]
@@ -438,6 +449,11 @@ def fog_struct(inv_viewproj, camera_position, density, height_falloff=0.0, heigh
     _set_shadow(p, shadow_ptr, shadow_size, shadow_viewproj, shadow_bias)
     p.frame_index = int(frame_index) & 0xffffffff
     return p
+
+
+def dof_struct(inv_z_scale, inv_z_bias, focus_distance, blur_scale, max_radius=DOF_MAX_RADIUS):
+    """an SvrDofPass (include/svr_dof.h) from Python values; (inv_z_scale, inv_z_bias): glmath.dof_depth_terms(proj)"""
+    return SvrDofPass(float(inv_z_scale), float(inv_z_bias), float(focus_distance), float(blur_scale), float(max_radius))
 
 
 def scene_struct(view, proj, viewproj, ambient, sun_dir, sun_color):
@@ -951,6 +967,16 @@ class Renderer:
         p = fog_struct(inv_viewproj, camera_position, density, height_falloff, height_base, max_distance, steps, fog_color, sun_dir,
                        sun_color, anisotropy, shadow_ptr, shadow_size, shadow_viewproj, shadow_bias, edge_sharpness, frame_index)
         self.lib.check(self.lib.lib.svr_fog_pass(self.h, C.byref(p)))
+
+    # ---- the depth of field pass (include/svr_dof.h)
+    def dof_pass(self, inv_z_scale, inv_z_bias, focus_distance, blur_scale, max_radius=DOF_MAX_RADIUS):
+        """svr_dof_pass: a thin-lens blur over the scissor's pixels of the RGBA16F colour target, in place.  (inv_z_scale,
+        inv_z_bias): glmath.dof_depth_terms(proj); blur_scale: the radius in pixels of a point at infinity
+        (glmath.dof_blur_scale); no radius is larger than max_radius"""
+        if not getattr(self.lib, "has_dof", False):
+            raise SvrError(-5, f"{self.lib.backend} has no depth of field pass (include/svr_dof.h)")
+        p = dof_struct(inv_z_scale, inv_z_bias, focus_distance, blur_scale, max_radius)
+        self.lib.check(self.lib.lib.svr_dof_pass(self.h, C.byref(p)))
 
     # ---- temporal antialiasing (include/svr_temporal.h)
     def _need_temporal(self):

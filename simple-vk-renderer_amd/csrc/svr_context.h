@@ -24,6 +24,7 @@
 #include "../../include/svr_ids.h"
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_fog.h"
+#include "../../include/svr_dof.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
@@ -259,10 +260,14 @@ using UpscaleOp = UpscaleLaunch;
 struct FogOp {
   FogLaunch launch{};
 };
+// svr_dof_pass: the kernels' parameters as recorded, by value (the scratch images by address)
+struct DofOp {
+  DofLaunch launch{};
+};
 
 struct LoggedOp {
   int slot;  // index into h_counters / op_done / h_stage
-  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp, FogOp> what;
+  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp, FogOp, DofOp> what;
   template <class Op> LoggedOp(int slot_, Op&& op) : slot(slot_), what(std::forward<Op>(op)) {}
   const PassOp* as_pass() const { return std::get_if<PassOp>(&what); }
 };
@@ -383,6 +388,9 @@ struct Context {
   // svr_fog_pass: the half-resolution images, (S.rgb, T) per block and then t_end per block (fog_blocks of the context's
   // extent each); allocated once, by the first fog pass
   DevPtr<float4> d_fog;
+  // svr_dof_pass: the prepared image (dof_texels of the context's extent, 8 bytes each) and then M per cell (dof_cells
+  // floats); allocated once, by the first depth of field pass
+  DevPtr<uint2> d_dof;
   // svr_temporal_resolve: the two history images (4 halves per texel, the context's extent), allocated and zeroed by the
   // first resolve.  temporal_read names the one the next resolve reads; temporal_has: a resolve was accepted, with the
   // scissor temporal_scissor.  All three change at an accepted call only, in call order.
@@ -469,6 +477,7 @@ int submit(SvrContext* ctx, const ExposureOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const OverlayOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const UpscaleOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const FogOp& op, int slot, bool replaying);
+int submit(SvrContext* ctx, const DofOp& op, int slot, bool replaying);
 // log the finished payload of any of those kinds in a free slot and submit it; the entry stays in the log if the submit
 // fails
 template <class Op> int log_op(SvrContext* ctx, Op&& op) {

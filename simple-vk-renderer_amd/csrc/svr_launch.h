@@ -3,6 +3,7 @@
 #include <cstddef>
 
 #include "../../include/svr_ambient.h"
+#include "../../include/svr_dof.h"
 #include "../../include/svr_exposure.h"
 #include "../../include/svr_fog.h"
 #include "../../include/svr_lighting.h"
@@ -237,6 +238,28 @@ struct FogLaunch {
 inline size_t fog_blocks(uint32_t w, uint32_t h) { return (size_t)((w + 1u) / 2u) * ((h + 1u) / 2u); }
 // one fog_march_kernel and one fog_composite_kernel, on s
 void launch_fog(const FogLaunch& A, hipStream_t s);
+// k_dof.hip: the depth of field pass (include/svr_dof.h)
+struct DofLaunch {
+  uint2* color;                 // the RGBA16F colour target, W texels per row: the scissor's RGB halves are rewritten in place
+  const float* depth;           // the depth target, read as it stands in stream order
+  uint32_t W;
+  uint32_t sx, sy, sw, sh;      // the scissor: the image of the pass
+  uint32_t pitch;               // C62: texels per row of the prepared image, sw rounded up to even
+  uint32_t cw, ch;              // C63: the cells, (sw + 7) / 8 by (sh + 7) / 8
+  uint2* prep;                  // the context's scratch: the prepared image (san(rgb) and c, four halves per texel)
+  float* cells;                 // ... and M per cell, cw per row
+  float inv_z_scale, inv_z_bias;
+  float neg_focus;              // C61: -focus_distance
+  float blur_scale;
+  float max_radius, neg_max_radius;
+  uint32_t Rc;                  // C63: (ceil(max_radius) + 7) / 8
+  const uint32_t* poison;
+};
+// C62, C63: the texels and the cells a context of W x H needs scratch for
+inline size_t dof_texels(uint32_t w, uint32_t h) { return (size_t)((w + 1u) & ~1u) * h; }
+inline size_t dof_cells(uint32_t w, uint32_t h) { return (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u); }
+// one dof_prepare_kernel and one dof_gather_kernel, on s
+void launch_dof(const DofLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

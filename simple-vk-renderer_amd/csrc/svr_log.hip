@@ -393,6 +393,10 @@ int submit(SvrContext* ctx, const FogOp& op, int, bool) {
   launch_fog(op.launch, ctx->stream);
   return launched();
 }
+int submit(SvrContext* ctx, const DofOp& op, int, bool) {
+  launch_dof(op.launch, ctx->stream);
+  return launched();
+}
 
 namespace {
 

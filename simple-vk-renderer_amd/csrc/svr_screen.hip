@@ -1,8 +1,8 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, auto-exposure, temporal antialiasing,
-// ambient occlusion, the UI overlay and the upscaled present, with their targets and read-backs.  Each validates its
-// arguments, allocates what its first call needs, records its kernels' parameters in a payload of its kind and logs it
-// (svr_context.h, svr_log.hip).
+// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, the depth of field pass, auto-exposure,
+// temporal antialiasing, ambient occlusion, the UI overlay and the upscaled present, with their targets and read-backs.
+// Each validates its arguments, allocates what its first call needs, records its kernels' parameters in a payload of
+// its kind and logs it (svr_context.h, svr_log.hip).
 #include <cmath>
 #include <cstddef>
 
@@ -303,6 +303,53 @@ int svr_fog_pass(SvrContext* ctx, const SvrFogPass* pass) {
   F.edge = pass->edge_sharpness;
   F.frame = pass->frame_index;
   F.poison = ctx->d_poison.get();
+  return log_op(ctx, std::move(op));
+}
+
+// ---------------------------------------------------------------- the depth of field pass (include/svr_dof.h)
+static_assert(sizeof(SvrDofPass) == 20 && offsetof(SvrDofPass, inv_z_scale) == 0 && offsetof(SvrDofPass, inv_z_bias) == 4 &&
+                  offsetof(SvrDofPass, focus_distance) == 8 && offsetof(SvrDofPass, blur_scale) == 12 && offsetof(SvrDofPass, max_radius) == 16,
+              "include/svr_dof.h");
+
+int svr_dof_pass(SvrContext* ctx, const SvrDofPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_dof_pass: null argument");
+  if (!(std::isfinite(pass->inv_z_scale) && std::isfinite(pass->inv_z_bias))) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_dof_pass: inv_z_scale and inv_z_bias must be finite");
+  if (!(std::isfinite(pass->focus_distance) && pass->focus_distance > 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_dof_pass: the focus distance must be finite and greater than 0");
+  if (!(std::isfinite(pass->blur_scale) && pass->blur_scale >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_dof_pass: the blur scale must be finite and at least 0");
+  if (!(pass->max_radius >= 0.0f && pass->max_radius <= (float)SVR_DOF_MAX_RADIUS))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_dof_pass: max_radius must be in 0..SVR_DOF_MAX_RADIUS");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_dof_pass: the colour target must be RGBA16F (the pass works in scene-linear HDR)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_dof_pass: not under svr_set_row_interleave with a stride above 1");
+  if (pass->blur_scale == 0.0f || pass->max_radius == 0.0f) return SVR_OK;  // a pinhole: the target keeps its bits, and no kernel is enqueued to rewrite them
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  // (both counts grow with the image's extent, so the images of any scissor fit in those of the whole target)
+  const size_t texels = dof_texels(ctx->W, ctx->H);
+  if (!ctx->d_dof) DEV_ALLOC(ctx->d_dof, texels * sizeof(uint2) + dof_cells(ctx->W, ctx->H) * sizeof(float));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  DofOp op;
+  DofLaunch& D = op.launch;
+  D.color = (uint2*)ctx->color;
+  D.depth = ctx->depth;
+  D.W = ctx->W;
+  D.sx = ctx->sx;
+  D.sy = ctx->sy;
+  D.sw = ctx->sw;
+  D.sh = ctx->sh;
+  D.pitch = (ctx->sw + 1u) & ~1u;
+  D.cw = (ctx->sw + 7u) / 8u;
+  D.ch = (ctx->sh + 7u) / 8u;
+  D.prep = ctx->d_dof.get();
+  D.cells = reinterpret_cast<float*>(ctx->d_dof.get() + texels);
+  D.inv_z_scale = pass->inv_z_scale;
+  D.inv_z_bias = pass->inv_z_bias;
+  D.neg_focus = -pass->focus_distance;
+  D.blur_scale = pass->blur_scale;
+  D.max_radius = pass->max_radius;
+  D.neg_max_radius = -pass->max_radius;
+  D.Rc = ((uint32_t)std::ceil(pass->max_radius) + 7u) / 8u;  // C63: R = 1 .. SVR_DOF_MAX_RADIUS, Rc = 1 or 2
+  D.poison = ctx->d_poison.get();
   return log_op(ctx, std::move(op));
 }
 

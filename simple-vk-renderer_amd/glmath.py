@@ -278,3 +278,20 @@ def render_extent(window_w, window_h, scale):
     a float product truncated to uint32, each way; at least 1"""
     s = f32(scale)
     return max(int(f32(window_w) * s), 1), max(int(f32(window_h) * s), 1)
+
+
+# ---- the depth of field pass (include/svr_dof.h): the caller's side, bit for bit host/svr_math.h's
+def dof_depth_terms(proj):
+    """(SvrDofPass.inv_z_scale, inv_z_bias) of a perspective projection, jittered or not: 1 / view distance =
+    depth * inv_z_scale + inv_z_bias, with depth = (proj[2][2] z + proj[3][2]) / -z.  Taken in double, rounded once each"""
+    p = np.asarray(proj, dtype=f32)
+    b = float(p[3][2])
+    return f32(1.0 / b), f32(float(p[2][2]) / b)
+
+
+def dof_blur_scale(focal_length, f_number, focus_distance, sensor_height, target_height):
+    """SvrDofPass.blur_scale of a thin lens: the radius, in pixels of a target of the given height, of the circle of
+    confusion of a point at infinity, 0.5 f^2 / (N (zf - f)) scaled from the sensor to the target.  Lengths in one unit;
+    taken in double from the fp32 values, rounded once"""
+    f, n, zf, sh, th = (float(f32(v)) for v in (focal_length, f_number, focus_distance, sensor_height, target_height))
+    return f32(((0.5 * f * f) / (n * (zf - f))) * th / sh)

@@ -19,6 +19,10 @@
 //           shafts from the scene's sun behind the transparent objects, in front of --taa and --post (16 steps, no shadow
 //           map); the pass as handed to the library is dumped as <prefix>.fog.  With --taa, frame_index advances per
 //           frame, so the resolve averages the dither away; without, it stays 0.  Not with --views or --ranks
+//       --dof <focus_distance>:<blur_scale>[:<max_radius>]: the depth of field pass (include/svr_dof.h, HIP library only) with
+//           --deferred 1: a thin-lens blur behind the fog pass (or the transparent objects), in front of --taa and --post;
+//           blur_scale is the radius in pixels of a point at infinity, max_radius (default 16) the largest radius; the
+//           pass as handed to the library is dumped as <prefix>.dof.  Not with --views or --ranks
 //       --taa <blend>: temporal antialiasing (include/svr_temporal.h, HIP library only): every frame is drawn with a sub-pixel
 //           jitter (Halton(2, 3) - 0.5 pixels, a period of 16 frames) and resolved against the reprojected, clamped history
 //           with the given weight of the current frame, behind the frame's last geometry or lighting pass and in front of
@@ -109,7 +113,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false, stats_overlay = false;
-  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, fog_arg, scale_arg, upscale_arg = "off";
+  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, fog_arg, dof_arg, scale_arg, upscale_arg = "off";
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -137,6 +141,7 @@ int main(int argc, char** argv) {
     else if (a == "--post") post_arg = argv[i + 1];  // <operator>:<levels> (include/svr_post.h)
     else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
     else if (a == "--fog") fog_arg = argv[i + 1];  // <density>:<falloff>[:<g>] (include/svr_fog.h)
+    else if (a == "--dof") dof_arg = argv[i + 1];  // <focus_distance>:<blur_scale>[:<max_radius>] (include/svr_dof.h)
     else if (a == "--ao") ao_arg = argv[i + 1];  // <radius>:<intensity> (include/svr_ambient.h)
     else if (a == "--auto-exposure") ae_arg = argv[i + 1];  // <key>:<adapt> (include/svr_exposure.h)
     else if (a == "--stats-overlay") stats_overlay = atoi(argv[i + 1]) != 0;  // include/svr_overlay.h
@@ -180,7 +185,8 @@ int main(int argc, char** argv) {
                     "                [--occlusion off|last|prepass]\n"
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
                     "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt] [--stats-overlay 1]\n"
-                    "                [--render-scale s --upscale sharpness|off] [--fog density:falloff[:g]]\n");
+                    "                [--render-scale s --upscale sharpness|off] [--fog density:falloff[:g]]\n"
+                    "                [--dof focus_distance:blur_scale[:max_radius]]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -245,6 +251,30 @@ int main(int argc, char** argv) {
     }
     if (ranks > 1) {
       fprintf(stderr, "--fog: not with --ranks (a band rank would clamp the upsample's taps at its band's edge)\n");
+      return 1;
+    }
+  }
+  float dof_focus = 0.f, dof_scale = 0.f, dof_max = (float)SVR_DOF_MAX_RADIUS;
+  if (!dof_arg.empty()) {
+    char tail = 0;
+    const int n = sscanf(dof_arg.c_str(), "%f:%f:%f%c", &dof_focus, &dof_scale, &dof_max, &tail);
+    char tail2 = 0;
+    const int n2 = n == 2 ? sscanf(dof_arg.c_str(), "%f:%f%c", &dof_focus, &dof_scale, &tail2) : 0;
+    const bool shape = n == 3 || (n == 2 && n2 == 2);
+    if (!shape || !(dof_focus > 0.f && dof_focus < INFINITY) || !(dof_scale >= 0.f && dof_scale < INFINITY) || !(dof_max >= 0.f && dof_max <= (float)SVR_DOF_MAX_RADIUS)) {
+      fprintf(stderr, "--dof: expected <focus_distance > 0>:<blur_scale >= 0>[:<max_radius in 0..16>], got '%s'\n", dof_arg.c_str());
+      return 2;
+    }
+    if (!deferred) {
+      fprintf(stderr, "--dof: needs --deferred 1 (the pass runs behind the lighting pass and the transparent objects)\n");
+      return 1;
+    }
+    if (views) {
+      fprintf(stderr, "--dof: not with --views (the pass works on the context's own targets)\n");
+      return 1;
+    }
+    if (ranks > 1) {
+      fprintf(stderr, "--dof: not with --ranks (a band rank would clamp its taps and cells at its band's edge)\n");
       return 1;
     }
   }
@@ -627,6 +657,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--fog: the library has no fog pass (include/svr_fog.h)\n");
     return 1;
   }
+  if (!dof_arg.empty() && !eng.api.svr_dof_pass) {
+    fprintf(stderr, "--dof: the library has no depth of field pass (include/svr_dof.h)\n");
+    return 1;
+  }
   if (!taa_arg.empty() && !eng.api.svr_temporal_resolve) {
     fprintf(stderr, "--taa: the library has no temporal pass (include/svr_temporal.h)\n");
     return 1;
@@ -656,6 +690,11 @@ int main(int argc, char** argv) {
     // behind the deferred frame's transparents, in front of the resolve (which averages the per-frame dither) and the post pass
     if (!fog_arg.empty() && !eng.fog_pass(fog_density, fog_falloff, fog_g, taa_blend > 0.f ? (uint32_t)f : 0u)) {
       fprintf(stderr, "%s\n", eng.error.rfind("--fog", 0) == 0 ? eng.error.c_str() : ("--fog: " + eng.error).c_str());
+      return 1;
+    }
+    // behind the fog pass, in front of the resolve and the post pass: on scene-linear values, so that bloom sees the bokeh
+    if (!dof_arg.empty() && !eng.dof_pass(dof_focus, dof_scale, dof_max)) {
+      fprintf(stderr, "%s\n", eng.error.rfind("--dof", 0) == 0 ? eng.error.c_str() : ("--dof: " + eng.error).c_str());
       return 1;
     }
     if (taa_blend > 0.f && !eng.temporal_resolve()) {  // behind the frame's last pass, in front of the post pass
@@ -704,6 +743,7 @@ int main(int argc, char** argv) {
     dump(prefix + ".color", color.data(), color.size());
     dump(prefix + ".depth", depth.data(), depth.size());
     if (!fog_arg.empty()) dump(prefix + ".fog", &eng.last_fog, 1);
+    if (!dof_arg.empty()) dump(prefix + ".dof", &eng.last_dof, 1);
     std::vector<uint8_t> swap;  // what copy_image leaves in the swapchain image (src/vk_engine.cpp:1277)
     std::string drawn;  // --stats-overlay: ... and what draw_imgui then draws onto it (src/vk_engine.cpp:1282)
     if (!(stats_overlay ? eng.stats_overlay(swap, drawn) : eng.read_swapchain(swap))) {

@@ -61,6 +61,7 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_upscale_to_swapchain = reinterpret_cast<decltype(svr_upscale_to_swapchain)>(dlsym(handle, "svr_upscale_to_swapchain"));
   svr_read_upscaled = reinterpret_cast<decltype(svr_read_upscaled)>(dlsym(handle, "svr_read_upscaled"));
   svr_fog_pass = reinterpret_cast<decltype(svr_fog_pass)>(dlsym(handle, "svr_fog_pass"));
+  svr_dof_pass = reinterpret_cast<decltype(svr_dof_pass)>(dlsym(handle, "svr_dof_pass"));
   return ok;
 }
 void SvrApi::unload() {
@@ -460,6 +461,26 @@ bool SvrEngine::fog_pass(float density, float falloff, float anisotropy, uint32_
   fp.frame_index = frame_index;
   last_fog = fp;
   if (api.svr_fog_pass(ctx, &fp)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::dof_pass(float focus_distance, float blur_scale, float max_radius) {
+  if (!api.svr_dof_pass) {
+    error = "--dof: the library has no depth of field pass (include/svr_dof.h)";
+    return false;
+  }
+  SvrDofPass dp{};
+  mat4 proj;
+  std::memcpy(proj.data(), scene_data.proj, 64);
+  svrm::dof_depth_terms(proj, &dp.inv_z_scale, &dp.inv_z_bias);
+  dp.focus_distance = focus_distance;
+  dp.blur_scale = blur_scale;
+  dp.max_radius = max_radius;
+  last_dof = dp;
+  if (api.svr_dof_pass(ctx, &dp)) {
     error = api.svr_last_error();
     return false;
   }

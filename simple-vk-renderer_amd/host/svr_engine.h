@@ -27,6 +27,7 @@
 #include "../../include/svr_ambient.h"
 #include "../../include/svr_exposure.h"
 #include "../../include/svr_fog.h"
+#include "../../include/svr_dof.h"
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_upscale.h"
 #include "../../include/svr_views.h"
@@ -72,6 +73,8 @@ struct SvrApi {
   SVR_FN(svr_upscale_to_swapchain) SVR_FN(svr_read_upscaled)
   // include/svr_fog.h: optional (HIP library only), needed by SvrEngine::fog_pass
   SVR_FN(svr_fog_pass)
+  // include/svr_dof.h: optional (HIP library only), needed by SvrEngine::dof_pass
+  SVR_FN(svr_dof_pass)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -210,6 +213,12 @@ struct SvrEngine {
   // last_fog: the pass as it was handed to the library (svr_demo dumps it as <prefix>.fog).
   SvrFogPass last_fog{};
   bool fog_pass(float density, float falloff, float anisotropy, uint32_t frame_index);
+  // The depth of field pass (svr_demo --deferred 1 --dof <focus_distance>:<blur_scale>[:<max_radius>], include/svr_dof.h):
+  // behind the fog pass, in front of the temporal resolve and the post pass.  The depth terms are those of the scene's
+  // projection (svrm::dof_depth_terms; a jitter does not move them).
+  // last_dof: the pass as it was handed to the library (svr_demo dumps it as <prefix>.dof).
+  SvrDofPass last_dof{};
+  bool dof_pass(float focus_distance, float blur_scale, float max_radius);
   // Auto-exposure (svr_demo --auto-exposure <key>:<adapt>, include/svr_exposure.h): meter the colour target behind the
   // frame's last pass and in front of the post pass, which then multiplies its exposure (a compensation) by the state's.
   // The first call turns svr_set_post_auto_exposure on.  Whole window, exposures clamped to [2^-10, 2^10].

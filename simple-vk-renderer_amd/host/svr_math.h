@@ -212,4 +212,20 @@ inline void render_extent(uint32_t window_w, uint32_t window_h, float scale, uin
   *h = rh < 1u ? 1u : rh;
 }
 
+// ---- the depth of field pass (include/svr_dof.h): the caller's side; glmath.py's dof_depth_terms and dof_blur_scale are
+// the same bit for bit (tests/test_dof_ref.py states them, tests/test_host_cpp_dof.py compares the two).
+// SvrDofPass.inv_z_scale and inv_z_bias of a perspective projection, jittered or not: 1 / view distance =
+// depth * scale + bias, with depth = (proj[2][2] z + proj[3][2]) / -z.  Taken in double, rounded once each.
+inline void dof_depth_terms(const mat4& proj, float* inv_z_scale, float* inv_z_bias) {
+  const double b = (double)proj.m[3][2];
+  *inv_z_scale = (float)(1.0 / b);
+  *inv_z_bias = (float)((double)proj.m[2][2] / b);
+}
+// SvrDofPass.blur_scale of a thin lens: the radius, in pixels of a target of the given height, of the circle of confusion
+// of a point at infinity, 0.5 f^2 / (N (zf - f)) scaled from the sensor to the target.  Taken in double, rounded once.
+inline float dof_blur_scale(float focal_length, float f_number, float focus_distance, float sensor_height, float target_height) {
+  const double f = focal_length, n = f_number, zf = focus_distance, sh = sensor_height, th = target_height;
+  return (float)(((0.5 * f * f) / (n * (zf - f))) * th / sh);
+}
+
 }  // namespace svrm
