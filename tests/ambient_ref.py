@@ -1,16 +1,15 @@
 """Test-side helpers of the ambient pass (include/svr_ambient.h): build and run tests/native/ambient_ref.cpp, the scalar
 restatement of DESIGN C32-C37 (and of C17-C19 with the ambient factor).  Depth travels as float32 [H, W], the normal plane
 as float32 [H, W, 4], matrices as 4 x 4 indexed [col][row] like glmath's or as 16 floats, column-major."""
-import atexit
 import functools
 import os
-import shutil
 import subprocess
 import tempfile
 
 import numpy as np
 
 import __graft_entry__ as g
+import native_ref as N
 
 pkg = g.load_package()
 A, GL = pkg.abi, pkg.glmath
@@ -19,14 +18,7 @@ NO_BLUR = 1
 NO_SURFACE, SMALL, EVALUATED, CAPPED = 1, 2, 3, 4  # the reference's "kind" of a pixel inside the scissor
 
 
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="ambient_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "ambient_ref")
-    src = os.path.join(g.ROOT, "tests", "native", "ambient_ref.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Werror", "-o", exe, src], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "ambient_ref", extra=("-Wall", "-Werror"))
 
 
 def m16(m):
@@ -34,12 +26,7 @@ def m16(m):
 
 
 def _run(mode, blob, size):
-    with tempfile.TemporaryDirectory(prefix="ambient_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(blob)
-        subprocess.run([ref_exe(), mode, fin, fout], check=True)
-        raw = open(fout, "rb").read()
+    raw = N.run(ref_exe(), blob, mode)
     assert len(raw) == size
     return raw
 

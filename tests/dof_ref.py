@@ -2,17 +2,15 @@
 restatement of DESIGN C61-C66, the fp64 statement of the same gather written from the definitions (dof64), the tap table
 from its formula, and the inputs the tests share.  Colour targets travel as uint16 [H, W, 4] arrays of fp16 bit patterns,
 depth as float32 [H, W] (bits 0 where nothing was drawn)."""
-import atexit
 import functools
 import math
-import os
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 
 import __graft_entry__ as g
+import native_ref as N
+from native_ref import SPECIALS, floats, halves, san_bits  # noqa: F401  (re-exported)
 
 GL = g.load_package().glmath
 f32 = np.float32
@@ -22,14 +20,7 @@ WRONG_VARIANTS = {1: "the sign of c flipped", 2: "min rule dropped", 3: "cover w
                   9: "tap clamp off by one", 10: "dist from the clamped offsets", 11: "even ring not turned", 12: "r clamped from above only"}
 
 
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="dof_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "dof_ref")
-    src = os.path.join(g.ROOT, "tests", "native", "dof_ref.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe, src], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "dof_ref")
 
 
 def run_ref(color, depth, terms, focus_distance, blur_scale, max_radius, scissor=None, variant=0):
@@ -42,12 +33,7 @@ def run_ref(color, depth, terms, focus_distance, blur_scale, max_radius, scissor
     sx, sy, sw, sh = scissor if scissor else (0, 0, w, h)
     hdr = np.array([w, h, sx, sy, sw, sh, variant, 0], np.uint32)
     par = np.array([terms[0], terms[1], focus_distance, blur_scale, max_radius], f32)
-    with tempfile.TemporaryDirectory(prefix="dof_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(hdr.tobytes() + par.tobytes() + color.tobytes() + depth.tobytes())
-        subprocess.run([ref_exe(), fin, fout], check=True)
-        raw = open(fout, "rb").read()
+    raw = N.run(ref_exe(), hdr.tobytes() + par.tobytes() + color.tobytes() + depth.tobytes())
     n = w * h * 8
     out = np.frombuffer(raw[:n], np.uint16).reshape(h, w, 4).copy()
     cw, ch = (int(v) for v in np.frombuffer(raw[n:n + 8], np.uint32))
@@ -74,30 +60,6 @@ def tap_table():
             x, y = (j / 3.0) * math.cos(a), (j / 3.0) * math.sin(a)
             t.append((0.0 if abs(x) < 2.0 ** -40 else x, 0.0 if abs(y) < 2.0 ** -40 else y))
     return np.array(t, np.float64).astype(f32)
-
-
-def halves(values):
-    """float array -> fp16 bit patterns (numpy's cast; for building inputs)"""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.asarray(values, dtype=f32).astype(np.float16).view(np.uint16)
-
-
-def floats(bits):
-    """fp16 bit patterns -> float32, exactly"""
-    with np.errstate(invalid="ignore"):
-        return np.asarray(bits, dtype=np.uint16).view(np.float16).astype(f32)
-
-
-def san_bits(bits):
-    """san as the bit operation on halves it is (C62): NaN, negatives and -0 become 0, +inf the largest half"""
-    bits = np.asarray(bits, np.uint16)
-    out = bits.copy()
-    out[bits >= 0x7c00] = 0
-    out[bits == 0x7c00] = 0x7bff
-    return out
-
-
-SPECIALS = np.array([0x7e00, 0xfe00, 0x7c01, 0x7c00, 0xfc00, 0xbc00, 0xc500, 0x8000, 0x7bff, 0x0001, 0x03ff, 0x8001, 0x0000, 0x3c00], np.uint16)
 
 
 def random_hdr(w, h, seed, specials=False):

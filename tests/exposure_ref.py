@@ -2,16 +2,12 @@
 restatement of DESIGN C38-C42, and an independent numpy fp64 statement of what the meter is for.  Colour targets travel as
 uint16 [H, W, 4] arrays of fp16 bit patterns, as Renderer.read_color gives them; a state is a dict of SvrExposureState's
 fields."""
-import atexit
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-import __graft_entry__ as g
+import native_ref as N
+from native_ref import floats, halves  # noqa: F401  (re-exported)
 
 f32 = np.float32
 BINS = 256
@@ -20,17 +16,7 @@ METER = {"key": 0.18, "low_fraction": 0.0, "high_fraction": 1.0, "min_exposure":
 WRONG_VARIANTS = {1: "bin shift off by one", 2: "black counted in bin 0", 3: "window over all pixels", 4: "floor for the window's upper end",
                   5: "clamp after the adapt step", 6: "snap ignored", 7: "sub-bin literals of the lower edges"}
 STATE_DTYPE = np.dtype([("exposure", "<f4"), ("target", "<f4"), ("mean_log2", "<f4"), ("counted", "<u4"), ("black", "<u4"), ("meters", "<u4")])
-SRC = os.path.join(g.ROOT, "tests", "native", "exposure_ref.cpp")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
-
-
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="exposure_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "exposure_ref")
-    subprocess.run(["g++", *FLAGS, "-o", exe, SRC], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "exposure_ref")
 
 
 def meter(**kw):
@@ -62,23 +48,14 @@ def run_ref(color, m=None, prev=None, snap=True, scissor=None, variant=0):
     sx, sy, sw, sh = scissor or (0, 0, w, h)
     hdr = np.array([w, h, sx, sy, sw, sh, 1 if snap else 0, variant], np.uint32).tobytes()
     par = np.array([m["key"], m["low_fraction"], m["high_fraction"], m["min_exposure"], m["max_exposure"], m["adapt"]], f32).tobytes()
-    with tempfile.TemporaryDirectory(prefix="exposure_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(hdr + par + state_bits(prev or FIRST_STATE).tobytes() + color.tobytes())
-        subprocess.run([ref_exe(), fin, fout], check=True)
-        raw = open(fout, "rb").read()
+    raw = N.run(ref_exe(), hdr + par + state_bits(prev or FIRST_STATE).tobytes() + color.tobytes())
     assert len(raw) == BINS * 4 + 24
     return np.frombuffer(raw, np.uint32, BINS, 0).copy(), state_of(np.frombuffer(raw, STATE_DTYPE, 1, BINS * 4)[0])
 
 
 def _floats_through(mode, values, out_dtype):
     values = np.ascontiguousarray(values, dtype=f32)
-    with tempfile.TemporaryDirectory(prefix="exposure_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        values.tofile(fin)
-        subprocess.run([ref_exe(), mode, fin, fout], check=True)
-        return np.fromfile(fout, out_dtype).reshape(values.shape)
+    return np.frombuffer(N.run(ref_exe(), values.tobytes(), mode), out_dtype).reshape(values.shape).copy()
 
 
 def exp2_poly(x):
@@ -89,16 +66,6 @@ def exp2_poly(x):
 def counters(lum):
     """the counter (C39: 0 .. 255, 256 = black) of each luminance of a float32 array"""
     return _floats_through("--bin", lum, np.uint32)
-
-
-def halves(values):
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.asarray(values, dtype=f32).astype(np.float16).view(np.uint16)
-
-
-def floats(bits):
-    with np.errstate(invalid="ignore"):
-        return np.asarray(bits, dtype=np.uint16).view(np.float16).astype(f32)
 
 
 def grey(h, w, value_bits, alpha=0x3c00):
@@ -118,8 +85,7 @@ def random_hdr(w, h, seed, specials=True, lo=-20.0, hi=16.0):
     out[..., 3] = rng.integers(0, 1 << 16, (h, w), dtype=np.uint16)
     if specials:
         edges = halves([2.0 ** k * (1 + j / 8) for k in range(-14, 16) for j in range(8)])
-        pool = np.concatenate([np.array([0x7e00, 0xfe00, 0x7c01, 0x7c00, 0xfc00, 0xbc00, 0xc500, 0x8000, 0x7bff, 0x0001, 0x03ff, 0x8001, 0x0000], np.uint16),
-                               edges, edges - 1])
+        pool = np.concatenate([N.SPECIALS[:13], edges, edges - 1])
         hit = rng.random((h, w, 3)) < 0.04
         out[..., :3][hit] = pool[rng.integers(0, pool.size, int(hit.sum()))]
     return out

@@ -3,17 +3,13 @@ DESIGN C55-C60, the fp64 statement of the same march written from the definition
 share.  Colour targets travel as uint16 [H, W, 4] arrays of fp16 bit patterns, depth as float32 [H, W] (reversed-Z: 1 at
 the near plane, bits 0 where nothing was drawn), a shadow map as float32 [Hs, Ws].  Matrices are 4 x 4 numpy arrays in
 the mathematical convention (M @ column vector); colmajor() gives the 16 floats the C structs hold."""
-import atexit
 import functools
 import math
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-import __graft_entry__ as g
+import native_ref as N
+from native_ref import SPECIALS, floats, halves  # noqa: F401  (re-exported)
 
 f32 = np.float32
 WRONG_VARIANTS = {1: "T updated before S", 2: "dither dropped", 3: "sample at the step's start", 4: "plain bilinear upsample",
@@ -24,14 +20,7 @@ DEFAULTS = dict(density=0.05, height_falloff=0.0, height_base=0.0, max_distance=
                 edge_sharpness=1.0, frame_index=0)
 
 
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="fog_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "fog_ref")
-    src = os.path.join(g.ROOT, "tests", "native", "fog_ref.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe, src], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "fog_ref")
 
 
 def colmajor(M):
@@ -55,35 +44,14 @@ def run_ref(color, depth, inv_viewproj, camera, scissor=None, shadow=None, varia
                           [p["anisotropy"]], (list(p["sun_dir"]) + [0.0])[:4], np.asarray(p["sun_color"], f32)[:3], [p["edge_sharpness"]],
                           np.asarray(svp, f32).reshape(16), [p["shadow_bias"], 0.0 if pin_o is None else pin_o]]).astype(f32)
     assert par.size == 53
-    with tempfile.TemporaryDirectory(prefix="fog_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(hdr.tobytes() + par.tobytes() + color.tobytes() + depth.tobytes())
-            if shadow is not None:
-                f.write(np.ascontiguousarray(shadow, dtype=f32).tobytes())
-        subprocess.run([ref_exe(), fin, fout], check=True)
-        raw = open(fout, "rb").read()
+    smap = b"" if shadow is None else np.ascontiguousarray(shadow, dtype=f32).tobytes()
+    raw = N.run(ref_exe(), hdr.tobytes() + par.tobytes() + color.tobytes() + depth.tobytes() + smap)
     n = w * h * 8
     out = np.frombuffer(raw[:n], np.uint16).reshape(h, w, 4).copy()
     gw, gh = np.frombuffer(raw[n:n + 8], np.uint32)
     st = np.frombuffer(raw[n + 8:n + 8 + gw * gh * 16], f32).reshape(gh, gw, 4).copy()
     te = np.frombuffer(raw[n + 8 + gw * gh * 16:], f32).reshape(gh, gw).copy()
     return dict(color=out, st=st, t_end=te)
-
-
-def halves(values):
-    """float array -> fp16 bit patterns (numpy's cast; for building inputs)"""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.asarray(values, dtype=f32).astype(np.float16).view(np.uint16)
-
-
-def floats(bits):
-    """fp16 bit patterns -> float32, exactly"""
-    with np.errstate(invalid="ignore"):
-        return np.asarray(bits, dtype=np.uint16).view(np.float16).astype(f32)
-
-
-SPECIALS = np.array([0x7e00, 0xfe00, 0x7c01, 0x7c00, 0xfc00, 0xbc00, 0xc500, 0x8000, 0x7bff, 0x0001, 0x03ff, 0x8001, 0x0000, 0x3c00], np.uint16)
 
 
 def random_hdr(w, h, seed, specials=False):

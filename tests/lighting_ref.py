@@ -1,29 +1,18 @@
 """Test-side helpers of the deferred lighting pass (include/svr_lighting.h): build and run tests/native/light_ref.cpp, the
 scalar brute-force restatement of DESIGN C17-C19, and apply the stores of C20 to what it returns."""
-import atexit
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 import __graft_entry__ as g
+import native_ref as N
 
 pkg = g.load_package()
 A = pkg.abi
 f32 = np.float32
 
 
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="light_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "light_ref")
-    src = os.path.join(g.ROOT, "tests", "native", "light_ref.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe, src], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "light_ref")
 
 
 def m16(m):
@@ -51,12 +40,7 @@ def run_ref(depth, normal, albedo, inv_vp, ambient, sun_dir, sun_color, lights=N
     parts += [np.ascontiguousarray(a, dtype=f32).tobytes() for a in (depth, normal, albedo)]
     if shadow is not None:
         parts.append(np.ascontiguousarray(shadow, dtype=f32).tobytes())
-    with tempfile.TemporaryDirectory(prefix="light_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(b"".join(parts))
-        subprocess.run([ref_exe(), fin, fout], check=True)
-        raw = open(fout, "rb").read()
+    raw = N.run(ref_exe(), b"".join(parts))
     n = w * h
     assert len(raw) == n * (16 + 1 + 12 + 1)
     return {"rgba": np.frombuffer(raw, f32, n * 4, 0).reshape(h, w, 4).copy(),

@@ -2,7 +2,7 @@
 // contract (C17-C19) with the ambient factor of include/svr_ambient.h.  Built by the tests with
 //   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math
 // so every operation below is one IEEE fp32 operation and std::fma the only fused one.  The tap tables are the kernel's
-// (csrc/svr_ambient_tables.h: literals).
+// (csrc/svr_ambient_tables.h: literals); C17 and the lighting chain of one pixel are ref_contract.h's.
 //
 //   ambient_ref ao <in> <out>
 // <in>  (little endian): uint32 W, H, sx, sy, sw, sh, flags; float inv_viewproj[16], radius, pixels_per_unit, bias,
@@ -16,37 +16,12 @@
 //
 //   ambient_ref tables <out>
 // <out>: float D[8][2], R[16][2], f[8]: the tables and the radius fractions of C34.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
 
 #include "../../simple-vk-renderer_amd/csrc/svr_ambient_tables.h"
+#include "ref_contract.h"
 
 namespace {
-
-struct Light {
-  float pos[3], radius, color[3], intensity;
-};
-
-bool read_all(FILE* f, void* dst, size_t bytes) { return bytes == 0 || std::fread(dst, 1, bytes, f) == bytes; }
-uint32_t bits(float v) {
-  uint32_t u;
-  std::memcpy(&u, &v, 4);
-  return u;
-}
-
-// column-major matrix times (x, y, z, w), the C0 chain
-void mat_vec(const float* m, float x, float y, float z, float w, float out[4]) {
-  for (int r = 0; r < 4; r++) {
-    float a = m[r] * x;
-    a = std::fma(m[4 + r], y, a);
-    a = std::fma(m[8 + r], z, a);
-    a = std::fma(m[12 + r], w, a);
-    out[r] = a;
-  }
-}
 
 float fraction(int k) { return ((float)((3 * k) & 7) + 0.5f) * 0.125f; }
 
@@ -85,9 +60,8 @@ int run_ao(const char* in_path, const char* out_path) {
       // C32
       const float z = depth[i];
       const float* nr = &normal[i * 4];
-      const float xn = std::fma((float)px + 0.5f, kx, -1.0f), yn = std::fma((float)py + 0.5f, ky, -1.0f);
       float h[4];
-      mat_vec(inv_vp, xn, yn, z, 1.0f, h);
+      unproject(inv_vp, (float)px + 0.5f, (float)py + 0.5f, kx, ky, z, h);
       const float nn = std::fma(nr[2], nr[2], std::fma(nr[1], nr[1], nr[0] * nr[0]));
       if (!(z > 0.0f && bits(nr[3]) != 0u && nn > 0.0f)) {
         raw[i * 2] = 1.0f;
@@ -95,8 +69,8 @@ int run_ao(const char* in_path, const char* out_path) {
         kind[i] = 1;
         continue;
       }
-      const float rw = 1.0f / h[3];
-      const float P[3] = {h[0] * rw, h[1] * rw, h[2] * rw};
+      float P[3];
+      divide_w(h, P);
       const float rl = 1.0f / std::sqrt(nn);
       const float nh[3] = {nr[0] * rl, nr[1] * rl, nr[2] * rl};
       // C33
@@ -123,11 +97,9 @@ int run_ao(const char* in_path, const char* out_path) {
         const float zt = depth[(size_t)ty * W + (size_t)tx];
         if (!(zt > 0.0f)) continue;
         // C35
-        const float xt = std::fma((float)tx + 0.5f, kx, -1.0f), yt = std::fma((float)ty + 0.5f, ky, -1.0f);
-        float g[4];
-        mat_vec(inv_vp, xt, yt, zt, 1.0f, g);
-        const float gw = 1.0f / g[3];
-        const float vx = g[0] * gw - P[0], vy = g[1] * gw - P[1], vz = g[2] * gw - P[2];
+        float g[3];
+        position(inv_vp, (float)tx + 0.5f, (float)ty + 0.5f, kx, ky, zt, g);
+        const float vx = g[0] - P[0], vy = g[1] - P[1], vz = g[2] - P[2];
         const float vv = std::fma(vz, vz, std::fma(vy, vy, vx * vx));
         if (!(vv < radius2)) continue;
         const float vn = std::fma(vz, nh[2], std::fma(vy, nh[1], vx * nh[0])) - bias;
@@ -181,16 +153,12 @@ int run_ao(const char* in_path, const char* out_path) {
 int run_light(const char* in_path, const char* out_path) {
   FILE* f = std::fopen(in_path, "rb");
   if (!f) return 2;
-  uint32_t hdr[5];
-  float inv_vp[16], ambient[4], sun_dir[4], sun_color[4], shadow_vp[16], bias;
-  if (!read_all(f, hdr, sizeof hdr) || !read_all(f, inv_vp, sizeof inv_vp) || !read_all(f, ambient, sizeof ambient) ||
-      !read_all(f, sun_dir, sizeof sun_dir) || !read_all(f, sun_color, sizeof sun_color) || !read_all(f, shadow_vp, sizeof shadow_vp) ||
-      !read_all(f, &bias, sizeof bias))
-    return 3;
-  const uint32_t W = hdr[0], H = hdr[1], n_lights = hdr[2], Ws = hdr[3], Hs = hdr[4];
+  LightFrame F;
+  if (!read_all(f, &F, sizeof F)) return 3;
+  const uint32_t W = F.W, H = F.H;
   const size_t n = (size_t)W * H;
-  std::vector<Light> lights(n_lights);
-  std::vector<float> depth(n), normal(n * 4), albedo(n * 4), shadow((size_t)Ws * Hs), ao(n);
+  std::vector<Light> lights(F.n_lights);
+  std::vector<float> depth(n), normal(n * 4), albedo(n * 4), shadow((size_t)F.Ws * F.Hs), ao(n);
   if (!read_all(f, lights.data(), lights.size() * sizeof(Light)) || !read_all(f, depth.data(), n * 4) || !read_all(f, normal.data(), n * 16) ||
       !read_all(f, albedo.data(), n * 16) || !read_all(f, shadow.data(), shadow.size() * 4) || !read_all(f, ao.data(), n * 4))
     return 3;
@@ -198,55 +166,14 @@ int run_light(const char* in_path, const char* out_path) {
 
   std::vector<float> rgba(n * 4, 0.0f), position(n * 3, 0.0f);
   std::vector<uint8_t> winner(n, 0), in_shadow(n, 0);
-  const float kx = 2.0f / (float)W, ky = 2.0f / (float)H;
   for (uint32_t py = 0; py < H; py++) {
     for (uint32_t px = 0; px < W; px++) {
       const size_t i = (size_t)py * W + px;
       if (bits(albedo[i * 4 + 3]) != 0x3F800000u) continue;
       winner[i] = 1;
-      const float* nrm = &normal[i * 4];
-      const float* c = &albedo[i * 4];
-      // C17
-      const float xn = std::fma((float)px + 0.5f, kx, -1.0f), yn = std::fma((float)py + 0.5f, ky, -1.0f);
-      float h[4];
-      mat_vec(inv_vp, xn, yn, depth[i], 1.0f, h);
-      const float rw = 1.0f / h[3];
-      const float p[3] = {h[0] * rw, h[1] * rw, h[2] * rw};
-      std::memcpy(&position[i * 3], p, 12);
-      // C18, with the ambient factor
-      const float d = std::fma(nrm[2], sun_dir[2], std::fma(nrm[1], sun_dir[1], nrm[0] * sun_dir[0]));
-      bool shadowed = false;
-      if (Ws) {
-        float q[4];
-        mat_vec(shadow_vp, p[0], p[1], p[2], 1.0f, q);
-        const float rq = 1.0f / q[3];
-        const float sx = std::fma(q[0] * rq, (float)Ws / 2.0f, (float)Ws / 2.0f);
-        const float sy = std::fma(q[1] * rq, (float)Hs / 2.0f, (float)Hs / 2.0f);
-        const float sz = q[2] * rq;
-        const float fx = std::floor(sx), fy = std::floor(sy);
-        if (q[3] > 0.0f && 0.0f <= fx && fx < (float)Ws && 0.0f <= fy && fy < (float)Hs)
-          shadowed = sz + bias < shadow[(size_t)fy * Ws + (size_t)fx];
-      }
+      bool shadowed;  // C17-C19, with the ambient factor
+      light_pixel(F, lights.data(), shadow.data(), px, py, depth[i], &normal[i * 4], &albedo[i * 4], &ao[i], &position[i * 3], shadowed, &rgba[i * 4]);
       in_shadow[i] = shadowed ? 1 : 0;
-      const float light = shadowed ? 0.1f : std::fmax(d, 0.1f);
-      float acc[3];
-      for (int ch = 0; ch < 3; ch++) acc[ch] = std::fma(c[ch] * light, sun_color[3], (c[ch] * ambient[ch]) * ao[i]);
-      // C19
-      for (uint32_t l = 0; l < n_lights; l++) {
-        const Light& pl = lights[l];
-        const float vx = pl.pos[0] - p[0], vy = pl.pos[1] - p[1], vz = pl.pos[2] - p[2];
-        const float d2 = std::fma(vz, vz, std::fma(vy, vy, vx * vx));
-        const float r2 = pl.radius * pl.radius;
-        if (!(d2 < r2)) continue;
-        const float ndl = std::fma(nrm[2], vz, std::fma(nrm[1], vy, nrm[0] * vx));
-        if (!(ndl > 0.0f)) continue;
-        const float t = 1.0f - d2 / r2;
-        const float k = ((ndl / std::sqrt(d2)) * ((t * t) / (d2 + 1.0f))) * pl.intensity;
-        for (int ch = 0; ch < 3; ch++) acc[ch] = std::fma(c[ch] * pl.color[ch], k, acc[ch]);
-      }
-      rgba[i * 4 + 0] = acc[0];
-      rgba[i * 4 + 1] = acc[1];
-      rgba[i * 4 + 2] = acc[2];
       rgba[i * 4 + 3] = 1.0f;
     }
   }

@@ -2,7 +2,7 @@
 // one pixel and one cell at a time, no tiles, no LDS.  Built by the tests with
 //   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math
 // so every operation below is one IEEE fp32 operation and std::fma the only fused one; `/` and std::sqrt are correctly
-// rounded, std::rint rounds ties to even.  The fp32 -> fp16 rounding is written out (h16), as in post_ref.cpp.
+// rounded, std::rint rounds ties to even.  The fp32 -> fp16 rounding is written out (h16) in ref_contract.h.
 //
 //   dof_ref <in> <out>
 //   dof_ref --taps          prints the tap table below, one tap per line: the bit patterns of x and y in hex
@@ -16,11 +16,9 @@
 //   4 1 / e instead of 1 / e^2            5 the centre tap left out            6 zero-offset taps counted
 //   7 the cell reach one cell short       8 M taken over the 32 x 16 tile      9 the taps' upper clamp off by one
 //  10 dist from the clamped offsets      11 the even ring not turned          12 r clamped from above only
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
+
+#include "ref_contract.h"
 
 namespace {
 
@@ -78,54 +76,6 @@ const float TAPS[49][2] = {
     {0x1.bb67aep-1f, -0x1.0p-1f},
     {0x1.ee8dd4p-1f, -0x1.0907dcp-2f},
 };
-
-uint32_t bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return u;
-}
-float from_bits(uint32_t u) {
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// fp32 -> fp16, round to nearest even, on the bit patterns
-uint16_t h16(float f) {
-  const uint32_t u = bits(f), sign = (u >> 16) & 0x8000u, mag = u & 0x7fffffffu;
-  if (mag > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((mag >> 13) & 0x3ffu));
-  if (mag >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);
-  if (mag < 0x33000000u) return (uint16_t)sign;
-  const int e = (int)(mag >> 23) - 127;
-  uint32_t m = (mag & 0x7fffffu) | 0x800000u;
-  int shift;
-  uint32_t base;
-  if (e >= -14) {
-    shift = 13;
-    base = (uint32_t)(e + 15) << 10;
-    m &= 0x7fffffu;
-  } else {
-    shift = -e - 1;
-    base = 0;
-  }
-  uint32_t q = m >> shift;
-  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-  if (rem > half || (rem == half && (q & 1u))) q++;
-  return (uint16_t)(sign | (base + q));
-}
-
-// fp16 -> fp32, exact
-float h2f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  if (e == 31u) return from_bits(sign | 0x7f800000u | (m << 13));
-  if (e != 0u) return from_bits(sign | ((e + 112u) << 23) | (m << 13));
-  const float v = (float)m * 5.9604644775390625e-8f;
-  return sign ? -v : v;
-}
-
-float san(float v) { return v > 0.0f ? (v < 65504.0f ? v : 65504.0f) : 0.0f; }
-float sat(float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; }
-uint32_t clampi(int64_t x, uint32_t n) { return x < 0 ? 0u : (x > (int64_t)n - 1 ? n - 1u : (uint32_t)x); }
 
 struct Pass {
   uint32_t W, H, sx, sy, sw, sh, variant, pad;

@@ -1,7 +1,8 @@
 // exposure_ref — scalar restatement of auto-exposure's contract (include/svr_exposure.h) for the
 // tests: one pixel at a time, one bin at a time.  Built by the tests with
 //   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math
-// so every operation below is one IEEE operation and std::fma the only fused one.
+// so every operation below is one IEEE operation and std::fma the only fused one.  C41's 2^x is ref_contract.h's
+// exp2_poly.
 //
 //   exposure_ref <in> <out>
 // <in>  (little endian): uint32 W, H, sx, sy, sw, sh, snap, variant; float key, low_fraction, high_fraction, min_exposure,
@@ -15,37 +16,13 @@
 //   3 the window is taken over all pixels, black included   4 floor where the window's upper end says ceil
 //   5 the clamp is applied after the adapt step, not to the target   6 the snap is ignored
 //   7 the sub-bin literals are those of the bins' lower edges
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
+
+#include "ref_contract.h"
 
 namespace {
 
 int g_variant = 0;
-
-uint32_t bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return u;
-}
-float from_bits(uint32_t u) {
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// fp16 -> fp32, exact
-float h2f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  if (e == 31u) return from_bits(sign | 0x7f800000u | (m << 13));
-  if (e != 0u) return from_bits(sign | ((e + 112u) << 23) | (m << 13));
-  const float v = (float)m * 5.9604644775390625e-8f;  // m * 2^-24, exact
-  return sign ? -v : v;
-}
-
-float san(float v) { return v > 0.0f ? (v < 65504.0f ? v : 65504.0f) : 0.0f; }
 
 // C38
 float luminance(float r, float g, float b) { return std::fma(0.0722f, san(b), std::fma(0.7152f, san(g), 0.2126f * san(r))); }
@@ -60,19 +37,6 @@ uint32_t counter_of(float L) {
 // C40: log2(1 + (j + 1/2) / 8)
 const double kSubLog2[8] = {0x1.663f6fac91316p-4, 0x1.fbc16b902680ap-3, 0x1.91bba891f1709p-2, 0x1.0c10500d63aa6p-1,
                             0x1.49a784bcd1b8bp-1, 0x1.82809d5be7073p-1, 0x1.b74948f5532dap-1, 0x1.e88c6b3626a73p-1};
-
-// C41
-float exp2_poly(float x) {
-  const float n = std::floor(x), f = x - n;
-  float p = 0x1.ca8f0ap-13f;
-  p = std::fma(p, f, 0x1.44d4d2p-10f);
-  p = std::fma(p, f, 0x1.3d54d8p-7f);
-  p = std::fma(p, f, 0x1.c67f5p-5f);
-  p = std::fma(p, f, 0x1.ebfdf2p-3f);
-  p = std::fma(p, f, 0x1.62e428p-1f);
-  p = std::fma(p, f, 1.0f);
-  return from_bits(bits(p) + ((uint32_t)(int32_t)n << 23));
-}
 
 struct Meter {
   float key, low, high, min_exposure, max_exposure, adapt;

@@ -2,7 +2,7 @@
 // and one pixel at a time, no tiles, no LDS.  Built by the tests with
 //   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math
 // so every operation below is one IEEE fp32 operation and std::fma the only fused one; `/` and std::sqrt are correctly
-// rounded.  The fp32 -> fp16 rounding is written out (h16), as in post_ref.cpp.
+// rounded.  The fp32 -> fp16 rounding is written out (h16) in ref_contract.h, with C17, C18's test and C41.
 //
 //   fog_ref <in> <out>
 // <in>  (little endian): uint32 W, H, sx, sy, sw, sh, steps, frame_index, shadow_w, shadow_h (0, 0: no map), variant,
@@ -15,86 +15,17 @@
 //   1 T is updated before S          2 no dither: o = 1/2 everywhere       3 the sample sits at the step's start
 //   4 plain bilinear upsample        5 the bias is subtracted              6 height is measured from the camera
 //   7 g is negated                   8 a block is marched to its nearest pixel     9 the taps' upper clamp is off by one
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
+
+#include "ref_contract.h"
 
 namespace {
 
 int g_variant = 0;
 
-uint32_t bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return u;
-}
-float from_bits(uint32_t u) {
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// fp32 -> fp16, round to nearest even, on the bit patterns
-uint16_t h16(float f) {
-  const uint32_t u = bits(f), sign = (u >> 16) & 0x8000u, mag = u & 0x7fffffffu;
-  if (mag > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((mag >> 13) & 0x3ffu));
-  if (mag >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);
-  if (mag < 0x33000000u) return (uint16_t)sign;
-  const int e = (int)(mag >> 23) - 127;
-  uint32_t m = (mag & 0x7fffffu) | 0x800000u;
-  int shift;
-  uint32_t base;
-  if (e >= -14) {
-    shift = 13;
-    base = (uint32_t)(e + 15) << 10;
-    m &= 0x7fffffu;
-  } else {
-    shift = -e - 1;
-    base = 0;
-  }
-  uint32_t q = m >> shift;
-  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-  if (rem > half || (rem == half && (q & 1u))) q++;
-  return (uint16_t)(sign | (base + q));
-}
-
-// fp16 -> fp32, exact
-float h2f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  if (e == 31u) return from_bits(sign | 0x7f800000u | (m << 13));
-  if (e != 0u) return from_bits(sign | ((e + 112u) << 23) | (m << 13));
-  const float v = (float)m * 5.9604644775390625e-8f;
-  return sign ? -v : v;
-}
-
-float san(float v) { return v > 0.0f ? (v < 65504.0f ? v : 65504.0f) : 0.0f; }
-
-// C41
-float exp2_poly(float x) {
-  const float n = std::floor(x), f = x - n;
-  float p = 0x1.ca8f0ap-13f;
-  p = std::fma(p, f, 0x1.44d4d2p-10f);
-  p = std::fma(p, f, 0x1.3d54d8p-7f);
-  p = std::fma(p, f, 0x1.c67f5p-5f);
-  p = std::fma(p, f, 0x1.ebfdf2p-3f);
-  p = std::fma(p, f, 0x1.62e428p-1f);
-  p = std::fma(p, f, 1.0f);
-  return from_bits(bits(p) + ((uint32_t)(int)n << 23));
-}
-
 float into(float x, float lo, float hi) {
   x = x > lo ? x : lo;
   return x < hi ? x : hi;
-}
-
-// the C0 chain: m (column-major) times (x, y, z, w)
-void mat_vec(const float* m, float x, float y, float z, float w, float* r) {
-  for (int k = 0; k < 4; k++) r[k] = m[k] * x;
-  for (int k = 0; k < 4; k++) r[k] = std::fma(m[4 + k], y, r[k]);
-  for (int k = 0; k < 4; k++) r[k] = std::fma(m[8 + k], z, r[k]);
-  for (int k = 0; k < 4; k++) r[k] = std::fma(m[12 + k], w, r[k]);
 }
 
 struct Pass {
@@ -111,11 +42,9 @@ float two_over_w, two_over_h;
 float pixel_t(uint32_t x, uint32_t y) {
   const float z = depth[(size_t)y * P.W + x];
   if (bits(z) == 0u) return P.max_distance;
-  const float xn = std::fma((float)x + 0.5f, two_over_w, -1.0f), yn = std::fma((float)y + 0.5f, two_over_h, -1.0f);
-  float h[4];
-  mat_vec(P.inv_viewproj, xn, yn, z, 1.0f, h);
-  const float rw = 1.0f / h[3];
-  const float vx = h[0] * rw - P.cam[0], vy = h[1] * rw - P.cam[1], vz = h[2] * rw - P.cam[2];
+  float p[3];
+  position(P.inv_viewproj, (float)x + 0.5f, (float)y + 0.5f, two_over_w, two_over_h, z, p);
+  const float vx = p[0] - P.cam[0], vy = p[1] - P.cam[1], vz = p[2] - P.cam[2];
   const float t = std::sqrt(std::fma(vz, vz, std::fma(vy, vy, vx * vx)));
   return t < P.max_distance ? t : P.max_distance;
 }
@@ -130,8 +59,6 @@ uint32_t fog_hash(uint32_t bx, uint32_t by, uint32_t frame) {
   h ^= h >> 16;
   return h;
 }
-
-uint32_t clampi(int64_t x, uint32_t n) { return x < 0 ? 0u : (x > (int64_t)n - 1 ? n - 1u : (uint32_t)x); }
 
 }  // namespace
 
@@ -190,11 +117,9 @@ int main(int argc, char** argv) {
       const float t_end = m;
       float d[3];
       {
-        const float xn = std::fma((float)x0 + 1.0f, two_over_w, -1.0f), yn = std::fma((float)y0 + 1.0f, two_over_h, -1.0f);
-        float h[4];
-        mat_vec(P.inv_viewproj, xn, yn, 1.0f, 1.0f, h);
-        const float rw = 1.0f / h[3];
-        const float vx = h[0] * rw - P.cam[0], vy = h[1] * rw - P.cam[1], vz = h[2] * rw - P.cam[2];
+        float p[3];  // C17 at the block's middle, a pixel corner, on the near plane
+        position(P.inv_viewproj, (float)x0 + 1.0f, (float)y0 + 1.0f, two_over_w, two_over_h, 1.0f, p);
+        const float vx = p[0] - P.cam[0], vy = p[1] - P.cam[1], vz = p[2] - P.cam[2];
         const float inv = 1.0f / std::sqrt(std::fma(vz, vz, std::fma(vy, vy, vx * vx)));
         d[0] = vx * inv; d[1] = vy * inv; d[2] = vz * inv;
       }
@@ -227,12 +152,7 @@ int main(int argc, char** argv) {
         if (has_map) {
           float q[4];
           for (int k = 0; k < 4; k++) q[k] = std::fma(ti, dq[k], q0[k]);
-          const float rq = 1.0f / q[3];
-          const float sx = std::fma(q[0] * rq, half_w, half_w), sy = std::fma(q[1] * rq, half_h, half_h);
-          const float sz = q[2] * rq;
-          const float fx = std::floor(sx), fy = std::floor(sy);
-          if (q[3] > 0.0f && fx >= 0.0f && fx < (float)P.shadow_w && fy >= 0.0f && fy < (float)P.shadow_h)
-            shadowed = sz + bias < shadow[(size_t)(uint32_t)fy * P.shadow_w + (uint32_t)fx];
+          shadowed = shadow_test(q, half_w, half_h, P.shadow_w, P.shadow_h, bias, shadow.data());
         }
         if (g_variant == 1) T = T * a;
         const float w = T * (1.0f - a);

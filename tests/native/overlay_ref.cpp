@@ -9,11 +9,9 @@
 // out: the image, a uint32 per pixel counting the fragments that reached it, uint32 {triangles, kept, tiles}.
 // variant: 0 is the contract; 1..9 are the wrong painters tests/test_overlay_ref.py must tell from it.
 #include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
+
+#include "ref_contract.h"  // clampi, the int overload
 
 namespace {
 
@@ -30,7 +28,6 @@ uint32_t un8(float f) { return (uint32_t)lrintf(fminf(fmaxf(f, 0.0f), 1.0f) * 25
 
 int64_t snap(float x) { return (int64_t)fminf(fmaxf(rintf(x * 256.0f), -8388608.0f), 8388608.0f); }
 
-int clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 int wrapi(int v, int n) { return ((v % n) + n) % n; }
 
 void tap(float coord, uint32_t extent, int variant, int& i0, int& i1, float& frac) {

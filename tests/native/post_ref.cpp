@@ -2,7 +2,8 @@
 // level images, one texel at a time, no tiles.  Built by the tests with
 //   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math
 // so every operation below is one IEEE fp32 operation and std::fma the only fused one.  The fp32 -> fp16 rounding is
-// written out here (h16), not taken from a library; tests/test_post_ref.py checks it against numpy over every case.
+// written out in ref_contract.h (h16), not taken from a library; tests/test_post_ref.py checks it against numpy over
+// every case, through --h16, and against h2f over every half, through --roundtrip.
 //
 //   post_ref <in> <out>
 // <in>  (little endian): uint32 W, H, sx, sy, sw, sh, levels, tonemap, variant; float exposure, bloom_threshold,
@@ -10,64 +11,17 @@
 // <out>: uint16 color[H][W][4] after the pass; then per level i < levels: uint32 w_i, h_i, uint16 B_i[h_i][w_i][4],
 //        uint16 U_i[h_i][w_i][4].
 //   post_ref --h16 <in> <out>: <in> is floats, <out> their h16 bit patterns.
+//   post_ref --roundtrip <in> <out>: <in> is fp16 bit patterns, <out> each one's h16(h2f()).
 // variant 0 is the contract.  1 .. 6 are deliberately wrong (the tests check that each one is told apart):
 //   1 the blur's upper edge clamp is off by one     2 the box taps sit on 2x-1, 2x     3 the upsample weights are swapped
 //   4 the threshold is applied before the box       5 the input's san is missing       6 the blur runs vertical first
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
+
+#include "ref_contract.h"
 
 namespace {
 
 int g_variant = 0;
-
-uint32_t bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return u;
-}
-float from_bits(uint32_t u) {
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// fp32 -> fp16, round to nearest even, on the bit patterns
-uint16_t h16(float f) {
-  const uint32_t u = bits(f), sign = (u >> 16) & 0x8000u, mag = u & 0x7fffffffu;
-  if (mag > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((mag >> 13) & 0x3ffu));  // NaN: quiet, payload's top bits
-  if (mag >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);  // >= 65520 rounds to infinity (and infinity itself)
-  if (mag < 0x33000000u) return (uint16_t)sign;               // < 2^-25: to zero (2^-25 itself ties to the even 0 below)
-  const int e = (int)(mag >> 23) - 127;                       // unbiased exponent, -25 .. 15
-  uint32_t m = (mag & 0x7fffffu) | 0x800000u;                 // 24-bit significand
-  int shift;                                                  // bits dropped
-  uint32_t base;
-  if (e >= -14) {                                             // normal half: 10 fraction bits kept
-    shift = 13;
-    base = (uint32_t)(e + 15) << 10;
-    m &= 0x7fffffu;
-  } else {                                                    // subnormal half: value = m * 2^(e-23), unit 2^-24
-    shift = -e - 1;                                           // 14 .. 24
-    base = 0;
-  }
-  uint32_t q = m >> shift;
-  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-  if (rem > half || (rem == half && (q & 1u))) q++;           // a carry walks into the exponent, which is what it should do
-  return (uint16_t)(sign | (base + q));
-}
-
-// fp16 -> fp32, exact
-float h2f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  if (e == 31u) return from_bits(sign | 0x7f800000u | (m << 13));
-  if (e != 0u) return from_bits(sign | ((e + 112u) << 23) | (m << 13));
-  const float v = (float)m * 5.9604644775390625e-8f;  // m * 2^-24, exact
-  return sign ? -v : v;
-}
-
-float san(float v) { return v > 0.0f ? (v < 65504.0f ? v : 65504.0f) : 0.0f; }
 
 struct Img {  // three fp32 channels
   uint32_t w = 0, h = 0;
@@ -77,8 +31,6 @@ struct Img {  // three fp32 channels
   float& at(uint32_t x, uint32_t y, int c) { return v[((size_t)y * w + x) * 3 + c]; }
   float at(uint32_t x, uint32_t y, int c) const { return v[((size_t)y * w + x) * 3 + c]; }
 };
-
-uint32_t clampi(int64_t x, uint32_t n) { return x < 0 ? 0u : (x > (int64_t)n - 1 ? n - 1u : (uint32_t)x); }
 
 // C23
 Img box(const Img& S) {
@@ -160,8 +112,22 @@ int main(int argc, char** argv) {
     std::fwrite(out.data(), 2, out.size(), f);
     return std::fclose(f) == 0 ? 0 : 4;
   }
+  if (argc == 4 && std::strcmp(argv[1], "--roundtrip") == 0) {
+    FILE* f = std::fopen(argv[2], "rb");
+    if (!f) return 2;
+    std::vector<uint16_t> v;
+    uint16_t buf[4096];
+    size_t n;
+    while ((n = std::fread(buf, 2, 4096, f)) > 0) v.insert(v.end(), buf, buf + n);
+    std::fclose(f);
+    for (uint16_t& h : v) h = h16(h2f(h));
+    f = std::fopen(argv[3], "wb");
+    if (!f) return 2;
+    std::fwrite(v.data(), 2, v.size(), f);
+    return std::fclose(f) == 0 ? 0 : 4;
+  }
   if (argc != 3) {
-    std::fprintf(stderr, "usage: post_ref <in> <out> | post_ref --h16 <in> <out>\n");
+    std::fprintf(stderr, "usage: post_ref <in> <out> | post_ref --h16 <in> <out> | post_ref --roundtrip <in> <out>\n");
     return 2;
   }
   FILE* f = std::fopen(argv[1], "rb");

@@ -2,7 +2,7 @@
 // tests: one pixel at a time, no tiles, every tap fetched where the contract says.  Built by the tests with
 //   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math
 // so every operation below is one IEEE fp32 operation and std::fma the only fused one.  The fp32 -> fp16 rounding is
-// post_ref.cpp's, written out on the bit patterns (tests/test_post_ref.py pins it against numpy over every case).
+// ref_contract.h's, written out on the bit patterns (tests/test_post_ref.py pins it against numpy over every case).
 //
 //   temporal_ref <in> <out>
 // <in>  (little endian): uint32 W, H, sx, sy, sw, sh, flags, history_valid, variant; float reproject[16] (column-major),
@@ -13,61 +13,14 @@
 //   1 the smallest depth of the 3 x 3 instead of the largest   2 taps clamp to the target's edge, not the scissor's
 //   3 the history sample sits at hx, not hx - 0.5               4 the clamp is applied after the blend
 //   5 fma(blend, c - hc, hc) also when blend is 1               6 the history's lerp runs vertical first
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
+
+#include "ref_contract.h"
 
 namespace {
 
 int g_variant = 0;
 
-uint32_t bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return u;
-}
-float from_bits(uint32_t u) {
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// fp32 -> fp16, round to nearest even, on the bit patterns
-uint16_t h16(float f) {
-  const uint32_t u = bits(f), sign = (u >> 16) & 0x8000u, mag = u & 0x7fffffffu;
-  if (mag > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((mag >> 13) & 0x3ffu));
-  if (mag >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);
-  if (mag < 0x33000000u) return (uint16_t)sign;
-  const int e = (int)(mag >> 23) - 127;
-  uint32_t m = (mag & 0x7fffffu) | 0x800000u;
-  int shift;
-  uint32_t base;
-  if (e >= -14) {
-    shift = 13;
-    base = (uint32_t)(e + 15) << 10;
-    m &= 0x7fffffu;
-  } else {
-    shift = -e - 1;
-    base = 0;
-  }
-  uint32_t q = m >> shift;
-  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-  if (rem > half || (rem == half && (q & 1u))) q++;
-  return (uint16_t)(sign | (base + q));
-}
-
-// fp16 -> fp32, exact
-float h2f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  if (e == 31u) return from_bits(sign | 0x7f800000u | (m << 13));
-  if (e != 0u) return from_bits(sign | ((e + 112u) << 23) | (m << 13));
-  const float v = (float)m * 5.9604644775390625e-8f;
-  return sign ? -v : v;
-}
-
-float san(float v) { return v > 0.0f ? (v < 65504.0f ? v : 65504.0f) : 0.0f; }
 float lerp(float t, float a, float b) { return std::fma(t, b - a, a); }
 
 struct Pass {
@@ -134,7 +87,7 @@ int main(int argc, char** argv) {
         }
       const size_t own = (size_t)py * P.W + px;
       for (int ch = 0; ch < 3; ch++) c[ch] = san(h2f(P.color[own * 4 + ch]));
-      // C29
+      // C29 (not ref_contract.h's unproject: the chain runs over the x, y and w rows only, z is never formed)
       const float xn = std::fma((float)px + 0.5f, two_over_w, -1.0f), yn = std::fma((float)py + 0.5f, two_over_h, -1.0f);
       float qx = m[0] * xn, qy = m[1] * xn, qw = m[3] * xn;
       qx = std::fma(m[4], yn, qx); qy = std::fma(m[5], yn, qy); qw = std::fma(m[7], yn, qw);

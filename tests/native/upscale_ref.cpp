@@ -11,11 +11,9 @@
 //   1 the taps' upper clamp is off by one        2 w0 and w3 are swapped               3 columns are filtered before rows
 //   4 the anti-ringing clamp is missing          5 the sharpen reads quantised neighbours
 //   6 the sharpen's neighbours are not clamped at the image border (P is evaluated outside the image instead)
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
+
+#include "ref_contract.h"
 
 namespace {
 
@@ -24,21 +22,6 @@ uint32_t W, H, DW, DH;
 float g_su, g_sv;
 std::vector<float> g_src;  // [H][W][4], decoded and saturated (C50)
 
-float from_bits(uint32_t u) {
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-// fp16 -> fp32, exact
-float h2f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  if (e == 31u) return from_bits(sign | 0x7f800000u | (m << 13));
-  if (e != 0u) return from_bits(sign | ((e + 112u) << 23) | (m << 13));
-  const float v = (float)m * 5.9604644775390625e-8f;  // m * 2^-24, exact
-  return sign ? -v : v;
-}
-
-float sat(float v) { return v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f; }
 float lo2(float a, float b) { return a < b ? a : b; }
 float hi2(float a, float b) { return a > b ? a : b; }
 uint32_t un8(float f) { return (uint32_t)(int)std::rint(lo2(hi2(f, 0.0f), 1.0f) * 255.0f); }  // round to nearest even

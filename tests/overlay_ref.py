@@ -2,16 +2,12 @@
 scalar restatement of DESIGN C43-C49, and make the lists the tests draw.  A list is a dict: vertices
 (abi.OVERLAY_VERTEX_DTYPE), indices (uint16), cmds (abi.OVERLAY_CMD_DTYPE), textures (a list of (texels, width, height,
 format), texels a uint8 array [h, w, 4] or [h, w]), display_pos and scale.  Images are uint32 [H, W] arrays of texel words."""
-import atexit
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 import __graft_entry__ as g
+import native_ref as N
 
 A = g.load_package().abi
 f32 = np.float32
@@ -19,18 +15,8 @@ BGRA, RGBA = 0, 1  # SVR_SWAPCHAIN_*
 WRONG_VARIANTS = {1: "the top-left rule mirrored", 2: "centres at corners", 3: "no quantisation between layers", 4: "reversed order",
                   5: "clip rounded instead of truncated", 6: "R/B swapped for the wrong format", 7: "A8 read as grey",
                   8: "wrap instead of clamp", 9: "premultiplied blend"}
-SRC = os.path.join(g.ROOT, "tests", "native", "overlay_ref.cpp")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
 NO_CLIP = (-1.0e6, -1.0e6, 1.0e6, 1.0e6)
-
-
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="overlay_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "overlay_ref")
-    subprocess.run(["g++", *FLAGS, "-o", exe, SRC], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "overlay_ref")
 
 
 def pack(r, g_, b, a=255):
@@ -82,12 +68,7 @@ def run_ref(image, fmt, lst, variant=0):
         assert len(raw) == tw * th * (1 if tf == A.OVERLAY_TEX_A8 else 4)
         parts += [np.array([tw, th, tf, 0], np.uint32).tobytes(), raw + b"\0" * (-len(raw) % 4)]
     parts.append(image.tobytes())
-    with tempfile.TemporaryDirectory(prefix="overlay_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(b"".join(parts))
-        subprocess.run([ref_exe(), fin, fout], check=True)
-        raw = np.fromfile(fout, np.uint32)
+    raw = np.frombuffer(N.run(ref_exe(), b"".join(parts)), np.uint32)
     assert raw.size == 2 * w * h + 3
     stats = dict(zip(("triangles", "kept", "tiles"), (int(v) for v in raw[2 * w * h:])))
     return raw[:w * h].reshape(h, w).copy(), raw[w * h:2 * w * h].reshape(h, w).copy(), stats

@@ -1,15 +1,11 @@
 """Test-side helpers of the post pass (include/svr_post.h): build and run tests/native/post_ref.cpp, the scalar restatement
 of DESIGN C22-C26.  Colour targets travel as uint16 [H, W, 4] arrays of fp16 bit patterns, as Renderer.read_color gives them."""
-import atexit
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-import __graft_entry__ as g
+import native_ref as N
+from native_ref import floats, halves  # noqa: F401  (re-exported)
 
 f32 = np.float32
 CLAMP, REINHARD, ACES = 0, 1, 2
@@ -18,14 +14,7 @@ WRONG_VARIANTS = {1: "edge clamp off by one", 2: "box on 2x-1", 3: "upsample wei
                   5: "missing san", 6: "vertical before horizontal"}
 
 
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="post_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "post_ref")
-    src = os.path.join(g.ROOT, "tests", "native", "post_ref.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe, src], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "post_ref")
 
 
 def level_extents(sw, sh, levels):
@@ -40,11 +29,13 @@ def level_extents(sw, sh, levels):
 def h16(values):
     """the reference's own fp32 -> fp16 rounding of a float32 array -> uint16 bit patterns"""
     values = np.ascontiguousarray(values, dtype=f32)
-    with tempfile.TemporaryDirectory(prefix="post_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        values.tofile(fin)
-        subprocess.run([ref_exe(), "--h16", fin, fout], check=True)
-        return np.fromfile(fout, np.uint16).reshape(values.shape)
+    return np.frombuffer(N.run(ref_exe(), values.tobytes(), "--h16"), np.uint16).reshape(values.shape).copy()
+
+
+def roundtrip(bits):
+    """h16(h2f()) of uint16 fp16 bit patterns, both the reference's own"""
+    bits = np.ascontiguousarray(bits, dtype=np.uint16)
+    return np.frombuffer(N.run(ref_exe(), bits.tobytes(), "--roundtrip"), np.uint16).reshape(bits.shape).copy()
 
 
 def run_ref(color, exposure=1.0, threshold=1.0, intensity=1.0, levels=4, tonemap=ACES, scissor=None, variant=0):
@@ -55,12 +46,7 @@ def run_ref(color, exposure=1.0, threshold=1.0, intensity=1.0, levels=4, tonemap
     sx, sy, sw, sh = scissor or (0, 0, w, h)
     hdr = np.array([w, h, sx, sy, sw, sh, levels, tonemap, variant], np.uint32).tobytes()
     par = np.array([exposure, threshold, intensity], f32).tobytes()
-    with tempfile.TemporaryDirectory(prefix="post_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(hdr + par + color.tobytes())
-        subprocess.run([ref_exe(), fin, fout], check=True)
-        raw = open(fout, "rb").read()
+    raw = N.run(ref_exe(), hdr + par + color.tobytes())
     out = {"color": np.frombuffer(raw, np.uint16, w * h * 4, 0).reshape(h, w, 4).copy(), "B": [], "U": []}
     at = w * h * 8
     for lw, lh in level_extents(sw, sh, levels):
@@ -73,18 +59,6 @@ def run_ref(color, exposure=1.0, threshold=1.0, intensity=1.0, levels=4, tonemap
     return out
 
 
-def halves(values):
-    """float array -> fp16 bit patterns (numpy's cast; for building inputs)"""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.asarray(values, dtype=f32).astype(np.float16).view(np.uint16)
-
-
-def floats(bits):
-    """fp16 bit patterns -> float32, exactly (signalling NaNs among them: numpy reports those as invalid)"""
-    with np.errstate(invalid="ignore"):
-        return np.asarray(bits, dtype=np.uint16).view(np.float16).astype(f32)
-
-
 def random_hdr(w, h, seed, specials=True, top=1.2, bright=200.0):
     """a seeded HDR colour target, uint16 [h, w, 4]: log-uniform values up to 10^top with spots `bright` times brighter, a random alpha half, and, with
     specials, texels of NaN, +-inf, negatives, -0, 65504 and subnormal halves sprinkled over it"""
@@ -95,7 +69,7 @@ def random_hdr(w, h, seed, specials=True, top=1.2, bright=200.0):
     out = halves(v)
     out[..., 3] = rng.integers(0, 1 << 16, (h, w), dtype=np.uint16)
     if specials:
-        pool = np.array([0x7e00, 0xfe00, 0x7c01, 0x7c00, 0xfc00, 0xbc00, 0xc500, 0x8000, 0x7bff, 0x0001, 0x03ff, 0x8001, 0x0000], np.uint16)
+        pool = N.SPECIALS[:13]
         hit = rng.random((h, w, 3)) < 0.03
         out[..., :3][hit] = pool[rng.integers(0, pool.size, int(hit.sum()))]
     return out

@@ -34,6 +34,18 @@ def load_oracle():
     return lib
 
 
+HOST_DIR = os.path.join(g.PKG_DIR, "host")
+
+
+def run_demo(lib_path, prefix, *extra, width, height, frames=2, timeout=300):
+    """build host/svr_demo if it is stale and run it over lib_path, dumping to prefix.* -> the finished process, its
+    stderr folded into stdout"""
+    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
+    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(width), "--height", str(height),
+                           "--frames", str(frames), "--dump", prefix, *extra],
+                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
+
+
 def _finish(r, stats=None):
     r.sync()
     out = {"color": r.read_color(), "depth": r.read_depth(), "rgba8": r.read_color(as_rgba8=True),

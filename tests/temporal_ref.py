@@ -1,16 +1,11 @@
 """Test-side helpers of the temporal pass (include/svr_temporal.h): build and run tests/native/temporal_ref.cpp, the scalar
 restatement of DESIGN C27-C31.  Colour and history images travel as uint16 [H, W, 4] arrays of fp16 bit patterns, as
 Renderer.read_color gives them; depth as float32 [H, W]; reproject as a 4 x 4 indexed [col][row] like glmath's matrices."""
-import atexit
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-import __graft_entry__ as g
+import native_ref as N
 
 f32 = np.float32
 RESET, NO_CLAMP = 1, 2
@@ -18,14 +13,7 @@ WRONG_VARIANTS = {1: "min depth instead of max", 2: "no edge clamp at the scisso
                   5: "fma(1, c - hc, hc) in place of c", 6: "vertical lerp before horizontal"}
 
 
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="temporal_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "temporal_ref")
-    src = os.path.join(g.ROOT, "tests", "native", "temporal_ref.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe, src], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "temporal_ref")
 
 
 def identity():
@@ -44,12 +32,7 @@ def run_ref(color, depth, history, reproject, blend, flags=0, history_valid=True
     sx, sy, sw, sh = scissor or (0, 0, w, h)
     hdr = np.array([w, h, sx, sy, sw, sh, flags, 1 if history_valid and not flags & RESET else 0, variant], np.uint32).tobytes()
     par = np.concatenate([np.asarray(reproject, f32).reshape(16), np.array([blend], f32)]).astype(f32).tobytes()
-    with tempfile.TemporaryDirectory(prefix="temporal_ref_io_") as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(hdr + par + color.tobytes() + depth.tobytes() + history.tobytes())
-        subprocess.run([ref_exe(), fin, fout], check=True)
-        raw = open(fout, "rb").read()
+    raw = N.run(ref_exe(), hdr + par + color.tobytes() + depth.tobytes() + history.tobytes())
     n = w * h
     assert len(raw) == n * 17
     return {"color": np.frombuffer(raw, np.uint16, n * 4, 0).reshape(h, w, 4).copy(),

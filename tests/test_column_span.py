@@ -11,15 +11,13 @@ import subprocess
 import pytest
 
 import __graft_entry__ as g
+import native_ref as N
 
 RECORDED = {(3840, 2160): 15437085, (1920, 1080): 3858752}  # rasterized_fragments_per_frame, profiles/frag_diet_bench_ab.txt
 
 
-def test_span_is_the_row_walk(tmp_path):
-    exe = str(tmp_path / "column_span_check")
-    src = os.path.join(g.ROOT, "tests", "native", "column_span_check.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(g.PKG_DIR, "csrc"), "-o", exe, src], check=True)
+def test_span_is_the_row_walk():
+    exe = N.build("column_span_check", include=(os.path.join(g.PKG_DIR, "csrc"),), extra=("-Wall",), sanitize=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     words = r.stdout.split()

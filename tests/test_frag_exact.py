@@ -4,10 +4,9 @@ extents as exponents (ldexpf for the product with a power of two), clamps as med
 their parity selects, and the quad partners' edge values by a flipped sign bit instead of fma(+-1, A, e).
 tests/native/frag_exact_check.cpp checks each over its ends and over more than 10^7 seeded values, built with the address and
 undefined-behaviour sanitizers.  CPU only."""
-import os
 import subprocess
 
-import __graft_entry__ as g
+import native_ref as N
 import test_frag_setup as host
 
 
@@ -15,10 +14,7 @@ def test_exact_identities(tmp_path):
     text = host.setup_helpers()
     assert " binding_min_lod(" in text
     (tmp_path / "frag_setup_under_test.h").write_text(text)
-    exe = str(tmp_path / "frag_exact_check")
-    src = os.path.join(g.ROOT, "tests", "native", "frag_exact_check.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", str(tmp_path), "-o", exe, src], check=True)
+    exe = N.build("frag_exact_check", include=(str(tmp_path),), extra=("-Wall",), sanitize=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     words = r.stdout.split()

@@ -8,6 +8,7 @@ import os
 import subprocess
 
 import __graft_entry__ as g
+import native_ref as N
 
 HEADER = os.path.join(g.PKG_DIR, "csrc", "svr_device.h")
 
@@ -24,10 +25,7 @@ def setup_helpers():
 
 def test_packed_constants_and_range_proofs(tmp_path):
     (tmp_path / "frag_setup_under_test.h").write_text(setup_helpers())
-    exe = str(tmp_path / "frag_setup_check")
-    src = os.path.join(g.ROOT, "tests", "native", "frag_setup_check.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", str(tmp_path), "-o", exe, src], check=True)
+    exe = N.build("frag_setup_check", include=(str(tmp_path),), extra=("-Wall",), sanitize=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     words = r.stdout.split()

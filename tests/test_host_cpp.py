@@ -25,9 +25,7 @@ W, H = 160, 90
 
 
 def run_demo(lib_path, prefix):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    p = subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                        "--frames", "2", "--dump", prefix], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    p = T.run_demo(lib_path, prefix, width=W, height=H, timeout=None)
     assert p.returncode == 0, p.stdout
     out = {"log": p.stdout}
     out["scene"] = np.fromfile(prefix + ".scene", dtype=np.float32)

@@ -1,24 +1,20 @@
 """svr_demo --ao <radius>:<intensity> (include/svr_ambient.h).  Without a GPU: the flag's refusals, through the oracle, which
 has no ambient pass.  On the GPU: an intensity of 0 gives the colour of a run without the flag, bit for bit, and an
 intensity of 1 does not."""
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 RADIUS = "0.6"
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_ao_on_a_library_without_it_fails_loudly(tmp_path, oracle):

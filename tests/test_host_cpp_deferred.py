@@ -2,24 +2,18 @@
 the scene's sun and ambient, and the transparent objects under SVR_DEPTH_LOAD (include/svr_attributes.h, svr_lighting.h,
 svr_load.h); every dump must be, byte for byte, what the forward run dumps.  The oracle has none of the three, so on the
 CPU the flag must fail loudly."""
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 DUMPS = ("color", "depth", "swapchain", "opaque", "transparent", "scene")
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_deferred_on_a_library_without_it_fails_loudly(tmp_path, oracle):

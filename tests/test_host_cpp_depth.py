@@ -1,23 +1,17 @@
 """svr_demo --depth-only 1: the C++ engine draws its frames as depth-only passes (include/svr_depth.h); the dumped depth
 must be, bit for bit, what a normal run dumps, and the colour what the background alone leaves.  The oracle has no
 depth-only pass, so on the CPU the flag must fail loudly."""
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_depth_only_on_a_library_without_it_fails_loudly(tmp_path, oracle):

@@ -4,6 +4,7 @@ path leaves when it runs the same pass (the dumped <prefix>.dof) over the target
 has no such pass, so on the CPU the flag must fail loudly, as must a malformed one.  The caller-side helpers of
 host/svr_math.h are held to glmath.py's bit for bit."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -12,6 +13,8 @@ import pytest
 
 import __graft_entry__ as g
 import dof_ref as DR
+import native_ref as N
+import svr_testlib as T
 
 pkg = g.load_package()
 A = pkg.abi
@@ -20,11 +23,7 @@ HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 96, 54
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_dof_on_a_library_without_it_fails_loudly(tmp_path, oracle):
@@ -68,9 +67,9 @@ int main() {
 
 
 def test_host_helpers_match_glmath(tmp_path):
-    src, exe = tmp_path / "helpers.cpp", tmp_path / "helpers"
+    src = tmp_path / "helpers.cpp"
     src.write_text(HELPERS_SRC)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I", HOST_DIR, "-o", str(exe), str(src)], check=True)
+    exe = N.build(str(src), include=(HOST_DIR,))
     rng = np.random.default_rng(3)
     rows = np.stack([rng.uniform(0.3, 2.0, 64), rng.uniform(0.5, 2.5, 64), rng.uniform(0.01, 0.2, 64), rng.uniform(1.0, 22.0, 64),
                      rng.uniform(0.3, 50.0, 64), rng.uniform(0.01, 0.05, 64), rng.integers(1, 4321, 64), np.zeros(64)], axis=1).astype(np.float32)

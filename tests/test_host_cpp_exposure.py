@@ -1,22 +1,17 @@
 """svr_demo --auto-exposure <key>:<adapt> (include/svr_exposure.h).  Without a GPU: the flag's refusals, through the oracle,
 which has no auto-exposure.  On the GPU the swapchain the C++ engine writes is the one Python produces with the same calls
 (tests/test_exposure_gpu.py)."""
+import functools
 import os
-import subprocess
 
 import pytest
 
-import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_auto_exposure_on_a_library_without_it_fails_loudly(tmp_path, oracle):

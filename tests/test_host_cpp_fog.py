@@ -3,26 +3,22 @@ deferred frame's transparent objects.  On the GPU the .color dump must be what t
 pass (the dumped <prefix>.fog) over the targets of the run without the flag; the oracle has no fog pass, so on the CPU the
 flag must fail loudly, as must a malformed one."""
 import ctypes as C
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as g
 import fog_ref as FR
+import svr_testlib as T
 
 pkg = g.load_package()
 A = pkg.abi
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 96, 54
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_fog_on_a_library_without_it_fails_loudly(tmp_path, oracle):

@@ -1,24 +1,18 @@
 """svr_demo --occlusion last|prepass: the C++ engine culls its frames against a depth pyramid (include/svr_occlusion.h),
 of the previous frame's depth or of a depth-only pass of its occluders; with a static camera every dump must be, byte for
 byte, what --occlusion off dumps.  The oracle has no pyramid, so on the CPU the flag must fail loudly."""
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 DUMPS = ("color", "depth", "swapchain", "opaque", "transparent", "scene")
 
 
-def run_demo(lib_path, prefix, *extra, frames=3):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H, frames=3)
 
 
 @pytest.mark.parametrize("mode", ["last", "prepass"])

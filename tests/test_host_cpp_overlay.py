@@ -2,27 +2,23 @@
 swapchain image and draws the reference's stats window onto it with svr_draw_overlay.  On the GPU the .swapchain dump must be
 overlay_ref applied to the .swapchain dump of the run without the flag, with the list rebuilt in Python from .overlay.txt;
 the oracle has no overlay pass, so on the CPU the flag must fail loudly."""
+import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as g
 import overlay_ref as R
+import svr_testlib as T
 
 pkg = g.load_package()
 A = pkg.abi
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_stats_overlay_on_a_library_without_it_fails_loudly(tmp_path, oracle):

@@ -1,24 +1,19 @@
 """svr_demo --post <operator>:<levels>: the C++ engine runs the HDR post pass (include/svr_post.h) behind every frame's
 last pass and before the swapchain copy.  On the GPU the .color dump must be post_ref applied to the .color dump of the run
 without the flag; the oracle has no post pass, so on the CPU the flag must fail loudly, as must a malformed one."""
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as g
 import post_ref as PR
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_post_on_a_library_without_it_fails_loudly(tmp_path, oracle):

@@ -1,23 +1,16 @@
 """svr_demo --retained 1: the C++ engine keeps its draw context in a draw list (include/svr_draw_list.h) and draws it
 with svr_draw_list; the frames must be those of the svr_draw_geometry path, bit for bit.  The oracle has no draw
 lists, so on the CPU the flag must fail loudly."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 
 
 def run_demo(lib_path, prefix, retained, frames=3):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, "--retained", "1" if retained else "0"],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    return T.run_demo(lib_path, prefix, "--retained", "1" if retained else "0", width=W, height=H, frames=frames)
 
 
 def test_retained_on_a_library_without_draw_lists_fails_loudly(tmp_path, oracle):

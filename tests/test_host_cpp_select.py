@@ -1,9 +1,7 @@
 """svr_demo --select X,Y: the C++ engine reads the ID target (include/svr_ids.h) after its last frame and names the
 RenderObject, mesh, surface and triangle that won pixel (X, Y).  It must name what the Python binding's pick gives for
 the same lists and camera, immediate and retained.  The oracle has no ID target: there the flag fails loudly."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,15 +12,11 @@ import test_host_cpp as HC
 
 pkg = g.load_package()
 A = pkg.abi
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = HC.W, HC.H
 
 
 def select(lib_path, prefix, x, y, retained=False):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", "2", "--dump", prefix, "--retained", "1" if retained else "0", "--select", f"{x},{y}"],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    return T.run_demo(lib_path, prefix, "--retained", "1" if retained else "0", "--select", f"{x},{y}", width=W, height=H)
 
 
 def test_select_on_a_library_without_ids_fails_loudly(tmp_path, oracle):

@@ -1,21 +1,16 @@
 """svr_demo --taa <blend> without a GPU: the oracle has no temporal pass, so the flag must fail loudly, as must a malformed
 blend and the combinations the header rules out.  The GPU run is test_temporal_gpu.py::test_demo_taa_equals_the_python_path."""
+import functools
 import os
-import subprocess
 
 import pytest
 
-import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_taa_on_a_library_without_it_fails_loudly(tmp_path, oracle):

@@ -2,26 +2,22 @@
 reference's render extent and presents into a window-sized swapchain image, through svr_upscale_to_swapchain's arithmetic or,
 with off, the scaled svr_copy_to_swapchain.  On the GPU the .swapchain dump must be what the Python binding gives for the
 dumped colour target; the oracle has no upscaled present, so on the CPU --upscale must fail loudly and off must work."""
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as g
+import svr_testlib as T
 
 pkg = g.load_package()
 A = pkg.abi
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 128, 72
 BGRA = 0
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_upscale_on_a_library_without_it_fails_loudly(tmp_path, oracle):

@@ -1,24 +1,18 @@
 """svr_demo --views N: the C++ engine draws N cameras (yaw stepped by 360/N) in one multiview pass
 (include/svr_views.h); every dumped layer must be, bit for bit, what a single-camera run with that view's yaw leaves
 in its colour and depth targets.  The oracle has no multiview, so on the CPU the flag must fail loudly."""
-import os
+import functools
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as g
+import svr_testlib as T
 
-HOST_DIR = os.path.join(g.PKG_DIR, "host")
 W, H = 160, 90  # 90 rows: every layer's last tile row is partial
 
 
-def run_demo(lib_path, prefix, *extra, frames=2):
-    subprocess.run(["make", "-s"], cwd=HOST_DIR, check=True)
-    return subprocess.run([os.path.join(HOST_DIR, "svr_demo"), "--lib", lib_path, "--width", str(W), "--height", str(H),
-                           "--frames", str(frames), "--dump", prefix, *extra],
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+run_demo = functools.partial(T.run_demo, width=W, height=H)
 
 
 def test_views_on_a_library_without_multiview_fails_loudly(tmp_path, oracle):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as g
+import native_ref as N
 import scenarios as SC
 
 pkg = g.load_package()
@@ -65,9 +66,9 @@ def cases():
 
 
 def test_glmath_agrees_with_svr_math_bit_for_bit(tmp_path):
-    src, exe, data = tmp_path / "probe.cpp", tmp_path / "probe", tmp_path / "cases.bin"
+    src, data = tmp_path / "probe.cpp", tmp_path / "cases.bin"
     src.write_text(PROBE_SRC)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Werror", "-I", HOST_DIR, "-o", str(exe), str(src)], check=True)
+    exe = N.build(str(src), include=(HOST_DIR,), extra=("-Wall", "-Werror"))
     cs = cases()
     with open(data, "wb") as f:
         f.write(np.uint32(len(cs)).tobytes())

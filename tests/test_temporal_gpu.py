@@ -9,6 +9,7 @@ import pytest
 
 import __graft_entry__ as g
 import lighting_ref as LR
+import native_ref as N
 import post_ref as PR
 import svr_testlib as T
 import temporal_ref as TR
@@ -51,10 +52,8 @@ def assert_history(r, want, scissor, what, valid=True):
 
 def san_bits(color):
     """h16(san(I)) on the RGB halves, alpha as it is"""
-    v = PR.floats(color[..., :3])
-    with np.errstate(invalid="ignore"):
-        out = color.copy()
-        out[..., :3] = PR.halves(np.where(v > 0, np.minimum(v, f32(65504.0)), f32(0)))
+    out = color.copy()
+    out[..., :3] = N.san_bits(color[..., :3])
     return out
 
 

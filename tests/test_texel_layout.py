@@ -6,6 +6,7 @@ import os
 import subprocess
 
 import __graft_entry__ as g
+import native_ref as N
 
 HEADER = os.path.join(g.PKG_DIR, "csrc", "svr_device.h")
 
@@ -22,10 +23,7 @@ def layout_functions():
 
 def test_levels_are_bijective_and_disjoint(tmp_path):
     (tmp_path / "texel_layout_under_test.h").write_text(layout_functions())
-    exe = str(tmp_path / "texel_layout_check")
-    src = os.path.join(g.ROOT, "tests", "native", "texel_layout_check.cpp")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", str(tmp_path), "-o", exe, src], check=True)
+    exe = N.build("texel_layout_check", include=(str(tmp_path),), extra=("-O1", "-Wall"), sanitize=True)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     words = r.stdout.split()

@@ -1,16 +1,15 @@
 """Test-side helpers of the upscaled present (include/svr_upscale.h): build and run tests/native/upscale_ref.cpp, the scalar
 restatement of DESIGN C50-C54, and the inputs the tests share.  RGBA16F colour targets travel as uint16 [H, W, 4] arrays of
 fp16 bit patterns, as Renderer.read_color gives them; RGBA8 ones as uint8 [H, W, 4]; destinations as uint8 [dh, dw, 4]."""
-import atexit
 import functools
 import os
-import shutil
 import subprocess
 import tempfile
 
 import numpy as np
 
-import __graft_entry__ as g
+import native_ref as N
+from native_ref import floats, halves  # noqa: F401  (re-exported)
 
 f32 = np.float32
 BGRA, RGBA = 0, 1
@@ -22,14 +21,7 @@ EXTENTS = [((1, 1), (5, 3)), ((2, 3), (70, 41)), ((37, 23), (61, 45)), ((16, 16)
            ((96, 80), (160, 131)), ((7, 2), (16384, 2))]
 
 
-@functools.lru_cache(maxsize=None)
-def ref_exe():
-    d = tempfile.mkdtemp(prefix="upscale_ref_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "upscale_ref")
-    src = os.path.join(g.ROOT, "tests", "native", "upscale_ref.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe, src], check=True)
-    return exe
+ref_exe = functools.partial(N.build, "upscale_ref")
 
 
 def run_ref(color, dw, dh, fmt=BGRA, sharpness=0.5, flags=0, variant=0, values=False):
@@ -49,27 +41,14 @@ def run_ref(color, dw, dh, fmt=BGRA, sharpness=0.5, flags=0, variant=0, values=F
         return (out, np.fromfile(fval, f32).reshape(dh, dw, 4)) if values else out
 
 
-def halves(values):
-    """float array -> fp16 bit patterns (numpy's cast; for building inputs)"""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.asarray(values, dtype=f32).astype(np.float16).view(np.uint16)
-
-
-def floats(bits):
-    """fp16 bit patterns -> float32, exactly"""
-    with np.errstate(invalid="ignore"):
-        return np.asarray(bits, dtype=np.uint16).view(np.float16).astype(f32)
-
-
 def random_target(w, h, seed, specials=False):
     """a seeded RGBA16F colour target, uint16 [h, w, 4]: values on both sides of 0 and of 1 (about a sixth below 0 and a sixth
     above 1); with specials, NaN, +-inf, negative halves, -0 and subnormals sprinkled over it"""
     rng = np.random.default_rng(seed)
     out = halves(rng.uniform(-0.25, 1.25, (h, w, 4)))
     if specials:
-        pool = np.array([0x7e00, 0xfe00, 0x7c01, 0x7c00, 0xfc00, 0xbc00, 0xc500, 0x8000, 0x7bff, 0x0001, 0x03ff, 0x8001, 0x0000, 0x3c00], np.uint16)
         hit = rng.random((h, w, 4)) < 0.08
-        out[hit] = pool[rng.integers(0, pool.size, int(hit.sum()))]
+        out[hit] = N.SPECIALS[rng.integers(0, N.SPECIALS.size, int(hit.sum()))]
     return out
 
 
