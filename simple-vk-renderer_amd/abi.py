@@ -139,6 +139,9 @@ FOG_MAX_STEPS = 64
 # include/svr_dof.h: the depth of field pass (a thin-lens blur gathered over the HDR colour target), HIP library only
 DOF_SYMBOLS = ["svr_dof_pass"]
 DOF_MAX_RADIUS = 16
+# include/svr_motion.h: the camera motion blur pass (streaks gathered along the reprojected velocity), HIP library only
+MOTION_SYMBOLS = ["svr_motion_blur_pass"]
+MOTION_MAX_BLUR = 16
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -215,6 +218,10 @@ class SvrUpscalePass(C.Structure):  # include/svr_upscale.h
 class SvrDofPass(C.Structure):  # include/svr_dof.h
     _fields_ = [("inv_z_scale", C.c_float), ("inv_z_bias", C.c_float), ("focus_distance", C.c_float), ("blur_scale", C.c_float),
                 ("max_radius", C.c_float)]
+
+
+class SvrMotionBlurPass(C.Structure):  # include/svr_motion.h
+    _fields_ = [("reproject", C.c_float * 16), ("shutter", C.c_float), ("max_blur", C.c_float)]
 
 
 class SvrFogPass(C.Structure):  # include/svr_fog.h
@@ -376,6 +383,9 @@ class SvrLib:
         self.has_dof = hasattr(L, "svr_dof_pass")
         if self.has_dof:
             L.svr_dof_pass.argtypes = [P, C.POINTER(SvrDofPass)]
+        self.has_motion = hasattr(L, "svr_motion_blur_pass")
+        if self.has_motion:
+            L.svr_motion_blur_pass.argtypes = [P, C.POINTER(SvrMotionBlurPass)]
         self.has_fog = hasattr(L, "svr_fog_pass")
         if self.has_fog:
             L.svr_fog_pass.argtypes = [P, C.POINTER(SvrFogPass)]
@@ -454,6 +464,16 @@ def fog_struct(inv_viewproj, camera_position, density, height_falloff=0.0, heigh
 def dof_struct(inv_z_scale, inv_z_bias, focus_distance, blur_scale, max_radius=DOF_MAX_RADIUS):
     """an SvrDofPass (include/svr_dof.h) from Python values; (inv_z_scale, inv_z_bias): glmath.dof_depth_terms(proj)"""
     return SvrDofPass(float(inv_z_scale), float(inv_z_bias), float(focus_distance), float(blur_scale), float(max_radius))
+
+
+def motion_struct(reproject, shutter, max_blur=MOTION_MAX_BLUR):
+    """an SvrMotionBlurPass (include/svr_motion.h) from Python values; reproject: 4 x 4 indexed [col][row] like glmath's
+    matrices (glmath.temporal_reproject)"""
+    p = SvrMotionBlurPass()
+    p.reproject = _f16m(reproject)
+    p.shutter = float(shutter)
+    p.max_blur = float(max_blur)
+    return p
 
 
 def scene_struct(view, proj, viewproj, ambient, sun_dir, sun_color):
@@ -977,6 +997,17 @@ class Renderer:
             raise SvrError(-5, f"{self.lib.backend} has no depth of field pass (include/svr_dof.h)")
         p = dof_struct(inv_z_scale, inv_z_bias, focus_distance, blur_scale, max_radius)
         self.lib.check(self.lib.lib.svr_dof_pass(self.h, C.byref(p)))
+
+    # ---- the camera motion blur pass (include/svr_motion.h)
+    def motion_blur_pass(self, reproject, shutter, max_blur=MOTION_MAX_BLUR):
+        """svr_motion_blur_pass: streaks along the camera's motion over the scissor's pixels of the RGBA16F colour target,
+        in place.  reproject: 4 x 4 indexed [col][row] like glmath's matrices (glmath.temporal_reproject, the one the
+        temporal resolve takes); shutter: the open part of the frame interval; no streak reaches farther than max_blur
+        pixels from its pixel"""
+        if not getattr(self.lib, "has_motion", False):
+            raise SvrError(-5, f"{self.lib.backend} has no motion blur pass (include/svr_motion.h)")
+        p = motion_struct(reproject, shutter, max_blur)
+        self.lib.check(self.lib.lib.svr_motion_blur_pass(self.h, C.byref(p)))
 
     # ---- temporal antialiasing (include/svr_temporal.h)
     def _need_temporal(self):

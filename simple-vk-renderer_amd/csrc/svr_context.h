@@ -25,6 +25,7 @@
 #include "../../include/svr_lighting.h"
 #include "../../include/svr_fog.h"
 #include "../../include/svr_dof.h"
+#include "../../include/svr_motion.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
@@ -264,10 +265,14 @@ struct FogOp {
 struct DofOp {
   DofLaunch launch{};
 };
+// svr_motion_blur_pass: the kernels' parameters as recorded, by value (the scratch images by address)
+struct MotionOp {
+  MotionLaunch launch{};
+};
 
 struct LoggedOp {
   int slot;  // index into h_counters / op_done / h_stage
-  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp, FogOp, DofOp> what;
+  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp, FogOp, DofOp, MotionOp> what;
   template <class Op> LoggedOp(int slot_, Op&& op) : slot(slot_), what(std::forward<Op>(op)) {}
   const PassOp* as_pass() const { return std::get_if<PassOp>(&what); }
 };
@@ -391,6 +396,9 @@ struct Context {
   // svr_dof_pass: the prepared image (dof_texels of the context's extent, 8 bytes each) and then M per cell (dof_cells
   // floats); allocated once, by the first depth of field pass
   DevPtr<uint2> d_dof;
+  // svr_motion_blur_pass: the prepared image (motion_texels of the context's extent, 16 bytes each) and then M per cell
+  // (motion_cells keys of 8 bytes); allocated once, by the first motion blur pass
+  DevPtr<uint4> d_motion;
   // svr_temporal_resolve: the two history images (4 halves per texel, the context's extent), allocated and zeroed by the
   // first resolve.  temporal_read names the one the next resolve reads; temporal_has: a resolve was accepted, with the
   // scissor temporal_scissor.  All three change at an accepted call only, in call order.
@@ -478,6 +486,7 @@ int submit(SvrContext* ctx, const OverlayOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const UpscaleOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const FogOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const DofOp& op, int slot, bool replaying);
+int submit(SvrContext* ctx, const MotionOp& op, int slot, bool replaying);
 // log the finished payload of any of those kinds in a free slot and submit it; the entry stays in the log if the submit
 // fails
 template <class Op> int log_op(SvrContext* ctx, Op&& op) {

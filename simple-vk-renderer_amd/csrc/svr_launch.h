@@ -7,6 +7,7 @@
 #include "../../include/svr_exposure.h"
 #include "../../include/svr_fog.h"
 #include "../../include/svr_lighting.h"
+#include "../../include/svr_motion.h"
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
@@ -260,6 +261,28 @@ inline size_t dof_texels(uint32_t w, uint32_t h) { return (size_t)((w + 1u) & ~1
 inline size_t dof_cells(uint32_t w, uint32_t h) { return (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u); }
 // one dof_prepare_kernel and one dof_gather_kernel, on s
 void launch_dof(const DofLaunch& A, hipStream_t s);
+// k_motion.hip: the camera motion blur pass (include/svr_motion.h)
+struct MotionLaunch {
+  uint2* color;                 // the RGBA16F colour target, W texels per row: the scissor's RGB halves are rewritten in place
+  const float* depth;           // the depth target, read as it stands in stream order
+  uint32_t W;
+  uint32_t sx, sy, sw, sh;      // the scissor: the image of the pass
+  uint32_t cw, ch;              // C69: the cells, (sw + 7) / 8 by (sh + 7) / 8
+  uint4* prep;                  // the context's scratch: the prepared image (C68: san(rgb), the velocity halves, the depth's bits), sw per row
+  unsigned long long* cells;    // ... and M per cell, cw per row
+  float reproject[16];          // C67
+  float two_over_w, two_over_h; // C17: divided once, on the host
+  float half_w, half_h;         // C29: W / 2, H / 2
+  float half_shutter;           // C67: 0.5 * shutter
+  float max_blur;
+  uint32_t Rc;                  // C69: (ceil(max_blur) + 7) / 8
+  const uint32_t* poison;
+};
+// C68, C69: the texels and the cells a context of W x H needs scratch for
+inline size_t motion_texels(uint32_t w, uint32_t h) { return (size_t)w * h; }
+inline size_t motion_cells(uint32_t w, uint32_t h) { return (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u); }
+// one motion_prepare_kernel and one motion_gather_kernel, on s
+void launch_motion(const MotionLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

@@ -397,6 +397,10 @@ int submit(SvrContext* ctx, const DofOp& op, int, bool) {
   launch_dof(op.launch, ctx->stream);
   return launched();
 }
+int submit(SvrContext* ctx, const MotionOp& op, int, bool) {
+  launch_motion(op.launch, ctx->stream);
+  return launched();
+}
 
 namespace {
 

@@ -1,5 +1,5 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, the depth of field pass, auto-exposure,
+// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, the depth of field pass, the motion blur pass, auto-exposure,
 // temporal antialiasing, ambient occlusion, the UI overlay and the upscaled present, with their targets and read-backs.
 // Each validates its arguments, allocates what its first call needs, records its kernels' parameters in a payload of
 // its kind and logs it (svr_context.h, svr_log.hip).
@@ -350,6 +350,51 @@ int svr_dof_pass(SvrContext* ctx, const SvrDofPass* pass) {
   D.neg_max_radius = -pass->max_radius;
   D.Rc = ((uint32_t)std::ceil(pass->max_radius) + 7u) / 8u;  // C63: R = 1 .. SVR_DOF_MAX_RADIUS, Rc = 1 or 2
   D.poison = ctx->d_poison.get();
+  return log_op(ctx, std::move(op));
+}
+
+// ---------------------------------------------------------------- the motion blur pass (include/svr_motion.h)
+static_assert(sizeof(SvrMotionBlurPass) == 72 && offsetof(SvrMotionBlurPass, reproject) == 0 && offsetof(SvrMotionBlurPass, shutter) == 64 &&
+                  offsetof(SvrMotionBlurPass, max_blur) == 68,
+              "include/svr_motion.h");
+
+int svr_motion_blur_pass(SvrContext* ctx, const SvrMotionBlurPass* pass) {
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_motion_blur_pass: null argument");
+  if (int e = finite_matrix("svr_motion_blur_pass", "reproject", pass->reproject)) return e;
+  if (!(std::isfinite(pass->shutter) && pass->shutter >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, "svr_motion_blur_pass: the shutter must be finite and at least 0");
+  if (!(pass->max_blur >= 0.0f && pass->max_blur <= (float)SVR_MOTION_MAX_BLUR))
+    return fail(SVR_ERR_INVALID_ARGUMENT, "svr_motion_blur_pass: max_blur must be in 0..SVR_MOTION_MAX_BLUR");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, "svr_motion_blur_pass: the colour target must be RGBA16F (the pass works in scene-linear HDR)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, "svr_motion_blur_pass: not under svr_set_row_interleave with a stride above 1");
+  if (pass->shutter == 0.0f || pass->max_blur == 0.0f) return SVR_OK;  // a closed shutter: the target keeps its bits, and no kernel is enqueued to rewrite them
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  // (both counts grow with the image's extent, so the images of any scissor fit in those of the whole target)
+  const size_t texels = motion_texels(ctx->W, ctx->H);
+  if (!ctx->d_motion) DEV_ALLOC(ctx->d_motion, texels * sizeof(uint4) + motion_cells(ctx->W, ctx->H) * sizeof(unsigned long long));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  MotionOp op;
+  MotionLaunch& M = op.launch;
+  M.color = (uint2*)ctx->color;
+  M.depth = ctx->depth;
+  M.W = ctx->W;
+  M.sx = ctx->sx;
+  M.sy = ctx->sy;
+  M.sw = ctx->sw;
+  M.sh = ctx->sh;
+  M.cw = (ctx->sw + 7u) / 8u;
+  M.ch = (ctx->sh + 7u) / 8u;
+  M.prep = ctx->d_motion.get();
+  M.cells = reinterpret_cast<unsigned long long*>(ctx->d_motion.get() + texels);
+  std::memcpy(M.reproject, pass->reproject, sizeof(M.reproject));
+  M.two_over_w = 2.0f / (float)ctx->W;
+  M.two_over_h = 2.0f / (float)ctx->H;
+  M.half_w = (float)ctx->W * 0.5f;
+  M.half_h = (float)ctx->H * 0.5f;
+  M.half_shutter = 0.5f * pass->shutter;
+  M.max_blur = pass->max_blur;
+  M.Rc = ((uint32_t)std::ceil(pass->max_blur) + 7u) / 8u;  // C69: R = 1 .. SVR_MOTION_MAX_BLUR, Rc = 1 or 2
+  M.poison = ctx->d_poison.get();
   return log_op(ctx, std::move(op));
 }
 

@@ -23,6 +23,11 @@
 //           --deferred 1: a thin-lens blur behind the fog pass (or the transparent objects), in front of --taa and --post;
 //           blur_scale is the radius in pixels of a point at infinity, max_radius (default 16) the largest radius; the
 //           pass as handed to the library is dumped as <prefix>.dof.  Not with --views or --ranks
+//       --motion-blur <shutter>:<yaw_degrees>[:<max_blur>]: the camera motion blur pass (include/svr_motion.h, HIP library
+//           only) with --deferred 1: streaks along the camera's motion behind --taa, in front of --auto-exposure and --post;
+//           the previous frame's camera is this frame's turned by yaw_degrees, so one frame is deterministic; max_blur
+//           (default 16) is the longest reach in pixels; the pass as handed to the library is dumped as <prefix>.motion.
+//           Not with --views or --ranks
 //       --taa <blend>: temporal antialiasing (include/svr_temporal.h, HIP library only): every frame is drawn with a sub-pixel
 //           jitter (Halton(2, 3) - 0.5 pixels, a period of 16 frames) and resolved against the reprojected, clamped history
 //           with the given weight of the current frame, behind the frame's last geometry or lighting pass and in front of
@@ -113,7 +118,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false, stats_overlay = false;
-  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, fog_arg, dof_arg, scale_arg, upscale_arg = "off";
+  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, fog_arg, dof_arg, motion_arg, scale_arg, upscale_arg = "off";
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -142,6 +147,7 @@ int main(int argc, char** argv) {
     else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
     else if (a == "--fog") fog_arg = argv[i + 1];  // <density>:<falloff>[:<g>] (include/svr_fog.h)
     else if (a == "--dof") dof_arg = argv[i + 1];  // <focus_distance>:<blur_scale>[:<max_radius>] (include/svr_dof.h)
+    else if (a == "--motion-blur") motion_arg = argv[i + 1];  // <shutter>:<yaw_degrees>[:<max_blur>] (include/svr_motion.h)
     else if (a == "--ao") ao_arg = argv[i + 1];  // <radius>:<intensity> (include/svr_ambient.h)
     else if (a == "--auto-exposure") ae_arg = argv[i + 1];  // <key>:<adapt> (include/svr_exposure.h)
     else if (a == "--stats-overlay") stats_overlay = atoi(argv[i + 1]) != 0;  // include/svr_overlay.h
@@ -186,7 +192,7 @@ int main(int argc, char** argv) {
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
                     "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt] [--stats-overlay 1]\n"
                     "                [--render-scale s --upscale sharpness|off] [--fog density:falloff[:g]]\n"
-                    "                [--dof focus_distance:blur_scale[:max_radius]]\n");
+                    "                [--dof focus_distance:blur_scale[:max_radius]] [--motion-blur shutter:yaw_degrees[:max_blur]]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -275,6 +281,31 @@ int main(int argc, char** argv) {
     }
     if (ranks > 1) {
       fprintf(stderr, "--dof: not with --ranks (a band rank would clamp its taps and cells at its band's edge)\n");
+      return 1;
+    }
+  }
+  float motion_shutter = 0.f, motion_yaw = 0.f, motion_max = (float)SVR_MOTION_MAX_BLUR;
+  if (!motion_arg.empty()) {
+    char tail = 0;
+    const int n = sscanf(motion_arg.c_str(), "%f:%f:%f%c", &motion_shutter, &motion_yaw, &motion_max, &tail);
+    char tail2 = 0;
+    const int n2 = n == 2 ? sscanf(motion_arg.c_str(), "%f:%f%c", &motion_shutter, &motion_yaw, &tail2) : 0;
+    const bool shape = n == 3 || (n == 2 && n2 == 2);
+    if (!shape || !(motion_shutter >= 0.f && motion_shutter < INFINITY) || !(motion_yaw > -INFINITY && motion_yaw < INFINITY) ||
+        !(motion_max >= 0.f && motion_max <= (float)SVR_MOTION_MAX_BLUR)) {
+      fprintf(stderr, "--motion-blur: expected <shutter >= 0>:<yaw_degrees>[:<max_blur in 0..16>], got '%s'\n", motion_arg.c_str());
+      return 2;
+    }
+    if (!deferred) {
+      fprintf(stderr, "--motion-blur: needs --deferred 1 (the pass runs behind the lighting pass and the transparent objects)\n");
+      return 1;
+    }
+    if (views) {
+      fprintf(stderr, "--motion-blur: not with --views (the pass works on the context's own targets)\n");
+      return 1;
+    }
+    if (ranks > 1) {
+      fprintf(stderr, "--motion-blur: not with --ranks (a band rank would clamp its taps and cells at its band's edge)\n");
       return 1;
     }
   }
@@ -661,6 +692,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--dof: the library has no depth of field pass (include/svr_dof.h)\n");
     return 1;
   }
+  if (!motion_arg.empty() && !eng.api.svr_motion_blur_pass) {
+    fprintf(stderr, "--motion-blur: the library has no motion blur pass (include/svr_motion.h)\n");
+    return 1;
+  }
   if (!taa_arg.empty() && !eng.api.svr_temporal_resolve) {
     fprintf(stderr, "--taa: the library has no temporal pass (include/svr_temporal.h)\n");
     return 1;
@@ -699,6 +734,11 @@ int main(int argc, char** argv) {
     }
     if (taa_blend > 0.f && !eng.temporal_resolve()) {  // behind the frame's last pass, in front of the post pass
       fprintf(stderr, "%s\n", eng.error.rfind("--taa", 0) == 0 ? eng.error.c_str() : ("--taa: " + eng.error).c_str());
+      return 1;
+    }
+    // behind the resolve, so that the history stays sharp; in front of the meter and the post pass, so that bloom sees the streaks
+    if (!motion_arg.empty() && !eng.motion_blur_pass(motion_shutter, motion_yaw, motion_max)) {
+      fprintf(stderr, "%s\n", eng.error.rfind("--motion-blur", 0) == 0 ? eng.error.c_str() : ("--motion-blur: " + eng.error).c_str());
       return 1;
     }
     if (!ae_arg.empty() && !eng.meter_exposure(ae_key, ae_adapt)) {  // behind the frame's last pass, in front of the post pass
@@ -744,6 +784,7 @@ int main(int argc, char** argv) {
     dump(prefix + ".depth", depth.data(), depth.size());
     if (!fog_arg.empty()) dump(prefix + ".fog", &eng.last_fog, 1);
     if (!dof_arg.empty()) dump(prefix + ".dof", &eng.last_dof, 1);
+    if (!motion_arg.empty()) dump(prefix + ".motion", &eng.last_motion, 1);
     std::vector<uint8_t> swap;  // what copy_image leaves in the swapchain image (src/vk_engine.cpp:1277)
     std::string drawn;  // --stats-overlay: ... and what draw_imgui then draws onto it (src/vk_engine.cpp:1282)
     if (!(stats_overlay ? eng.stats_overlay(swap, drawn) : eng.read_swapchain(swap))) {

@@ -62,6 +62,7 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_read_upscaled = reinterpret_cast<decltype(svr_read_upscaled)>(dlsym(handle, "svr_read_upscaled"));
   svr_fog_pass = reinterpret_cast<decltype(svr_fog_pass)>(dlsym(handle, "svr_fog_pass"));
   svr_dof_pass = reinterpret_cast<decltype(svr_dof_pass)>(dlsym(handle, "svr_dof_pass"));
+  svr_motion_blur_pass = reinterpret_cast<decltype(svr_motion_blur_pass)>(dlsym(handle, "svr_motion_blur_pass"));
   return ok;
 }
 void SvrApi::unload() {
@@ -481,6 +482,29 @@ bool SvrEngine::dof_pass(float focus_distance, float blur_scale, float max_radiu
   dp.max_radius = max_radius;
   last_dof = dp;
   if (api.svr_dof_pass(ctx, &dp)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::motion_blur_pass(float shutter, float yaw_degrees, float max_blur) {
+  if (!api.svr_motion_blur_pass) {
+    error = "--motion-blur: the library has no motion blur pass (include/svr_motion.h)";
+    return false;
+  }
+  SvrMotionBlurPass mp{};
+  // update_scene's matrices without the jitter, for this frame's camera and for the one turned by yaw_degrees
+  mat4 proj = svrm::perspective(svrm::radians(70.f), (float)width / (float)height, 10000.f, 0.1f);
+  proj.m[1][1] *= -1;
+  Camera prev = main_camera;
+  prev.yaw += svrm::radians(yaw_degrees);
+  const mat4 m = svrm::temporal_reproject(svrm::mul(proj, prev.get_view_matrix()), svrm::mul(proj, main_camera.get_view_matrix()));
+  std::memcpy(mp.reproject, m.data(), 64);
+  mp.shutter = shutter;
+  mp.max_blur = max_blur;
+  last_motion = mp;
+  if (api.svr_motion_blur_pass(ctx, &mp)) {
     error = api.svr_last_error();
     return false;
   }

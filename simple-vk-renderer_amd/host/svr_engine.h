@@ -28,6 +28,7 @@
 #include "../../include/svr_exposure.h"
 #include "../../include/svr_fog.h"
 #include "../../include/svr_dof.h"
+#include "../../include/svr_motion.h"
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_upscale.h"
 #include "../../include/svr_views.h"
@@ -75,6 +76,8 @@ struct SvrApi {
   SVR_FN(svr_fog_pass)
   // include/svr_dof.h: optional (HIP library only), needed by SvrEngine::dof_pass
   SVR_FN(svr_dof_pass)
+  // include/svr_motion.h: optional (HIP library only), needed by SvrEngine::motion_blur_pass
+  SVR_FN(svr_motion_blur_pass)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -219,6 +222,12 @@ struct SvrEngine {
   // last_dof: the pass as it was handed to the library (svr_demo dumps it as <prefix>.dof).
   SvrDofPass last_dof{};
   bool dof_pass(float focus_distance, float blur_scale, float max_radius);
+  // The camera motion blur pass (svr_demo --deferred 1 --motion-blur <shutter>:<yaw_degrees>[:<max_blur>],
+  // include/svr_motion.h): behind the temporal resolve, in front of the meter and the post pass.  The previous frame's
+  // camera is this frame's turned by yaw_degrees, so one frame is deterministic; both matrices are without jitter.
+  // last_motion: the pass as it was handed to the library (svr_demo dumps it as <prefix>.motion).
+  SvrMotionBlurPass last_motion{};
+  bool motion_blur_pass(float shutter, float yaw_degrees, float max_blur);
   // Auto-exposure (svr_demo --auto-exposure <key>:<adapt>, include/svr_exposure.h): meter the colour target behind the
   // frame's last pass and in front of the post pass, which then multiplies its exposure (a compensation) by the state's.
   // The first call turns svr_set_post_auto_exposure on.  Whole window, exposures clamped to [2^-10, 2^10].
