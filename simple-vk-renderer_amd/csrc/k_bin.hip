@@ -22,13 +22,13 @@
 
 namespace svr {
 
+// The record holds edges 1 and 2 unbiased (struct TriRec); box_overlaps decides coverage and takes them biased: edge_set
+// forms that once per triangle.
 __device__ __forceinline__ EdgeSet load_edges(const TriRec* rec) {
-  EdgeSet e;
   const double2* p = reinterpret_cast<const double2*>(rec);
   double2 a = p[2], b = p[3], c = p[4], d = p[5];
-  e.A0 = a.x; e.A1 = a.y; e.A2 = b.x; e.B0 = b.y; e.B1 = c.x; e.B2 = c.y; e.C0 = d.x; e.C1 = d.y;
-  e.C2 = rec->C[2];
-  return e;
+  const double A[3] = {a.x, a.y, b.x}, B[3] = {b.y, c.x, c.y}, C[3] = {d.x, d.y, rec->C[2]};
+  return edge_set(A, B, C);
 }
 
 struct RecBox {
@@ -184,9 +184,7 @@ __device__ __forceinline__ void clip_and_bin(const FrameParams& P, ClipLds& L, u
       for (unsigned long long todo = __ballot(made); todo; todo &= todo - 1ull) {
         const int l = __ffsll((long long)todo) - 1;
         const TriGeom& gm = L.geom[l];
-        EdgeSet e;
-        e.A0 = gm.A[0]; e.A1 = gm.A[1]; e.A2 = gm.A[2]; e.B0 = gm.B[0]; e.B1 = gm.B[1]; e.B2 = gm.B[2];
-        e.C0 = gm.C[0]; e.C1 = gm.C[1]; e.C2 = gm.C[2];
+        const EdgeSet e = edge_set(gm);
         bin_one(P, (uint32_t)__shfl((int)rec, l), gm.minx, gm.miny, gm.maxx, gm.maxy, MV ? (uint32_t)__shfl((int)transparent, l) : (__shfl((int)transparent, l) ? P.n_tiles : 0u), e, n_setup);
       }
       __builtin_amdgcn_wave_barrier();  // ... before the next step's pieces overwrite them

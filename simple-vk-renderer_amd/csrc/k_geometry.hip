@@ -313,7 +313,8 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int half = 0; half < 2; half++) {
+    for (int half = 1; half >= 0; half--) {  // (the shading half first: it holds inv_area's second copy, TriRec::pad2, which
+                                             // then dies with the first one; in the other order it outlives the header half)
       if (DO && !IDS && half == 1) continue;  // no shading half, no ID piece
 #pragma unroll
       for (uint32_t r = 0; r < 2u; r++) {  // records 32 r .. 32 r + 31
@@ -348,9 +349,7 @@ __global__ __launch_bounds__(256, 4) void setup_kernel(FrameParams P) {
       if (big) P.big_queue[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = seq;
     }
   }
-  EdgeSet e;
-  e.A0 = g.A[0]; e.A1 = g.A[1]; e.A2 = g.A[2]; e.B0 = g.B[0]; e.B1 = g.B[1]; e.B2 = g.B[2];
-  e.C0 = g.C[0]; e.C1 = g.C[1]; e.C2 = g.C[2];
+  const EdgeSet e = edge_set(g);
   emit_small_pairs(P, ok && tr.nt <= SMALL_MAX_TILES, tr, g.minx, g.miny, g.maxx, g.maxy,
                    bin_base<MV>(P, d.flags), e, seq, s_tot);
 }

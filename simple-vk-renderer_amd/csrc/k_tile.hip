@@ -49,28 +49,10 @@ constexpr int BATCH = 64;  // triangles staged per LDS batch == wave size
 constexpr uint32_t SREC = 7;  // pieces (uint4) per staged record
 
 // ------------------------------------------------------------------------------------------------
-// texture unit (C8, C9)
-constexpr float kG0 = 0x1.c51282p-2f, kG1 = -0x1.14a3a2p-2f, kG2 = 0x1.37536ap-3f, kG3 = -0x1.778474p-5f;
-
-__device__ __forceinline__ float lod_from_rho2(float rho2) {
-  uint32_t bits = f2u(rho2);
-  int e = (int)(bits >> 23) - 127;
-  float m = u2f((bits & 0x7fffffu) | 0x3f800000u);
-  float t = m - 1.0f;
-  float g = fmaf(fmaf(fmaf(kG3, t, kG2), t, kG1), t, kG0);
-  float s = t * (1.0f - t);
-  float l = fmaf(s, g, t);
-  float lam = 0.5f * ((float)e + l);
-  lam = (rho2 <= 0x1p+100f) ? lam : 50.0f;
-  lam = (rho2 >= 0x1p-100f) ? lam : -50.0f;  // also NaN
-  return lam;
-}
-
+// texture unit (C8, C9; the LOD itself, C10, is svr_device.h lod_from_rho2)
 __device__ __forceinline__ float lerpf(float a, float b, float t) { return fmaf(t, b - a, a); }
 // x clamped into [lo, hi] for lo <= hi and x not a NaN: the value of fminf(fmaxf(x, lo), hi), in one instruction
 __device__ __forceinline__ float clamp_med3(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
-// 1.0 where the edge carries the top-left bias (flag bit F_T1 or F_T2 set), else 0.0: the bit itself, converted
-__device__ __forceinline__ double top_left_bias(uint32_t flags, uint32_t bit) { return (double)((flags / bit) & 1u); }
 
 struct TexD {
   uint32_t base_off;  // level 0 in the texel arena
@@ -206,21 +188,27 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   const float4* f4 = reinterpret_cast<const float4*>(tr);
   const double2* d2 = reinterpret_cast<const double2*>(tr);
   // every load of the record is issued up front: nothing below depends on another load except the texels
-  uint4 hdr = q4[0];
-  float4 zrow = f4[1];
+  // COMMON reads THIRTEEN pieces: piece 0 would give it the flags, of which it wants nothing (the kind is its own, the
+  // edges come unbiased), and piece 1 inv_area, which piece 14 carries again (TriRec::pad2)
+  uint4 hdr = make_uint4(0u, 0u, 0u, 0u);
+  float4 zrow = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (!COMMON) {
+    hdr = q4[0];
+    zrow = f4[1];
+  }
   double2 c2 = d2[2], c3 = d2[3], c4 = d2[4], c5 = d2[5], c6 = d2[6];
   uint4 td = q4[7];
   float4 s0 = f4[8], s1 = f4[9], s2 = f4[10], s3 = f4[11], s4 = f4[12], s5 = f4[13], s6 = f4[14];
   // s0 = q0,dq1,dq2,a0[0] | s1 = a0[1..4] | s2 = a0[5..7],da1[0] | s3 = da1[1..4] | s4 = da1[5..7],da2[0]
-  // s5 = da2[1..4] | s6 = da2[5..7],pad
+  // s5 = da2[1..4] | s6 = da2[5..7],inv_area
   uint32_t flags = hdr.w;
-  float inv_area = zrow.w;
+  float inv_area = COMMON ? s6.w : zrow.w;
   double A1, B1, A2, B2, e1, e2;
-  double C1 = c5.y, C2 = c6.x;
+  double C1 = c5.y, C2 = c6.x;  // unbiased (struct TriRec)
   A1 = c2.y; B1 = c4.x; A2 = c3.x; B2 = c4.y;
   double dx = (double)px, dy = (double)py;
-  e1 = fma(A1, dx, fma(B1, dy, C1)) + top_left_bias(flags, F_T1);
-  e2 = fma(A2, dx, fma(B2, dy, C2)) + top_left_bias(flags, F_T2);
+  e1 = fma(A1, dx, fma(B1, dy, C1));
+  e2 = fma(A2, dx, fma(B2, dy, C2));
   TexD t;
   t.base_off = (uint32_t)(unsigned long long)__double_as_longlong(c6.y);
   const uint32_t tk = (uint32_t)((unsigned long long)__double_as_longlong(c6.y) >> 32);  // tex_consts (svr_device.h): COMMON reads its levels out of these bytes
@@ -291,8 +279,10 @@ __device__ __forceinline__ float4 shade_pixel(const FrameParams& P, uint32_t rec
   float mx = COMMON ? ldexpf(dudx, (int)t.lw) : dudx * W0, my = COMMON ? ldexpf(dvdx, (int)t.lh) : dvdx * H0;
   float nx_ = COMMON ? ldexpf(dudy, (int)t.lw) : dudy * W0, ny_ = COMMON ? ldexpf(dvdy, (int)t.lh) : dvdy * H0;
   float rho2 = fmaxf(fmaf(mx, mx, my * my), fmaf(nx_, nx_, ny_ * ny_));
-  // (lod_from_rho2 returns no NaN and a binding's min_lod <= max_lod, svr_api.hip make_binding: the chain is a median)
-  float lambda = COMMON ? clamp_med3(lod_from_rho2(rho2), t.min_lod, t.max_lod) : fminf(fmaxf(lod_from_rho2(rho2), t.min_lod), t.max_lod);
+  // (lod_from_rho2 returns no NaN and a binding's min_lod <= max_lod, svr_api.hip make_binding: the chain is a median.
+  // COMMON: the clamps lie in [-50, 50] (make_key), so the chain without its upper range select clamps to the same bits,
+  // DESIGN.md C10b; the lower one, which is also the NaN guard, stays)
+  float lambda = COMMON ? clamp_med3(lod_from_rho2<false>(rho2), t.min_lod, t.max_lod) : fminf(fmaxf(lod_from_rho2(rho2), t.min_lod), t.max_lod);
   const bool linear = COMMON ? true : (((lambda <= 0.0f) ? (t.filters & 1u) : ((t.filters >> 1) & 1u)) != 0u);
   int q = COMMON ? (int)(tk >> 24) : (int)t.levels - 1;
   const bool mip_linear = COMMON ? true : (((t.filters >> 2) & 1u) != 0u);
@@ -492,11 +482,11 @@ __device__ __forceinline__ void scan_columns(const FrameParams& P, uint4* s_cov,
           float bc[2][4];
 #pragma unroll
           for (int i = 0; i < 3; i++) {
-            const float A = (float)dd[4 + i], B = (float)dd[7 + i], C = (float)dd[10 + i] + ((i == 1 && (h.w & F_T1)) || (i == 2 && (h.w & F_T2)) ? 1.0f : 0.0f);
+            const float A = (float)dd[4 + i], B = (float)dd[7 + i], C = (float)dd[10 + i];  // (edges 1, 2: unbiased, as the record holds them)
             const float M = (fabsf(C) + fmaxf(fabsf(A * x0), fabsf(A * x1)) + fmaxf(fabsf(B * y0), fabsf(B * y1))) * 0x1p-21f;
             const float e00 = fmaf(A, x0, fmaf(B, y0, C)), e10 = fmaf(A, x1, fmaf(B, y0, C));
             const float e01 = fmaf(A, x0, fmaf(B, y1, C)), e11 = fmaf(A, x1, fmaf(B, y1, C));
-            all_in = all_in && fminf(fminf(e00, e10), fminf(e01, e11)) >= M + 1.0f;  // (+1: the bias of edges 1, 2 was added above; edge 0's is in C)
+            all_in = all_in && fminf(fminf(e00, e10), fminf(e01, e11)) >= M + 1.0f;  // (+1: edges 1, 2 are unbiased here and may carry a bias of 1; edge 0's is in C)
             if (i) {
               bc[i - 1][0] = e00 * zr.w; bc[i - 1][1] = e10 * zr.w; bc[i - 1][2] = e01 * zr.w; bc[i - 1][3] = e11 * zr.w;
               slack = fmaxf(slack, M * zr.w);
@@ -594,11 +584,13 @@ __device__ __forceinline__ void scan_columns(const FrameParams& P, uint4* s_cov,
       const double2* d = reinterpret_cast<const double2*>(rec);
       double2 c2 = d[2], c3 = d[3], c4 = d[4], c5 = d[5], c6 = d[6];
       double B0 = c3.y, B1 = c4.x, B2 = c4.y;
-      double u1 = top_left_bias(flags, F_T1), u2 = top_left_bias(flags, F_T2);
       double dx = (double)col, dy = (double)y0;
       double f0 = fma(c2.x, dx, fma(B0, dy, c5.x));
-      double f1 = fma(c2.y, dx, fma(B1, dy, c5.y));
-      double f2 = fma(c3.x, dx, fma(B2, dy, c6.x));
+      // edges 1 and 2: the record's constants are unbiased (struct TriRec).  h is the value the barycentrics want, f = h - u
+      // the one coverage is decided on — once per item, here; the biases are dead from the span on
+      double h1 = fma(c2.y, dx, fma(B1, dy, c5.y));
+      double h2 = fma(c3.x, dx, fma(B2, dy, c6.x));
+      double f1 = h1 - edge_bias(flags, F_T1), f2 = h2 - edge_bias(flags, F_T2);  // exact: integers below 2^53
       // The rows of the column on which all three edges are >= 0 are one interval (the triangle is convex), found once
       // and exactly (svr_span.h) instead of by three compares on every row of the box: an item that covers nothing -- two
       // in five -- ends here, and the others walk their covered rows only, without edge 0 and without a compare.
@@ -607,7 +599,7 @@ __device__ __forceinline__ void scan_columns(const FrameParams& P, uint4* s_cov,
       if (kn == 0) continue;
       if (INSTR) n_raster += (uint32_t)kn;
       const double dk = (double)k0;
-      double g1 = fma(B1, dk, f1) + u1, g2 = fma(B2, dk, f2) + u2;  // unbiased at the span's first row (exact: integers below 2^53)
+      double g1 = fma(B1, dk, h1), g2 = fma(B2, dk, h2);  // unbiased at the span's first row (exact: integers below 2^53)
       unsigned long long* cell = s_depth + (y0 + k0 - ty0) * TILE + (col - tx0);
       for (; kn > 0; kn--) {
         float b1 = (float)g1 * zr.w, b2 = (float)g2 * zr.w;
@@ -635,8 +627,9 @@ __device__ __forceinline__ uint32_t resolve_record(const FrameParams& P, uint32_
   for (uint32_t c = 0; c < h.w; c++) {
     const TriRec* t = P.recs + h.z + c;
     if (t->minx > t->maxx || px < t->minx || px > t->maxx || py < t->miny || py > t->maxy) continue;
-    if (fma(t->A[0], dx, fma(t->B[0], dy, t->C[0])) >= 0.0 && fma(t->A[1], dx, fma(t->B[1], dy, t->C[1])) >= 0.0 &&
-        fma(t->A[2], dx, fma(t->B[2], dy, t->C[2])) >= 0.0)
+    const uint32_t fl = t->flags;  // edges 1 and 2 are stored unbiased (struct TriRec): g - u >= 0 is g >= u
+    if (fma(t->A[0], dx, fma(t->B[0], dy, t->C[0])) >= 0.0 && fma(t->A[1], dx, fma(t->B[1], dy, t->C[1])) >= edge_bias(fl, F_T1) &&
+        fma(t->A[2], dx, fma(t->B[2], dy, t->C[2])) >= edge_bias(fl, F_T2))
       return h.z + c;
   }
   return rec;  // unreachable for a pixel that produced a fragment
@@ -836,20 +829,19 @@ __device__ __forceinline__ void scan_columns_ordered(const FrameParams& P, uint4
         double B0 = c3.y, B1 = c4.x, B2 = c4.y;
         double dx = (double)(tx0 + colx), dy = (double)(by0 + t);  // (exact integers below 2^53: the same values the row-by-row additions reach)
         double f0 = fma(c2.x, dx, fma(B0, dy, c5.x));
-        // edges 1 and 2 are walked UNBIASED (g = f + 1 where C carries the top-left bias, else f): that is the value the
-        // barycentrics want, and for integers "f >= 0" is "g > 0" there and "g >= 0" elsewhere — two compares where
-        // holding the two 1.0 / 0.0 in registers across walk and flush cost four VGPRs and an add per row
-        // (walking edges 1 and 2 unbiased, with "g > 0" / "g >= 0" picked per lane, saves the two adds and four
-        // registers below but pays more in the compares' mask logic: +4 % on the curtain tiles)
-        const double u1 = top_left_bias(flags, F_T1), u2 = top_left_bias(flags, F_T2);
+        // edges 1 and 2 are walked UNBIASED, as the record holds them (struct TriRec): g is the value the barycentrics
+        // want, and coverage is g - u >= 0, i.e. "g >= u" against the 1.0 / 0.0 in registers — one compare per edge and
+        // row, as before, and no add.  (Picking "g > 0" / "g >= 0" per lane instead would free those four registers but
+        // pays more in the compares' mask logic: +4 % on the curtain tiles.)
+        const double u1 = edge_bias(flags, F_T1), u2 = edge_bias(flags, F_T2);
         double g1 = fma(c2.y, dx, fma(B1, dy, c5.y));
         double g2 = fma(c3.x, dx, fma(B2, dy, c6.x));
 #pragma unroll 1
         for (; t < rpw; t++) {  // the same absolute row by0 + t in every lane
           int y = by0 + t;
-          bool inside = act && y >= y0 && y <= y1 && f0 >= 0.0 && g1 >= 0.0 && g2 >= 0.0;
+          bool inside = act && y >= y0 && y <= y1 && f0 >= 0.0 && g1 >= u1 && g2 >= u2;
           if (INSTR) n_raster += inside ? 1u : 0u;
-          float b1 = (float)(g1 + u1) * zr.w, b2 = (float)(g2 + u2) * zr.w;
+          float b1 = (float)g1 * zr.w, b2 = (float)g2 * zr.w;
           float z = fmaf(b2, zr.z, fmaf(b1, zr.y, zr.x));
           z = fminf(fmaxf(z, 0.0f), 1.0f) + 0.0f;
           bool pass = inside && f2u(z) >= s_z[(y - ty0) * TILE + colx];  // GREATER_OR_EQUAL vs opaque depth, no write

@@ -66,8 +66,10 @@ TexBinding make_binding(const ImageRes& im, const SvrSamplerDesc& s) {
   tb.pad0 = tex_consts(im.lw, im.lh, im.levels);
   tb.wh = im.w | (im.h << 16);
   tb.info = im.lw | (im.lh << 8) | (im.levels << 16) | (filters << 24);
-  tb.min_lod = binding_min_lod(s.min_lod, s.max_lod);  // min_lod <= max_lod from here on: the fragment stage's median relies on it
-  tb.max_lod = s.max_lod;
+  // min_lod <= max_lod from here on: the fragment stage's median relies on it.  And -50 <= min_lod, max_lod <= 50 wherever the
+  // sampler's range reaches into that interval (binding_lod_range: no result changes): the common-case stage's LOD chain relies
+  // on that, and a range that stays outside marks the binding TEX_WIDE_LODS: make_key then withholds the common-case bit.
+  if (!binding_lod_range(binding_min_lod(s.min_lod, s.max_lod), s.max_lod, tb.min_lod, tb.max_lod)) tb.info |= TEX_WIDE_LODS << 24;
   return tb;
 }
 

@@ -8,8 +8,19 @@ namespace svr {
 constexpr int SMALL_MAX_TILES = 16;  // above this a triangle's tiles are walked by a whole wave
 
 struct EdgeSet {
-  double A0, A1, A2, B0, B1, B2, C0, C1, C2;
+  double A0, A1, A2, B0, B1, B2, C0, C1, C2;  // all three constants BIASED: binning decides coverage
 };
+// ... from the nine coefficients as the record holds them, edges 1 and 2 unbiased (struct TriRec): their bias is taken off
+// here, once per triangle (exact: integers below 2^53), and read off the edge's own steps — binning keeps no flags
+__device__ __forceinline__ EdgeSet edge_set(const double (&A)[3], const double (&B)[3], const double (&C)[3]) {
+  EdgeSet e;
+  e.A0 = A[0]; e.A1 = A[1]; e.A2 = A[2]; e.B0 = B[0]; e.B1 = B[1]; e.B2 = B[2];
+  e.C0 = C[0];
+  e.C1 = C[1] - edge_bias(A[1], B[1]);
+  e.C2 = C[2] - edge_bias(A[2], B[2]);
+  return e;
+}
+__device__ __forceinline__ EdgeSet edge_set(const TriGeom& g) { return edge_set(g.A, g.B, g.C); }
 
 // can any pixel centre of [x0,x1]x[y0,y1] be inside? (max of each edge function over the box)
 __device__ __forceinline__ bool box_overlaps(const EdgeSet& e, int x0, int y0, int x1, int y1) {

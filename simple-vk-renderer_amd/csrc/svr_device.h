@@ -109,7 +109,7 @@ struct TexBinding {
   uint32_t base_off;        // RGBA8 texels of level 0: byte offset in the context's texel arena (FrameParams::tex_arena)
   uint32_t pad0;            // tex_consts(lw, lh, levels): the layout's level-independent constants, four bytes (below)
   uint32_t wh;              // w | h << 16   (extent <= 16384 each)
-  uint32_t info;            // lw | lh << 8 | levels << 16 | filters << 24; filters = mag | min<<1 | mip<<2
+  uint32_t info;            // lw | lh << 8 | levels << 16 | filters << 24; filters = mag | min<<1 | mip<<2 | TEX_WIDE_LODS
   float min_lod, max_lod;
   uint32_t pad[2];
 };
@@ -182,6 +182,20 @@ __host__ __device__ inline uint32_t packed_mip_offset(uint32_t k, uint32_t level
 // which is fminf(fmaxf(lod, lo), hi) only for lo <= hi.  For lo > hi that chain gives hi whatever lod is, and so does either
 // form with lo = hi.  (svr_create_sampler admits no such pair: this is the guarantee stated where the pair is made.)
 __host__ __device__ inline float binding_min_lod(float lo, float hi) { return lo <= hi ? lo : hi; }
+// What lod_from_rho2's range selects return, and the bound on the LOD clamps of a binding that may carry the key's
+// common-case bit (make_key): the stage's LOD chain runs without the selects there.
+constexpr float LOD_SELECT = 50.0f;
+// The clamps a binding carries for a sampler's lo <= hi: narrowed into [-LOD_SELECT, LOD_SELECT] wherever that changes no
+// result.  The LOD every stage clamps lies in that interval (the selects, or C10b), so min(max(x, lo), hi) is the same
+// value with hi lowered to LOD_SELECT while lo <= LOD_SELECT, and with lo raised to -LOD_SELECT while hi >= -LOD_SELECT
+// (a sampler with VK_LOD_CLAMP_NONE, 1000, is the usual case).  A range wholly outside — lo > 50 or hi < -50: every pixel
+// gets that one end — is left as it is; the function returns false for it, and the binding is marked TEX_WIDE_LODS.
+constexpr uint32_t TEX_WIDE_LODS = 8u;  // in TexBinding::info's filters byte: make_key gives such a binding no common-case bit
+__host__ __device__ inline bool binding_lod_range(float lo, float hi, float& out_lo, float& out_hi) {
+  out_lo = (hi >= -LOD_SELECT && lo < -LOD_SELECT) ? -LOD_SELECT : lo;
+  out_hi = (lo <= LOD_SELECT && hi > LOD_SELECT) ? LOD_SELECT : hi;
+  return out_lo >= -LOD_SELECT && out_hi <= LOD_SELECT;
+}
 
 // Range proofs of the common-case fragment stage, once per TRIANGLE (setup_triangle; DESIGN.md C10a has the derivation).
 // True: at every pixel centre the triangle covers, (i) the 1/w plane at the pixel and at its two quad partners, as
@@ -217,8 +231,13 @@ __host__ __device__ inline bool frag_ranges_ok(float q0, float dq1, float dq2, d
 
 // A set-up triangle, 256 bytes: first half is all the coverage/depth loop reads, second half only
 // the winners' shading reads.  Edge functions are evaluated at integer pixel indices (px,py):
-// e_i = A[i]*px + B[i]*py + C[i]  (C already carries the top-left bias); everything is an exact
-// integer < 2^53 held in a double.  (An int32 form for triangles under 64 px, evaluated with
+// e_i = A[i]*px + B[i]*py + C[i]; everything is an exact integer < 2^53 held in a double.
+// C[0] carries edge 0's top-left bias (nothing interpolates with edge 0: only "inside" reads it).  C[1] and C[2] are
+// UNBIASED: g_i = A[i]*px + B[i]*py + C[i] is the value the barycentrics are made of, and the coverage predicate of
+// those two edges is g_i - u_i >= 0 with u_i = 1 where the flag bit F_T1 / F_T2 is set, else 0 — formed once per work
+// item or triangle where coverage is decided (edge_bias below), never per pixel.  (Until the fragment stage's third cut
+// C[1], C[2] were stored biased and every consumer of barycentrics added u_i back, pixel by pixel.)
+// (An int32 form for triangles under 64 px, evaluated with
 // v_mad_i32_i24, was measured 7 % SLOWER in the tile kernel: at its occupancy a lone wave issues one
 // VALU instruction per ~4 cycles, which is also the cost of a 16-lane/clk v_fma_f64.)
 struct TriRec {
@@ -233,7 +252,8 @@ struct TriRec {
   // ---- shading half
   float q0, dq1, dq2;              // 1/w
   float a0[8], da1[8], da2[8];     // varyings pre-divided by w: normal.xyz, color.rgb, uv
-  float pad2;
+  float pad2;                      // inv_area again (piece 14's w): the common-case fragment stage reads it here, with the last varyings, and
+                                   // neither piece 0 nor piece 1
   uint32_t object, primitive;      // ID instances only (else 0): DrawDesc::pad and the triangle's index in its draw (a clipper
                                    // piece: its parent's); the tile kernel's ID target takes them from the winning record
   float pad3[2];
@@ -243,6 +263,12 @@ static_assert(offsetof(TriRec, object) == 240, "TriRec layout: the ID words are 
 constexpr uint32_t REC_ID_PIECE = offsetof(TriRec, object) / 16u;
 static_assert(offsetof(TriRec, A) == 32 && offsetof(TriRec, tex_off) == 104 && offsetof(TriRec, tex_wh) == 112 &&
                   offsetof(TriRec, q0) == 128, "TriRec layout");
+static_assert(offsetof(TriRec, pad2) == 236, "TriRec layout: inv_area's second copy is piece 14's w");
+// u_i of TriRec::C above: 1.0 where edge 1 / edge 2 is not top-left (flag bit F_T1 / F_T2 set), else 0.0 — the bit itself, converted
+__host__ __device__ inline double edge_bias(uint32_t flags, uint32_t bit) { return (double)((flags / bit) & 1u); }
+// ... and the same from the edge's own steps, for binning, which holds the edges and not the flags: an edge is top-left
+// where dy < 0 or dy == 0 and dx > 0 (setup_triangle), and A = -256 dy, B = 256 dx
+__host__ __device__ inline double edge_bias(double A, double B) { return (A > 0.0 || (A == 0.0 && B > 0.0)) ? 0.0 : 1.0; }
 
 struct ClipItem {
   uint32_t draw;
@@ -422,6 +448,29 @@ __device__ __forceinline__ uint32_t bin_base(const FrameParams& P, uint32_t flag
 __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ uint32_t f2u(float f) { return __float_as_uint(f); }
 
+// C10: lambda = log2(rho) = log2(rho2) / 2 from the float's exponent and a cubic on its mantissa.
+// SELECTS: the contract's form, which replaces lambda by 50 above rho2 = 2^100 and by -50 below 2^-100 (and for a NaN).
+// !SELECTS: without the UPPER select, for a caller that clamps the result with clamp_med3(., lo, hi), -50 <= lo <= hi <= 50
+// (the common-case fragment stage: make_key withholds the common-case bit from a binding outside that range).  Above 2^100,
+// +inf included, the chain itself gives lambda >= 50, which clamps to hi as the 50 it replaces does: the clamped values are
+// the same bits for EVERY rho2 — DESIGN.md C10b has the argument, tests/test_frag_third.py runs both forms over every
+// exponent.  The lower select stays in both forms: it is also the NaN guard, and C10a does not keep a NaN out of rho2.
+constexpr float kG0 = 0x1.c51282p-2f, kG1 = -0x1.14a3a2p-2f, kG2 = 0x1.37536ap-3f, kG3 = -0x1.778474p-5f;
+template <bool SELECTS = true>
+__device__ __forceinline__ float lod_from_rho2(float rho2) {
+  uint32_t bits = f2u(rho2);
+  int e = (int)(bits >> 23) - 127;
+  float m = u2f((bits & 0x7fffffu) | 0x3f800000u);
+  float t = m - 1.0f;
+  float g = fmaf(fmaf(fmaf(kG3, t, kG2), t, kG1), t, kG0);
+  float s = t * (1.0f - t);
+  float l = fmaf(s, g, t);
+  float lam = 0.5f * ((float)e + l);
+  if (SELECTS) lam = (rho2 <= 0x1p+100f) ? lam : LOD_SELECT;
+  lam = (rho2 >= 0x1p-100f) ? lam : -LOD_SELECT;  // also NaN
+  return lam;
+}
+
 // 1.0f / x, correctly rounded (the contract's "IEEE 1/x"), without the compiler's division expansion
 // (v_div_scale x2, v_rcp, five fma, v_div_fmas, v_div_fixup: ~11 instructions where the fragment stage runs
 // three of them per pixel).  v_rcp_f32 is good to 1 ulp; VARIANT picks the refinement, and
@@ -597,19 +646,20 @@ __device__ __forceinline__ void store_invalid(TriRec* rec) {
 // submission number (they cannot change an order between different triangles):
 //   bit 0  the record came through the clipper: the main slot only links to the pieces
 //   bit 1  the fragment stage is the common case — mesh.frag, a LINEAR/LINEAR/MIPMAP_LINEAR sampler, an image
-//          with power-of-two extents —
+//          with power-of-two extents, LOD clamps inside [-LOD_SELECT, LOD_SELECT] (the host's make_binding narrows every
+//          range it can narrow without changing a result and marks the others TEX_WIDE_LODS; lod_from_rho2<false> rests on it) —
 //          for which the tile kernel has a specialised instance (a wave whose pixels all carry it takes it).
 //          setup_triangle clears it again for a triangle that fails the stage's range proofs (frag_ranges_ok)
 __device__ __forceinline__ uint32_t make_key(uint32_t seq, uint32_t draw_flags, const TexBinding& tex, bool clipped) {
   bool pow2 = (tex.wh & 0xffffu) == (1u << (tex.info & 0xffu)) && (tex.wh >> 16) == (1u << ((tex.info >> 8) & 0xffu));
-  bool common = ((draw_flags >> F_KIND_SHIFT) & 3u) == PIPE_MESH && (tex.info >> 24) == 7u && pow2;
+  bool common = ((draw_flags >> F_KIND_SHIFT) & 3u) == PIPE_MESH && (tex.info >> 24) == 7u && pow2;  // (== 7: three LINEAR filters and no TEX_WIDE_LODS)
   return ((seq + 1u) << 2) | (common ? 2u : 0u) | (clipped ? 1u : 0u);
 }
 
 // what binning needs of a set-up triangle, still in registers
 struct TriGeom {
   int minx, miny, maxx, maxy;
-  double A[3], B[3], C[3];
+  double A[3], B[3], C[3];  // as the record holds them: C[1], C[2] unbiased (svr_bin.h edge_set makes binning's)
 };
 
 __device__ inline bool setup_triangle(const FrameParams& P, const VOut* v0, const VOut* v1, const VOut* v2,
@@ -647,7 +697,7 @@ __device__ inline bool setup_triangle(const FrameParams& P, const VOut* v0, cons
   }
 
   int Xs[3] = {X0, X1, X2}, Ys[3] = {Y0, Y1, Y2};
-  double A[3], B[3], C[3];
+  double A[3], B[3], C[3];  // C[1], C[2]: the record's, unbiased (struct TriRec)
   uint32_t flags = draw_flags;
 #pragma unroll
   for (int i = 0; i < 3; i++) {
@@ -658,7 +708,7 @@ __device__ inline bool setup_triangle(const FrameParams& P, const VOut* v0, cons
     long long Cu = Ce + 128 * (Ae + Be);
     A[i] = (double)(Ae * 256);
     B[i] = (double)(Be * 256);
-    C[i] = (double)(Cu + (top_left ? 0 : -1));
+    C[i] = (double)(i == 0 ? Cu + (top_left ? 0 : -1) : Cu);
     if (!top_left && i == 1) flags |= F_T1;
     if (!top_left && i == 2) flags |= F_T2;
   }
@@ -713,11 +763,11 @@ __device__ inline bool setup_triangle(const FrameParams& P, const VOut* v0, cons
     sh[11 + k] = p1 - p0;
     sh[19 + k] = p2 - p0;
   }
+  sh[27] = inv_area;  // TriRec::pad2
 #pragma unroll
-  for (int k = 27; k < 32; k++) sh[k] = 0.0f;
+  for (int k = 28; k < 32; k++) sh[k] = 0.0f;
 #pragma unroll
-  for (int k = 0; k < 8; k++) rec[8 + k] = make_uint4(f2u(sh[4 * k]), f2u(sh[4 * k + 1]), f2u(sh[4 * k + 2]), f2u(sh[4 * k + 3]));
-  return true;
+  for (int k = 0; k < 8; k++) rec[8 + k] = make_uint4(f2u(sh[4 * k]), f2u(sh[4 * k + 1]), f2u(sh[4 * k + 2]), f2u(sh[4 * k + 3]));  return true;
 }
 
 }  // namespace svr
