@@ -142,6 +142,9 @@ DOF_MAX_RADIUS = 16
 # include/svr_motion.h: the camera motion blur pass (streaks gathered along the reprojected velocity), HIP library only
 MOTION_SYMBOLS = ["svr_motion_blur_pass"]
 MOTION_MAX_BLUR = 16
+# include/svr_reflect.h: the reflection pass (screen-space rays marched through the depth target), HIP library only
+REFLECT_SYMBOLS = ["svr_reflect_pass"]
+REFLECT_MAX_STEPS, REFLECT_MAX_REFINE = 64, 8
 DRAW_DESC_BYTES, WAVE_CHUNK_BYTES = 192, 8  # the records svr_debug_read_records returns (csrc/svr_device.h)
 
 
@@ -222,6 +225,14 @@ class SvrDofPass(C.Structure):  # include/svr_dof.h
 
 class SvrMotionBlurPass(C.Structure):  # include/svr_motion.h
     _fields_ = [("reproject", C.c_float * 16), ("shutter", C.c_float), ("max_blur", C.c_float)]
+
+
+class SvrReflectPass(C.Structure):  # include/svr_reflect.h
+    _fields_ = [("viewproj", C.c_float * 16), ("inv_viewproj", C.c_float * 16), ("camera_position", C.c_float * 3),
+                ("inv_z_scale", C.c_float), ("inv_z_bias", C.c_float), ("max_distance", C.c_float), ("steps", C.c_uint32),
+                ("refine", C.c_uint32), ("thickness", C.c_float), ("f0", C.c_float), ("intensity", C.c_float),
+                ("distance_fade", C.c_float), ("edge_width", C.c_float), ("resolve", C.c_uint32), ("depth_tolerance", C.c_float),
+                ("frame_index", C.c_uint32)]
 
 
 class SvrFogPass(C.Structure):  # include/svr_fog.h
@@ -386,6 +397,9 @@ class SvrLib:
         self.has_motion = hasattr(L, "svr_motion_blur_pass")
         if self.has_motion:
             L.svr_motion_blur_pass.argtypes = [P, C.POINTER(SvrMotionBlurPass)]
+        self.has_reflect = hasattr(L, "svr_reflect_pass")
+        if self.has_reflect:
+            L.svr_reflect_pass.argtypes = [P, C.POINTER(SvrReflectPass)]
         self.has_fog = hasattr(L, "svr_fog_pass")
         if self.has_fog:
             L.svr_fog_pass.argtypes = [P, C.POINTER(SvrFogPass)]
@@ -473,6 +487,23 @@ def motion_struct(reproject, shutter, max_blur=MOTION_MAX_BLUR):
     p.reproject = _f16m(reproject)
     p.shutter = float(shutter)
     p.max_blur = float(max_blur)
+    return p
+
+
+def reflect_struct(viewproj, inv_viewproj, camera_position, inv_z_scale, inv_z_bias, max_distance=20.0, steps=16, refine=4, thickness=0.1,
+                   f0=0.04, intensity=1.0, distance_fade=1.0, edge_width=16.0, resolve=1, depth_tolerance=0.05, frame_index=0):
+    """an SvrReflectPass (include/svr_reflect.h) from Python values; the matrices: 4 x 4 indexed [col][row] like glmath's;
+    (inv_z_scale, inv_z_bias): glmath.dof_depth_terms(proj)"""
+    p = SvrReflectPass()
+    p.viewproj = _f16m(viewproj)
+    p.inv_viewproj = _f16m(inv_viewproj)
+    p.camera_position = (C.c_float * 3)(*[float(x) for x in camera_position])
+    p.inv_z_scale, p.inv_z_bias, p.max_distance = float(inv_z_scale), float(inv_z_bias), float(max_distance)
+    p.steps, p.refine = int(steps), int(refine)
+    p.thickness, p.f0, p.intensity, p.distance_fade, p.edge_width = float(thickness), float(f0), float(intensity), float(distance_fade), float(edge_width)
+    p.resolve = int(resolve)
+    p.depth_tolerance = float(depth_tolerance)
+    p.frame_index = int(frame_index) & 0xffffffff
     return p
 
 
@@ -1008,6 +1039,19 @@ class Renderer:
             raise SvrError(-5, f"{self.lib.backend} has no motion blur pass (include/svr_motion.h)")
         p = motion_struct(reproject, shutter, max_blur)
         self.lib.check(self.lib.lib.svr_motion_blur_pass(self.h, C.byref(p)))
+
+    # ---- the reflection pass (include/svr_reflect.h)
+    def reflect_pass(self, viewproj, inv_viewproj, camera_position, inv_z_scale, inv_z_bias, max_distance=20.0, steps=16, refine=4, thickness=0.1,
+                     f0=0.04, intensity=1.0, distance_fade=1.0, edge_width=16.0, resolve=1, depth_tolerance=0.05, frame_index=0):
+        """svr_reflect_pass: screen-space reflections over the scissor's pixels of the RGBA16F colour target, in place: one
+        ray per opaque pixel, marched `steps` samples over max_distance world units through the depth target and refined by
+        `refine` bisections.  viewproj: what the G-buffer was drawn with, inv_viewproj its inverse, 4 x 4 indexed [col][row]
+        like glmath's matrices; (inv_z_scale, inv_z_bias): glmath.dof_depth_terms(proj).  Needs the normal and albedo planes"""
+        if not getattr(self.lib, "has_reflect", False):
+            raise SvrError(-5, f"{self.lib.backend} has no reflection pass (include/svr_reflect.h)")
+        p = reflect_struct(viewproj, inv_viewproj, camera_position, inv_z_scale, inv_z_bias, max_distance, steps, refine, thickness, f0, intensity,
+                           distance_fade, edge_width, resolve, depth_tolerance, frame_index)
+        self.lib.check(self.lib.lib.svr_reflect_pass(self.h, C.byref(p)))
 
     # ---- temporal antialiasing (include/svr_temporal.h)
     def _need_temporal(self):

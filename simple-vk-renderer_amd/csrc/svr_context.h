@@ -2,7 +2,7 @@
 // the payload of each kind of logged operation, SvrContext itself, and the internal functions that cross files.
 //   svr_api.hip     context life cycle, resources, targets, options, read-backs, every geometry entry point
 //   svr_log.hip     a pass's submit and retirement, the operation log and its replay
-//   svr_screen.hip  the operations over finished targets: depth pyramid, lighting, post, fog, exposure, temporal, ambient,
+//   svr_screen.hip  the operations over finished targets: depth pyramid, lighting, reflection, post, fog, exposure, temporal, ambient,
 //                   overlay, upscaled present
 // Host code only.  The C ABI is the extern "C" functions of those files; everything here is internal (namespace svr).
 #pragma once
@@ -26,6 +26,7 @@
 #include "../../include/svr_fog.h"
 #include "../../include/svr_dof.h"
 #include "../../include/svr_motion.h"
+#include "../../include/svr_reflect.h"
 #include "../../include/svr_post.h"
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_ambient.h"
@@ -269,10 +270,14 @@ struct DofOp {
 struct MotionOp {
   MotionLaunch launch{};
 };
+// svr_reflect_pass: the kernels' parameters as recorded, by value (the planes and the scratch images by address)
+struct ReflectOp {
+  ReflectLaunch launch{};
+};
 
 struct LoggedOp {
   int slot;  // index into h_counters / op_done / h_stage
-  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp, FogOp, DofOp, MotionOp> what;
+  std::variant<PassOp, ClearOp, BackgroundOp, BlitOp, PyramidOp, LightOp, PostOp, TemporalOp, AmbientOp, ExposureOp, OverlayOp, UpscaleOp, FogOp, DofOp, MotionOp, ReflectOp> what;
   template <class Op> LoggedOp(int slot_, Op&& op) : slot(slot_), what(std::forward<Op>(op)) {}
   const PassOp* as_pass() const { return std::get_if<PassOp>(&what); }
 };
@@ -399,6 +404,9 @@ struct Context {
   // svr_motion_blur_pass: the prepared image (motion_texels of the context's extent, 16 bytes each) and then M per cell
   // (motion_cells keys of 8 bytes); allocated once, by the first motion blur pass
   DevPtr<uint4> d_motion;
+  // svr_reflect_pass: the trace texels (reflect_texels of the context's extent, 16 bytes each) and then a word per cell
+  // (reflect_cells); allocated once, by the first reflection pass
+  DevPtr<float4> d_reflect;
   // svr_temporal_resolve: the two history images (4 halves per texel, the context's extent), allocated and zeroed by the
   // first resolve.  temporal_read names the one the next resolve reads; temporal_has: a resolve was accepted, with the
   // scissor temporal_scissor.  All three change at an accepted call only, in call order.
@@ -487,6 +495,7 @@ int submit(SvrContext* ctx, const UpscaleOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const FogOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const DofOp& op, int slot, bool replaying);
 int submit(SvrContext* ctx, const MotionOp& op, int slot, bool replaying);
+int submit(SvrContext* ctx, const ReflectOp& op, int slot, bool replaying);
 // log the finished payload of any of those kinds in a free slot and submit it; the entry stays in the log if the submit
 // fails
 template <class Op> int log_op(SvrContext* ctx, Op&& op) {

@@ -10,6 +10,7 @@
 #include "../../include/svr_motion.h"
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_post.h"
+#include "../../include/svr_reflect.h"
 #include "../../include/svr_temporal.h"
 #include "../../include/svr_upscale.h"
 #include "svr_device.h"
@@ -283,6 +284,40 @@ inline size_t motion_texels(uint32_t w, uint32_t h) { return (size_t)w * h; }
 inline size_t motion_cells(uint32_t w, uint32_t h) { return (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u); }
 // one motion_prepare_kernel and one motion_gather_kernel, on s
 void launch_motion(const MotionLaunch& A, hipStream_t s);
+// k_reflect.hip: the reflection pass (include/svr_reflect.h)
+struct ReflectLaunch {
+  uint2* color;                 // the RGBA16F colour target, W texels per row: the scissor's RGB halves are rewritten in place
+  const float* depth;           // the depth target, read as it stands in stream order
+  const float4* normal;         // the SVR_ATTR_NORMAL plane
+  const float4* albedo;         // the SVR_ATTR_ALBEDO plane: w says whether an opaque winner wrote the texel (C73)
+  uint32_t W;
+  uint32_t sx, sy, sw, sh;      // the scissor: the image of the pass
+  uint32_t cw, ch;              // the trace's cells, (sw + 7) / 8 by (sh + 7) / 8
+  float4* trace;                // the context's scratch: the trace texels (C77), sw per row
+  uint32_t* cells;              // ... and per cell, cw per row: whether any of its trace texels is not 0
+  float two_over_w, two_over_h; // C17: divided once, on the host
+  float half_w, half_h;         // C75: W / 2, H / 2
+  float x_lo, x_hi, y_lo, y_hi; // C75: the scissor as floats, sx <= fx < sx + sw (exact: the extents are below 2^24)
+  float viewproj[16], inv_viewproj[16];
+  float cam[3];
+  float inv_z_scale, inv_z_bias;
+  float delta;                  // C75: max_distance / steps, one quotient at the call
+  float rmax;                   // C77: 1 / max_distance, likewise
+  uint32_t steps, refine;
+  float q_max;                  // C75: 1 + thickness, one sum at the call
+  float f0, one_minus_f0;       // C77
+  float intensity, distance_fade;
+  float inv_edge;               // C77: 1 / edge_width; 0: no edge fade
+  uint32_t resolve;
+  float depth_tolerance;
+  uint32_t frame;
+  const uint32_t* poison;
+};
+// C77: the texels and the cells a context of W x H needs scratch for
+inline size_t reflect_texels(uint32_t w, uint32_t h) { return (size_t)w * h; }
+inline size_t reflect_cells(uint32_t w, uint32_t h) { return (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u); }
+// one reflect_trace_kernel and one reflect_resolve_kernel, on s
+void launch_reflect(const ReflectLaunch& A, hipStream_t s);
 void launch_rcp_sweep(int variant, unsigned long long first, unsigned long long count, unsigned long long* out19, hipStream_t s);
 
 }  // namespace svr

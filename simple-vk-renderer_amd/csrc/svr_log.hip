@@ -401,6 +401,10 @@ int submit(SvrContext* ctx, const MotionOp& op, int, bool) {
   launch_motion(op.launch, ctx->stream);
   return launched();
 }
+int submit(SvrContext* ctx, const ReflectOp& op, int, bool) {
+  launch_reflect(op.launch, ctx->stream);
+  return launched();
+}
 
 namespace {
 

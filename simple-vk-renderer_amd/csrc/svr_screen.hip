@@ -1,5 +1,5 @@
 // svr_screen.hip — the operations over finished targets (host code; no kernels here): the depth pyramid and occlusion
-// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, the depth of field pass, the motion blur pass, auto-exposure,
+// culling's calls, the deferred lighting pass, the HDR post pass, the fog pass, the depth of field pass, the motion blur pass, the reflection pass, auto-exposure,
 // temporal antialiasing, ambient occlusion, the UI overlay and the upscaled present, with their targets and read-backs.
 // Each validates its arguments, allocates what its first call needs, records its kernels' parameters in a payload of
 // its kind and logs it (svr_context.h, svr_log.hip).
@@ -395,6 +395,87 @@ int svr_motion_blur_pass(SvrContext* ctx, const SvrMotionBlurPass* pass) {
   M.max_blur = pass->max_blur;
   M.Rc = ((uint32_t)std::ceil(pass->max_blur) + 7u) / 8u;  // C69: R = 1 .. SVR_MOTION_MAX_BLUR, Rc = 1 or 2
   M.poison = ctx->d_poison.get();
+  return log_op(ctx, std::move(op));
+}
+
+// ---------------------------------------------------------------- the reflection pass (include/svr_reflect.h)
+static_assert(sizeof(SvrReflectPass) == 192 && offsetof(SvrReflectPass, inv_viewproj) == 64 && offsetof(SvrReflectPass, camera_position) == 128 &&
+                  offsetof(SvrReflectPass, inv_z_scale) == 140 && offsetof(SvrReflectPass, steps) == 152 && offsetof(SvrReflectPass, thickness) == 160 &&
+                  offsetof(SvrReflectPass, resolve) == 180 && offsetof(SvrReflectPass, frame_index) == 188,
+              "include/svr_reflect.h");
+
+int svr_reflect_pass(SvrContext* ctx, const SvrReflectPass* pass) {
+  const std::string who = "svr_reflect_pass: ";
+  if (!ctx || !pass) return fail(SVR_ERR_INVALID_ARGUMENT, who + "null argument");
+  if (int e = finite_matrix("svr_reflect_pass", "viewproj", pass->viewproj)) return e;
+  if (int e = finite_matrix("svr_reflect_pass", "inv_viewproj", pass->inv_viewproj)) return e;
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(pass->camera_position[k])) return fail(SVR_ERR_INVALID_ARGUMENT, who + "camera_position must be finite");
+  if (!(std::isfinite(pass->inv_z_scale) && std::isfinite(pass->inv_z_bias))) return fail(SVR_ERR_INVALID_ARGUMENT, who + "inv_z_scale and inv_z_bias must be finite");
+  if (!(std::isfinite(pass->max_distance) && pass->max_distance > 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, who + "max_distance must be finite and greater than 0");
+  if (pass->steps < 1u || pass->steps > SVR_REFLECT_MAX_STEPS) return fail(SVR_ERR_INVALID_ARGUMENT, who + "steps must be in 1..SVR_REFLECT_MAX_STEPS");
+  if (pass->refine > SVR_REFLECT_MAX_REFINE) return fail(SVR_ERR_INVALID_ARGUMENT, who + "refine must be in 0..SVR_REFLECT_MAX_REFINE");
+  if (!(std::isfinite(pass->thickness) && pass->thickness >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, who + "the thickness must be finite and at least 0");
+  if (!(pass->f0 >= 0.0f && pass->f0 <= 1.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, who + "f0 must be in 0..1");
+  if (!(std::isfinite(pass->intensity) && pass->intensity >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, who + "the intensity must be finite and at least 0");
+  if (!(pass->distance_fade >= 0.0f && pass->distance_fade <= 1.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, who + "distance_fade must be in 0..1");
+  if (!(std::isfinite(pass->edge_width) && pass->edge_width >= 0.0f)) return fail(SVR_ERR_INVALID_ARGUMENT, who + "the edge width must be finite and at least 0");
+  if (pass->resolve > 1u) return fail(SVR_ERR_INVALID_ARGUMENT, who + "resolve must be 0 or 1");
+  if (!(std::isfinite(pass->depth_tolerance) && pass->depth_tolerance >= 0.0f))
+    return fail(SVR_ERR_INVALID_ARGUMENT, who + "the depth tolerance must be finite and at least 0");
+  if (!ctx->attr[2] || !ctx->attr[3])
+    return fail(SVR_ERR_INVALID_ARGUMENT, who + "needs the SVR_ATTR_NORMAL and SVR_ATTR_ALBEDO planes (svr_enable_attributes / svr_bind_attribute_target)");
+  if (ctx->fmt != SVR_COLOR_RGBA16F) return fail(SVR_ERR_UNSUPPORTED, who + "the colour target must be RGBA16F (the pass works in scene-linear HDR)");
+  if (ctx->rstride > 1u) return fail(SVR_ERR_UNSUPPORTED, who + "not under svr_set_row_interleave with a stride above 1");
+  if (pass->intensity == 0.0f) return SVR_OK;  // no reflection: the target keeps its bits, and no kernel is enqueued to rewrite them
+  if (int e = use_device(ctx)) return e;
+  if (int e = poll_pending(ctx)) return e;
+  // (both counts grow with the image's extent, so the images of any scissor fit in those of the whole target)
+  const size_t texels = reflect_texels(ctx->W, ctx->H);
+  if (!ctx->d_reflect) DEV_ALLOC(ctx->d_reflect, texels * sizeof(float4) + reflect_cells(ctx->W, ctx->H) * sizeof(uint32_t));
+  if (int e = flush_clear(ctx)) return e;  // this call writes colour: a deferred clear lands first
+  ReflectOp op;
+  ReflectLaunch& R = op.launch;
+  R.color = (uint2*)ctx->color;
+  R.depth = ctx->depth;
+  R.normal = (const float4*)ctx->attr[2];
+  R.albedo = (const float4*)ctx->attr[3];
+  R.W = ctx->W;
+  R.sx = ctx->sx;
+  R.sy = ctx->sy;
+  R.sw = ctx->sw;
+  R.sh = ctx->sh;
+  R.cw = (ctx->sw + 7u) / 8u;
+  R.ch = (ctx->sh + 7u) / 8u;
+  R.trace = ctx->d_reflect.get();
+  R.cells = reinterpret_cast<uint32_t*>(ctx->d_reflect.get() + texels);
+  R.two_over_w = 2.0f / (float)ctx->W;
+  R.two_over_h = 2.0f / (float)ctx->H;
+  R.half_w = (float)ctx->W * 0.5f;
+  R.half_h = (float)ctx->H * 0.5f;
+  R.x_lo = (float)ctx->sx;
+  R.x_hi = (float)(ctx->sx + ctx->sw);
+  R.y_lo = (float)ctx->sy;
+  R.y_hi = (float)(ctx->sy + ctx->sh);
+  std::memcpy(R.viewproj, pass->viewproj, sizeof(R.viewproj));
+  std::memcpy(R.inv_viewproj, pass->inv_viewproj, sizeof(R.inv_viewproj));
+  std::memcpy(R.cam, pass->camera_position, sizeof(R.cam));
+  R.inv_z_scale = pass->inv_z_scale;
+  R.inv_z_bias = pass->inv_z_bias;
+  R.delta = pass->max_distance / (float)pass->steps;  // C75
+  R.rmax = 1.0f / pass->max_distance;                 // C77
+  R.steps = pass->steps;
+  R.refine = pass->refine;
+  R.q_max = 1.0f + pass->thickness;
+  R.f0 = pass->f0;
+  R.one_minus_f0 = 1.0f - pass->f0;
+  R.intensity = pass->intensity;
+  R.distance_fade = pass->distance_fade;
+  R.inv_edge = pass->edge_width > 0.0f ? 1.0f / pass->edge_width : 0.0f;
+  R.resolve = pass->resolve;
+  R.depth_tolerance = pass->depth_tolerance;
+  R.frame = pass->frame_index;
+  R.poison = ctx->d_poison.get();
   return log_op(ctx, std::move(op));
 }
 

@@ -15,6 +15,11 @@
 //       --post clamp|reinhard|aces:<levels> [--exposure E] [--bloom-threshold T] [--bloom-intensity I]: the HDR post pass
 //           (include/svr_post.h, HIP library only) behind every frame's last pass and before the swapchain copy: the
 //           .color and .swapchain dumps are taken after it
+//       --reflect <intensity>:<max_distance>[:<steps>]: the reflection pass (include/svr_reflect.h, HIP library only) with
+//           --deferred 1: screen-space reflections behind the lighting pass and the transparent objects, in front of --fog
+//           (steps defaults to 16; 4 bisections, 3 x 3 resolve); the pass as handed to the library is dumped as
+//           <prefix>.reflect, and the G-buffer's planes it read as <prefix>.normal and <prefix>.albedo.  With --taa,
+//           frame_index advances per frame; without, it stays 0.  Not with --views or --ranks
 //       --fog <density>:<falloff>[:<g>]: the fog pass (include/svr_fog.h, HIP library only) with --deferred 1: height fog and sun
 //           shafts from the scene's sun behind the transparent objects, in front of --taa and --post (16 steps, no shadow
 //           map); the pass as handed to the library is dumped as <prefix>.fog.  With --taa, frame_index advances per
@@ -118,7 +123,7 @@ int main(int argc, char** argv) {
   int frames = 2, background = 0, retained = 0;
   uint32_t views = 0;
   bool depth_only = false, deferred = false, stats_overlay = false;
-  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, fog_arg, dof_arg, motion_arg, scale_arg, upscale_arg = "off";
+  std::string occlusion = "off", post_arg, taa_arg, ao_arg, ae_arg, fog_arg, reflect_arg, dof_arg, motion_arg, scale_arg, upscale_arg = "off";
   SvrPostPass post{1.0f, 1.0f, 1.0f, 0, SVR_TONEMAP_CLAMP};
   float yaw = 0.f;
   bool set_yaw = false;
@@ -145,6 +150,7 @@ int main(int argc, char** argv) {
     else if (a == "--deferred") deferred = atoi(argv[i + 1]) != 0;  // G-buffer pass, lighting pass, transparent objects under LOAD
     else if (a == "--post") post_arg = argv[i + 1];  // <operator>:<levels> (include/svr_post.h)
     else if (a == "--taa") taa_arg = argv[i + 1];  // <blend> (include/svr_temporal.h)
+    else if (a == "--reflect") reflect_arg = argv[i + 1];  // <intensity>:<max_distance>[:<steps>] (include/svr_reflect.h)
     else if (a == "--fog") fog_arg = argv[i + 1];  // <density>:<falloff>[:<g>] (include/svr_fog.h)
     else if (a == "--dof") dof_arg = argv[i + 1];  // <focus_distance>:<blur_scale>[:<max_radius>] (include/svr_dof.h)
     else if (a == "--motion-blur") motion_arg = argv[i + 1];  // <shutter>:<yaw_degrees>[:<max_blur>] (include/svr_motion.h)
@@ -192,7 +198,8 @@ int main(int argc, char** argv) {
                     "                [--post clamp|reinhard|aces:<levels> --exposure E --bloom-threshold T --bloom-intensity I]\n"
                     "                [--taa blend] [--ao radius:intensity] [--auto-exposure key:adapt] [--stats-overlay 1]\n"
                     "                [--render-scale s --upscale sharpness|off] [--fog density:falloff[:g]]\n"
-                    "                [--dof focus_distance:blur_scale[:max_radius]] [--motion-blur shutter:yaw_degrees[:max_blur]]\n");
+                    "                [--dof focus_distance:blur_scale[:max_radius]] [--motion-blur shutter:yaw_degrees[:max_blur]]\n"
+                    "                [--reflect intensity:max_distance[:steps]]\n");
     return 2;
   }
   float taa_blend = 0.f;
@@ -233,6 +240,32 @@ int main(int argc, char** argv) {
     }
     if (ranks > 1) {
       fprintf(stderr, "--ao: not with --ranks (a band rank would cut taps at its band's edge)\n");
+      return 1;
+    }
+  }
+  float reflect_intensity = 0.f, reflect_distance = 0.f;
+  unsigned reflect_steps = 16;
+  if (!reflect_arg.empty()) {
+    char tail = 0;
+    const int n = sscanf(reflect_arg.c_str(), "%f:%f:%u%c", &reflect_intensity, &reflect_distance, &reflect_steps, &tail);
+    char tail2 = 0;
+    const int n2 = n == 2 ? sscanf(reflect_arg.c_str(), "%f:%f%c", &reflect_intensity, &reflect_distance, &tail2) : 0;
+    const bool shape = (n == 3 && reflect_arg.find('-', reflect_arg.rfind(':')) == std::string::npos) || (n == 2 && n2 == 2);
+    if (!shape || !(reflect_intensity >= 0.f && reflect_intensity < INFINITY) || !(reflect_distance > 0.f && reflect_distance < INFINITY) ||
+        reflect_steps < 1 || reflect_steps > SVR_REFLECT_MAX_STEPS) {
+      fprintf(stderr, "--reflect: expected <intensity >= 0>:<max_distance > 0>[:<steps in 1..64>], got '%s'\n", reflect_arg.c_str());
+      return 2;
+    }
+    if (!deferred) {
+      fprintf(stderr, "--reflect: needs --deferred 1 (the pass runs behind the lighting pass and the transparent objects)\n");
+      return 1;
+    }
+    if (views) {
+      fprintf(stderr, "--reflect: not with --views (the pass works on the context's own targets)\n");
+      return 1;
+    }
+    if (ranks > 1) {
+      fprintf(stderr, "--reflect: not with --ranks (a band rank would reflect what its own rows hold)\n");
       return 1;
     }
   }
@@ -684,6 +717,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--post: the library has no post pass (include/svr_post.h)\n");
     return 1;
   }
+  if (!reflect_arg.empty() && !eng.api.svr_reflect_pass) {
+    fprintf(stderr, "--reflect: the library has no reflection pass (include/svr_reflect.h)\n");
+    return 1;
+  }
   if (!fog_arg.empty() && !eng.api.svr_fog_pass) {
     fprintf(stderr, "--fog: the library has no fog pass (include/svr_fog.h)\n");
     return 1;
@@ -720,6 +757,12 @@ int main(int argc, char** argv) {
     }
     if (!eng.draw_background() || !(views ? eng.draw_geometry_views() : (depth_only ? eng.draw_depth() : (deferred ? eng.draw_deferred() : eng.draw_geometry())))) {
       fprintf(stderr, "draw failed: %s\n", eng.error.c_str());
+      return 1;
+    }
+    // behind the lighting pass and the deferred frame's transparents, in front of the fog pass: the medium also lies between the
+    // camera and a reflection
+    if (!reflect_arg.empty() && !eng.reflect_pass(reflect_intensity, reflect_distance, reflect_steps, taa_blend > 0.f ? (uint32_t)f : 0u)) {
+      fprintf(stderr, "%s\n", eng.error.rfind("--reflect", 0) == 0 ? eng.error.c_str() : ("--reflect: " + eng.error).c_str());
       return 1;
     }
     // behind the deferred frame's transparents, in front of the resolve (which averages the per-frame dither) and the post pass
@@ -782,6 +825,16 @@ int main(int argc, char** argv) {
     }
     dump(prefix + ".color", color.data(), color.size());
     dump(prefix + ".depth", depth.data(), depth.size());
+    if (!reflect_arg.empty()) {
+      std::vector<float> normal, albedo;
+      if (!eng.read_attribute(SVR_ATTR_NORMAL, normal) || !eng.read_attribute(SVR_ATTR_ALBEDO, albedo)) {
+        fprintf(stderr, "readback failed: %s\n", eng.error.c_str());
+        return 1;
+      }
+      dump(prefix + ".reflect", &eng.last_reflect, 1);
+      dump(prefix + ".normal", normal.data(), normal.size());
+      dump(prefix + ".albedo", albedo.data(), albedo.size());
+    }
     if (!fog_arg.empty()) dump(prefix + ".fog", &eng.last_fog, 1);
     if (!dof_arg.empty()) dump(prefix + ".dof", &eng.last_dof, 1);
     if (!motion_arg.empty()) dump(prefix + ".motion", &eng.last_motion, 1);

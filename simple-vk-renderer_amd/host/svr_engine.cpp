@@ -63,6 +63,8 @@ bool SvrApi::load(const std::string& path, std::string* err) {
   svr_fog_pass = reinterpret_cast<decltype(svr_fog_pass)>(dlsym(handle, "svr_fog_pass"));
   svr_dof_pass = reinterpret_cast<decltype(svr_dof_pass)>(dlsym(handle, "svr_dof_pass"));
   svr_motion_blur_pass = reinterpret_cast<decltype(svr_motion_blur_pass)>(dlsym(handle, "svr_motion_blur_pass"));
+  svr_reflect_pass = reinterpret_cast<decltype(svr_reflect_pass)>(dlsym(handle, "svr_reflect_pass"));
+  svr_read_attribute = reinterpret_cast<decltype(svr_read_attribute)>(dlsym(handle, "svr_read_attribute"));
   return ok;
 }
 void SvrApi::unload() {
@@ -428,6 +430,54 @@ bool SvrEngine::post_pass(const SvrPostPass& pass) {
     return false;
   }
   if (api.svr_post_pass(ctx, &pass)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::reflect_pass(float intensity, float max_distance, uint32_t steps, uint32_t frame_index) {
+  if (!api.svr_reflect_pass) {
+    error = "--reflect: the library has no reflection pass (include/svr_reflect.h)";
+    return false;
+  }
+  SvrReflectPass rp{};
+  mat4 viewproj, proj;
+  std::memcpy(viewproj.data(), scene_data.viewproj, 64);
+  std::memcpy(proj.data(), scene_data.proj, 64);
+  const mat4 inv = svrm::inverse(viewproj);
+  std::memcpy(rp.viewproj, viewproj.data(), 64);
+  std::memcpy(rp.inv_viewproj, inv.data(), 64);
+  rp.camera_position[0] = main_camera.position.x;
+  rp.camera_position[1] = main_camera.position.y;
+  rp.camera_position[2] = main_camera.position.z;
+  svrm::dof_depth_terms(proj, &rp.inv_z_scale, &rp.inv_z_bias);
+  rp.max_distance = max_distance;
+  rp.steps = steps;
+  rp.refine = 4;
+  rp.thickness = 0.1f;
+  rp.f0 = 0.04f;
+  rp.intensity = intensity;
+  rp.distance_fade = 1.f;
+  rp.edge_width = 16.f;
+  rp.resolve = 1;
+  rp.depth_tolerance = 0.05f;
+  rp.frame_index = frame_index;
+  last_reflect = rp;
+  if (api.svr_reflect_pass(ctx, &rp)) {
+    error = api.svr_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool SvrEngine::read_attribute(int attr, std::vector<float>& out) {
+  if (!api.svr_read_attribute) {
+    error = "the library has no attribute targets (include/svr_attributes.h)";
+    return false;
+  }
+  out.resize((size_t)width * height * 4);
+  if (api.svr_read_attribute(ctx, attr, out.data(), out.size() * 4)) {
     error = api.svr_last_error();
     return false;
   }

@@ -29,6 +29,7 @@
 #include "../../include/svr_fog.h"
 #include "../../include/svr_dof.h"
 #include "../../include/svr_motion.h"
+#include "../../include/svr_reflect.h"
 #include "../../include/svr_overlay.h"
 #include "../../include/svr_upscale.h"
 #include "../../include/svr_views.h"
@@ -78,6 +79,9 @@ struct SvrApi {
   SVR_FN(svr_dof_pass)
   // include/svr_motion.h: optional (HIP library only), needed by SvrEngine::motion_blur_pass
   SVR_FN(svr_motion_blur_pass)
+  // include/svr_reflect.h: optional (HIP library only), needed by SvrEngine::reflect_pass; svr_read_attribute
+  // (include/svr_attributes.h) by SvrEngine::read_attribute
+  SVR_FN(svr_reflect_pass) SVR_FN(svr_read_attribute)
 #undef SVR_FN
   bool load(const std::string& path, std::string* err);
   void unload();
@@ -209,6 +213,16 @@ struct SvrEngine {
   // The HDR post pass (svr_demo --post <operator>:<levels>, include/svr_post.h): exposure, bloom and the operator over the
   // colour target, after the frame's last pass and before the swapchain copy.
   bool post_pass(const SvrPostPass& pass);
+  // The reflection pass (svr_demo --deferred 1 --reflect <intensity>:<max_distance>[:<steps>], include/svr_reflect.h): behind
+  // the lighting pass and the deferred frame's transparents, in front of the fog pass.  The camera is the scene's: its
+  // viewproj, the inverse of it and the main camera's position; the depth terms are those of the scene's projection
+  // (svrm::dof_depth_terms).  4 bisections, thickness 0.1, f0 0.04, the weight fades to nothing at max_distance and over 16
+  // pixels at the window's border, 3 x 3 resolve with a depth tolerance of 0.05.
+  // last_reflect: the pass as it was handed to the library (svr_demo dumps it as <prefix>.reflect).
+  SvrReflectPass last_reflect{};
+  bool reflect_pass(float intensity, float max_distance, uint32_t steps, uint32_t frame_index);
+  // one plane of the G-buffer, four floats per texel (svr_demo --reflect dumps <prefix>.normal and <prefix>.albedo)
+  bool read_attribute(int attr, std::vector<float>& out);
   // The fog pass (svr_demo --deferred 1 --fog <density>:<falloff>[:<g>], include/svr_fog.h): behind the deferred frame's
   // transparents, in front of the temporal resolve and the post pass.  The camera is the scene's: the inverse of its
   // viewproj and the main camera's position; the sun is the scene's direction and colour (rgb times w), the fog's own
