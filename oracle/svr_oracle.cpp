@@ -1164,8 +1164,10 @@ static int blit_to(SvrContext* ctx, uint32_t dw, uint32_t dh, int fmt, uint8_t* 
       load_color(ctx, (size_t)j1 * ctx->W + i0, t01);
       load_color(ctx, (size_t)j1 * ctx->W + i1, t11);
       for (int c = 0; c < 4; c++) {
-        float top = std::fmaf(a, t10[c] - t00[c], t00[c]), bot = std::fmaf(a, t11[c] - t01[c], t01[c]);
-        o[c] = std::fmaf(b, bot - top, top);
+        // a tap of weight 0 takes no part: beside an infinity or a NaN the identity extent stays the format conversion
+        float top = a == 0.0f ? t00[c] : std::fmaf(a, t10[c] - t00[c], t00[c]);
+        float bot = a == 0.0f ? t01[c] : std::fmaf(a, t11[c] - t01[c], t01[c]);
+        o[c] = b == 0.0f ? top : std::fmaf(b, bot - top, top);
       }
       uint8_t* d = dst + ((size_t)j * dw + i) * 4;
       if (fmt == SVR_SWAPCHAIN_B8G8R8A8) {

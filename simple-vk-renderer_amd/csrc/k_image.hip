@@ -226,9 +226,11 @@ __global__ __launch_bounds__(256) void blit_kernel(const void* color, int fmt, u
     j0 = min(max(j0, 0), (int)H - 1); j1 = min(max(j1, 0), (int)H - 1);
     float4 t00 = load_target(color, fmt, (size_t)j0 * W + i0), t10 = load_target(color, fmt, (size_t)j0 * W + i1);
     float4 t01 = load_target(color, fmt, (size_t)j1 * W + i0), t11 = load_target(color, fmt, (size_t)j1 * W + i1);
+    // a tap of weight 0 takes no part (0 x inf is no part of a blit): an identity extent stays the plain format conversion
+    // beside an infinity or a NaN
     auto filt = [&](float c00, float c10, float c01, float c11) {
-      float top = fmaf(a, c10 - c00, c00), bot = fmaf(a, c11 - c01, c01);
-      return fmaf(b, bot - top, top);
+      float top = a == 0.0f ? c00 : fmaf(a, c10 - c00, c00), bot = a == 0.0f ? c01 : fmaf(a, c11 - c01, c01);
+      return b == 0.0f ? top : fmaf(b, bot - top, top);
     };
     uint32_t r = un8(filt(t00.x, t10.x, t01.x, t11.x)), g = un8(filt(t00.y, t10.y, t01.y, t11.y));
     uint32_t bl = un8(filt(t00.z, t10.z, t01.z, t11.z)), al = un8(filt(t00.w, t10.w, t01.w, t11.w));

@@ -15,6 +15,7 @@ scene, position (x, y, w) -> clip (x, y, 9/8 - w/8, w), whose kept range is 1 <=
 import numpy as np
 
 import __graft_entry__ as g
+import image_ref as IR
 import raster_ref as RR
 import scenarios as SC
 
@@ -405,7 +406,7 @@ _CHAINS = {}
 
 
 def set_mip_chain(case, chain):
-    """the chain read back from a library; both libraries must return the same one (mip generation is pinned elsewhere)"""
+    """the chain read back from a library; both libraries must return the same one (mip_chain_by_rule holds it to S3)"""
     key = (case.tex, case.mipmapped)
     if key in _CHAINS:
         assert len(chain) == len(_CHAINS[key]) and all(np.array_equal(a, b) for a, b in zip(chain, _CHAINS[key])), \
@@ -416,13 +417,17 @@ def set_mip_chain(case, chain):
 
 def mip_chain_by_rule(case):
     """The read-back chain, checked against the rules the reference states for it: floor(log2(max(w, h))) + 1 levels when
-    mip-mapped, level extent max(1, w >> l)."""
+    mip-mapped, level extent max(1, w >> l), and every level equal to the chain tests/image_ref.py makes of the texture by
+    rule (S3) - so what families C and D sample rests on nothing a library supplied."""
     chain = _CHAINS[(case.tex, case.mipmapped)]
     w, h = TEXTURES[case.tex]
     assert len(chain) == (int(np.floor(np.log2(max(w, h)))) + 1 if case.mipmapped else 1), f"{case.tex}: {len(chain)} levels"
     for l, level in enumerate(chain):
         assert level.shape[:2] == (max(1, h >> l), max(1, w >> l)), f"{case.tex} level {l}: extent {level.shape[:2]}"
     assert np.array_equal(chain[0], texture(case.tex))
+    by_rule = IR.mip_chain(texture(case.tex))[:len(chain)]
+    for l, (level, want) in enumerate(zip(chain, by_rule)):
+        assert np.array_equal(level, want), f"{case.tex} level {l}: the chain read back is not the one the rules give"
     return chain
 
 
@@ -430,10 +435,14 @@ def mip_chain_by_rule(case):
 class Rig:
     """One context per target size; images, samplers and materials are made once."""
 
-    def __init__(self, lib, width, height, attributes=False):
+    def __init__(self, lib, width, height, attributes=False, color_format=A.COLOR_RGBA16F, instrumented=True, tuning=None):
         self.lib, self.width, self.height, self.attributes = lib, width, height, attributes
-        self.r = lib.create(width, height)
-        self.r.set_option(A.OPT_COUNT_FRAGMENTS, 1)  # instrumented: the oracle's trace needs it, and HIP passes self-check
+        self.color_format, self.instrumented = color_format, instrumented
+        self.r = lib.create(width, height, color_format)
+        # instrumented by default: the oracle's trace needs it, and HIP passes self-check; off: the timed tile_kernel instances
+        self.r.set_option(A.OPT_COUNT_FRAGMENTS, 1 if instrumented else 0)
+        if tuning is not None:
+            self.r.set_option(A.OPT_TUNING, tuning)
         if attributes:
             self.r.enable_attributes(A.ATTR_ALL)
         self.images, self.samplers, self.materials = {}, {}, {}
@@ -494,9 +503,11 @@ class Rig:
         r.trace_pixel(-1, -1)
         r.clear_color((0.0, 0.0, 0.0, 0.0))
         r.draw_geometry(scene, ro)
-        color = r.read_color().view(np.float16).astype(np.float32)
+        codes = r.read_color()
+        # "color": the stored values - halves, or the bytes of an RGBA8 target (0 .. 255)
+        color = codes.view(np.float16).astype(np.float32) if self.color_format == A.COLOR_RGBA16F else codes.astype(np.float32)
         out = {"covered": color[..., 3] != 0.0, "depth": r.read_depth(), "color": color,
-               "fragments": int(r.get_stats().rasterized_fragments)}
+               "fragments": int(r.get_stats().rasterized_fragments) if self.instrumented else None}
         if self.attributes:
             out["bary"], out["uv"], out["albedo"] = (r.read_attribute(a) for a in (A.ATTR_BARY, A.ATTR_UV, A.ATTR_ALBEDO))
         traces = []
