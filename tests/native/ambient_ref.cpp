@@ -9,6 +9,8 @@
 //       intensity, sharpness; float depth[H][W], normal[H][W][4].
 // <out>: float raw[H][W][2] (C36's (a, 1/w)), float out[H][W] (C37), both zero outside the scissor; uint8 kind[H][W]:
 //        0 outside the scissor, 1 no surface, 2 rpx below one pixel, 3 evaluated, 4 evaluated at the reach cap.
+//        Bits 16-23 of flags name a deliberately wrong variant of one rule (0: the contract; the list is at run_ao), for
+//        tests/test_ambient_ref.py to show that the fp64 statement of tests/ambient_ref.py catches each.
 //
 //   ambient_ref light <in> <out>
 // <in>  as tests/native/light_ref.cpp's, then float ao[H][W].  <out>: as light_ref's.  acc starts from
@@ -24,6 +26,24 @@
 namespace {
 
 float fraction(int k) { return ((float)((3 * k) & 7) + 0.5f) * 0.125f; }
+
+// the wrong variants (bits 16-23 of flags): one rule each, everything else the contract's
+enum Variant : uint32_t {
+  V_NONE = 0,
+  V_ROTATION_FROM_SCISSOR = 1,  // the rotation indexed by scissor-relative coordinates
+  V_FRACTION_FROM_K = 2,        // f_k from k instead of 3k & 7
+  V_TRUNCATE = 3,               // rintf replaced by truncation
+  V_TAP_AT_CORNER = 4,          // the tap unprojected at its texel's corner
+  V_TAP_CLAMPED_IN = 5,         // a tap outside the scissor clamped in instead of dropped
+  V_NORMAL_AS_STORED = 6,       // the normal not normalised
+  V_BIAS_ADDED = 7,
+  V_NO_RANGE_TEST = 8,
+  V_BLUR_CLAMPED_TO_IMAGE = 9,  // the blur's coordinates clamped to the image instead of the scissor
+  V_BLUR_ABSOLUTE = 10,         // the blur accepts |hw_t - hw_c| <= sharpness
+  V_BLUR_3X3 = 11,
+  V_REACH_8 = 12,               // the reach cap at 8
+  V_COUNT
+};
 
 int run_tables(const char* out_path) {
   FILE* o = std::fopen(out_path, "wb");
@@ -41,7 +61,9 @@ int run_ao(const char* in_path, const char* out_path) {
   uint32_t hdr[7];
   float inv_vp[16], par[5];
   if (!read_all(f, hdr, sizeof hdr) || !read_all(f, inv_vp, sizeof inv_vp) || !read_all(f, par, sizeof par)) return 3;
-  const uint32_t W = hdr[0], H = hdr[1], sx = hdr[2], sy = hdr[3], sw = hdr[4], sh = hdr[5], flags = hdr[6];
+  const uint32_t W = hdr[0], H = hdr[1], sx = hdr[2], sy = hdr[3], sw = hdr[4], sh = hdr[5], flags = hdr[6] & 0xffffu;
+  const uint32_t variant = (hdr[6] >> 16) & 0xffu;
+  if (variant >= V_COUNT || (hdr[6] >> 24)) return 3;
   const float radius = par[0], ppu = par[1], bias = par[2], intensity = par[3], sharpness = par[4];
   const size_t n = (size_t)W * H;
   std::vector<float> depth(n), normal(n * 4);
@@ -73,36 +95,45 @@ int run_ao(const char* in_path, const char* out_path) {
       divide_w(h, P);
       const float rl = 1.0f / std::sqrt(nn);
       const float nh[3] = {nr[0] * rl, nr[1] * rl, nr[2] * rl};
+      const float* nu = variant == V_NORMAL_AS_STORED ? nr : nh;
       // C33
       float rpx = radius_px * h[3];
-      rpx = rpx < 16.0f ? rpx : 16.0f;
+      const float cap = variant == V_REACH_8 ? 8.0f : 16.0f;
+      rpx = rpx < cap ? rpx : cap;
       if (!(rpx >= 1.0f)) {
         raw[i * 2] = 1.0f;
         raw[i * 2 + 1] = h[3];
         kind[i] = 2;
         continue;
       }
-      kind[i] = rpx == 16.0f ? 4 : 3;
+      kind[i] = rpx == cap ? 4 : 3;
       // C34
-      const float* rot = SVR_AMBIENT_R[(py & 3u) * 4u + (px & 3u)];
+      const uint32_t rx = variant == V_ROTATION_FROM_SCISSOR ? px - sx : px, ry = variant == V_ROTATION_FROM_SCISSOR ? py - sy : py;
+      const float* rot = SVR_AMBIENT_R[(ry & 3u) * 4u + (rx & 3u)];
       float sum = 0.0f;
       for (int k = 0; k < 8; k++) {
         const float dx = SVR_AMBIENT_D[k][0], dy = SVR_AMBIENT_D[k][1];
         const float ux = dx * rot[0] - dy * rot[1], uy = std::fma(dx, rot[1], dy * rot[0]);
-        const float rf = rpx * fraction(k);
-        const float ox = std::rint(rf * ux), oy = std::rint(rf * uy);
+        const float rf = rpx * (variant == V_FRACTION_FROM_K ? ((float)k + 0.5f) * 0.125f : fraction(k));
+        const float ox = variant == V_TRUNCATE ? std::trunc(rf * ux) : std::rint(rf * ux);
+        const float oy = variant == V_TRUNCATE ? std::trunc(rf * uy) : std::rint(rf * uy);
         if (ox == 0.0f && oy == 0.0f) continue;
-        const long tx = (long)px + (long)ox, ty = (long)py + (long)oy;
+        long tx = (long)px + (long)ox, ty = (long)py + (long)oy;
+        if (variant == V_TAP_CLAMPED_IN) {
+          tx = tx < (long)sx ? (long)sx : (tx > (long)(sx + sw) - 1 ? (long)(sx + sw) - 1 : tx);
+          ty = ty < (long)sy ? (long)sy : (ty > (long)(sy + sh) - 1 ? (long)(sy + sh) - 1 : ty);
+        }
         if (tx < (long)sx || tx >= (long)(sx + sw) || ty < (long)sy || ty >= (long)(sy + sh)) continue;
         const float zt = depth[(size_t)ty * W + (size_t)tx];
         if (!(zt > 0.0f)) continue;
         // C35
         float g[3];
-        position(inv_vp, (float)tx + 0.5f, (float)ty + 0.5f, kx, ky, zt, g);
+        const float centre = variant == V_TAP_AT_CORNER ? 0.0f : 0.5f;
+        position(inv_vp, (float)tx + centre, (float)ty + centre, kx, ky, zt, g);
         const float vx = g[0] - P[0], vy = g[1] - P[1], vz = g[2] - P[2];
         const float vv = std::fma(vz, vz, std::fma(vy, vy, vx * vx));
-        if (!(vv < radius2)) continue;
-        const float vn = std::fma(vz, nh[2], std::fma(vy, nh[1], vx * nh[0])) - bias;
+        if (!(vv < radius2) && variant != V_NO_RANGE_TEST) continue;
+        const float vn = std::fma(vz, nu[2], std::fma(vy, nu[1], vx * nu[0])) - (variant == V_BIAS_ADDED ? -bias : bias);
         sum = sum + (vn > 0.0f ? vn : 0.0f) / (vv + 0.0001f);
       }
       // C36
@@ -125,14 +156,17 @@ int run_ao(const char* in_path, const char* out_path) {
         out[i] = 1.0f;
         continue;
       }
-      const float lim = sharpness * hc;
+      const float lim = variant == V_BLUR_ABSOLUTE ? sharpness : sharpness * hc;
+      const long bx0 = variant == V_BLUR_CLAMPED_TO_IMAGE ? 0 : (long)sx, bx1 = variant == V_BLUR_CLAMPED_TO_IMAGE ? (long)W : (long)(sx + sw);
+      const long by0 = variant == V_BLUR_CLAMPED_TO_IMAGE ? 0 : (long)sy, by1 = variant == V_BLUR_CLAMPED_TO_IMAGE ? (long)H : (long)(sy + sh);
+      const int br = variant == V_BLUR_3X3 ? 1 : 2;
       float sum = 0.0f;
       uint32_t count = 0;
-      for (int dy = -2; dy <= 2; dy++) {
-        for (int dx = -2; dx <= 2; dx++) {
+      for (int dy = -br; dy <= br; dy++) {
+        for (int dx = -br; dx <= br; dx++) {
           long tx = (long)px + dx, ty = (long)py + dy;
-          tx = tx < (long)sx ? (long)sx : (tx > (long)(sx + sw) - 1 ? (long)(sx + sw) - 1 : tx);
-          ty = ty < (long)sy ? (long)sy : (ty > (long)(sy + sh) - 1 ? (long)(sy + sh) - 1 : ty);
+          tx = tx < bx0 ? bx0 : (tx > bx1 - 1 ? bx1 - 1 : tx);
+          ty = ty < by0 ? by0 : (ty > by1 - 1 ? by1 - 1 : ty);
           const size_t j = (size_t)ty * W + (size_t)tx;
           if ((dx == 0 && dy == 0) || std::fabs(raw[j * 2 + 1] - hc) <= lim) {
             sum = sum + raw[j * 2];

@@ -2,7 +2,8 @@
 
 The reference is tests/native/ambient_ref.cpp (ambient_ref.py), the scalar restatement of DESIGN C32-C37 that
 test_ambient_ref.py pins on the CPU.  It is fed the depth and normal planes the HIP library itself holds, so every
-comparison here is on bit patterns, over the whole plane, with no tolerance."""
+comparison with it is on bit patterns, over the whole plane, with no tolerance.  Part 6 adds the scissor's and the staging's
+edges and, without the restatement in between, the comparison with ambient_ref.ao64 under its own ties and bound."""
 import numpy as np
 import pytest
 
@@ -315,3 +316,126 @@ def test_refusals(hip):
     AR.assert_planes(r.read_ambient_raw(), before[1], "nor the raw plane")
     assert_color(r.read_color(), before[2], "nor colour")
     r.close()
+
+
+# ---------------------------------------------------------------- 6. scissor edges, alignment, specials, and the fp64 statement
+def ambient_over(hip, depth, normal, inv_vp, ppu, scissor, flags, params=AR.PLANE_PARAMS):
+    """one pass over caller-bound planes -> (the raw plane, the bound ambient tensor, which held SENTINEL everywhere)"""
+    torch = pytest.importorskip("torch")
+    h, w = depth.shape
+    t_color = torch.zeros((h, w, 2), dtype=torch.int32, device="cuda")
+    t_depth = torch.from_numpy(np.ascontiguousarray(depth, dtype=f32)).cuda()
+    t_normal = torch.from_numpy(np.ascontiguousarray(normal, dtype=f32)).cuda()
+    t_ao = torch.full((h, w), float(SENTINEL), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    r = hip.create(w, h)
+    r.bind_targets(t_color.data_ptr(), t_depth.data_ptr())
+    r.bind_attribute_target(A.ATTR_NORMAL, t_normal.data_ptr())
+    r.bind_ambient_target(t_ao.data_ptr())
+    if scissor:
+        r.set_scissor(*scissor)
+    r.ambient_pass(np.asarray(inv_vp, f32).reshape(4, 4), params["radius"], ppu, params["bias"], params["intensity"], params["sharpness"], flags)
+    raw = r.read_ambient_raw()  # (fences)
+    out = t_ao.cpu().numpy()
+    r.close()
+    return raw, out
+
+
+def assert_pass_is(raw, out, ref, scissor, what):
+    """bit patterns over the whole plane: the raw plane zero and the target untouched outside the scissor"""
+    inside = AR.inside_of(out.shape, scissor)
+    AR.assert_planes(raw, ref["raw"], f"{what}: the raw (a, 1/w) plane")
+    AR.assert_planes(out, np.where(inside, ref["out"], SENTINEL), f"{what}: the ambient target")
+
+
+@pytest.mark.parametrize("flags", [0, A.AMBIENT_NO_BLUR], ids=["blur", "no_blur"])
+@pytest.mark.parametrize("name", list(AR.EDGE_SCISSORS))
+def test_degenerate_and_seam_scissors(hip, name, flags):
+    scissor = AR.EDGE_SCISSORS[name]
+    depth, normal, inv_vp, ppu, _ = AR.plane_case(None, 0)
+    ref = AR.run_ref(depth, normal, inv_vp, ppu=ppu, flags=flags, scissor=scissor, **AR.PLANE_PARAMS)
+    assert (ref["kind"] != 0).sum() == scissor[2] * scissor[3]
+    raw, out = ambient_over(hip, depth, normal, inv_vp, ppu, scissor, flags)
+    assert_pass_is(raw, out, ref, scissor, name)
+
+
+@pytest.mark.parametrize("scissor", [AR.ODD_SCISSOR, AR.EDGE_SCISSORS["one_into_a_second_tile_at_the_end"]], ids=["odd_scissor", "at_the_end"])
+def test_nothing_outside_the_scissor_is_read(hip, scissor):
+    """every texel outside the scissor holds what would show if it were read: NaN or a near, occluding depth, a NaN normal"""
+    depth, normal, inv_vp, ppu, _ = AR.plane_case(None, 0)
+    ref = AR.run_ref(depth, normal, inv_vp, ppu=ppu, scissor=scissor, **AR.PLANE_PARAMS)
+    bad_depth, bad_normal = AR.poisoned_outside(depth, normal, scissor)
+    shown = AR.run_ref(np.nan_to_num(bad_depth, nan=0.9), normal, inv_vp, ppu=ppu, scissor=None, **AR.PLANE_PARAMS)
+    inside = AR.inside_of(depth.shape, scissor)
+    assert (shown["out"][inside] != ref["out"][inside]).mean() > 0.02, "a pass that read past the scissor would differ"
+    raw, out = ambient_over(hip, bad_depth, bad_normal, inv_vp, ppu, scissor, 0)
+    assert_pass_is(raw, out, ref, scissor, "planes poisoned outside the scissor")
+
+
+@pytest.mark.parametrize("w", [64, 65, 66, 67])
+def test_alignment_parities(hip, w):
+    """row starts and scissor origins at every residue of a 16-byte group: with the width and the origin, every row of the
+    staging takes the 16-byte load, none does, or some rows do, and the right edge falls at every place inside a group"""
+    depth, normal, inv_vp, ppu = AR.small_plane(w)
+    h = depth.shape[0]
+    vector_rows = set()
+    for x0 in range(5):
+        scissor = (x0, 0, w - x0, h)
+        vector_rows.add(sum((y * w + x0) % 4 == 0 for y in range(h)))
+        ref = AR.run_ref(depth, normal, inv_vp, ppu=ppu, scissor=scissor, **AR.PLANE_PARAMS)
+        assert (ref["out"][:, x0:] < 1).mean() > 0.1 and (ref["kind"] == AR.CAPPED).any()
+        raw, out = ambient_over(hip, depth, normal, inv_vp, ppu, scissor, 0)
+        assert_pass_is(raw, out, ref, scissor, f"width {w}, origin {x0}")
+    assert vector_rows == ({0, h} if w % 4 == 0 else {0, h // 2} if w % 2 == 0 else {h // 4})  # rows whose start is 16-byte aligned
+
+
+def assert_bits_or_nan(got, want, what):
+    nan = np.isnan(want)
+    AR.assert_planes(np.where(nan, f32(0), got), np.where(nan, f32(0), want), what)
+    assert np.isnan(got[nan]).all(), f"{what}: a NaN of the reference's is a NaN"
+
+
+@pytest.mark.parametrize("flags", [0, A.AMBIENT_NO_BLUR], ids=["blur", "no_blur"])
+def test_specials(hip, flags):
+    """infinite, negative, -0.0 and subnormal depths, a normal w of -0.0, infinite and underflowing normals: a kernel built to
+    flush fp32 denormals, or whose max prefers the other operand, differs from the contract here"""
+    depth, normal, inv_vp, ppu = AR.special_plane()
+    assert np.isinf(depth).any() and (depth < 0).any() and ((depth > 0) & (depth < 1e-38)).any() and not np.isnan(depth).any()
+    assert (AR.bits(normal[..., 3]) == 0x80000000).any() and np.isinf(normal).any()
+    ref = AR.run_ref(depth, normal, inv_vp, ppu=ppu, flags=flags, **AR.PLANE_PARAMS)
+    tiny = (depth > 0) & (depth < 1e-38) & (ref["kind"] != AR.NO_SURFACE)
+    assert tiny.any() and (ref["raw"][..., 1][tiny] != 0).all(), "a subnormal depth is a surface"
+    raw, out = ambient_over(hip, depth, normal, inv_vp, ppu, None, flags)
+    for c, part in enumerate(("a", "1/w")):
+        assert_bits_or_nan(raw[..., c], ref["raw"][..., c], f"specials: the raw plane's {part}")
+    assert_bits_or_nan(out, ref["out"], "specials: the ambient target")
+
+
+@pytest.mark.parametrize("scissor", [None, AR.ODD_SCISSOR], ids=["whole", "odd_scissor"])
+def test_behind_the_eye_plane(hip, scissor):
+    depth, normal = AR.plane_case(None, 0)[:2]
+    inv_vp, ppu = AR.behind_the_eye(*AR.PLANE)
+    ref = AR.run_ref(depth, normal, inv_vp, ppu=ppu, scissor=scissor, **AR.PLANE_PARAMS)
+    AR.assert_behind_the_eye(ref, scissor or (0, 0) + AR.PLANE)
+    raw, out = ambient_over(hip, depth, normal, inv_vp, ppu, scissor, 0)
+    assert_pass_is(raw, out, ref, scissor or (0, 0) + AR.PLANE, "h.w < 0 on the left")
+
+
+@pytest.mark.parametrize("case", ["random_planes", "crease"])
+def test_against_the_fp64_statement(hip, case):
+    """the HIP library against ambient_ref.ao64 itself, with its ties and its bound: no CPU restatement in between"""
+    if case == "random_planes":
+        depth, normal, inv_vp, ppu, _ = AR.plane_case(AR.ODD_SCISSOR, 0)
+        scissor, params, st = AR.ODD_SCISSOR, AR.PLANE_PARAMS, AR.plane_statement(AR.ODD_SCISSOR)
+    else:
+        depth, normal, inv_vp, ppu, _ = AR.analytic_scene(case)
+        scissor, params, st = (0, 0) + AR.SCENE, AR.SCENE_PARAMS, AR.scene_statement(case)
+    AR.assert_statement_is_telling(st, 0, scissor)
+    AR.assert_statement_is_telling(st, AR.NO_BLUR, scissor)
+    raw, out = ambient_over(hip, depth, normal, inv_vp, ppu, scissor, 0, params)
+    for flags, plane, what in ((0, out, "the ambient target"), (AR.NO_BLUR, raw[..., 0], "the raw plane's a")):
+        worst, at, beyond = AR.compare64(plane, st, flags, scissor)
+        print(f"{case}, {what}: largest |HIP - ao64| / bound = {worst:.4f} at (y, x) = {at}")
+        assert beyond == 0, f"{case}, {what}: {beyond} compared pixels beyond the bound, the worst {worst:.3g} bounds off at (y, x) = {at}"
+    keep = AR.inside_of(out.shape, scissor) & ~st["tie_a"]
+    assert np.allclose(raw[..., 1][keep], st["hw"][keep], rtol=16 * AR.EPS, atol=0)
